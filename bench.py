@@ -12,7 +12,16 @@ resident in HBM before the timed region (slowness is broadcast over RCCL and han
 solver as a device pointer); the receiver traveltimes are all-gathered over RCCL inside
 every step (a few KB).
 
-  python bench.py --gpus 1 --steps 5 --warmup 1
+A plain run sets up, warms up, times the --steps steps and prints the result line.  --full adds, after the
+timed region, everything else the benchmark measures: the measured copy bandwidth, the evaluate-all kernel,
+the single-source, tolerance-mode, eight-source, heterogeneous and WENO legs, and the CPU baseline
+(--no-single-source / --no-cpu-baseline leave parts of it out).  --dump-outputs DIR writes what the last
+timed step computed (rank 0): DIR/tt_rcv.npy, the receiver traveltimes raytrace returned (every rank's,
+in rank order, when the run is distributed); DIR/tt_field_sample.npy, the node traveltime field of each
+of rank 0's sources at a fixed, seeded sample of nodes (float32, sources x nodes); DIR/tt_field_sample_index.npy,
+the flat (x-fastest) node indices of that sample; DIR/sweep_iterations.npy, the sweep-iterations of each source.
+
+  python bench.py --gpus 1 --steps 5 --warmup 1 [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -318,6 +327,29 @@ def weno_leg(local_rank, n=256, arith=0):
     return out
 
 
+DUMP_FIELD_NODES = 1 << 16   # nodes of each source's field in the sample tt_field_sample.npy
+
+
+def dump_outputs(out_dir, grid, tt_rcv, niter):
+    """--dump-outputs: the receiver traveltimes, a fixed sample (seed 0) of every slot's node field and the sweep-iterations
+    of the last timed step, as .npy files (at most 64 sources x 2^16 nodes x 4 B = 16 MB of fields)."""
+    import ttcr_amd
+
+    os.makedirs(out_dir, exist_ok=True)
+    n_nodes = grid.get_number_of_nodes()
+    idx = np.unique(np.random.default_rng(0).integers(0, n_nodes, min(DUMP_FIELD_NODES, n_nodes)))
+    buf = np.empty(n_nodes, dtype=grid._dtype)   # (one host buffer for every slot: ttcr_fsm_get_tt, as Grid3d._flat_tt)
+    sample = np.empty((grid.n_threads, idx.size), dtype=np.float32)
+    for i in range(grid.n_threads):
+        ttcr_amd._lib.check(grid._lib.ttcr_fsm_get_tt(grid._h, i, buf.ctypes.data_as(C.c_void_p), n_nodes))
+        sample[i] = buf[idx]
+    tt_rcv = np.asarray(tt_rcv)
+    np.save(os.path.join(out_dir, "tt_rcv.npy"), tt_rcv if tt_rcv.dtype in (np.float32, np.float64) else tt_rcv.astype(np.float64))
+    np.save(os.path.join(out_dir, "tt_field_sample.npy"), sample)
+    np.save(os.path.join(out_dir, "tt_field_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "sweep_iterations.npy"), np.asarray(niter, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -326,8 +358,12 @@ def main():
     ap.add_argument("--size", type=int, default=512, help="nodes per axis")
     ap.add_argument("--sources", type=int, default=64, help="total sources of the job (sharded over the GPUs)")
     ap.add_argument("--sources-per-gpu", type=int, default=0, help="override: fixed sources per GPU (weak scaling)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-single-source", action="store_true", help="skip the 1-source leg of the N=1 run")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run every other leg of the benchmark "
+                    "(copy bandwidth, evaluate-all kernel, single-source, tolerance, eight-source, heterogeneous, WENO, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-single-source", action="store_true", help="with --full: leave out the evaluate-all kernel and the "
+                    "single-source, tolerance, eight-source, heterogeneous and WENO legs")
     ap.add_argument("--max-batch", type=int, default=0)
     ap.add_argument("--opt", action="append", default=[], help="key=value handed to ttcr_fsm_set_option (tuning / bisecting)")
     ap.add_argument("--per-step", action="store_true", help="print launches / evaluated updates of every timed step to stderr")
@@ -336,6 +372,8 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl == RCCL; gloo only to "
                     "exercise the multi-rank path on a single-GPU box)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -459,6 +497,13 @@ def main():
     iters_per_src = list(step_niter[-1])
     # every timed step solves the same sources on the same model: launch count and iteration counts must not move
     odd_steps = [k for k in range(args.steps) if step_launches[k] != step_launches[0] or step_niter[k] != step_niter[0]]
+    if args.dump_outputs and rank == 0:   # (before any other solve overwrites the fields of the last timed step)
+        if use_dist:   # every rank's receiver traveltimes of the last step, in rank order
+            rows = [(hi - lo) * rcv1.shape[0] for lo, hi in (shard_bounds(n_total, world, k) for k in range(world))]
+            tt_all = np.concatenate([g[:r].cpu().numpy() for g, r in zip(gathered, rows)])
+        else:
+            tt_all = tt
+        dump_outputs(args.dump_outputs, grid, tt_all, iters_per_src)
 
     stats = torch.tensor([el, sweep_ms, float(node_iters), float(launches)], dtype=torch.float64, device=cdev)
     per_rank = [(S, el)]
@@ -549,7 +594,7 @@ def main():
                                          "priced at nothing -- frac_contract_all_updates is SURVEY 8(d)'s 104 B x N x iterations / time, "
                                          "which counts them; frac_real_traffic is the PMC traffic of profiles/ over the same time"},
         }
-        if world == 1:
+        if world == 1 and args.full:
             try:
                 cp = measured_copy_bandwidth(dev)
                 out["roofline"]["measured_copy_GBs"] = round(cp, 1)
@@ -559,7 +604,7 @@ def main():
             except Exception as e:   # (reported, never fatal: the contract fields above do not depend on it)
                 out["roofline"]["measured_copy_GBs"] = None
                 sys.stderr.write("copy bandwidth not measured: %s\n" % e)
-        if world == 1 and not args.no_single_source:
+        if world == 1 and args.full and not args.no_single_source:
             # the kernel with every node update evaluated (exact skipping switched off), same grid, same sources, same
             # process: the roofline of the sweep kernel itself, where algorithmic bytes and evaluated work coincide
             try:
@@ -634,7 +679,7 @@ def main():
                         out[name] = weno_leg(local_rank, arith=2)
                 except Exception as e:   # (reported, never fatal)
                     out[name] = {"error": str(e)[:300]}
-        if not args.no_cpu_baseline and world == 1:   # the CPU leg is timed on rank 0 of the single-GPU run only
+        if args.full and not args.no_cpu_baseline and world == 1:   # the CPU leg is timed on rank 0 of the single-GPU run only
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out))
     if use_dist:

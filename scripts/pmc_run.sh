@@ -3,12 +3,13 @@
 # (MI355X_MICROARCH.md: FETCH_SIZE and WRITE_SIZE do not fit one pass; no trace domains with --pmc).
 # usage: scripts/pmc_run.sh <tag> <bench args...>
 set -u
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 TAG=$1; shift
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for C in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $C --output-format csv -d $OUT -o ${TAG}_$C -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline "$@" > $OUT/bench_$C.log 2>&1
+  rocprofv3 --pmc $C --output-format csv -d $OUT -o ${TAG}_$C -- python $ROOT/bench.py --full --no-cpu-baseline "$@" > $OUT/bench_$C.log 2>&1
   tail -1 $OUT/bench_$C.log | cut -c1-200
 done
 python - <<PY

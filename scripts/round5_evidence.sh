@@ -6,8 +6,8 @@ set -u
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 O=$(realpath -m ${1:-$ROOT/gpurun_out/r05}); mkdir -p $O
 cd $ROOT
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_512x64.json 2> $O/bench_512x64.err; echo "bench rc $?"; tail -c 300 $O/bench_512x64.json; echo
-CMD="python $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-single-source"
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_512x64.json 2> $O/bench_512x64.err; echo "bench rc $?"; tail -c 300 $O/bench_512x64.json; echo
+CMD="python $ROOT/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-single-source"
 cd /tmp && export TMPDIR=/tmp
 for TAG in r05_512x64 r05_512x64_skip0; do
   mkdir -p $O/raw
@@ -35,7 +35,7 @@ unset TTCR_FSM_SKIP
 cd $ROOT && python scripts/pmc_to_json.py $O r05_512x64 512 64 $O/traffic.json
 python scripts/pmc_to_json.py $O r05_512x64_skip0 512 64 $O/traffic_skip0.json
 # SQ counters of the two kernels (two --pmc passes each)
-SQCMD="python $ROOT/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-single-source"
+SQCMD="python $ROOT/bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --no-single-source"
 timeout 600 bash scripts/sq_counters.sh $O/sq_counters_512x64_default.txt $SQCMD > /dev/null 2>&1
 TTCR_FSM_SKIP=0 timeout 600 bash scripts/sq_counters.sh $O/sq_counters_512x64_skip0.txt $SQCMD > /dev/null 2>&1
 tail -3 $O/sq_counters_512x64_default.txt; tail -3 $O/sq_counters_512x64_skip0.txt

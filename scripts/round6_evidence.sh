@@ -7,7 +7,7 @@ set -u
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 O=$(realpath -m ${1:-$ROOT/gpurun_out/r06}); mkdir -p $O
 cd $ROOT
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_512x64.json 2> $O/bench_512x64.err; echo "bench rc $?"; tail -c 200 $O/bench_512x64.json; echo
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_512x64.json 2> $O/bench_512x64.err; echo "bench rc $?"; tail -c 200 $O/bench_512x64.json; echo
 summarise() {   # <raw dir> <tag>: per-kernel sums of the two counter passes -> $O/<tag>_{FETCH,WRITE}_SIZE_summary.csv
   python3 - <<PY
 import csv, glob, collections
@@ -22,7 +22,7 @@ for C in ("FETCH_SIZE","WRITE_SIZE"):
 PY
 }
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-single-source"
+BENCH="python $ROOT/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-single-source"
 for TAG in r06_512x64 r06_512x64_arith1; do
   mkdir -p $O/raw
   CMD="$BENCH"; [ $TAG = r06_512x64_arith1 ] && CMD="$BENCH --opt arith=1"
