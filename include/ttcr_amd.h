@@ -326,6 +326,37 @@ int ttcr_fsm_raytrace_multi_m(ttcr_fsm_grid* g, int n_src, const int* tx_off, co
 int ttcr_fsm_multi_m_size(const ttcr_fsm_grid* g, size_t* n_rows, size_t* nnz);
 int ttcr_fsm_get_multi_m(const ttcr_fsm_grid* g, long long* row_off, long long* j, void* v);
 
+/* The M tape: the matrix of ttcr_fsm_raytrace_multi_m (with_rays = 0) kept on the device for M^T w, the gradient of a misfit with
+ * respect to node velocity.  No reference counterpart: it derives from the same walk, Grid3Drn::getRaypath(Tx, t0, Rx, m_data, RxNo,
+ * tt, threadNo) (ttcr/Grid3Drn.h:1503-1800), whose records are merged on the device instead of being copied to the host.
+ * ttcr_fsm_raytrace_multi_tape: sources and receivers laid out like ttcr_fsm_raytrace_multi_m; tt_out as that call gives it (the
+ * fields are solved and walked by the same batched path); *tape receives a new tape whose rows are the receiver rows in layout order.
+ * Its entries are those of ttcr_fsm_get_multi_m with node indices >= n_nodes dropped, nodes ascending within a row; the values are
+ * merged exactly as the host assembly merges them (contributions of one node summed in push order, starting from the first one).
+ * 3-D node grids only (TTCR_ERR_UNSUPPORTED otherwise, with compute_M's message).  On a multi-device grid every replica walks its own
+ * sources and the parts are put together on the first listed device: the tape is bit-identical to that of a one-device grid.
+ * A tape owns its device memory and stream: it stays valid after later calls on the grid, after ttcr_fsm_set_slowness and after
+ * ttcr_fsm_destroy of the grid, until ttcr_fsm_tape_free (NULL: no-op).  Calls on one tape from several threads are serialised.
+ * ttcr_fsm_tape_size: rows, columns (= n_nodes) and entries.  ttcr_fsm_tape_bytes: device memory the tape holds:
+ *   8 (n_rows + 1 + n_nodes + 1) + 2 nnz (4 + elem) + (n_rows + n_nodes) elem   (elem = 4 or 8 bytes, the grid dtype).
+ * ttcr_fsm_tape_device: the HIP device the tape lives on.
+ * ttcr_fsm_tape_get_csr: host copy, row_off[n_rows + 1], j[nnz] node indices, v[nnz] values of the grid dtype.
+ * ttcr_fsm_tape_vjp: grad[n] = sum over the entries of node n, rows ascending, of fl(v * w[row]), summed left to right from +0 in the
+ *   grid dtype, without atomics (reproducible to the bit, independent of the device list and of n_slots).  w: n_rows values, grad:
+ *   n_nodes values (x fastest), both of the grid dtype; *_on_device != 0: a device pointer on the tape's device, else host memory.
+ *   The call returns with grad written.  The tape runs on its own stream: the caller makes sure a device-resident w is complete
+ *   before the call (e.g. synchronise the stream that produced it).
+ * Argument errors (a NULL tape or pointer) return TTCR_ERR_VALUE before any device call. */
+typedef struct ttcr_fsm_tape ttcr_fsm_tape; /* opaque */
+int ttcr_fsm_raytrace_multi_tape(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off,
+                                 const void* rx, void* tt_out, ttcr_fsm_tape** tape);
+int ttcr_fsm_tape_size(const ttcr_fsm_tape* t, size_t* n_rows, size_t* n_cols, size_t* nnz);
+int ttcr_fsm_tape_bytes(const ttcr_fsm_tape* t, size_t* bytes);
+int ttcr_fsm_tape_device(const ttcr_fsm_tape* t, int* device);
+int ttcr_fsm_tape_get_csr(const ttcr_fsm_tape* t, long long* row_off, long long* j, void* v);
+int ttcr_fsm_tape_vjp(const ttcr_fsm_tape* t, const void* w, int w_on_device, void* grad, int grad_on_device);
+int ttcr_fsm_tape_free(ttcr_fsm_tape* t);
+
 /* Replaces: Grid2D::raytrace(Tx, t0, Rx, traveltimes, l_data, threadNo) (ttcr/Grid2D.h:616-640) and the overload with r_data
  * AND l_data (:583-614) -> Grid2Drn::getRaypath(Tx, t0, Rx, [r_data,] l_data, tt, threadNo) (ttcr/Grid2Drn.h:1852-2190): what
  * `compute_L=True` of the Python layer reaches for 2-D grids with cell slowness (src/ttcrpy/rgrid.pyx:3889-3893, :4060-4143).

@@ -69,6 +69,13 @@ SYMBOLS = {
     "ttcr_fsm_raytrace_multi_m": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I]),
     "ttcr_fsm_multi_m_size": (_I, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "ttcr_fsm_get_multi_m": (_I, [_P, _P, _P, _P]),
+    "ttcr_fsm_raytrace_multi_tape": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, C.POINTER(_P)]),
+    "ttcr_fsm_tape_size": (_I, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "ttcr_fsm_tape_bytes": (_I, [_P, C.POINTER(C.c_size_t)]),
+    "ttcr_fsm_tape_device": (_I, [_P, C.POINTER(_I)]),
+    "ttcr_fsm_tape_get_csr": (_I, [_P, _P, _P, _P]),
+    "ttcr_fsm_tape_vjp": (_I, [_P, _P, _I, _P, _I]),
+    "ttcr_fsm_tape_free": (_I, [_P]),
     "ttcr_fsm_raytrace_multi_l": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I]),
     "ttcr_fsm_multi_l_size": (_I, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "ttcr_fsm_get_multi_l": (_I, [_P, _P, _P, _P]),

@@ -7,6 +7,7 @@ which a fused multiply-add would not (ttcr_amd/csrc/fsm_kernels.h header).
 Two translation units, compiled to objects under ttcr_amd/csrc/_obj and linked:
   fsm_capi.hip    the C ABI, the host side and every kernel but one
   fsm_fast.hip    the sweep kernels with tolerance-grade arithmetic (option "arith" = 1)
+  fsm_tape.hip    the M tape: compute_M's rows merged on the device, node index, M^T w (hipCUB sorts)
 """
 import os
 import shutil
@@ -19,8 +20,10 @@ LIB = os.path.join(HERE, "libttcr_amd.so")
 INC = os.path.join("..", "..", "include", "ttcr_amd.h")
 # source -> (extra flags, files it is compiled from)
 UNITS = {
-    "fsm_capi.hip": ([], ["fsm_capi.hip", "fsm_kernels.h", "fsm_fast_api.h", "fsm_march_levels.inc", "fsm_fast.hip", INC]),
+    "fsm_capi.hip": ([], ["fsm_capi.hip", "fsm_kernels.h", "fsm_fast_api.h", "fsm_march_levels.inc", "fsm_fast.hip", "fsm_tape_api.h",
+                          "fsm_tape.hip", INC]),
     "fsm_fast.hip": ([], ["fsm_fast.hip", "fsm_fast_api.h", "fsm_kernels.h", "fsm_march_levels.inc"]),
+    "fsm_tape.hip": ([], ["fsm_tape.hip", "fsm_tape_api.h"]),
 }
 SOURCES = list(UNITS)
 DEPS = sorted({d for _, ds in UNITS.values() for d in ds})

@@ -26,6 +26,7 @@
 #include "../../include/ttcr_amd.h"
 #include "fsm_kernels.h"
 #include "fsm_fast_api.h"
+#include "fsm_tape_api.h"
 
 #ifndef FSM_CHUNK3
 #define FSM_CHUNK3 8
@@ -110,6 +111,10 @@ class GridBase {
                                   void* tt_out, bool both) = 0;
     virtual void multi_m_size(size_t* n_rows, size_t* nnz) const = 0;
     virtual void get_multi_m(long long* row_off, long long* j, void* v) const = 0;
+    // the same matrix (without rays) kept on the device: the (row, node, value) entries of every receiver row of the call, rows in call
+    // order, nodes ascending within a row, on `device` (the M tape, ttcr_fsm_raytrace_multi_tape)
+    virtual void raytrace_multi_tape(int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off, const void* rx,
+                                     void* tt_out, TapeRows& out) = 0;
     // the raytrace overloads with l_data (2-D cell grids): ray-projection matrix L, one CSR row per receiver
     virtual void raytrace_l(int slot, int n_tx, const void* tx, const void* t0, int n_rx, const void* rx, void* tt_out, bool with_rays) = 0;
     virtual void slot_l_size(int slot, size_t* n_rows, size_t* nnz) const = 0;
@@ -2169,8 +2174,11 @@ class GridT : public GridBase {
     DevBuf<T> d_msegs, d_mlong;
     DevBuf<int> d_mnseg;
     // records of every receiver's walk: seg_off[q] .. seg_off[q+1] in segs (5 values each), traveltimes of the overload in out
+    // sink (the M tape): the records stay on the device and are merged there into (row_base + receiver, node, value) entries appended
+    // to *sink, chunk by chunk (fsm_tape_api.h); segs stays empty
+    TapeChunk m_chunk;
     void walk_m(int slot, int n_tx, const T* txp, const T* t0p, int n, const T* p, T* out, bool both, std::vector<long long>& seg_off,
-                std::vector<T>& segs) {
+                std::vector<T>& segs, TapeRows* sink = nullptr, int row_base = 0) {
         seg_off.assign(1, 0);
         segs.clear();
         if (n <= 0) return;
@@ -2211,6 +2219,11 @@ class GridT : public GridBase {
             HIP_CHECK(hipStreamSynchronize(stream));
             for (int q = 0; q < m; ++q)
                 if (st[q] != 0 && st[q] != 3) throw_walk_error(st[q], pc + (size_t)3 * q, txp, max_steps);
+            if (sink) {
+                walk_m_to_tape(slot, n_tx, rg, m, cap, st, ns, both, max_steps, *sink, row_base + c0);
+                for (int q = 0; q < m; ++q) seg_off.push_back(seg_off.back() + ns[q]);
+                continue;
+            }
             size_t base = segs.size(), tot = 0;
             for (int q = 0; q < m; ++q) tot += (size_t)5 * ns[q];
             segs.resize(base + tot);   // (once per chunk: the copies below are asynchronous)
@@ -2241,6 +2254,35 @@ class GridT : public GridBase {
             HIP_CHECK(hipStreamSynchronize(stream));
         }
     }
+    // one chunk of walk_m into the tape: the records of the walks that fitted are expanded where the walk left them, a long walk (status 3)
+    // is walked again alone with room and expanded from there, then the chunk's contributions are merged
+    void walk_m_to_tape(int slot, int n_tx, const RayGeom<T>& rg, int m, long cap, const std::vector<int>& st, const std::vector<int>& ns,
+                        bool both, long max_steps, TapeRows& sink, int row_base) {
+        std::vector<long long> roff(m + 1, 0);
+        for (int q = 0; q < m; ++q) roff[q + 1] = roff[q] + ns[q];
+        MGeom<T> mg{xmin, ymin, zmin, dx, (size_t)ncx + 1, (size_t)ncy + 1, n_nodes};
+        m_chunk.begin(roff.data(), m, sizeof(T), stream);
+        m_chunk.expand<T>(d_msegs.p, cap, d_rstat.p, 0, m, mg, stream);
+        for (int q = 0; q < m; ++q) {
+            if (st[q] != 3) continue;
+            const long need = (long)ns[q] + 1;
+            d_mlong.reserve((size_t)need * 5);
+            if (both)
+                fsm_raypath3d_m<T, true><<<1, 64, 0, stream>>>(tt_ptr(slot), NS, d_s.p, rg, n_tx, d_rsrc.p, d_rt0.p, d_rx.p + (size_t)3 * q, 1,
+                                                               d_out.p + q, d_rstat.p + q, max_steps, d_mlong.p, need, d_mnseg.p + q);
+            else
+                fsm_raypath3d_m<T, false><<<1, 64, 0, stream>>>(tt_ptr(slot), NS, d_s.p, rg, n_tx, d_rsrc.p, d_rt0.p, d_rx.p + (size_t)3 * q, 1,
+                                                                d_out.p + q, d_rstat.p + q, max_steps, d_mlong.p, need, d_mnseg.p + q);
+            HIP_CHECK(hipGetLastError());
+            int st2 = 0, ns2 = 0;
+            HIP_CHECK(hipMemcpyAsync(&st2, d_rstat.p + q, sizeof(int), hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipMemcpyAsync(&ns2, d_mnseg.p + q, sizeof(int), hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipStreamSynchronize(stream));
+            if (st2 != 0 || ns2 != ns[q]) throw DeviceError("compute_M: a long walk did not retrace to the same length");
+            m_chunk.expand<T>(d_mlong.p, need, d_rstat.p, q, 1, mg, stream);
+        }
+        m_chunk.merge<T>(row_base, mg, sink, stream);
+    }
     // rows of M from the records of walk_m: appended to (mo, mj, mv); mo ends with the running entry count
     void assemble_m(int n_rx, const std::vector<long long>& seg_off, const std::vector<T>& segs, std::vector<long long>& mo,
                     std::vector<long long>& mj, std::vector<T>& mv) const {
@@ -2248,24 +2290,17 @@ class GridT : public GridBase {
         for (int r = 0; r < n_rx; ++r) {
             const size_t row0 = mj.size();
             for (long long q = seg_off[r]; q < seg_off[r + 1]; ++q) {
-                const T* sg = segs.data() + 5 * (size_t)q;
-                const T ds = sg[3];
-                T sq = sg[4];
-                sq *= sq;
-                const size_t ix = (size_t)((sg[0] - xmin) / dx), iy = (size_t)((sg[1] - ymin) / dx), iz = (size_t)((sg[2] - zmin) / dx);
-                for (size_t ii = 0; ii < 2; ++ii)
-                    for (size_t jj = 0; jj < 2; ++jj)
-                        for (size_t kk = 0; kk < 2; ++kk) {
-                            const size_t iv = ix + ii, jv = iy + jj, kv = iz + kk;
-                            const T dvdv = (T)((1. - std::abs(sg[0] - iv * dx) / dx) * (1. - std::abs(sg[1] - jv * dx) / dx) *
-                                               (1. - std::abs(sg[2] - kv * dx) / dx));
-                            const long long j = (long long)((kv * nny + jv) * nnx + iv);
-                            const T v = -sq * ds * dvdv;
-                            size_t e = row0;
-                            for (; e < mj.size(); ++e)
-                                if (mj[e] == j) { mv[e] += v; break; }
-                            if (e == mj.size()) { mj.push_back(j); mv.push_back(v); }
-                        }
+                long long jt[8];
+                T vt[8];
+                m_record_terms<T>(segs.data() + 5 * (size_t)q, xmin, ymin, zmin, dx, nnx, nny, jt, vt);
+                for (int c = 0; c < 8; ++c) {
+                    const long long j = jt[c];
+                    const T v = vt[c];
+                    size_t e = row0;
+                    for (; e < mj.size(); ++e)
+                        if (mj[e] == j) { mv[e] += v; break; }
+                    if (e == mj.size()) { mj.push_back(j); mv.push_back(v); }
+                }
             }
             mo.push_back((long long)mj.size());
         }
@@ -2295,6 +2330,41 @@ class GridT : public GridBase {
             assemble_m(rx_off[n + 1] - rx_off[n], m_seg_off[n], m_segs[n], multi_m_off, multi_m_j, multi_m_v);
             std::vector<T>().swap(m_segs[n]);
         }
+    }
+    // the M tape: the walks of raytrace_multi_m (without rays), each source's rows merged on the device, then put together in source order
+    std::vector<TapeRows> m_tape_src;
+    void raytrace_multi_tape(int n_src, const int* tx_off, const void* tx_v, const void* t0_v, const int* rx_off, const void* rx_v,
+                             void* tt_out_v, TapeRows& out) override {
+        if (dim != 3) throw Unsupported("compute_M is implemented for 3-D grids only");
+        if (cell) throw Unsupported("compute_M not defined for grids with slowness defined for cells");
+        HIP_CHECK(hipSetDevice(device));
+        out.release();
+        out.elem = sizeof(T);
+        if (n_src <= 0) return;
+        m_seg_off.assign(n_src, std::vector<long long>{0});
+        m_segs.assign(n_src, std::vector<T>());
+        m_tape_src.clear();
+        m_tape_src.resize(n_src);
+        m_walk_mode = true; m_walk_both = false;
+        try {
+            raytrace_multi(n_src, tx_off, tx_v, t0_v, rx_off, rx_v, tt_out_v, -1, nullptr, false);
+        } catch (...) { m_walk_mode = false; m_tape_src.clear(); m_chunk.release(); throw; }
+        m_walk_mode = false;
+        size_t tot = 0;
+        for (const TapeRows& r : m_tape_src) tot += r.n;
+        out.grow(tot, stream);
+        for (TapeRows& r : m_tape_src) {
+            if (r.n > 0) {
+                HIP_CHECK(hipMemcpyAsync(out.row + out.n, r.row, r.n * sizeof(int), hipMemcpyDeviceToDevice, stream));
+                HIP_CHECK(hipMemcpyAsync(out.col + out.n, r.col, r.n * sizeof(int), hipMemcpyDeviceToDevice, stream));
+                HIP_CHECK(hipMemcpyAsync((T*)out.val + out.n, r.val, r.n * sizeof(T), hipMemcpyDeviceToDevice, stream));
+                out.n += r.n;
+            }
+        }
+        HIP_CHECK(hipStreamSynchronize(stream));
+        m_tape_src.clear();
+        m_chunk.release();
+        for (auto& v : m_seg_off) std::vector<long long>().swap(v);
     }
     void multi_m_size(size_t* n_rows, size_t* nnz) const override { *n_rows = multi_m_off.size() - 1; *nnz = multi_m_j.size(); }
     void get_multi_m(long long* row_off, long long* j, void* v) const override {
@@ -2693,7 +2763,8 @@ class GridT : public GridBase {
                     for (size_t b = 0; b < sl.size(); ++b) {
                         const int n = sr[b];
                         walk_m(sl[b], tx_off[n + 1] - tx_off[n], tx.data() + (size_t)3 * tx_off[n], t0 + tx_off[n], rx_off[n + 1] - rx_off[n],
-                               rx.data() + (size_t)3 * rx_off[n], tt_out + rx_off[n], m_walk_both, m_seg_off[n], m_segs[n]);
+                               rx.data() + (size_t)3 * rx_off[n], tt_out + rx_off[n], m_walk_both, m_seg_off[n], m_segs[n],
+                               m_tape_src.empty() ? nullptr : &m_tape_src[n], rx_off[n]);
                     }
                 } else if (!(ttrp || return_rays)) {
                     interp_batch(sl, sr, rx_off, rx.data(), tt_out);
@@ -2894,6 +2965,85 @@ class MultiGrid : public GridBase {
             },
             [](GridBase& g, size_t* nr, size_t* nnz) { g.multi_m_size(nr, nnz); },
             [](GridBase& g, long long* off, long long* idx, void* v) { g.get_multi_m(off, idx, v); });
+    }
+    // The M tape: the sources go to the replicas like sharded_matrix_call sends them, every replica merges its rows on its own device, and
+    // the parts are put together in row order on the first device (rows shifted by the receiver rows in front of the part).
+    void raytrace_multi_tape(int n_src, const int* tx_off, const void* tx_v, const void* t0_v, const int* rx_off, const void* rx_v,
+                             void* tt_out_v, TapeRows& out) override {
+        if (dim != 3) throw Unsupported("compute_M is implemented for 3-D grids only");
+        const auto wall0 = std::chrono::steady_clock::now();
+        timing = Timing();
+        timing.n_sources = n_src;
+        HIP_CHECK(hipSetDevice(rep[0]->device));
+        out.release();
+        out.elem = elem_size;
+        if (n_src <= 0) return;
+        const char* tx = (const char*)tx_v; const char* t0 = (const char*)t0_v; const char* rx = (const char*)rx_v;
+        char* tt_out = (char*)tt_out_v;
+        const int nd = (int)rep.size();
+        std::vector<int> first(nd + 1, 0);
+        {
+            long long before = 0;
+            for (int d = 0; d < nd; ++d) {
+                first[d] = (int)((long long)n_src * before / n_slots);
+                before += rep[d]->n_slots;
+            }
+            first[nd] = n_src;
+        }
+        std::vector<TapeRows> part(nd);
+        std::vector<Timing> pt(nd);
+        std::vector<std::exception_ptr> errs(nd);
+        auto work = [&](int d) {
+            try {
+                const int s0 = first[d], m = first[d + 1] - first[d];
+                if (m <= 0) return;
+                GridBase& g = *rep[d];
+                std::vector<int> to(m + 1), ro(m + 1);
+                for (int q = 0; q <= m; ++q) { to[q] = tx_off[s0 + q] - tx_off[s0]; ro[q] = rx_off[s0 + q] - rx_off[s0]; }
+                std::vector<char> stt(elem_size * (size_t)std::max(ro[m], 1));
+                g.raytrace_multi_tape(m, to.data(), tx + pt_bytes * tx_off[s0], t0 + elem_size * tx_off[s0], ro.data(), rx + pt_bytes * rx_off[s0],
+                                      stt.data(), part[d]);
+                std::memcpy(tt_out + elem_size * rx_off[s0], stt.data(), elem_size * (size_t)ro[m]);
+                pt[d] = g.timing;
+            } catch (...) { errs[d] = std::current_exception(); }
+        };
+        std::vector<std::thread> th;
+        for (int d = 1; d < nd; ++d) th.emplace_back(work, d);
+        work(0);
+        for (auto& t : th) t.join();
+        auto drop_parts = [&] {
+            for (int d = 0; d < nd; ++d) { (void)hipSetDevice(rep[d]->device); part[d].release(); }
+            (void)hipSetDevice(rep[0]->device);
+        };
+        for (auto& e : errs)
+            if (e) { drop_parts(); std::rethrow_exception(e); }
+        HIP_CHECK(hipSetDevice(rep[0]->device));
+        size_t tot = 0;
+        for (const TapeRows& r : part) tot += r.n;
+        try {
+            out.grow(tot, nullptr);
+            for (int d = 0; d < nd; ++d) {
+                const TapeRows& r = part[d];
+                if (r.n == 0) continue;
+                // (device to device across replicas: peer access where the constructor could enable it, staged otherwise)
+                HIP_CHECK(hipMemcpy(out.row + out.n, r.row, r.n * sizeof(int), hipMemcpyDefault));
+                HIP_CHECK(hipMemcpy(out.col + out.n, r.col, r.n * sizeof(int), hipMemcpyDefault));
+                HIP_CHECK(hipMemcpy((char*)out.val + out.n * elem_size, r.val, r.n * elem_size, hipMemcpyDefault));
+                tape_shift_rows(out.row + out.n, r.n, rx_off[first[d]], nullptr);
+                out.n += r.n;
+            }
+            HIP_CHECK(hipDeviceSynchronize());
+        } catch (...) { drop_parts(); throw; }
+        drop_parts();
+        for (int d = 0; d < nd; ++d) {
+            timing.sweep_ms = std::max(timing.sweep_ms, pt[d].sweep_ms);
+            timing.launches += pt[d].launches;
+            timing.node_updates += pt[d].node_updates;
+            timing.evaluated_updates += pt[d].evaluated_updates;
+            timing.iterations = std::max(timing.iterations, pt[d].iterations);
+        }
+        for (int s2 = 0; s2 < n_slots; ++s2) { int l; GridBase& g = of(s2, l); g.get_niter(l, &niter[s2], &niterw[s2]); }
+        timing.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
     }
     void raytrace_multi_l(int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off, const void* rx, void* tt_out,
                           bool with_rays) override {
@@ -3393,6 +3543,115 @@ int ttcr_fsm_raytrace_rm(ttcr_fsm_grid* g, int slot, int n_tx, const void* tx, c
 int ttcr_fsm_raytrace_multi_m(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off,
                               const void* rx, void* tt_out, int with_rays) {
     return guarded_on(g, [&] { g->impl->raytrace_multi_m(n_src, tx_off, tx, t0, rx_off, rx, tt_out, with_rays != 0); });
+}
+// ---- the M tape (fsm_tape_api.h): owns its device memory and stream, independent of the grid it came from
+struct ttcr_fsm_tape {
+    int dtype = TTCR_F32;
+    ttcr_amd::MTapeDev t;
+    std::mutex mu;
+    ~ttcr_fsm_tape() { t.release(); }
+};
+
+int ttcr_fsm_raytrace_multi_tape(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off,
+                                 const void* rx, void* tt_out, ttcr_fsm_tape** tape) {
+    if (!tape) {
+        g_last_error = "null tape output pointer";
+        return TTCR_ERR_VALUE;
+    }
+    *tape = nullptr;
+    if (n_src < 0 || (n_src > 0 && (!tx_off || !tx || !t0 || !rx_off || !rx || !tt_out))) {
+        g_last_error = "raytrace_multi_tape: null array or negative source count";
+        return TTCR_ERR_VALUE;
+    }
+    return guarded_on(g, [&] {
+        GridBase& G = *g->impl;
+        ttcr_amd::TapeRows rows;
+        G.raytrace_multi_tape(n_src, tx_off, tx, t0, rx_off, rx, tt_out, rows);
+        std::unique_ptr<ttcr_fsm_tape> tp(new ttcr_fsm_tape());
+        ttcr_amd::MTapeDev& t = tp->t;
+        tp->dtype = G.dtype;
+        t.device = G.device;
+        t.elem = G.elem_size;
+        t.n_rows = n_src > 0 ? (size_t)rx_off[n_src] : 0;
+        t.nn = G.n_nodes;
+        HIP_CHECK(hipSetDevice(t.device));
+        HIP_CHECK(hipStreamCreateWithFlags(&t.stream, hipStreamNonBlocking));
+        if (G.dtype == TTCR_F32) ttcr_amd::tape_finish<float>(t, rows);
+        else ttcr_amd::tape_finish<double>(t, rows);
+        *tape = tp.release();
+    });
+}
+int ttcr_fsm_tape_size(const ttcr_fsm_tape* t, size_t* n_rows, size_t* n_cols, size_t* nnz) {
+    if (!t || !n_rows || !n_cols || !nnz) {
+        g_last_error = "null tape or output pointer";
+        return TTCR_ERR_VALUE;
+    }
+    *n_rows = t->t.n_rows;
+    *n_cols = t->t.nn;
+    *nnz = t->t.nnz;
+    return TTCR_OK;
+}
+int ttcr_fsm_tape_bytes(const ttcr_fsm_tape* t, size_t* bytes) {
+    if (!t || !bytes) {
+        g_last_error = "null tape or output pointer";
+        return TTCR_ERR_VALUE;
+    }
+    *bytes = t->t.bytes();
+    return TTCR_OK;
+}
+int ttcr_fsm_tape_device(const ttcr_fsm_tape* t, int* device) {
+    if (!t || !device) {
+        g_last_error = "null tape or output pointer";
+        return TTCR_ERR_VALUE;
+    }
+    *device = t->t.device;
+    return TTCR_OK;
+}
+int ttcr_fsm_tape_get_csr(const ttcr_fsm_tape* t, long long* row_off, long long* j, void* v) {
+    if (!t || !row_off || (t->t.nnz > 0 && (!j || !v))) {
+        g_last_error = "null tape or output pointer";
+        return TTCR_ERR_VALUE;
+    }
+    ttcr_fsm_tape* tm = const_cast<ttcr_fsm_tape*>(t);
+    std::lock_guard<std::mutex> lock(tm->mu);
+    return guarded([&] {
+        const ttcr_amd::MTapeDev& d = t->t;
+        HIP_CHECK(hipSetDevice(d.device));
+        std::vector<int> col(d.nnz);
+        HIP_CHECK(hipMemcpyAsync(row_off, d.row_off, (d.n_rows + 1) * sizeof(long long), hipMemcpyDeviceToHost, d.stream));
+        if (d.nnz > 0) {
+            HIP_CHECK(hipMemcpyAsync(col.data(), d.col, d.nnz * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+            HIP_CHECK(hipMemcpyAsync(v, d.val, d.nnz * d.elem, hipMemcpyDeviceToHost, d.stream));
+        }
+        HIP_CHECK(hipStreamSynchronize(d.stream));
+        for (size_t e = 0; e < d.nnz; ++e) j[e] = col[e];
+    });
+}
+int ttcr_fsm_tape_vjp(const ttcr_fsm_tape* t, const void* w, int w_on_device, void* grad, int grad_on_device) {
+    if (!t || (!w && t->t.n_rows > 0) || !grad) {
+        g_last_error = "null tape, w or grad";
+        return TTCR_ERR_VALUE;
+    }
+    ttcr_fsm_tape* tm = const_cast<ttcr_fsm_tape*>(t);
+    std::lock_guard<std::mutex> lock(tm->mu);
+    return guarded([&] {
+        const ttcr_amd::MTapeDev& d = t->t;
+        HIP_CHECK(hipSetDevice(d.device));
+        const void* dw = w;
+        void* dg = grad_on_device ? grad : d.g_tmp;
+        if (!w_on_device) {
+            if (d.n_rows > 0) HIP_CHECK(hipMemcpyAsync(d.w_tmp, w, d.n_rows * d.elem, hipMemcpyHostToDevice, d.stream));
+            dw = d.w_tmp;
+        }
+        if (tm->dtype == TTCR_F32) ttcr_amd::tape_vjp<float>(d, (const float*)dw, (float*)dg);
+        else ttcr_amd::tape_vjp<double>(d, (const double*)dw, (double*)dg);
+        if (!grad_on_device) HIP_CHECK(hipMemcpyAsync(grad, d.g_tmp, d.nn * d.elem, hipMemcpyDeviceToHost, d.stream));
+        HIP_CHECK(hipStreamSynchronize(d.stream));
+    });
+}
+int ttcr_fsm_tape_free(ttcr_fsm_tape* t) {
+    if (!t) return TTCR_OK;
+    return guarded([&] { delete t; });
 }
 int ttcr_fsm_raytrace_multi_l(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off,
                               const void* rx, void* tt_out, int with_rays) {

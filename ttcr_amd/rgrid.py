@@ -336,6 +336,41 @@ class _GridBase:
         tms = [np.asarray(e[1], dtype=np.float64) for e in events]
         return pts, tms, [rcv[e[2], :] for e in events], [e[2] for e in events]
 
+    def raytrace_tape(self, source, rcv, slowness=None, aggregate_src=False):
+        """raytrace_tape(source, rcv, slowness=None, aggregate_src=False) -> (tt, tape)
+
+        Traveltimes of raytrace(..., compute_M=True) (same source / receiver handling, bit-equal tt) and an MTape that keeps the
+        matrix M of that call (d tt / d node velocity, the reference's ray-frozen derivative) on the device: tape.vjp(w) = M^T w without
+        a host copy of M, tape.to_csr() = the stacked rows of compute_M's matrices.  3-D node grids only (NotImplementedError
+        otherwise, like compute_M)."""
+        source = np.asarray(source)
+        rcv = np.asarray(rcv)
+        if source.ndim != 2 or rcv.ndim != 2:
+            raise ValueError('source and rcv should be 2D arrays')
+        if self.cell_slowness:
+            raise NotImplementedError('compute_M not defined for grids with slowness defined for cells')
+        vTx, vt0, vRx, iRx = self._split_sources(source, rcv, aggregate_src)
+        if slowness is not None:
+            self.set_slowness(slowness)
+        dt = self._dtype
+        nd = self._ndim
+        tx = np.ascontiguousarray(np.vstack(vTx), dtype=dt).reshape(-1, nd)
+        t0 = np.ascontiguousarray(np.concatenate(vt0), dtype=dt)
+        rx = np.ascontiguousarray(np.vstack(vRx), dtype=dt).reshape(-1, nd)
+        tx_off = np.zeros(len(vTx) + 1, dtype=np.int32)
+        rx_off = np.zeros(len(vTx) + 1, dtype=np.int32)
+        tx_off[1:] = np.cumsum([len(t) for t in vTx])
+        rx_off[1:] = np.cumsum([len(r) for r in vRx])
+        out = np.empty(max(rx.shape[0], 1), dtype=dt)
+        h = C.c_void_p()
+        _lib.check(self._lib.ttcr_fsm_raytrace_multi_tape(self._h, len(vTx), _ptr(tx_off), _ptr(tx), _ptr(t0), _ptr(rx_off), _ptr(rx),
+                                                          _ptr(out), C.byref(h)))
+        tape = MTape(self._lib, h, dt, np.concatenate(iRx).astype(np.int64), rcv.shape[0])
+        tt = np.zeros((rcv.shape[0],), dtype=dt)
+        for n in range(len(vTx)):
+            tt[iRx[n]] = out[rx_off[n]:rx_off[n + 1]]
+        return tt, tape
+
     def _run(self, vTx, vt0, vRx, iRx, n_rcv, thread_no, return_rays=False):
         dt = self._dtype
         nd = self._ndim
@@ -373,6 +408,94 @@ class _GridBase:
                 a, b = off[rx_off[n] + k], off[rx_off[n] + k + 1]
                 rays[row] = np.array(pts[a:b], dtype=np.float64)
         return tt, rays
+
+
+class MTape:
+    """The matrix M of a raytrace_tape call kept on the device (ttcr_fsm_raytrace_multi_tape, include/ttcr_amd.h).  Its rows are the
+    call's (event, receiver) rows: events in the order raytrace takes them, each event's receivers in rcv order -- the rows of
+    scipy.sparse.vstack(M_list) for the M_list that raytrace(..., compute_M=True) returns.  Columns are nodes (x fastest).  M is the
+    reference's ray-frozen derivative of traveltime with respect to node velocity, not the exact derivative of the returned tt.
+    The tape does not depend on the grid any more: later calls, set_slowness and deleting the grid leave it as it is."""
+
+    def __init__(self, lib, handle, dtype, rows, n_data):
+        self._lib = lib
+        self._h = handle
+        self.dtype = np.dtype(dtype)
+        self._rows = rows          # data row (index into rcv) of every tape row
+        self.n_data = int(n_data)
+        nr, nc, nnz = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        _lib.check(lib.ttcr_fsm_tape_size(handle, C.byref(nr), C.byref(nc), C.byref(nnz)))
+        self.n_rows, self.n_cols, self.nnz = nr.value, nc.value, nnz.value
+        d, b = C.c_int(0), C.c_size_t(0)
+        _lib.check(lib.ttcr_fsm_tape_device(handle, C.byref(d)))
+        _lib.check(lib.ttcr_fsm_tape_bytes(handle, C.byref(b)))
+        self.device, self.nbytes = d.value, b.value
+        self._rows_dev = None
+
+    def _handle(self):
+        if not self._h:
+            raise ValueError('the tape has been freed')
+        return self._h
+
+    @property
+    def shape(self):
+        return (self.n_rows, self.n_cols)
+
+    def to_csr(self):
+        """The rows of the tape as a scipy CSR matrix (n_rows x n_nodes, float64 like compute_M's matrices)."""
+        import scipy.sparse as sp
+
+        off = np.zeros(self.n_rows + 1, dtype=np.int64)
+        jj = np.empty(max(self.nnz, 1), dtype=np.int64)
+        vv = np.empty(max(self.nnz, 1), dtype=self.dtype)
+        _lib.check(self._lib.ttcr_fsm_tape_get_csr(self._handle(), _ptr(off), _ptr(jj), _ptr(vv)))
+        return sp.csr_matrix((vv[:self.nnz].astype(np.float64), jj[:self.nnz], off), shape=self.shape)
+
+    def vjp(self, w):
+        """M^T w: w holds one value per data row of the raytrace_tape call (rcv order); the result holds one value per node, in M's
+        column order (x fastest), in the grid dtype.  A torch tensor in gives a torch tensor out on the same device; a tensor on the
+        tape's device is used in place (torch's current stream is synchronised first, the result is ready when the call returns)."""
+        if not self._h:
+            raise ValueError('the tape has been freed')
+        if type(w).__module__.startswith('torch'):
+            return self._vjp_torch(w)
+        w = np.asarray(w)
+        if w.ndim != 1 or w.shape[0] != self.n_data:
+            raise ValueError('w should hold %d values (one per data row), got shape %s' % (self.n_data, w.shape))
+        wt = np.ascontiguousarray(w[self._rows], dtype=self.dtype)
+        g = np.empty(max(self.n_cols, 1), dtype=self.dtype)
+        _lib.check(self._lib.ttcr_fsm_tape_vjp(self._h, _ptr(wt), 0, _ptr(g), 0))
+        return g[:self.n_cols]
+
+    def _vjp_torch(self, w):
+        import torch
+
+        if w.dim() != 1 or w.shape[0] != self.n_data:
+            raise ValueError('w should hold %d values (one per data row), got shape %s' % (self.n_data, tuple(w.shape)))
+        tdt = torch.float32 if self.dtype == np.float32 else torch.float64
+        if w.device.type != 'cuda':
+            g = self.vjp(w.detach().numpy())
+            return torch.from_numpy(g).to(w.device)
+        dev = torch.device('cuda', self.device)
+        if self._rows_dev is None:
+            self._rows_dev = torch.as_tensor(self._rows, device=dev)
+        wt = w.detach().to(device=dev, dtype=tdt).index_select(0, self._rows_dev).contiguous()
+        g = torch.empty(max(self.n_cols, 1), dtype=tdt, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        _lib.check(self._lib.ttcr_fsm_tape_vjp(self._h, C.c_void_p(wt.data_ptr()), 1, C.c_void_p(g.data_ptr()), 1))
+        return g[:self.n_cols].to(w.device)
+
+    def free(self):
+        """Release the device memory now (also done when the tape is collected)."""
+        if self._lib is not None and self._h:
+            self._lib.ttcr_fsm_tape_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 # ======================================================================================= 3-D
