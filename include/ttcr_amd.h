@@ -357,6 +357,46 @@ int ttcr_fsm_tape_get_csr(const ttcr_fsm_tape* t, long long* row_off, long long*
 int ttcr_fsm_tape_vjp(const ttcr_fsm_tape* t, const void* w, int w_on_device, void* grad, int grad_on_device);
 int ttcr_fsm_tape_free(ttcr_fsm_tape* t);
 
+/* The field tape: the exact discrete adjoint of the first-order 3-D node solver (adjoint-state gradient).  No reference counterpart.
+ * ttcr_fsm_raytrace_multi_adjoint: sources and receivers laid out like ttcr_fsm_raytrace_multi; the same batched solves; tt_out holds the
+ * INTERPOLATED receiver traveltimes (Grid3Drn::getTraveltime, ttcr/Grid3Drn.h:794-930), bit-equal to ttcr_fsm_raytrace_multi on a grid with
+ * tt_from_rp = 0 whatever this grid's setting (forced for the call, as the l_data overloads force it).  *tape receives a new tape that
+ * holds every event's traveltime field (device-to-device copies), one copy of the node slowness, per event the nodes the source
+ * initialisation froze with their distances, and per receiver row the interpolation stencil with its weights.
+ * 3-D node grids without the WENO stage only (TTCR_ERR_UNSUPPORTED otherwise, the message names the reason).  On a multi-device grid the
+ * fields are copied to the first listed device and the adjoint runs there.  A tape owns its device memory and stream: it stays valid
+ * after later calls on the grid, after ttcr_fsm_set_slowness and after ttcr_fsm_destroy of the grid, until ttcr_fsm_adjoint_free (NULL:
+ * no-op).  If the memory cannot be allocated the call fails with TTCR_ERR_DEVICE and a message that names the byte count.  Calls on one
+ * tape from several threads are serialised.
+ * ttcr_fsm_adjoint_size: events, receiver rows and nodes.  ttcr_fsm_adjoint_bytes: device memory the tape holds, about
+ *   n_events n_nodes (5 elem + 2) bytes (fields, D, seeds, two lam buffers; two byte masks) plus the small lists.
+ * ttcr_fsm_adjoint_device: the HIP device the tape lives on.  ttcr_fsm_adjoint_get_field: host copy of the field of one event, n_nodes
+ *   values of the grid dtype, x fastest (node (k * nny + j) * nnx + i).
+ * ttcr_fsm_adjoint_vjp: grad = d loss / d node slowness (n_nodes values, x fastest) for the cotangents w (one value per receiver row, may
+ *   be NULL) and field_cot (n_events * n_nodes values, one per node of every event's field, may be NULL; not both).  With T the field, s
+ *   the slowness and F the frozen nodes of an event: a node m outside F couples, along each axis, to the smaller of its two neighbours
+ *   (outside the grid: +inf; tie: the lower index) if that is < T[m]; D_m = sum over those axes, x, y, z, of (T[m] - a_axis).  Seeds
+ *   g = field_cot + sum over the receiver rows, in row order, of w[row] * weight on the nodes of the row's stencil;
+ *   lam[j] = g[j] + sum over the neighbours n of j (x-, x+, y-, y+, z-, z+) that are outside F and couple to j of
+ *   fl(fl(lam[n] * (T[n] - T[j])) / D_n);  grad_e[m] = fl(fl(lam[m] * fl(dx * fl(s[m] * dx))) / D_m), or fl(d_m * lam[m]) for m in F;
+ *   grad = sum of grad_e over the events, ascending, from +0.  Everything in the grid dtype, without fused multiply-add and without
+ *   floating-point atomics: lam is the unique fixed point of the gather formula, so the bits depend neither on the schedule nor on
+ *   n_slots nor on the device list.  schedule: 0 the tiled relaxation (tiles staged in LDS), 1 the global Jacobi baseline (bit-equal,
+ *   slower); anything else is TTCR_ERR_VALUE.  *passes (may be NULL): relaxation passes launched.  *_on_device != 0: a device pointer on
+ *   the tape's device, else host memory.  The call returns with grad written; the tape runs on its own stream: the caller makes sure
+ *   device-resident inputs are complete before the call.
+ * Argument errors (a NULL tape or pointer, w and field_cot both NULL) return TTCR_ERR_VALUE before any device call. */
+typedef struct ttcr_fsm_adjoint ttcr_fsm_adjoint; /* opaque */
+int ttcr_fsm_raytrace_multi_adjoint(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off,
+                                    const void* rx, void* tt_out, ttcr_fsm_adjoint** tape);
+int ttcr_fsm_adjoint_size(const ttcr_fsm_adjoint* t, size_t* n_events, size_t* n_rows, size_t* n_nodes);
+int ttcr_fsm_adjoint_bytes(const ttcr_fsm_adjoint* t, size_t* bytes);
+int ttcr_fsm_adjoint_device(const ttcr_fsm_adjoint* t, int* device);
+int ttcr_fsm_adjoint_get_field(const ttcr_fsm_adjoint* t, size_t event, void* out);
+int ttcr_fsm_adjoint_vjp(const ttcr_fsm_adjoint* t, const void* w, int w_on_device, const void* field_cot, int fc_on_device, void* grad,
+                         int grad_on_device, int schedule, int* passes);
+int ttcr_fsm_adjoint_free(ttcr_fsm_adjoint* t);
+
 /* Replaces: Grid2D::raytrace(Tx, t0, Rx, traveltimes, l_data, threadNo) (ttcr/Grid2D.h:616-640) and the overload with r_data
  * AND l_data (:583-614) -> Grid2Drn::getRaypath(Tx, t0, Rx, [r_data,] l_data, tt, threadNo) (ttcr/Grid2Drn.h:1852-2190): what
  * `compute_L=True` of the Python layer reaches for 2-D grids with cell slowness (src/ttcrpy/rgrid.pyx:3889-3893, :4060-4143).

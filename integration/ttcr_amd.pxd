@@ -67,6 +67,18 @@ cdef extern from "ttcr_amd.h" nogil:
                                   const void* rx, void* tt_out, int with_rays)
     int ttcr_fsm_multi_m_size(const ttcr_fsm_grid* g, size_t* n_rows, size_t* nnz)
     int ttcr_fsm_get_multi_m(const ttcr_fsm_grid* g, long long* row_off, long long* j, void* v)
+    # the field tape: exact discrete adjoint of the first-order 3-D node solver (adjoint-state gradient)
+    ctypedef struct ttcr_fsm_adjoint:
+        pass
+    int ttcr_fsm_raytrace_multi_adjoint(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0,
+                                        const int* rx_off, const void* rx, void* tt_out, ttcr_fsm_adjoint** tape)
+    int ttcr_fsm_adjoint_size(const ttcr_fsm_adjoint* t, size_t* n_events, size_t* n_rows, size_t* n_nodes)
+    int ttcr_fsm_adjoint_bytes(const ttcr_fsm_adjoint* t, size_t* bytes)
+    int ttcr_fsm_adjoint_device(const ttcr_fsm_adjoint* t, int* device)
+    int ttcr_fsm_adjoint_get_field(const ttcr_fsm_adjoint* t, size_t event, void* out)
+    int ttcr_fsm_adjoint_vjp(const ttcr_fsm_adjoint* t, const void* w, int w_on_device, const void* field_cot, int fc_on_device,
+                             void* grad, int grad_on_device, int schedule, int* passes)
+    int ttcr_fsm_adjoint_free(ttcr_fsm_adjoint* t)
     int ttcr_fsm_slot_m_size(const ttcr_fsm_grid* g, int slot, size_t* n_rows, size_t* nnz)
     int ttcr_fsm_get_slot_m(const ttcr_fsm_grid* g, int slot, long long* row_off, long long* j, void* v)
     int ttcr_fsm_raytrace_l(ttcr_fsm_grid* g, int slot, int n_tx, const void* tx, const void* t0, int n_rx, const void* rx,

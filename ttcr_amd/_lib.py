@@ -76,6 +76,13 @@ SYMBOLS = {
     "ttcr_fsm_tape_get_csr": (_I, [_P, _P, _P, _P]),
     "ttcr_fsm_tape_vjp": (_I, [_P, _P, _I, _P, _I]),
     "ttcr_fsm_tape_free": (_I, [_P]),
+    "ttcr_fsm_raytrace_multi_adjoint": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, C.POINTER(_P)]),
+    "ttcr_fsm_adjoint_size": (_I, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "ttcr_fsm_adjoint_bytes": (_I, [_P, C.POINTER(C.c_size_t)]),
+    "ttcr_fsm_adjoint_device": (_I, [_P, C.POINTER(_I)]),
+    "ttcr_fsm_adjoint_get_field": (_I, [_P, C.c_size_t, _P]),
+    "ttcr_fsm_adjoint_vjp": (_I, [_P, _P, _I, _P, _I, _P, _I, _I, C.POINTER(_I)]),
+    "ttcr_fsm_adjoint_free": (_I, [_P]),
     "ttcr_fsm_raytrace_multi_l": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I]),
     "ttcr_fsm_multi_l_size": (_I, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "ttcr_fsm_get_multi_l": (_I, [_P, _P, _P, _P]),

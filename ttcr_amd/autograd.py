@@ -9,11 +9,20 @@ raytrace(..., compute_M=True)[0].  The backward is M^T g (MTape.vjp, on the devi
 reference's matrix of d tt / d velocity with the rays held fixed: the gradient of the ray-frozen (linearised) problem, not the exact
 derivative of the returned tt.  A model in slowness composes in torch: raytrace(grid, 1 / s, ...).
 
+    tt = ttcr_amd.autograd.raytrace_adjoint(grid, velocity, source, rcv, aggregate_src=False, return_fields=False)
+
+is the same operator with the EXACT derivative: the forward runs grid.raytrace_adjoint (interpolated receiver traveltimes, as a grid
+with tt_from_rp=0 returns them; 3-D node grids with weno=0), the backward is the adjoint-state gradient FieldTape.vjp -- the derivative
+of the returned tt through the solver's own first-order update -- times d slowness / d velocity = -1 / velocity**2, in velocity's layout.
+With return_fields=True it returns (tt, fields), fields the (n_events, nx, ny, nz) traveltime fields, differentiable too: a loss on the
+grid traveltimes has a gradient.
+
 torch is imported when this module is used, never by `import ttcr_amd`.
 """
 import numpy as np
 
 _Fn = None
+_AdjFn = None
 
 
 def _function():
@@ -53,3 +62,53 @@ def raytrace(grid, velocity, source, rcv, aggregate_src=False):
     source = np.asarray(source)
     rcv = np.asarray(rcv)
     return _function().apply(velocity, grid, source, rcv, bool(aggregate_src))
+
+
+def _adjoint_function():
+    global _AdjFn
+    if _AdjFn is not None:
+        return _AdjFn
+    import torch
+
+    class RaytraceAdjointFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, velocity, grid, source, rcv, aggregate_src, return_fields):
+            grid.set_velocity(velocity.detach().cpu().numpy())
+            tt, tape = grid.raytrace_adjoint(source, rcv, aggregate_src=aggregate_src)
+            nx, ny, nz = grid.x.size, grid.y.size, grid.z.size
+            ctx.tape = tape
+            ctx.layout = (tuple(velocity.shape), (nx, ny, nz))
+            ctx.save_for_backward(velocity)
+            out = torch.from_numpy(tt).to(velocity.device)
+            if not return_fields:
+                return out
+            f = np.stack([tape.field(e).reshape(nz, ny, nx).transpose(2, 1, 0) for e in range(tape.n_events)])
+            return out, torch.from_numpy(np.ascontiguousarray(f)).to(velocity.device)
+
+        @staticmethod
+        def backward(ctx, g, gf=None):
+            shape, (nx, ny, nz) = ctx.layout
+            (velocity,) = ctx.saved_tensors
+            fc = None
+            if gf is not None:   # (n_events, nx, ny, nz) in C order -> node order x fastest
+                fc = gf.permute(0, 3, 2, 1).contiguous().reshape(gf.shape[0], -1)
+            gn = ctx.tape.vjp(g.contiguous(), fc)
+            # node order x fastest -> (nx, ny, nz) in C order -> velocity's layout; d slowness / d velocity = -1 / velocity^2
+            gs = gn.reshape(nz, ny, nx).permute(2, 1, 0).contiguous().reshape(shape).to(velocity.dtype)
+            return -gs / (velocity * velocity), None, None, None, None, None
+
+    _AdjFn = RaytraceAdjointFn
+    return _AdjFn
+
+
+def raytrace_adjoint(grid, velocity, source, rcv, aggregate_src=False, return_fields=False):
+    """Traveltimes at `rcv` (interpolated, as with tt_from_rp=0) for the model `velocity` (torch tensor, node grid layout), differentiable
+    with respect to velocity by the adjoint-state method: backward = -(FieldTape.vjp) / velocity**2, the exact derivative of the returned
+    values.  return_fields=True: (tt, fields) with the (n_events, nx, ny, nz) traveltime fields, differentiable as well."""
+    if grid._ndim != 3:
+        raise NotImplementedError('the adjoint-state gradient is implemented for 3-D grids only')
+    if grid.cell_slowness:
+        raise NotImplementedError('the adjoint-state gradient is not implemented for grids with slowness defined for cells')
+    source = np.asarray(source)
+    rcv = np.asarray(rcv)
+    return _adjoint_function().apply(velocity, grid, source, rcv, bool(aggregate_src), bool(return_fields))

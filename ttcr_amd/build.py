@@ -8,6 +8,7 @@ Two translation units, compiled to objects under ttcr_amd/csrc/_obj and linked:
   fsm_capi.hip    the C ABI, the host side and every kernel but one
   fsm_fast.hip    the sweep kernels with tolerance-grade arithmetic (option "arith" = 1)
   fsm_tape.hip    the M tape: compute_M's rows merged on the device, node index, M^T w (hipCUB sorts)
+  fsm_adjoint.hip the field tape: discrete adjoint of the first-order 3-D update (coupling, seeds, relaxation, gradient)
 """
 import os
 import shutil
@@ -21,9 +22,10 @@ INC = os.path.join("..", "..", "include", "ttcr_amd.h")
 # source -> (extra flags, files it is compiled from)
 UNITS = {
     "fsm_capi.hip": ([], ["fsm_capi.hip", "fsm_kernels.h", "fsm_fast_api.h", "fsm_march_levels.inc", "fsm_fast.hip", "fsm_tape_api.h",
-                          "fsm_tape.hip", INC]),
+                          "fsm_tape.hip", "fsm_adjoint_api.h", "fsm_adjoint.hip", INC]),
     "fsm_fast.hip": ([], ["fsm_fast.hip", "fsm_fast_api.h", "fsm_kernels.h", "fsm_march_levels.inc"]),
     "fsm_tape.hip": ([], ["fsm_tape.hip", "fsm_tape_api.h"]),
+    "fsm_adjoint.hip": ([], ["fsm_adjoint.hip", "fsm_adjoint_api.h"]),
 }
 SOURCES = list(UNITS)
 DEPS = sorted({d for _, ds in UNITS.values() for d in ds})

@@ -1,0 +1,477 @@
+// ttcr_amd/csrc/fsm_adjoint.hip -- translation unit of the field tape's kernels (coupling, seeds, relaxation, gradient); see
+// fsm_adjoint_api.h and DESIGN.md 6b.  Compiled with -ffp-contract=off like every other unit: each product, difference, quotient and sum
+// below is rounded on its own, in the order the definition writes them.
+#include "fsm_adjoint_api.h"
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <limits>
+#include <numeric>
+#include <sstream>
+
+#define ADJ_CHECK(expr)                                                                                           \
+    do {                                                                                                          \
+        hipError_t _e = (expr);                                                                                   \
+        if (_e != hipSuccess) {                                                                                   \
+            std::ostringstream _m;                                                                                \
+            _m << "HIP error " << hipGetErrorString(_e) << " at " << __FILE__ << ":" << __LINE__ << " (" #expr ")"; \
+            throw AdjDeviceError(_m.str());                                                                       \
+        }                                                                                                         \
+    } while (0)
+
+namespace ttcr_amd {
+
+namespace {
+
+constexpr int ADJ_THREADS = 256;
+constexpr int ADJ_RING = 8;     // rows of the flag ring
+constexpr int ADJ_CHECK_EVERY = 4;   // passes between two reads of the flags by the host (extra passes at the fixed point change nothing)
+// interior edge of a relaxation tile: with its one-node halo, lam, T and D of a tile take 3 * (edge + 2)^3 * sizeof(T) bytes of LDS --
+// 48 KiB (fp32, 16^3) and 40.5 KiB (fp64, 12^3), so three workgroups of 256 threads fit the 160 KiB of a CU
+template <typename T> struct AdjTile;
+template <> struct AdjTile<float> { static constexpr int edge = 14; };
+template <> struct AdjTile<double> { static constexpr int edge = 10; };
+
+template <typename T>
+struct AdjGeom {
+    int nnx, nny, nnz;
+    size_t nn;
+    T dx;
+};
+
+unsigned blocks_for(size_t n, unsigned b = ADJ_THREADS) { return (unsigned)std::max<size_t>(1, (n + b - 1) / b); }
+
+__device__ __forceinline__ bool same_bits(float a, float b) { return __float_as_uint(a) == __float_as_uint(b); }
+__device__ __forceinline__ bool same_bits(double a, double b) { return __double_as_longlong(a) == __double_as_longlong(b); }
+
+template <typename T>
+__global__ void adj_copy_field_kernel(const T* __restrict__ src, int ts, T* __restrict__ dst, size_t n) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = src[i * ts];
+}
+
+template <typename T>
+__global__ void adj_mark_frozen_kernel(const long long* __restrict__ key, const T* __restrict__ d, size_t n, unsigned char* __restrict__ frozen,
+                                       T* __restrict__ D) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    frozen[key[i]] = 1;
+    D[key[i]] = d[i];
+}
+
+// Coupling pass, one thread per node, events in blockIdx.y.  For node m of field F (T = F[m]):
+//   own side: per axis the smaller neighbour (outside the grid +inf, on a tie the lower index), active iff it is < T; D = sum of (T - a)
+//             over the active axes in axis order (frozen nodes keep the d that adj_mark_frozen_kernel wrote);
+//   inflow:   bit 2 * axis + side is set iff that neighbour n is not frozen, has m as its smaller neighbour along the axis and F[m] < F[n].
+// A node that is not frozen and has no active axis cannot occur in a solved field: *err is raised.
+template <typename T>
+__global__ void adj_couple_kernel(const T* __restrict__ fields, AdjGeom<T> g, const unsigned char* __restrict__ frozen,
+                                  unsigned char* __restrict__ inmask, T* __restrict__ D, int* __restrict__ err) {
+    const size_t m = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (m >= g.nn) return;
+    const size_t base = (size_t)blockIdx.y * g.nn;
+    const T* F = fields + base;
+    const unsigned char* fz = frozen + base;
+    const T inf = std::numeric_limits<T>::infinity();
+    const int pos[3] = {(int)(m % g.nnx), (int)((m / g.nnx) % g.nny), (int)(m / ((size_t)g.nnx * g.nny))};
+    const int ext[3] = {g.nnx, g.nny, g.nnz};
+    const size_t st[3] = {1, (size_t)g.nnx, (size_t)g.nnx * g.nny};
+    const T t = F[m];
+    const bool self_frozen = fz[m] != 0;
+    unsigned in = 0;
+    T Dm = 0;
+    bool any = false;
+    for (int ax = 0; ax < 3; ++ax) {
+        const T lo = pos[ax] > 0 ? F[m - st[ax]] : inf;
+        const T hi = pos[ax] < ext[ax] - 1 ? F[m + st[ax]] : inf;
+        if (!self_frozen) {
+            const T a = hi < lo ? hi : lo;
+            if (a < t) {
+                const T d = t - a;
+                Dm = any ? Dm + d : d;
+                any = true;
+            }
+        }
+        if (pos[ax] > 0 && !fz[m - st[ax]]) {   // m is the upper neighbour of n = m - st: chosen iff strictly smaller than n's lower one
+            const T other = pos[ax] > 1 ? F[m - 2 * st[ax]] : inf;
+            if (t < other && t < lo) in |= 1u << (2 * ax);
+        }
+        if (pos[ax] < ext[ax] - 1 && !fz[m + st[ax]]) {   // m is the lower neighbour of n = m + st: chosen unless n's upper one is smaller
+            const T other = pos[ax] < ext[ax] - 2 ? F[m + 2 * st[ax]] : inf;
+            if (!(other < t) && t < hi) in |= 1u << (2 * ax + 1);
+        }
+    }
+    inmask[base + m] = (unsigned char)in;
+    if (!self_frozen) {
+        D[base + m] = Dm;
+        if (!any) atomicOr(err, 1);
+    }
+}
+
+// g = field cotangent (or +0)
+template <typename T>
+__global__ void adj_seed_fill_kernel(const T* __restrict__ fc, T* __restrict__ g, size_t n) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) g[i] = fc ? fc[i] : (T)0;
+}
+
+// receiver part: the entries are sorted by (event, node) and keep row order, then stencil order, within a node; the first entry of a node
+// adds the whole run, left to right -- the bits of one serial chain over the rows of the event
+template <typename T>
+__global__ void adj_seed_rows_kernel(const long long* __restrict__ key, const int* __restrict__ row, const T* __restrict__ wt, size_t n,
+                                     const T* __restrict__ w, T* __restrict__ g) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long long k = key[i];
+    if (i > 0 && key[i - 1] == k) return;
+    T a = g[k];
+    for (size_t r = i; r < n && key[r] == k; ++r) a = a + w[row[r]] * wt[r];
+    g[k] = a;
+}
+
+// lam[j] = g[j] + sum over the flagged neighbours, order x-, x+, y-, y+, z-, z+, of fl(fl(lam[n] * (T[n] - T[j])) / D[n])
+#define ADJ_TERM(bit, off)                                              \
+    if (in & (1u << (bit))) acc = acc + (L[(off)] * (F[(off)] - tj)) / Dn[(off)];
+
+// Global Jacobi pass (the correctness baseline): out = gather(in) for every node of every event that still changed in the previous pass.
+template <typename T>
+__global__ void adj_jacobi_kernel(const T* __restrict__ fields, const T* __restrict__ D, const unsigned char* __restrict__ inmask,
+                                  const T* __restrict__ g, const T* __restrict__ lam_in, T* __restrict__ lam_out, AdjGeom<T> geo,
+                                  const int* __restrict__ prev, int* __restrict__ cur) {
+    const int e = blockIdx.y;
+    if (prev && prev[e] == 0) return;   // (both buffers of the event hold the fixed point already)
+    const size_t m = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    int changed = 0;
+    if (m < geo.nn) {
+        const size_t idx = (size_t)e * geo.nn + m;
+        const long long sy = geo.nnx, sz = (long long)geo.nnx * geo.nny;
+        const T* L = lam_in + idx;
+        const T* F = fields + idx;
+        const T* Dn = D + idx;
+        const unsigned in = inmask[idx];
+        const T tj = F[0];
+        T acc = g[idx];
+        ADJ_TERM(0, -1) ADJ_TERM(1, 1) ADJ_TERM(2, -sy) ADJ_TERM(3, sy) ADJ_TERM(4, -sz) ADJ_TERM(5, sz)
+        changed = !same_bits(acc, L[0]);
+        lam_out[idx] = acc;
+    }
+    if (__syncthreads_or(changed) && threadIdx.x == 0) cur[e] = 1;
+}
+
+// Tiled relaxation: one workgroup per tile and event.  lam, T and D of the tile and its one-node halo are staged in LDS, the interior is
+// relaxed there (Jacobi steps between barriers) until no value of it changes, then written back in place.  A tile runs in pass p > 0 only
+// if one of its six face neighbours changed in pass p - 1 or later (stamps).  Tiles of one pass may read a neighbour's values of this pass
+// or of the previous one: both are intermediate values of the same relaxation, the fixed point is the same, and a pass in which no tile
+// changed a bit has read final values everywhere.
+template <typename T, int TI>
+__global__ __launch_bounds__(ADJ_THREADS) void adj_tiled_kernel(const T* __restrict__ fields, const T* __restrict__ D,
+                                                                 const unsigned char* __restrict__ inmask, const T* __restrict__ g,
+                                                                 T* lam, AdjGeom<T> geo, int ntx, int nty, int ntz, int* stamps, int pass,
+                                                                 int* __restrict__ cur) {
+    constexpr int TH = TI + 2, NH = TH * TH * TH, NI = TI * TI * TI, NPT = (NI + ADJ_THREADS - 1) / ADJ_THREADS;
+    __shared__ T sL[NH], sF[NH], sD[NH];
+    const int e = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
+    const int tx = tile % ntx, ty = (tile / ntx) % nty, tz = tile / (ntx * nty);
+    int* st = stamps + (size_t)e * ntx * nty * ntz;
+    if (pass > 0) {
+        const int since = pass - 1;
+        bool run = false;
+        if (tx > 0) run |= st[tile - 1] >= since;
+        if (tx < ntx - 1) run |= st[tile + 1] >= since;
+        if (ty > 0) run |= st[tile - ntx] >= since;
+        if (ty < nty - 1) run |= st[tile + ntx] >= since;
+        if (tz > 0) run |= st[tile - ntx * nty] >= since;
+        if (tz < ntz - 1) run |= st[tile + ntx * nty] >= since;
+        if (!run) return;
+    }
+    const size_t base = (size_t)e * geo.nn;
+    const int x0 = tx * TI - 1, y0 = ty * TI - 1, z0 = tz * TI - 1;
+    for (int h = tid; h < NH; h += ADJ_THREADS) {
+        const int x = x0 + h % TH, y = y0 + (h / TH) % TH, z = z0 + h / (TH * TH);
+        const bool inside = x >= 0 && x < geo.nnx && y >= 0 && y < geo.nny && z >= 0 && z < geo.nnz;
+        const size_t idx = base + ((size_t)(inside ? z : 0) * geo.nny + (inside ? y : 0)) * geo.nnx + (inside ? x : 0);
+        sL[h] = inside ? lam[idx] : (T)0;
+        sF[h] = inside ? fields[idx] : (T)0;
+        sD[h] = inside ? D[idx] : (T)1;
+    }
+    // the interior nodes of this thread: LDS index, seed, inflow mask (0 for nodes outside the grid: they stay as loaded)
+    int hq[NPT];
+    T gq[NPT];
+    unsigned inq[NPT];
+    size_t mq[NPT];
+    for (int q = 0; q < NPT; ++q) {
+        const int n = tid + q * ADJ_THREADS;
+        hq[q] = -1; gq[q] = 0; inq[q] = 0; mq[q] = 0;
+        if (n >= NI) continue;
+        const int lx = n % TI, ly = (n / TI) % TI, lz = n / (TI * TI);
+        const int x = x0 + 1 + lx, y = y0 + 1 + ly, z = z0 + 1 + lz;
+        if (x >= geo.nnx || y >= geo.nny || z >= geo.nnz) continue;
+        hq[q] = ((lz + 1) * TH + ly + 1) * TH + lx + 1;
+        mq[q] = base + ((size_t)z * geo.nny + y) * geo.nnx + x;
+        gq[q] = g[mq[q]];
+        inq[q] = inmask[mq[q]];
+    }
+    __syncthreads();
+    bool tile_changed = false;
+    for (int it = 0; it <= NI; ++it) {
+        T nv[NPT];
+        for (int q = 0; q < NPT; ++q) {
+            if (hq[q] < 0) continue;
+            const T* L = sL + hq[q];
+            const T* F = sF + hq[q];
+            const T* Dn = sD + hq[q];
+            const unsigned in = inq[q];
+            const T tj = F[0];
+            T acc = gq[q];
+            ADJ_TERM(0, -1) ADJ_TERM(1, 1) ADJ_TERM(2, -TH) ADJ_TERM(3, TH) ADJ_TERM(4, -TH * TH) ADJ_TERM(5, TH * TH)
+            nv[q] = acc;
+        }
+        __syncthreads();   // every read of this step is done
+        int ch = 0;
+        for (int q = 0; q < NPT; ++q) {
+            if (hq[q] < 0) continue;
+            if (!same_bits(nv[q], sL[hq[q]])) { sL[hq[q]] = nv[q]; ch = 1; }
+        }
+        if (!__syncthreads_or(ch)) break;
+        tile_changed = true;
+    }
+    if (!tile_changed) return;
+    for (int q = 0; q < NPT; ++q)
+        if (hq[q] >= 0) lam[mq[q]] = sL[hq[q]];
+    if (tid == 0) { st[tile] = pass; cur[e] = 1; }
+}
+#undef ADJ_TERM
+
+// grad[m] = sum over the events, ascending, from +0, of  d * lam (frozen)  or  fl(fl(lam * fl(dx * fl(s * dx))) / D)
+template <typename T>
+__global__ void adj_grad_kernel(const T* __restrict__ lam, const T* __restrict__ D, const unsigned char* __restrict__ frozen,
+                                const T* __restrict__ s, AdjGeom<T> geo, size_t n_events, T* __restrict__ grad) {
+    const size_t m = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (m >= geo.nn) return;
+    const T c = geo.dx * (s[m] * geo.dx);
+    T acc = 0;
+    for (size_t e = 0; e < n_events; ++e) {
+        const size_t idx = e * geo.nn + m;
+        const T l = lam[idx];
+        const T v = frozen[idx] ? D[idx] * l : (l * c) / D[idx];
+        acc = acc + v;
+    }
+    grad[m] = acc;
+}
+
+struct Alloc {
+    AdjTapeDev& t;
+    size_t planned;
+    template <typename P>
+    void operator()(P*& p, size_t bytes) {
+        const size_t b = std::max<size_t>(bytes, 1);
+        void* raw = nullptr;
+        if (hipMalloc(&raw, b) != hipSuccess) {
+            (void)hipGetLastError();
+            std::ostringstream m;
+            m << "the field tape needs " << planned << " bytes of device memory on device " << t.device << " (an allocation of " << b
+              << " bytes failed)";
+            throw AdjDeviceError(m.str());
+        }
+        p = (P*)raw;
+        t.total_bytes += b;
+    }
+};
+
+template <typename P>
+void dev_free(P*& p) {
+    if (p) (void)hipFree((void*)p);
+    p = nullptr;
+}
+
+size_t tiles_of(const AdjTapeDev& t) {
+    const int ed = adj_tile_edge(t.elem);
+    return (size_t)((t.nnx + ed - 1) / ed) * ((t.nny + ed - 1) / ed) * ((t.nnz + ed - 1) / ed);
+}
+
+// every byte the finished tape holds (the figure an allocation failure names): fields, D, g, lam, lam2; inmask, frozen; slowness and the
+// staged gradient; the staged w; the seed entries (8 per row at most); flags, stamps, error flag
+size_t planned_bytes(const AdjTapeDev& t) {
+    const size_t en = t.n_events * t.nn;
+    return 5 * en * t.elem + 2 * en + 2 * t.nn * t.elem + t.n_rows * t.elem + 8 * t.n_rows * (8 + 4 + t.elem) +
+           (ADJ_RING * t.n_events + t.n_events * tiles_of(t) + 1) * sizeof(int);
+}
+
+}  // namespace
+
+int adj_tile_edge(size_t elem) { return elem == 4 ? AdjTile<float>::edge : AdjTile<double>::edge; }
+
+void AdjTapeDev::release() {
+    if (!fields && !stream) return;
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    dev_free(fields); dev_free(slowness); dev_free(D); dev_free(inmask); dev_free(frozen); dev_free(g); dev_free(lam); dev_free(lam2);
+    dev_free(sd_key); dev_free(sd_row); dev_free(sd_w); dev_free(flags); dev_free(stamps); dev_free(err); dev_free(w_tmp); dev_free(grad_tmp);
+    if (stream) (void)hipStreamDestroy(stream);
+    stream = nullptr;
+    total_bytes = 0;
+}
+
+void adj_alloc_fields(AdjTapeDev& t) {
+    ADJ_CHECK(hipSetDevice(t.device));
+    Alloc alloc{t, planned_bytes(t)};
+    alloc(t.fields, t.n_events * t.nn * t.elem);
+    alloc(t.slowness, t.nn * t.elem);
+}
+
+template <typename T>
+void adj_copy_field(const T* src, int ts, T* dst, size_t n, hipStream_t stream) {
+    if (n == 0) return;
+    adj_copy_field_kernel<T><<<std::min(blocks_for(n), 16384u), ADJ_THREADS, 0, stream>>>(src, ts, dst, n);
+    ADJ_CHECK(hipGetLastError());
+}
+
+template <typename T>
+void adj_finish(AdjTapeDev& t, const AdjSink& sink) {
+    ADJ_CHECK(hipSetDevice(t.device));
+    const size_t en = t.n_events * t.nn;
+    if (t.n_events > 65535) throw std::runtime_error("the field tape takes at most 65535 events per call");
+    // frozen nodes: one entry per (event, node), the last writer's d
+    std::vector<long long> fk;
+    std::vector<T> fd;
+    for (size_t e = 0; e < t.n_events; ++e)
+        for (size_t q = 0; q < sink.fr_node[e].size(); ++q) {
+            fk.push_back((long long)(e * t.nn) + sink.fr_node[e][q]);
+            fd.push_back((T)sink.fr_d[e][q]);
+        }
+    // seed entries: row order, then stencil order, kept within a node by the stable sort
+    std::vector<long long> key;
+    std::vector<int> row;
+    std::vector<T> wt;
+    for (size_t r = 0; r < t.n_rows; ++r)
+        for (int c = 0; c < sink.st_cnt[r]; ++c) {
+            key.push_back((long long)((size_t)sink.st_event[r] * t.nn) + sink.st_node[8 * r + c]);
+            row.push_back((int)r);
+            wt.push_back((T)sink.st_w[8 * r + c]);
+        }
+    std::vector<size_t> ord(key.size());
+    std::iota(ord.begin(), ord.end(), (size_t)0);
+    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return key[a] < key[b]; });
+    std::vector<long long> key2(key.size());
+    std::vector<int> row2(key.size());
+    std::vector<T> wt2(key.size());
+    for (size_t q = 0; q < ord.size(); ++q) { key2[q] = key[ord[q]]; row2[q] = row[ord[q]]; wt2[q] = wt[ord[q]]; }
+    t.n_seed = key2.size();
+    t.n_tiles = tiles_of(t);
+
+    Alloc alloc{t, planned_bytes(t)};
+    alloc(t.D, en * t.elem);
+    alloc(t.g, en * t.elem);
+    alloc(t.lam, en * t.elem);
+    alloc(t.lam2, en * t.elem);
+    alloc(t.inmask, en);
+    alloc(t.frozen, en);
+    alloc(t.sd_key, t.n_seed * sizeof(long long));
+    alloc(t.sd_row, t.n_seed * sizeof(int));
+    alloc(t.sd_w, t.n_seed * t.elem);
+    alloc(t.flags, ADJ_RING * t.n_events * sizeof(int));
+    alloc(t.stamps, t.n_events * t.n_tiles * sizeof(int));
+    alloc(t.err, sizeof(int));
+    alloc(t.w_tmp, t.n_rows * t.elem);
+    alloc(t.grad_tmp, t.nn * t.elem);
+    long long* d_fk = nullptr;
+    T* d_fd = nullptr;
+    hipStream_t s = t.stream;
+    try {
+        if (t.n_seed > 0) {
+            ADJ_CHECK(hipMemcpyAsync(t.sd_key, key2.data(), t.n_seed * sizeof(long long), hipMemcpyHostToDevice, s));
+            ADJ_CHECK(hipMemcpyAsync(t.sd_row, row2.data(), t.n_seed * sizeof(int), hipMemcpyHostToDevice, s));
+            ADJ_CHECK(hipMemcpyAsync(t.sd_w, wt2.data(), t.n_seed * sizeof(T), hipMemcpyHostToDevice, s));
+        }
+        ADJ_CHECK(hipMemsetAsync(t.err, 0, sizeof(int), s));
+        if (en > 0) {
+            ADJ_CHECK(hipMemsetAsync(t.frozen, 0, en, s));
+            if (!fk.empty()) {
+                ADJ_CHECK(hipMalloc((void**)&d_fk, fk.size() * sizeof(long long)));
+                ADJ_CHECK(hipMalloc((void**)&d_fd, fd.size() * sizeof(T)));
+                ADJ_CHECK(hipMemcpyAsync(d_fk, fk.data(), fk.size() * sizeof(long long), hipMemcpyHostToDevice, s));
+                ADJ_CHECK(hipMemcpyAsync(d_fd, fd.data(), fd.size() * sizeof(T), hipMemcpyHostToDevice, s));
+                adj_mark_frozen_kernel<T><<<blocks_for(fk.size()), ADJ_THREADS, 0, s>>>(d_fk, d_fd, fk.size(), t.frozen, (T*)t.D);
+                ADJ_CHECK(hipGetLastError());
+            }
+            const AdjGeom<T> geo{t.nnx, t.nny, t.nnz, t.nn, (T)t.dx};
+            adj_couple_kernel<T><<<dim3(blocks_for(t.nn), (unsigned)t.n_events), ADJ_THREADS, 0, s>>>((const T*)t.fields, geo, t.frozen, t.inmask,
+                                                                                                   (T*)t.D, t.err);
+            ADJ_CHECK(hipGetLastError());
+        }
+        int h_err = 0;
+        ADJ_CHECK(hipMemcpyAsync(&h_err, t.err, sizeof(int), hipMemcpyDeviceToHost, s));
+        ADJ_CHECK(hipStreamSynchronize(s));
+        dev_free(d_fk);
+        dev_free(d_fd);
+        if (h_err) throw std::runtime_error("adjoint: internal error, a node that is not frozen has no upwind neighbour (the field is not a solved one)");
+    } catch (...) {
+        dev_free(d_fk);
+        dev_free(d_fd);
+        throw;
+    }
+}
+
+template <typename T>
+int adj_vjp(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, int schedule) {
+    ADJ_CHECK(hipSetDevice(t.device));
+    hipStream_t s = t.stream;
+    const size_t E = t.n_events, en = E * t.nn;
+    const AdjGeom<T> geo{t.nnx, t.nny, t.nnz, t.nn, (T)t.dx};
+    T* g = (T*)t.g;
+    T* lam = (T*)t.lam;
+    int passes = 0;
+    if (en > 0) {
+        adj_seed_fill_kernel<T><<<std::min(blocks_for(en), 65536u), ADJ_THREADS, 0, s>>>(d_fc, g, en);
+        ADJ_CHECK(hipGetLastError());
+        if (d_w && t.n_seed > 0) {
+            adj_seed_rows_kernel<T><<<blocks_for(t.n_seed), ADJ_THREADS, 0, s>>>(t.sd_key, t.sd_row, (const T*)t.sd_w, t.n_seed, d_w, g);
+            ADJ_CHECK(hipGetLastError());
+        }
+        ADJ_CHECK(hipMemcpyAsync(lam, g, en * sizeof(T), hipMemcpyDeviceToDevice, s));
+        if (schedule == 0) ADJ_CHECK(hipMemsetAsync(t.stamps, 0xFF, E * t.n_tiles * sizeof(int), s));
+        const int ed = adj_tile_edge(sizeof(T));
+        const int ntx = (t.nnx + ed - 1) / ed, nty = (t.nny + ed - 1) / ed, ntz = (t.nnz + ed - 1) / ed;
+        std::vector<int> h_flags((size_t)ADJ_RING * E);
+        T* in = lam;
+        T* out = (T*)t.lam2;
+        const size_t max_passes = t.nn + ADJ_CHECK_EVERY + 1;   // (the depth of the DAG is below the node count)
+        for (;;) {
+            for (int k = 0; k < ADJ_CHECK_EVERY; ++k, ++passes) {
+                int* cur = t.flags + (size_t)(passes % ADJ_RING) * E;
+                const int* prev = passes > 0 ? t.flags + (size_t)((passes - 1) % ADJ_RING) * E : nullptr;
+                ADJ_CHECK(hipMemsetAsync(cur, 0, E * sizeof(int), s));
+                if (schedule == 0) {
+                    adj_tiled_kernel<T, AdjTile<T>::edge><<<dim3((unsigned)t.n_tiles, (unsigned)E), ADJ_THREADS, 0, s>>>(
+                        (const T*)t.fields, (const T*)t.D, t.inmask, g, lam, geo, ntx, nty, ntz, t.stamps, passes, cur);
+                } else {
+                    adj_jacobi_kernel<T><<<dim3(blocks_for(t.nn), (unsigned)E), ADJ_THREADS, 0, s>>>((const T*)t.fields, (const T*)t.D, t.inmask, g,
+                                                                                                    in, out, geo, prev, cur);
+                    std::swap(in, out);
+                }
+                ADJ_CHECK(hipGetLastError());
+            }
+            ADJ_CHECK(hipMemcpyAsync(h_flags.data(), t.flags, h_flags.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+            ADJ_CHECK(hipStreamSynchronize(s));
+            const int* last = h_flags.data() + (size_t)((passes - 1) % ADJ_RING) * E;
+            bool any = false;
+            for (size_t e = 0; e < E; ++e) any = any || last[e] != 0;
+            if (!any) break;
+            if ((size_t)passes > max_passes) throw std::runtime_error("adjoint: internal error, the relaxation did not reach its fixed point");
+        }
+        if (schedule != 0) lam = in;   // (the buffer the last pass wrote; both hold the fixed point)
+    }
+    if (t.nn > 0) {
+        adj_grad_kernel<T><<<blocks_for(t.nn), ADJ_THREADS, 0, s>>>(lam, (const T*)t.D, t.frozen, (const T*)t.slowness, geo, E, d_grad);
+        ADJ_CHECK(hipGetLastError());
+    }
+    return passes;
+}
+
+template void adj_copy_field<float>(const float*, int, float*, size_t, hipStream_t);
+template void adj_copy_field<double>(const double*, int, double*, size_t, hipStream_t);
+template void adj_finish<float>(AdjTapeDev&, const AdjSink&);
+template void adj_finish<double>(AdjTapeDev&, const AdjSink&);
+template int adj_vjp<float>(AdjTapeDev&, const float*, const float*, float*, int);
+template int adj_vjp<double>(AdjTapeDev&, const double*, const double*, double*, int);
+
+}  // namespace ttcr_amd

@@ -1,0 +1,84 @@
+// ttcr_amd/csrc/fsm_adjoint_api.h -- the field tape (ttcr_fsm_raytrace_multi_adjoint, include/ttcr_amd.h): what the host side (fsm_capi.hip)
+// sees of the kernels that back-propagate a cotangent through the first-order Godunov update of the 3-D node solver.  The kernels live in a
+// translation unit of their own (fsm_adjoint.hip).  Definition: DESIGN.md 6b; tests/adjoint_reference.py restates it in numpy.
+//
+// Per tape, once:   frozen marks -> coupling pass (per node and event: D, the sum of the active upwind differences, and the 6-bit mask of the
+//                   neighbours that have this node as an active upwind neighbour).
+// Per VJP:          seed (g = field cotangent + receiver rows through the interpolation stencil, one serial chain per node in row order)
+//                   -> relaxation of lam = g + gather(lam) to its fixed point (tiled in LDS, or the global Jacobi baseline)
+//                   -> gradient (events summed in ascending order from +0 inside the thread).
+// No floating-point atomics anywhere: every value is one fixed expression of final values, so the bits do not depend on the schedule.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <stdexcept>
+#include <vector>
+
+namespace ttcr_amd {
+
+// an allocation or a copy of the tape failed on the device (the C ABI turns it into TTCR_ERR_DEVICE)
+struct AdjDeviceError : std::runtime_error {
+    using std::runtime_error::runtime_error;
+};
+
+// What the solves of a call leave for the tape.  The fields and the slowness go straight to device memory of `device` (allocated by the
+// caller before the solves); the small lists are collected on the host.  Replicas of a multi-device grid fill disjoint events and rows.
+struct AdjSink {
+    int device = 0;
+    size_t elem = 4, nn = 0;
+    void* fields = nullptr;     // n_events * nn values: event e at fields + e * nn * elem
+    void* slowness = nullptr;   // nn values (written with event 0)
+    // frozen nodes of every event (fsm_init_source): node and distance d of the point that wrote it last (a T value, held exactly)
+    std::vector<std::vector<int>> fr_node;
+    std::vector<std::vector<double>> fr_d;
+    // interpolation stencil of every receiver row (interp3d_stencil): 8 slots per row, st_cnt[row] of them used
+    std::vector<int> st_cnt, st_event;
+    std::vector<long long> st_node;
+    std::vector<double> st_w;
+};
+
+struct AdjTapeDev {
+    int device = 0;
+    size_t elem = 0, n_events = 0, n_rows = 0, nn = 0;
+    int nnx = 0, nny = 0, nnz = 0;
+    double dx = 0;
+    void* fields = nullptr;           // n_events * nn
+    void* slowness = nullptr;         // nn
+    void* D = nullptr;                // n_events * nn: D of a non-frozen node, d of a frozen one
+    unsigned char* inmask = nullptr;  // n_events * nn: bit 2 * axis + side (x-, x+, y-, y+, z-, z+): that neighbour feeds this node
+    unsigned char* frozen = nullptr;  // n_events * nn: 1 = frozen
+    void* g = nullptr;                // n_events * nn: the seeds of the running VJP
+    void* lam = nullptr;              // n_events * nn
+    void* lam2 = nullptr;             // n_events * nn: second buffer of the Jacobi baseline; a host field cotangent is staged here
+    size_t n_seed = 0;                // stencil entries, sorted by (event, node), rows ascending within a node
+    long long* sd_key = nullptr;      // event * nn + node
+    int* sd_row = nullptr;
+    void* sd_w = nullptr;
+    int* flags = nullptr;             // ring of per-event "a value changed in pass p" flags
+    int* stamps = nullptr;            // per event and tile: the last pass that changed the tile
+    int* err = nullptr;               // internal error flag of the coupling pass
+    void* w_tmp = nullptr;            // n_rows (host w staged here)
+    void* grad_tmp = nullptr;         // nn (host grad staged here)
+    size_t n_tiles = 0;
+    size_t total_bytes = 0;
+    hipStream_t stream = nullptr;
+    size_t bytes() const { return total_bytes; }
+    void release();
+};
+
+// edge of a relaxation tile (interior nodes) for an element size
+int adj_tile_edge(size_t elem);
+// allocates fields and slowness (what the solves write into); throws AdjDeviceError naming the byte count
+void adj_alloc_fields(AdjTapeDev& t);
+// strided field (element n at src[n * ts]) -> contiguous dst, both on the current device
+template <typename T>
+void adj_copy_field(const T* src, int ts, T* dst, size_t n, hipStream_t stream);
+// uploads the lists of the sink, allocates the work arrays, marks the frozen nodes and runs the coupling pass
+template <typename T>
+void adj_finish(AdjTapeDev& t, const AdjSink& sink);
+// d_w (n_rows, may be null), d_fc (n_events * nn, may be null), d_grad (nn): all on the tape's device; returns the passes launched
+template <typename T>
+int adj_vjp(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, int schedule);
+
+}  // namespace ttcr_amd

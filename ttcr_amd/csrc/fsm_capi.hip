@@ -27,6 +27,7 @@
 #include "fsm_kernels.h"
 #include "fsm_fast_api.h"
 #include "fsm_tape_api.h"
+#include "fsm_adjoint_api.h"
 
 #ifndef FSM_CHUNK3
 #define FSM_CHUNK3 8
@@ -115,6 +116,14 @@ class GridBase {
     // order, nodes ascending within a row, on `device` (the M tape, ttcr_fsm_raytrace_multi_tape)
     virtual void raytrace_multi_tape(int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off, const void* rx,
                                      void* tt_out, TapeRows& out) = 0;
+    // the field tape (ttcr_fsm_raytrace_multi_adjoint): the batched solves of raytrace_multi with interpolated receiver traveltimes
+    // (whatever tt_from_rp says); after each batch every event's field, frozen nodes and receiver stencils go to `sink`
+    virtual void raytrace_multi_adjoint(int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off, const void* rx,
+                                        void* tt_out, AdjSink& sink) = 0;
+    // node counts and spacing of a grid the adjoint is defined for; Unsupported (with the reason) for every other grid
+    virtual void adjoint_geometry(int* nn3, double* spacing) const = 0;
+    AdjSink* adj_sink = nullptr;          // set for the duration of such a call
+    std::vector<int> adj_src, adj_row;    // a replica of a multi-device grid: event and first row, in the call, of each source of ITS call
     // the raytrace overloads with l_data (2-D cell grids): ray-projection matrix L, one CSR row per receiver
     virtual void raytrace_l(int slot, int n_tx, const void* tx, const void* t0, int n_rx, const void* rx, void* tt_out, bool with_rays) = 0;
     virtual void slot_l_size(int slot, size_t* n_rows, size_t* nnz) const = 0;
@@ -2366,6 +2375,80 @@ class GridT : public GridBase {
         m_chunk.release();
         for (auto& v : m_seg_off) std::vector<long long>().swap(v);
     }
+    // ---- the field tape (fsm_adjoint_api.h)
+    void adjoint_geometry(int* nn3, double* spacing) const override {
+        if (dim != 3) throw Unsupported("the adjoint-state gradient is implemented for 3-D grids only");
+        if (cell) throw Unsupported("the adjoint-state gradient is not implemented for grids with slowness defined for cells");
+        if (weno) throw Unsupported("the adjoint-state gradient is implemented for the first-order solver only (weno = 0)");
+        nn3[0] = (int)ncx + 1; nn3[1] = (int)ncy + 1; nn3[2] = (int)ncz + 1;
+        *spacing = (double)dx;
+    }
+    void raytrace_multi_adjoint(int n_src, const int* tx_off, const void* tx_v, const void* t0_v, const int* rx_off, const void* rx_v,
+                                void* tt_out_v, AdjSink& sink) override {
+        int nn3[3];
+        double sp;
+        adjoint_geometry(nn3, &sp);
+        adj_sink = &sink;
+        try {
+            raytrace_multi(n_src, tx_off, tx_v, t0_v, rx_off, rx_v, tt_out_v, -1, nullptr, false);
+        } catch (...) { adj_sink = nullptr; throw; }
+        adj_sink = nullptr;
+    }
+    DevBuf<T> d_adj_tmp;
+    // after the solves of a batch: field (device to device), frozen nodes as fsm_init_source wrote them, receiver stencils
+    void adj_record(const std::vector<int>& sl, const std::vector<int>& sr, const int* tx_off, const T* tx, const T* t0, const int* rx_off,
+                    const T* rx) {
+        AdjSink& sk = *adj_sink;
+        const int nnx = (int)ncx + 1, nny = (int)ncy + 1, nnz = (int)ncz + 1;
+        for (size_t b = 0; b < sl.size(); ++b) {
+            const int n = sr[b];
+            const size_t e = adj_src.empty() ? (size_t)n : (size_t)adj_src[n];
+            const size_t row0 = adj_row.empty() ? (size_t)rx_off[n] : (size_t)adj_row[n];
+            T* dst = (T*)sk.fields + e * n_nodes;
+            if (sk.device == device) {
+                adj_copy_field<T>(tt_ptr(sl[b]), NS, dst, n_nodes, stream);
+            } else {   // (another device: gathered here, then copied across)
+                d_adj_tmp.reserve(n_nodes);
+                adj_copy_field<T>(tt_ptr(sl[b]), NS, d_adj_tmp.p, n_nodes, stream);
+                HIP_CHECK(hipMemcpyAsync(dst, d_adj_tmp.p, n_nodes * sizeof(T), hipMemcpyDefault, stream));
+                HIP_CHECK(hipStreamSynchronize(stream));
+            }
+            if (e == 0) HIP_CHECK(hipMemcpyAsync(sk.slowness, d_s.p, n_nodes * sizeof(T), hipMemcpyDefault, stream));
+            // frozen nodes: the points in order, the later writer wins (fsm_init_source, 3-D branch, first order)
+            std::vector<int>& fn = sk.fr_node[e];
+            std::vector<double>& fd = sk.fr_d[e];
+            fn.clear(); fd.clear();
+            auto put = [&](long long m, T d) {
+                for (size_t q = 0; q < fn.size(); ++q)
+                    if (fn[q] == (int)m) { fd[q] = (double)d; return; }
+                fn.push_back((int)m); fd.push_back((double)d);
+            };
+            for (int q = tx_off[n]; q < tx_off[n + 1]; ++q) {
+                const InitPoint<T> p = locate(tx + (size_t)3 * q, t0[q]);
+                const int b0 = p.on_node ? -1 : 0;
+                if (p.on_node) put(((long long)p.k * nny + p.j) * nnx + p.i, (T)0);
+                for (int kk = p.k + b0; kk <= p.k + 1; ++kk)
+                    for (int jj = p.j + b0; jj <= p.j + 1; ++jj)
+                        for (int ii = p.i + b0; ii <= p.i + 1; ++ii) {
+                            if (ii < 0 || ii >= nnx || jj < 0 || jj >= nny || kk < 0 || kk >= nnz) continue;
+                            if (ii == p.i && jj == p.j && kk == p.k) continue;
+                            const T x = node_coord_h(xmin, (uint32_t)ii, dx), y = node_coord_h(ymin, (uint32_t)jj, dx), z = node_coord_h(zmin, (uint32_t)kk, dx);
+                            const T d2 = (x - p.x) * (x - p.x) + (y - p.y) * (y - p.y) + (z - p.z) * (z - p.z);
+                            put(((long long)kk * nny + jj) * nnx + ii, (T)std::sqrt((double)d2));
+                        }
+            }
+            for (int r = rx_off[n]; r < rx_off[n + 1]; ++r) {
+                const size_t row = row0 + (size_t)(r - rx_off[n]);
+                long long nd[8];
+                T wt[8];
+                const int cnt = interp3d_stencil<T>(rx[3 * (size_t)r], rx[3 * (size_t)r + 1], rx[3 * (size_t)r + 2], nnx, nny, nnz, dx, xmin, ymin, zmin, nd, wt);
+                sk.st_cnt[row] = cnt;
+                sk.st_event[row] = (int)e;
+                for (int c = 0; c < cnt; ++c) { sk.st_node[8 * row + c] = nd[c]; sk.st_w[8 * row + c] = (double)wt[c]; }
+            }
+        }
+        HIP_CHECK(hipStreamSynchronize(stream));
+    }
     void multi_m_size(size_t* n_rows, size_t* nnz) const override { *n_rows = multi_m_off.size() - 1; *nnz = multi_m_j.size(); }
     void get_multi_m(long long* row_off, long long* j, void* v) const override {
         std::memcpy(row_off, multi_m_off.data(), multi_m_off.size() * sizeof(long long));
@@ -2748,7 +2831,11 @@ class GridT : public GridBase {
                 }
                 solve_batch(sl, sr, tx_off, tx.data(), t0);
                 hp_mark("solve_batch tail");
-                if (l_walk_mode) {
+                if (adj_sink) {
+                    // the field tape: interpolated receiver traveltimes whatever tt_from_rp says, then the batch's fields and lists
+                    interp_batch(sl, sr, rx_off, rx.data(), tt_out);
+                    adj_record(sl, sr, tx_off, tx.data(), t0, rx_off, rx.data());
+                } else if (l_walk_mode) {
                     // the l_data overloads for every source of the call (raytrace_multi_l): the walk gives traveltimes, entries and rays
                     for (size_t b = 0; b < sl.size(); ++b) {
                         const int n = sr[b];
@@ -3045,6 +3132,20 @@ class MultiGrid : public GridBase {
         for (int s2 = 0; s2 < n_slots; ++s2) { int l; GridBase& g = of(s2, l); g.get_niter(l, &niter[s2], &niterw[s2]); }
         timing.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
     }
+    // The field tape: the sources go to the replicas like raytrace_multi sends them; every replica copies its fields to the sink's device.
+    void adjoint_geometry(int* nn3, double* spacing) const override { rep[0]->adjoint_geometry(nn3, spacing); }
+    void raytrace_multi_adjoint(int n_src, const int* tx_off, const void* tx_v, const void* t0_v, const int* rx_off, const void* rx_v,
+                                void* tt_out_v, AdjSink& sink) override {
+        int nn3[3];
+        double sp;
+        adjoint_geometry(nn3, &sp);
+        for (auto& r : rep) r->adj_sink = &sink;
+        auto clear = [&] { for (auto& r : rep) { r->adj_sink = nullptr; r->adj_src.clear(); r->adj_row.clear(); } };
+        try {
+            raytrace_multi(n_src, tx_off, tx_v, t0_v, rx_off, rx_v, tt_out_v, -1, nullptr, false);
+        } catch (...) { clear(); throw; }
+        clear();
+    }
     void raytrace_multi_l(int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off, const void* rx, void* tt_out,
                           bool with_rays) override {
         sharded_matrix_call(
@@ -3152,6 +3253,11 @@ class MultiGrid : public GridBase {
                         std::memcpy(st0.data() + elem_size * to[q], t0 + elem_size * tx_off[n], elem_size * (to[q + 1] - to[q]));
                         std::memcpy(srx.data() + pt_bytes * ro[q], rx + pt_bytes * rx_off[n], pt_bytes * (ro[q + 1] - ro[q]));
                     }
+                    if (g.adj_sink) {
+                        g.adj_src.resize(m);
+                        g.adj_row.resize(m);
+                        for (int q = 0; q < m; ++q) { g.adj_src[q] = mine[q].src; g.adj_row[q] = rx_off[mine[q].src]; }
+                    }
                     g.raytrace_multi(m, to.data(), stx.data(), st0.data(), ro.data(), srx.data(), stt.data(), -1, ls.data(), want_rays);
                     dev_t[d].sweep_ms += g.timing.sweep_ms;
                     dev_t[d].launches += g.timing.launches;
@@ -3237,6 +3343,14 @@ static int guarded_on(G* g, F&& f) {
     }
     std::lock_guard<std::mutex> lock(g->impl->mu);
     return guarded(std::forward<F>(f));
+}
+
+// (the field tape's kernel unit reports device failures with its own exception type)
+template <typename F>
+static void adj_device_errors(F&& f) {
+    try {
+        f();
+    } catch (const ttcr_amd::AdjDeviceError& e) { throw DeviceError(e.what()); }
 }
 
 static int pick_device(int device) {
@@ -3650,6 +3764,144 @@ int ttcr_fsm_tape_vjp(const ttcr_fsm_tape* t, const void* w, int w_on_device, vo
     });
 }
 int ttcr_fsm_tape_free(ttcr_fsm_tape* t) {
+    if (!t) return TTCR_OK;
+    return guarded([&] { delete t; });
+}
+// ---- the field tape (fsm_adjoint_api.h): owns its device memory and stream, independent of the grid it came from
+struct ttcr_fsm_adjoint {
+    int dtype = TTCR_F32;
+    ttcr_amd::AdjTapeDev t;
+    std::mutex mu;
+    ~ttcr_fsm_adjoint() { t.release(); }
+};
+
+int ttcr_fsm_raytrace_multi_adjoint(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off,
+                                    const void* rx, void* tt_out, ttcr_fsm_adjoint** tape) {
+    if (!tape) {
+        g_last_error = "null tape output pointer";
+        return TTCR_ERR_VALUE;
+    }
+    *tape = nullptr;
+    if (n_src < 0 || (n_src > 0 && (!tx_off || !tx || !t0 || !rx_off || !rx || !tt_out))) {
+        g_last_error = "raytrace_multi_adjoint: null array or negative source count";
+        return TTCR_ERR_VALUE;
+    }
+    return guarded_on(g, [&] {
+        GridBase& G = *g->impl;
+        int nn3[3];
+        double spacing = 0;
+        G.adjoint_geometry(nn3, &spacing);
+        std::unique_ptr<ttcr_fsm_adjoint> tp(new ttcr_fsm_adjoint());
+        ttcr_amd::AdjTapeDev& t = tp->t;
+        tp->dtype = G.dtype;
+        t.device = G.device;
+        t.elem = G.elem_size;
+        t.n_events = (size_t)n_src;
+        t.n_rows = n_src > 0 ? (size_t)rx_off[n_src] : 0;
+        t.nn = G.n_nodes;
+        t.nnx = nn3[0]; t.nny = nn3[1]; t.nnz = nn3[2];
+        t.dx = spacing;
+        adj_device_errors([&] {
+            HIP_CHECK(hipSetDevice(t.device));
+            HIP_CHECK(hipStreamCreateWithFlags(&t.stream, hipStreamNonBlocking));
+            ttcr_amd::adj_alloc_fields(t);
+            ttcr_amd::AdjSink sink;
+            sink.device = t.device; sink.elem = t.elem; sink.nn = t.nn;
+            sink.fields = t.fields; sink.slowness = t.slowness;
+            sink.fr_node.resize(t.n_events); sink.fr_d.resize(t.n_events);
+            sink.st_cnt.assign(t.n_rows, 0); sink.st_event.assign(t.n_rows, 0);
+            sink.st_node.assign(8 * t.n_rows, 0); sink.st_w.assign(8 * t.n_rows, 0.0);
+            G.raytrace_multi_adjoint(n_src, tx_off, tx, t0, rx_off, rx, tt_out, sink);
+            HIP_CHECK(hipSetDevice(t.device));
+            HIP_CHECK(hipDeviceSynchronize());   // (the replicas of a multi-device grid wrote from their own streams)
+            if (G.dtype == TTCR_F32) ttcr_amd::adj_finish<float>(t, sink);
+            else ttcr_amd::adj_finish<double>(t, sink);
+        });
+        *tape = tp.release();
+    });
+}
+int ttcr_fsm_adjoint_size(const ttcr_fsm_adjoint* t, size_t* n_events, size_t* n_rows, size_t* n_nodes) {
+    if (!t || !n_events || !n_rows || !n_nodes) {
+        g_last_error = "null tape or output pointer";
+        return TTCR_ERR_VALUE;
+    }
+    *n_events = t->t.n_events;
+    *n_rows = t->t.n_rows;
+    *n_nodes = t->t.nn;
+    return TTCR_OK;
+}
+int ttcr_fsm_adjoint_bytes(const ttcr_fsm_adjoint* t, size_t* bytes) {
+    if (!t || !bytes) {
+        g_last_error = "null tape or output pointer";
+        return TTCR_ERR_VALUE;
+    }
+    *bytes = t->t.bytes();
+    return TTCR_OK;
+}
+int ttcr_fsm_adjoint_device(const ttcr_fsm_adjoint* t, int* device) {
+    if (!t || !device) {
+        g_last_error = "null tape or output pointer";
+        return TTCR_ERR_VALUE;
+    }
+    *device = t->t.device;
+    return TTCR_OK;
+}
+int ttcr_fsm_adjoint_get_field(const ttcr_fsm_adjoint* t, size_t event, void* out) {
+    if (!t || !out) {
+        g_last_error = "null tape or output pointer";
+        return TTCR_ERR_VALUE;
+    }
+    if (event >= t->t.n_events) {
+        g_last_error = "event index out of range";
+        return TTCR_ERR_VALUE;
+    }
+    ttcr_fsm_adjoint* tm = const_cast<ttcr_fsm_adjoint*>(t);
+    std::lock_guard<std::mutex> lock(tm->mu);
+    return guarded([&] {
+        const ttcr_amd::AdjTapeDev& d = t->t;
+        HIP_CHECK(hipSetDevice(d.device));
+        HIP_CHECK(hipMemcpyAsync(out, (const char*)d.fields + event * d.nn * d.elem, d.nn * d.elem, hipMemcpyDeviceToHost, d.stream));
+        HIP_CHECK(hipStreamSynchronize(d.stream));
+    });
+}
+int ttcr_fsm_adjoint_vjp(const ttcr_fsm_adjoint* t, const void* w, int w_on_device, const void* field_cot, int fc_on_device, void* grad,
+                         int grad_on_device, int schedule, int* passes) {
+    if (!t || !grad || (!w && !field_cot)) {
+        g_last_error = !t ? "null tape" : (!grad ? "null grad" : "w and field_cot are both null: nothing to back-propagate");
+        return TTCR_ERR_VALUE;
+    }
+    if (schedule != 0 && schedule != 1) {
+        g_last_error = "schedule: 0 (tiled) or 1 (global Jacobi)";
+        return TTCR_ERR_VALUE;
+    }
+    ttcr_fsm_adjoint* tm = const_cast<ttcr_fsm_adjoint*>(t);
+    std::lock_guard<std::mutex> lock(tm->mu);
+    return guarded([&] {
+        ttcr_amd::AdjTapeDev& d = tm->t;
+        adj_device_errors([&] {
+            HIP_CHECK(hipSetDevice(d.device));
+            const void* dw = w;
+            const void* dfc = field_cot;
+            void* dg = grad_on_device ? grad : d.grad_tmp;
+            if (w && !w_on_device) {
+                if (d.n_rows > 0) HIP_CHECK(hipMemcpyAsync(d.w_tmp, w, d.n_rows * d.elem, hipMemcpyHostToDevice, d.stream));
+                dw = d.w_tmp;
+            }
+            if (field_cot && !fc_on_device) {   // (staged in the Jacobi baseline's second buffer, which is not in use before the seeds are formed)
+                if (d.n_events * d.nn > 0)
+                    HIP_CHECK(hipMemcpyAsync(d.lam2, field_cot, d.n_events * d.nn * d.elem, hipMemcpyHostToDevice, d.stream));
+                dfc = d.lam2;
+            }
+            int np = 0;
+            if (tm->dtype == TTCR_F32) np = ttcr_amd::adj_vjp<float>(d, (const float*)dw, (const float*)dfc, (float*)dg, schedule);
+            else np = ttcr_amd::adj_vjp<double>(d, (const double*)dw, (const double*)dfc, (double*)dg, schedule);
+            if (!grad_on_device) HIP_CHECK(hipMemcpyAsync(grad, d.grad_tmp, d.nn * d.elem, hipMemcpyDeviceToHost, d.stream));
+            HIP_CHECK(hipStreamSynchronize(d.stream));
+            if (passes) *passes = np;
+        });
+    });
+}
+int ttcr_fsm_adjoint_free(ttcr_fsm_adjoint* t) {
     if (!t) return TTCR_OK;
     return guarded([&] { delete t; });
 }

@@ -3198,6 +3198,51 @@ __device__ __forceinline__ T interp3d_pt(const T* __restrict__ Tn, int ts, T px,
     return tt;
 }
 
+// Stencil and weights of interp3d_pt (the adjoint of the receiver interpolation, fsm_adjoint_api.h): the nodes it reads, in the order it
+// reads them (x outer, y, z inner; an axis the point lies on contributes its one plane and no factor), clamped like TT above, and for each
+// the product of its per-axis weights, taken z first, then y, then x -- the order in which the nested interpolation applies them.  Returns
+// the number of entries (1, 2, 4 or 8).  interp3d_pt's value is sum(weight * T) re-associated.
+template <typename T>
+__host__ __device__ inline int interp3d_stencil(T px, T py, T pz, int nnx, int nny, int nnz, T dx, T xmin, T ymin, T zmin, long long* node,
+                                                T* wt) {
+    const double small2 = 1.e-4 * 1.e-4;
+    const T p[3] = {px, py, pz}, cmin[3] = {xmin, ymin, zmin};
+    const int ext[3] = {nnx, nny, nnz};
+    uint32_t lo[3];
+    bool on[3];
+    T w1[3], w2[3];
+    for (int a = 0; a < 3; ++a) {
+        const double v = small2 + (double)((p[a] - cmin[a]) / dx);
+        lo[a] = v < 0 ? 0u : (v >= 4294967295.0 ? 4294967295u : (uint32_t)v);
+        const T off = p[a] - (cmin[a] + (T)lo[a] * dx);
+        on[a] = (double)(off < 0 ? -off : off) < small2;
+        w1[a] = (cmin[a] + (T)(lo[a] + 1) * dx - p[a]) / dx;
+        w2[a] = (p[a] - (cmin[a] + (T)lo[a] * dx)) / dx;
+    }
+    int n = 0;
+    for (int ii = 0; ii < (on[0] ? 1 : 2); ++ii)
+        for (int jj = 0; jj < (on[1] ? 1 : 2); ++jj)
+            for (int kk = 0; kk < (on[2] ? 1 : 2); ++kk, ++n) {
+                const int s[3] = {ii, jj, kk};
+                uint32_t c[3];
+                for (int a = 0; a < 3; ++a) {
+                    c[a] = lo[a] + (uint32_t)s[a];
+                    c[a] = c[a] < (uint32_t)ext[a] ? c[a] : (uint32_t)ext[a] - 1u;
+                }
+                T w = 1;
+                bool first = true;
+                for (int a = 2; a >= 0; --a) {
+                    if (on[a]) continue;
+                    const T f = s[a] ? w2[a] : w1[a];
+                    w = first ? f : w * f;
+                    first = false;
+                }
+                node[n] = ((long long)c[2] * nny + c[1]) * nnx + c[0];
+                wt[n] = w;
+            }
+    return n;
+}
+
 template <typename T>
 __global__ void fsm_interp3d(const T* __restrict__ Tn, int ts, const T* __restrict__ pts, T* __restrict__ out, int n,
                              int nnx, int nny, int nnz, T dx, T xmin, T ymin, T zmin) {

@@ -353,6 +353,19 @@ class _GridBase:
         if slowness is not None:
             self.set_slowness(slowness)
         dt = self._dtype
+        tx_off, tx, t0, rx_off, rx, out = self._event_arrays(vTx, vt0, vRx)
+        h = C.c_void_p()
+        _lib.check(self._lib.ttcr_fsm_raytrace_multi_tape(self._h, len(vTx), _ptr(tx_off), _ptr(tx), _ptr(t0), _ptr(rx_off), _ptr(rx),
+                                                          _ptr(out), C.byref(h)))
+        tape = MTape(self._lib, h, dt, np.concatenate(iRx).astype(np.int64), rcv.shape[0])
+        tt = np.zeros((rcv.shape[0],), dtype=dt)
+        for n in range(len(vTx)):
+            tt[iRx[n]] = out[rx_off[n]:rx_off[n + 1]]
+        return tt, tape
+
+    def _event_arrays(self, vTx, vt0, vRx):
+        """The events of _split_sources in the layout of the ttcr_fsm_raytrace_multi* calls, and room for their traveltimes."""
+        dt = self._dtype
         nd = self._ndim
         tx = np.ascontiguousarray(np.vstack(vTx), dtype=dt).reshape(-1, nd)
         t0 = np.ascontiguousarray(np.concatenate(vt0), dtype=dt)
@@ -361,11 +374,33 @@ class _GridBase:
         rx_off = np.zeros(len(vTx) + 1, dtype=np.int32)
         tx_off[1:] = np.cumsum([len(t) for t in vTx])
         rx_off[1:] = np.cumsum([len(r) for r in vRx])
-        out = np.empty(max(rx.shape[0], 1), dtype=dt)
+        return tx_off, tx, t0, rx_off, rx, np.empty(max(rx.shape[0], 1), dtype=dt)
+
+    def raytrace_adjoint(self, source, rcv, slowness=None, aggregate_src=False):
+        """raytrace_adjoint(source, rcv, slowness=None, aggregate_src=False) -> (tt, tape)
+
+        Traveltimes at the receivers (same source / receiver handling as raytrace_tape) and a FieldTape that keeps every event's
+        traveltime field on the device for the adjoint-state gradient: tape.vjp(w, field_cotangent) is the exact derivative, with
+        respect to node slowness, of  w . tt + field_cotangent . fields  through the first-order solver's own update.  The receiver
+        traveltimes of this call are the INTERPOLATED ones (what a grid with tt_from_rp=0 returns, bit for bit): the call forces that
+        for its own solves whatever the grid's tt_from_rp setting.  3-D node grids with weno=0 only (NotImplementedError otherwise)."""
+        source = np.asarray(source)
+        rcv = np.asarray(rcv)
+        if source.ndim != 2 or rcv.ndim != 2:
+            raise ValueError('source and rcv should be 2D arrays')
+        if self._ndim != 3:
+            raise NotImplementedError('the adjoint-state gradient is implemented for 3-D grids only')
+        if self.cell_slowness:
+            raise NotImplementedError('the adjoint-state gradient is not implemented for grids with slowness defined for cells')
+        vTx, vt0, vRx, iRx = self._split_sources(source, rcv, aggregate_src)
+        if slowness is not None:
+            self.set_slowness(slowness)
+        dt = self._dtype
+        tx_off, tx, t0, rx_off, rx, out = self._event_arrays(vTx, vt0, vRx)
         h = C.c_void_p()
-        _lib.check(self._lib.ttcr_fsm_raytrace_multi_tape(self._h, len(vTx), _ptr(tx_off), _ptr(tx), _ptr(t0), _ptr(rx_off), _ptr(rx),
-                                                          _ptr(out), C.byref(h)))
-        tape = MTape(self._lib, h, dt, np.concatenate(iRx).astype(np.int64), rcv.shape[0])
+        _lib.check(self._lib.ttcr_fsm_raytrace_multi_adjoint(self._h, len(vTx), _ptr(tx_off), _ptr(tx), _ptr(t0), _ptr(rx_off), _ptr(rx),
+                                                             _ptr(out), C.byref(h)))
+        tape = FieldTape(self._lib, h, dt, np.concatenate(iRx).astype(np.int64), rcv.shape[0])
         tt = np.zeros((rcv.shape[0],), dtype=dt)
         for n in range(len(vTx)):
             tt[iRx[n]] = out[rx_off[n]:rx_off[n + 1]]
@@ -489,6 +524,119 @@ class MTape:
         """Release the device memory now (also done when the tape is collected)."""
         if self._lib is not None and self._h:
             self._lib.ttcr_fsm_tape_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class FieldTape:
+    """The traveltime fields of a raytrace_adjoint call kept on the device (ttcr_fsm_raytrace_multi_adjoint, include/ttcr_amd.h), with
+    what the exact discrete adjoint of the first-order update needs besides them: the node slowness, the nodes each source froze and
+    the interpolation stencil of every (event, receiver) row.  Events are in the order raytrace takes them.  The tape does not depend
+    on the grid any more: later calls, set_slowness and deleting the grid leave it as it is."""
+
+    SCHEDULES = {'tiled': 0, 'jacobi': 1}
+
+    def __init__(self, lib, handle, dtype, rows, n_data):
+        self._lib = lib
+        self._h = handle
+        self.dtype = np.dtype(dtype)
+        self._rows = rows          # data row (index into rcv) of every tape row
+        self.n_data = int(n_data)
+        ne, nr, nc = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        _lib.check(lib.ttcr_fsm_adjoint_size(handle, C.byref(ne), C.byref(nr), C.byref(nc)))
+        self.n_events, self.n_rows, self.n_cols = ne.value, nr.value, nc.value
+        d, b = C.c_int(0), C.c_size_t(0)
+        _lib.check(lib.ttcr_fsm_adjoint_device(handle, C.byref(d)))
+        _lib.check(lib.ttcr_fsm_adjoint_bytes(handle, C.byref(b)))
+        self.device, self.nbytes = d.value, b.value
+        self.passes = 0            # relaxation passes of the last vjp
+        self._rows_dev = None
+
+    def _handle(self):
+        if not self._h:
+            raise ValueError('the tape has been freed')
+        return self._h
+
+    def field(self, event):
+        """Host copy of the traveltime field of one event: n_cols values of the grid dtype, node order (x fastest)."""
+        out = np.empty(max(self.n_cols, 1), dtype=self.dtype)
+        _lib.check(self._lib.ttcr_fsm_adjoint_get_field(self._handle(), int(event), _ptr(out)))
+        return out[:self.n_cols]
+
+    def _schedule(self, schedule):
+        if schedule not in self.SCHEDULES:
+            raise ValueError("schedule should be 'tiled' or 'jacobi', got %r" % (schedule,))
+        return self.SCHEDULES[schedule]
+
+    def vjp(self, w=None, field_cotangent=None, schedule='tiled'):
+        """d loss / d node slowness (n_cols values, x fastest, grid dtype) for  loss = w . tt + field_cotangent . fields.
+        w: one value per data row of the raytrace_adjoint call (rcv order); field_cotangent: (n_events, n_cols) values, node order x
+        fastest; either may be None, not both.  schedule: 'tiled' (default) or 'jacobi', the bit-equal baseline.  Torch tensors in give
+        a torch tensor out; tensors on the tape's device are used in place (torch's current stream is synchronised first, the result is
+        ready when the call returns)."""
+        self._handle()
+        sch = self._schedule(schedule)
+        if w is None and field_cotangent is None:
+            raise ValueError('w and field_cotangent are both None: nothing to back-propagate')
+        if any(type(a).__module__.startswith('torch') for a in (w, field_cotangent) if a is not None):
+            return self._vjp_torch(w, field_cotangent, sch)
+        wt = fc = None
+        if w is not None:
+            w = np.asarray(w)
+            if w.ndim != 1 or w.shape[0] != self.n_data:
+                raise ValueError('w should hold %d values (one per data row), got shape %s' % (self.n_data, w.shape))
+            wt = np.ascontiguousarray(w[self._rows], dtype=self.dtype)
+        if field_cotangent is not None:
+            fc = np.ascontiguousarray(field_cotangent, dtype=self.dtype)
+            if fc.size != self.n_events * self.n_cols:
+                raise ValueError('field_cotangent should hold %d x %d values, got shape %s' % (self.n_events, self.n_cols, fc.shape))
+        g = np.empty(max(self.n_cols, 1), dtype=self.dtype)
+        np_ = C.c_int(0)
+        _lib.check(self._lib.ttcr_fsm_adjoint_vjp(self._h, _ptr(wt) if wt is not None else None, 0, _ptr(fc) if fc is not None else None, 0,
+                                                  _ptr(g), 0, sch, C.byref(np_)))
+        self.passes = np_.value
+        return g[:self.n_cols]
+
+    def _vjp_torch(self, w, fc, sch):
+        import torch
+
+        tdt = torch.float32 if self.dtype == np.float32 else torch.float64
+        ref = w if (w is not None and type(w).__module__.startswith('torch')) else fc
+        if ref.device.type != 'cuda':
+            host = [a.detach().numpy() if hasattr(a, 'detach') else a for a in (w, fc)]
+            return torch.from_numpy(self.vjp(host[0], host[1], 'jacobi' if sch else 'tiled')).to(ref.device)
+        dev = torch.device('cuda', self.device)
+        wt = fct = None
+        if w is not None:
+            w = torch.as_tensor(w)
+            if w.dim() != 1 or w.shape[0] != self.n_data:
+                raise ValueError('w should hold %d values (one per data row), got shape %s' % (self.n_data, tuple(w.shape)))
+            if self._rows_dev is None:
+                self._rows_dev = torch.as_tensor(self._rows, device=dev)
+            wt = w.detach().to(device=dev, dtype=tdt).index_select(0, self._rows_dev).contiguous()
+        if fc is not None:
+            fc = torch.as_tensor(fc)
+            if fc.numel() != self.n_events * self.n_cols:
+                raise ValueError('field_cotangent should hold %d x %d values, got shape %s' % (self.n_events, self.n_cols, tuple(fc.shape)))
+            fct = fc.detach().to(device=dev, dtype=tdt).contiguous()
+        g = torch.empty(max(self.n_cols, 1), dtype=tdt, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        np_ = C.c_int(0)
+        _lib.check(self._lib.ttcr_fsm_adjoint_vjp(self._h, C.c_void_p(wt.data_ptr()) if wt is not None else None, 1,
+                                                  C.c_void_p(fct.data_ptr()) if fct is not None else None, 1, C.c_void_p(g.data_ptr()), 1,
+                                                  sch, C.byref(np_)))
+        self.passes = np_.value
+        return g[:self.n_cols].to(ref.device)
+
+    def free(self):
+        """Release the device memory now (also done when the tape is collected)."""
+        if self._lib is not None and self._h:
+            self._lib.ttcr_fsm_adjoint_free(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
