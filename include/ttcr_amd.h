@@ -385,7 +385,21 @@ int ttcr_fsm_tape_free(ttcr_fsm_tape* t);
  *   slower); anything else is TTCR_ERR_VALUE.  *passes (may be NULL): relaxation passes launched.  *_on_device != 0: a device pointer on
  *   the tape's device, else host memory.  The call returns with grad written; the tape runs on its own stream: the caller makes sure
  *   device-resident inputs are complete before the call.
- * Argument errors (a NULL tape or pointer, w and field_cot both NULL) return TTCR_ERR_VALUE before any device call. */
+ * ttcr_fsm_adjoint_jvp: the forward mode of the same linearisation: for a slowness perturbation ds (n_nodes values, shared
+ *   by the events), per event mu = dT/ds . ds with  mu[m] = fl(d_m * ds[m])  for m in F, and otherwise  mu[m] = fl(acc / D_m),
+ *   acc = fl(fl(dx * fl(s[m] * dx)) * ds[m]), then for the active axes x, y, z:  acc = fl(acc + fl(mu[u_axis] * fl(T[m] - a_axis)))  (u_axis
+ *   the upwind neighbour chosen above, a_axis its T);  dtt[row] = from +0, over the row's stencil entries in stencil order,
+ *   acc = fl(acc + fl(weight * mu[node])).  dtt: n_rows values in tape row order; dfields: n_events * n_nodes values (mu of every event);
+ *   either may be NULL, not both.  mu is the unique fixed point of a gather from strictly smaller T: the bits depend on no schedule, as
+ *   for the vjp; schedule and *passes as there.  The first jvp (or gn) of a tape allocates the stencil in row order, a staging row
+ *   and the stamps of its own tiles: 4 (n_rows + 1) + n_entries (8 + elem) + n_rows elem + 4 n_events n_tiles bytes, n_entries the
+ *   stencil entries of all rows (at most 8 per row), n_tiles the product over the axes of ceil(nodes / edge), edge = 10 (fp32) or 8
+ *   (fp64), which ttcr_fsm_adjoint_bytes reports from then on; TTCR_ERR_DEVICE with the byte count if that fails.
+ * ttcr_fsm_adjoint_gn: the Gauss-Newton product out = J^T (row_weight * (J v)) (n_nodes values): the jvp of v, every row multiplied by
+ *   row_weight[row] (n_rows values in tape row order; NULL: no weight), the vjp of the result -- with the bits of the two calls composed,
+ *   and no host copy in between.  *passes_jvp, *passes_vjp (may be NULL): the passes of the two relaxations.
+ * Argument errors (a NULL tape or pointer, w and field_cot both NULL, dtt and dfields both NULL) return TTCR_ERR_VALUE before any device
+ * call. */
 typedef struct ttcr_fsm_adjoint ttcr_fsm_adjoint; /* opaque */
 int ttcr_fsm_raytrace_multi_adjoint(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off,
                                     const void* rx, void* tt_out, ttcr_fsm_adjoint** tape);
@@ -395,6 +409,10 @@ int ttcr_fsm_adjoint_device(const ttcr_fsm_adjoint* t, int* device);
 int ttcr_fsm_adjoint_get_field(const ttcr_fsm_adjoint* t, size_t event, void* out);
 int ttcr_fsm_adjoint_vjp(const ttcr_fsm_adjoint* t, const void* w, int w_on_device, const void* field_cot, int fc_on_device, void* grad,
                          int grad_on_device, int schedule, int* passes);
+int ttcr_fsm_adjoint_jvp(const ttcr_fsm_adjoint* t, const void* ds, int ds_on_device, void* dtt, int dtt_on_device, void* dfields,
+                         int df_on_device, int schedule, int* passes);
+int ttcr_fsm_adjoint_gn(const ttcr_fsm_adjoint* t, const void* v, int v_on_device, const void* row_weight, int rw_on_device, void* out,
+                        int out_on_device, int schedule, int* passes_jvp, int* passes_vjp);
 int ttcr_fsm_adjoint_free(ttcr_fsm_adjoint* t);
 
 /* Replaces: Grid2D::raytrace(Tx, t0, Rx, traveltimes, l_data, threadNo) (ttcr/Grid2D.h:616-640) and the overload with r_data

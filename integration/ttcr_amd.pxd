@@ -78,6 +78,11 @@ cdef extern from "ttcr_amd.h" nogil:
     int ttcr_fsm_adjoint_get_field(const ttcr_fsm_adjoint* t, size_t event, void* out)
     int ttcr_fsm_adjoint_vjp(const ttcr_fsm_adjoint* t, const void* w, int w_on_device, const void* field_cot, int fc_on_device,
                              void* grad, int grad_on_device, int schedule, int* passes)
+    # forward mode of the same linearisation: J v (receiver rows and / or fields) and the Gauss-Newton product J^T (row_weight * J v)
+    int ttcr_fsm_adjoint_jvp(const ttcr_fsm_adjoint* t, const void* ds, int ds_on_device, void* dtt, int dtt_on_device,
+                             void* dfields, int df_on_device, int schedule, int* passes)
+    int ttcr_fsm_adjoint_gn(const ttcr_fsm_adjoint* t, const void* v, int v_on_device, const void* row_weight, int rw_on_device,
+                            void* out, int out_on_device, int schedule, int* passes_jvp, int* passes_vjp)
     int ttcr_fsm_adjoint_free(ttcr_fsm_adjoint* t)
     int ttcr_fsm_slot_m_size(const ttcr_fsm_grid* g, int slot, size_t* n_rows, size_t* nnz)
     int ttcr_fsm_get_slot_m(const ttcr_fsm_grid* g, int slot, long long* row_off, long long* j, void* v)

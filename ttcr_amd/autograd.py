@@ -15,7 +15,8 @@ is the same operator with the EXACT derivative: the forward runs grid.raytrace_a
 with tt_from_rp=0 returns them; 3-D node grids with weno=0), the backward is the adjoint-state gradient FieldTape.vjp -- the derivative
 of the returned tt through the solver's own first-order update -- times d slowness / d velocity = -1 / velocity**2, in velocity's layout.
 With return_fields=True it returns (tt, fields), fields the (n_events, nx, ny, nz) traveltime fields, differentiable too: a loss on the
-grid traveltimes has a gradient.
+grid traveltimes has a gradient.  Forward mode works as well (torch.autograd.forward_ad): the tangent of the outputs for a velocity
+tangent tv is FieldTape.jvp(-(tv / velocity**2)), J v of the same linearisation, in the layout of the outputs.
 
 torch is imported when this module is used, never by `import ttcr_amd`.
 """
@@ -79,6 +80,8 @@ def _adjoint_function():
             ctx.tape = tape
             ctx.layout = (tuple(velocity.shape), (nx, ny, nz))
             ctx.save_for_backward(velocity)
+            ctx.save_for_forward(velocity)
+            ctx.return_fields = return_fields
             out = torch.from_numpy(tt).to(velocity.device)
             if not return_fields:
                 return out
@@ -96,6 +99,17 @@ def _adjoint_function():
             # node order x fastest -> (nx, ny, nz) in C order -> velocity's layout; d slowness / d velocity = -1 / velocity^2
             gs = gn.reshape(nz, ny, nx).permute(2, 1, 0).contiguous().reshape(shape).to(velocity.dtype)
             return -gs / (velocity * velocity), None, None, None, None, None
+
+        @staticmethod
+        def jvp(ctx, tv, *_):
+            shape, (nx, ny, nz) = ctx.layout
+            (velocity,) = ctx.saved_tensors
+            # d slowness = -(tv / velocity^2), velocity's layout -> (nx, ny, nz) in C order -> node order x fastest
+            ds = (-(tv / (velocity * velocity))).reshape(nx, ny, nz).permute(2, 1, 0).contiguous().reshape(-1)
+            if not ctx.return_fields:
+                return ctx.tape.jvp(ds)
+            dtt, df = ctx.tape.jvp(ds, return_fields=True)
+            return dtt, df.reshape(df.shape[0], nz, ny, nx).permute(0, 3, 2, 1).contiguous()
 
     _AdjFn = RaytraceAdjointFn
     return _AdjFn

@@ -1,5 +1,5 @@
-// ttcr_amd/csrc/fsm_adjoint.hip -- translation unit of the field tape's kernels (coupling, seeds, relaxation, gradient); see
-// fsm_adjoint_api.h and DESIGN.md 6b.  Compiled with -ffp-contract=off like every other unit: each product, difference, quotient and sum
+// ttcr_amd/csrc/fsm_adjoint.hip -- translation unit of the field tape's kernels (coupling, seeds, relaxation, gradient; the forward-mode
+// tangent: relaxation, receiver rows); see fsm_adjoint_api.h and DESIGN.md 6b, 6c.  Compiled with -ffp-contract=off like every other unit: each product, difference, quotient and sum
 // below is rounded on its own, in the order the definition writes them.
 #include "fsm_adjoint_api.h"
 
@@ -9,6 +9,7 @@
 #include <limits>
 #include <numeric>
 #include <sstream>
+#include <string>
 
 #define ADJ_CHECK(expr)                                                                                           \
     do {                                                                                                          \
@@ -258,6 +259,182 @@ __global__ void adj_grad_kernel(const T* __restrict__ lam, const T* __restrict__
     grad[m] = acc;
 }
 
+// ---- forward mode: mu = dT/ds . ds per event, the same triangular system run the other way.
+// interior edge of a tangent tile: mu and T of a tile with its one-node halo take 2 * (edge + 2)^3 * sizeof(T) bytes of LDS (13.5 KiB fp32,
+// 15.6 KiB fp64).  Smaller than the adjoint's tile (a step re-evaluates every node of the tile, and a tile needs about 3 * edge steps), so
+// the forward mode keeps stamps of its own.
+template <typename T> struct TanTile;
+template <> struct TanTile<float> { static constexpr int edge = 10; };
+template <> struct TanTile<double> { static constexpr int edge = 8; };
+
+// Global Jacobi pass of the tangent (the correctness baseline): out = gather(in).  The upwind choice is recomputed from the field:
+//   mu[m] = fl(d_m * ds[m])                                                           m frozen
+//   mu[m] = fl(acc / D_m), acc = fl(fl(dx * fl(s[m] * dx)) * ds[m]), then per active axis x, y, z: acc = fl(acc + fl(mu[u] * fl(T[m] - a)))
+template <typename T>
+__global__ void tan_jacobi_kernel(const T* __restrict__ fields, const T* __restrict__ D, const unsigned char* __restrict__ frozen,
+                                  const T* __restrict__ s, const T* __restrict__ ds, const T* __restrict__ mu_in, T* __restrict__ mu_out,
+                                  AdjGeom<T> geo, const int* __restrict__ prev, int* __restrict__ cur) {
+    const int e = blockIdx.y;
+    if (prev && prev[e] == 0) return;   // (both buffers of the event hold the fixed point already)
+    const size_t m = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    int changed = 0;
+    if (m < geo.nn) {
+        const size_t idx = (size_t)e * geo.nn + m;
+        const T inf = std::numeric_limits<T>::infinity();
+        const int pos[3] = {(int)(m % geo.nnx), (int)((m / geo.nnx) % geo.nny), (int)(m / ((size_t)geo.nnx * geo.nny))};
+        const int ext[3] = {geo.nnx, geo.nny, geo.nnz};
+        const long long st[3] = {1, (long long)geo.nnx, (long long)geo.nnx * geo.nny};
+        const T* F = fields + idx;
+        const T* L = mu_in + idx;
+        const T t = F[0];
+        T v;
+        if (frozen[idx]) {
+            v = D[idx] * ds[m];
+        } else {
+            T acc = (geo.dx * (s[m] * geo.dx)) * ds[m];
+            for (int ax = 0; ax < 3; ++ax) {
+                const T lo = pos[ax] > 0 ? F[-st[ax]] : inf;
+                const T hi = pos[ax] < ext[ax] - 1 ? F[st[ax]] : inf;
+                const bool up = hi < lo;
+                const T a = up ? hi : lo;
+                if (a < t) acc = acc + (up ? L[st[ax]] : L[-st[ax]]) * (t - a);
+            }
+            v = acc / D[idx];
+        }
+        changed = !same_bits(v, L[0]);
+        mu_out[idx] = v;
+    }
+    if (__syncthreads_or(changed) && threadIdx.x == 0) cur[e] = 1;
+}
+
+// Tiled relaxation of the tangent: one workgroup per tile and event.  mu and T of the tile and its one-node halo are staged in LDS (+inf
+// for T outside the grid, so that the upwind choice of 6b falls out of the staged values); every thread keeps, for its interior nodes, the
+// own term, D, the upwind choice (2 bits per axis: active, upper) and the differences T[m] - a in registers, so a Jacobi step reads mu only.
+// Frozen nodes: own term d * ds, no axis, divisor 1 (exact).  Stamps and passes as in adj_tiled_kernel.
+template <typename T, int TI>
+__global__ __launch_bounds__(ADJ_THREADS) void tan_tiled_kernel(const T* __restrict__ fields, const T* __restrict__ D,
+                                                                 const unsigned char* __restrict__ frozen, const T* __restrict__ s,
+                                                                 const T* __restrict__ ds, T* mu, AdjGeom<T> geo, int ntx, int nty, int ntz,
+                                                                 int* stamps, int pass, int* __restrict__ cur) {
+    constexpr int TH = TI + 2, NH = TH * TH * TH, NI = TI * TI * TI, NPT = (NI + ADJ_THREADS - 1) / ADJ_THREADS;
+    __shared__ T sL[NH], sF[NH];
+    const int e = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
+    const int tx = tile % ntx, ty = (tile / ntx) % nty, tz = tile / (ntx * nty);
+    int* st = stamps + (size_t)e * ntx * nty * ntz;
+    if (pass > 0) {
+        const int since = pass - 1;
+        bool run = false;
+        if (tx > 0) run |= st[tile - 1] >= since;
+        if (tx < ntx - 1) run |= st[tile + 1] >= since;
+        if (ty > 0) run |= st[tile - ntx] >= since;
+        if (ty < nty - 1) run |= st[tile + ntx] >= since;
+        if (tz > 0) run |= st[tile - ntx * nty] >= since;
+        if (tz < ntz - 1) run |= st[tile + ntx * nty] >= since;
+        if (!run) return;
+    }
+    const T inf = std::numeric_limits<T>::infinity();
+    const size_t base = (size_t)e * geo.nn;
+    const int x0 = tx * TI - 1, y0 = ty * TI - 1, z0 = tz * TI - 1;
+    for (int h = tid; h < NH; h += ADJ_THREADS) {
+        const int x = x0 + h % TH, y = y0 + (h / TH) % TH, z = z0 + h / (TH * TH);
+        const bool inside = x >= 0 && x < geo.nnx && y >= 0 && y < geo.nny && z >= 0 && z < geo.nnz;
+        const size_t idx = base + ((size_t)(inside ? z : 0) * geo.nny + (inside ? y : 0)) * geo.nnx + (inside ? x : 0);
+        sL[h] = inside ? mu[idx] : (T)0;
+        sF[h] = inside ? fields[idx] : inf;
+    }
+    __syncthreads();
+    // the interior nodes of this thread (hq < 0: outside the grid)
+    int hq[NPT];
+    unsigned cq[NPT];
+    T bq[NPT], dq[NPT], c0[NPT], c1[NPT], c2[NPT];
+    for (int q = 0; q < NPT; ++q) {
+        const int n = tid + q * ADJ_THREADS;
+        hq[q] = -1; cq[q] = 0; bq[q] = 0; dq[q] = 1; c0[q] = 0; c1[q] = 0; c2[q] = 0;
+        if (n >= NI) continue;
+        const int lx = n % TI, ly = (n / TI) % TI, lz = n / (TI * TI);
+        const int x = x0 + 1 + lx, y = y0 + 1 + ly, z = z0 + 1 + lz;
+        if (x >= geo.nnx || y >= geo.nny || z >= geo.nnz) continue;
+        const int h = ((lz + 1) * TH + ly + 1) * TH + lx + 1;
+        const size_t m = ((size_t)z * geo.nny + y) * geo.nnx + x;
+        hq[q] = h;
+        if (frozen[base + m]) {
+            bq[q] = D[base + m] * ds[m];
+            continue;
+        }
+        bq[q] = (geo.dx * (s[m] * geo.dx)) * ds[m];
+        dq[q] = D[base + m];
+        const T t = sF[h];
+        unsigned code = 0;
+        {
+            const T lo = sF[h - 1], hi = sF[h + 1];
+            const bool up = hi < lo;
+            const T a = up ? hi : lo;
+            if (a < t) { code |= up ? 3u : 1u; c0[q] = t - a; }
+        }
+        {
+            const T lo = sF[h - TH], hi = sF[h + TH];
+            const bool up = hi < lo;
+            const T a = up ? hi : lo;
+            if (a < t) { code |= up ? 12u : 4u; c1[q] = t - a; }
+        }
+        {
+            const T lo = sF[h - TH * TH], hi = sF[h + TH * TH];
+            const bool up = hi < lo;
+            const T a = up ? hi : lo;
+            if (a < t) { code |= up ? 48u : 16u; c2[q] = t - a; }
+        }
+        cq[q] = code;
+    }
+    bool tile_changed = false;
+    for (int it = 0; it <= NI; ++it) {
+        T nv[NPT];
+        for (int q = 0; q < NPT; ++q) {
+            if (hq[q] < 0) continue;
+            const T* L = sL + hq[q];
+            const unsigned code = cq[q];
+            T acc = bq[q];
+            if (code & 1u) acc = acc + L[(code & 2u) ? 1 : -1] * c0[q];
+            if (code & 4u) acc = acc + L[(code & 8u) ? TH : -TH] * c1[q];
+            if (code & 16u) acc = acc + L[(code & 32u) ? TH * TH : -TH * TH] * c2[q];
+            nv[q] = acc / dq[q];
+        }
+        __syncthreads();   // every read of this step is done
+        int ch = 0;
+        for (int q = 0; q < NPT; ++q) {
+            if (hq[q] < 0) continue;
+            if (!same_bits(nv[q], sL[hq[q]])) { sL[hq[q]] = nv[q]; ch = 1; }
+        }
+        if (!__syncthreads_or(ch)) break;
+        tile_changed = true;
+    }
+    if (!tile_changed) return;
+    for (int q = 0; q < NPT; ++q) {
+        if (hq[q] < 0) continue;
+        const int n = tid + q * ADJ_THREADS;
+        const int x = x0 + 1 + n % TI, y = y0 + 1 + (n / TI) % TI, z = z0 + 1 + n / (TI * TI);
+        mu[base + ((size_t)z * geo.nny + y) * geo.nnx + x] = sL[hq[q]];
+    }
+    if (tid == 0) { st[tile] = pass; cur[e] = 1; }
+}
+
+// dtt[row] = from +0, over the row's stencil entries in interp3d_stencil order: acc = fl(acc + fl(weight * mu[node])); one thread per row
+template <typename T>
+__global__ void tan_rows_kernel(const int* __restrict__ off, const long long* __restrict__ key, const T* __restrict__ wt, size_t n_rows,
+                                const T* __restrict__ mu, T* __restrict__ dtt) {
+    const size_t r = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (r >= n_rows) return;
+    T acc = 0;
+    for (int c = off[r]; c < off[r + 1]; ++c) acc = acc + wt[c] * mu[key[c]];
+    dtt[r] = acc;
+}
+
+// w[row] = fl(rw[row] * w[row])
+template <typename T>
+__global__ void tan_scale_rows_kernel(const T* __restrict__ rw, T* __restrict__ w, size_t n_rows) {
+    const size_t r = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (r < n_rows) w[r] = rw[r] * w[r];
+}
+
 struct Alloc {
     AdjTapeDev& t;
     size_t planned;
@@ -283,10 +460,8 @@ void dev_free(P*& p) {
     p = nullptr;
 }
 
-size_t tiles_of(const AdjTapeDev& t) {
-    const int ed = adj_tile_edge(t.elem);
-    return (size_t)((t.nnx + ed - 1) / ed) * ((t.nny + ed - 1) / ed) * ((t.nnz + ed - 1) / ed);
-}
+size_t tiles_of(const AdjTapeDev& t, int ed) { return (size_t)((t.nnx + ed - 1) / ed) * ((t.nny + ed - 1) / ed) * ((t.nnz + ed - 1) / ed); }
+size_t tiles_of(const AdjTapeDev& t) { return tiles_of(t, adj_tile_edge(t.elem)); }
 
 // every byte the finished tape holds (the figure an allocation failure names): fields, D, g, lam, lam2; inmask, frozen; slowness and the
 // staged gradient; the staged w; the seed entries (8 per row at most); flags, stamps, error flag
@@ -299,6 +474,7 @@ size_t planned_bytes(const AdjTapeDev& t) {
 }  // namespace
 
 int adj_tile_edge(size_t elem) { return elem == 4 ? AdjTile<float>::edge : AdjTile<double>::edge; }
+int adj_tan_tile_edge(size_t elem) { return elem == 4 ? TanTile<float>::edge : TanTile<double>::edge; }
 
 void AdjTapeDev::release() {
     if (!fields && !stream) return;
@@ -306,6 +482,7 @@ void AdjTapeDev::release() {
     if (stream) (void)hipStreamSynchronize(stream);
     dev_free(fields); dev_free(slowness); dev_free(D); dev_free(inmask); dev_free(frozen); dev_free(g); dev_free(lam); dev_free(lam2);
     dev_free(sd_key); dev_free(sd_row); dev_free(sd_w); dev_free(flags); dev_free(stamps); dev_free(err); dev_free(w_tmp); dev_free(grad_tmp);
+    dev_free(rw_off); dev_free(rw_key); dev_free(rw_w); dev_free(rw_tmp); dev_free(tan_stamps);
     if (stream) (void)hipStreamDestroy(stream);
     stream = nullptr;
     total_bytes = 0;
@@ -357,6 +534,11 @@ void adj_finish(AdjTapeDev& t, const AdjSink& sink) {
     for (size_t q = 0; q < ord.size(); ++q) { key2[q] = key[ord[q]]; row2[q] = row[ord[q]]; wt2[q] = wt[ord[q]]; }
     t.n_seed = key2.size();
     t.n_tiles = tiles_of(t);
+    // the same entries in row order, for the forward mode: kept on the host until the first jvp uploads them
+    t.h_rw_off.assign(t.n_rows + 1, 0);
+    for (size_t r = 0; r < t.n_rows; ++r) t.h_rw_off[r + 1] = t.h_rw_off[r] + sink.st_cnt[r];
+    t.h_rw_key = key;
+    t.h_rw_w.assign(wt.begin(), wt.end());
 
     Alloc alloc{t, planned_bytes(t)};
     alloc(t.D, en * t.elem);
@@ -411,6 +593,35 @@ void adj_finish(AdjTapeDev& t, const AdjSink& sink) {
     }
 }
 
+// Passes until one changes nothing in any event: launch(pass, prev, cur) enqueues pass `pass`, which raises cur[e] if it changed a value of
+// event e (prev: the flags of the pass before, null for pass 0).  The host reads the flags every ADJ_CHECK_EVERY passes.  Returns the
+// passes launched.
+template <typename Launch>
+int relax_to_fixed_point(AdjTapeDev& t, const char* what, Launch launch) {
+    hipStream_t s = t.stream;
+    const size_t E = t.n_events;
+    std::vector<int> h_flags((size_t)ADJ_RING * E);
+    const size_t max_passes = t.nn + ADJ_CHECK_EVERY + 1;   // (the depth of the DAG is below the node count)
+    int passes = 0;
+    for (;;) {
+        for (int k = 0; k < ADJ_CHECK_EVERY; ++k, ++passes) {
+            int* cur = t.flags + (size_t)(passes % ADJ_RING) * E;
+            const int* prev = passes > 0 ? t.flags + (size_t)((passes - 1) % ADJ_RING) * E : nullptr;
+            ADJ_CHECK(hipMemsetAsync(cur, 0, E * sizeof(int), s));
+            launch(passes, prev, cur);
+            ADJ_CHECK(hipGetLastError());
+        }
+        ADJ_CHECK(hipMemcpyAsync(h_flags.data(), t.flags, h_flags.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+        ADJ_CHECK(hipStreamSynchronize(s));
+        const int* last = h_flags.data() + (size_t)((passes - 1) % ADJ_RING) * E;
+        bool any = false;
+        for (size_t e = 0; e < E; ++e) any = any || last[e] != 0;
+        if (!any) return passes;
+        if ((size_t)passes > max_passes)
+            throw std::runtime_error(std::string(what) + ": internal error, the relaxation did not reach its fixed point");
+    }
+}
+
 template <typename T>
 int adj_vjp(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, int schedule) {
     ADJ_CHECK(hipSetDevice(t.device));
@@ -431,33 +642,18 @@ int adj_vjp(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, int schedule)
         if (schedule == 0) ADJ_CHECK(hipMemsetAsync(t.stamps, 0xFF, E * t.n_tiles * sizeof(int), s));
         const int ed = adj_tile_edge(sizeof(T));
         const int ntx = (t.nnx + ed - 1) / ed, nty = (t.nny + ed - 1) / ed, ntz = (t.nnz + ed - 1) / ed;
-        std::vector<int> h_flags((size_t)ADJ_RING * E);
         T* in = lam;
         T* out = (T*)t.lam2;
-        const size_t max_passes = t.nn + ADJ_CHECK_EVERY + 1;   // (the depth of the DAG is below the node count)
-        for (;;) {
-            for (int k = 0; k < ADJ_CHECK_EVERY; ++k, ++passes) {
-                int* cur = t.flags + (size_t)(passes % ADJ_RING) * E;
-                const int* prev = passes > 0 ? t.flags + (size_t)((passes - 1) % ADJ_RING) * E : nullptr;
-                ADJ_CHECK(hipMemsetAsync(cur, 0, E * sizeof(int), s));
-                if (schedule == 0) {
-                    adj_tiled_kernel<T, AdjTile<T>::edge><<<dim3((unsigned)t.n_tiles, (unsigned)E), ADJ_THREADS, 0, s>>>(
-                        (const T*)t.fields, (const T*)t.D, t.inmask, g, lam, geo, ntx, nty, ntz, t.stamps, passes, cur);
-                } else {
-                    adj_jacobi_kernel<T><<<dim3(blocks_for(t.nn), (unsigned)E), ADJ_THREADS, 0, s>>>((const T*)t.fields, (const T*)t.D, t.inmask, g,
-                                                                                                    in, out, geo, prev, cur);
-                    std::swap(in, out);
-                }
-                ADJ_CHECK(hipGetLastError());
+        passes = relax_to_fixed_point(t, "adjoint", [&](int pass, const int* prev, int* cur) {
+            if (schedule == 0) {
+                adj_tiled_kernel<T, AdjTile<T>::edge><<<dim3((unsigned)t.n_tiles, (unsigned)E), ADJ_THREADS, 0, s>>>(
+                    (const T*)t.fields, (const T*)t.D, t.inmask, g, lam, geo, ntx, nty, ntz, t.stamps, pass, cur);
+            } else {
+                adj_jacobi_kernel<T><<<dim3(blocks_for(t.nn), (unsigned)E), ADJ_THREADS, 0, s>>>((const T*)t.fields, (const T*)t.D, t.inmask, g,
+                                                                                                in, out, geo, prev, cur);
+                std::swap(in, out);
             }
-            ADJ_CHECK(hipMemcpyAsync(h_flags.data(), t.flags, h_flags.size() * sizeof(int), hipMemcpyDeviceToHost, s));
-            ADJ_CHECK(hipStreamSynchronize(s));
-            const int* last = h_flags.data() + (size_t)((passes - 1) % ADJ_RING) * E;
-            bool any = false;
-            for (size_t e = 0; e < E; ++e) any = any || last[e] != 0;
-            if (!any) break;
-            if ((size_t)passes > max_passes) throw std::runtime_error("adjoint: internal error, the relaxation did not reach its fixed point");
-        }
+        });
         if (schedule != 0) lam = in;   // (the buffer the last pass wrote; both hold the fixed point)
     }
     if (t.nn > 0) {
@@ -467,11 +663,100 @@ int adj_vjp(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, int schedule)
     return passes;
 }
 
+// what the first jvp adds to the tape: the stencil in row order (offsets, keys, weights), a staging row for a host row_weight and the
+// stamps of the tangent tiles
+size_t adj_jvp_extra_bytes(const AdjTapeDev& t) {
+    return (t.n_rows + 1) * sizeof(int) + t.n_seed * (sizeof(long long) + t.elem) + t.n_rows * t.elem +
+           t.n_events * tiles_of(t, adj_tan_tile_edge(t.elem)) * sizeof(int);
+}
+
+template <typename T>
+void adj_jvp_prepare(AdjTapeDev& t) {
+    if (t.rw_off) return;
+    ADJ_CHECK(hipSetDevice(t.device));
+    Alloc alloc{t, adj_jvp_extra_bytes(t)};
+    const size_t before = t.total_bytes;
+    try {
+        alloc(t.rw_off, (t.n_rows + 1) * sizeof(int));
+        alloc(t.rw_key, t.n_seed * sizeof(long long));
+        alloc(t.rw_w, t.n_seed * sizeof(T));
+        alloc(t.rw_tmp, t.n_rows * sizeof(T));
+        t.n_tan_tiles = tiles_of(t, TanTile<T>::edge);
+        alloc(t.tan_stamps, t.n_events * t.n_tan_tiles * sizeof(int));
+        const std::vector<T> wt(t.h_rw_w.begin(), t.h_rw_w.end());
+        ADJ_CHECK(hipMemcpyAsync(t.rw_off, t.h_rw_off.data(), (t.n_rows + 1) * sizeof(int), hipMemcpyHostToDevice, t.stream));
+        if (t.n_seed > 0) {
+            ADJ_CHECK(hipMemcpyAsync(t.rw_key, t.h_rw_key.data(), t.n_seed * sizeof(long long), hipMemcpyHostToDevice, t.stream));
+            ADJ_CHECK(hipMemcpyAsync(t.rw_w, wt.data(), t.n_seed * sizeof(T), hipMemcpyHostToDevice, t.stream));
+        }
+        ADJ_CHECK(hipStreamSynchronize(t.stream));   // (wt leaves scope)
+    } catch (...) {
+        dev_free(t.rw_off); dev_free(t.rw_key); dev_free(t.rw_w); dev_free(t.rw_tmp); dev_free(t.tan_stamps);
+        t.total_bytes = before;
+        throw;
+    }
+}
+
+template <typename T>
+int adj_jvp(AdjTapeDev& t, const T* d_ds, T* d_dtt, T* d_dfields, int schedule) {
+    ADJ_CHECK(hipSetDevice(t.device));
+    adj_jvp_prepare<T>(t);
+    hipStream_t s = t.stream;
+    const size_t E = t.n_events, en = E * t.nn;
+    const AdjGeom<T> geo{t.nnx, t.nny, t.nnz, t.nn, (T)t.dx};
+    T* mu = (T*)t.lam;
+    int passes = 0;
+    if (en > 0) {
+        ADJ_CHECK(hipMemsetAsync(mu, 0, en * sizeof(T), s));   // (+0: any start reaches the fixed point)
+        if (schedule == 0) ADJ_CHECK(hipMemsetAsync(t.tan_stamps, 0xFF, E * t.n_tan_tiles * sizeof(int), s));
+        constexpr int ed = TanTile<T>::edge;
+        const int ntx = (t.nnx + ed - 1) / ed, nty = (t.nny + ed - 1) / ed, ntz = (t.nnz + ed - 1) / ed;
+        const unsigned tiles = (unsigned)t.n_tan_tiles;
+        T* in = mu;
+        T* out = (T*)t.lam2;
+        passes = relax_to_fixed_point(t, "tangent", [&](int pass, const int* prev, int* cur) {
+            if (schedule == 0) {
+                tan_tiled_kernel<T, ed><<<dim3(tiles, (unsigned)E), ADJ_THREADS, 0, s>>>((const T*)t.fields, (const T*)t.D, t.frozen,
+                                                                                        (const T*)t.slowness, d_ds, mu, geo, ntx, nty, ntz,
+                                                                                        t.tan_stamps, pass, cur);
+            } else {
+                tan_jacobi_kernel<T><<<dim3(blocks_for(t.nn), (unsigned)E), ADJ_THREADS, 0, s>>>(
+                    (const T*)t.fields, (const T*)t.D, t.frozen, (const T*)t.slowness, d_ds, in, out, geo, prev, cur);
+                std::swap(in, out);
+            }
+        });
+        if (schedule != 0) mu = in;   // (the buffer the last pass wrote; both hold the fixed point)
+    }
+    if (d_dtt && t.n_rows > 0) {
+        tan_rows_kernel<T><<<blocks_for(t.n_rows), ADJ_THREADS, 0, s>>>(t.rw_off, t.rw_key, (const T*)t.rw_w, t.n_rows, mu, d_dtt);
+        ADJ_CHECK(hipGetLastError());
+    }
+    if (d_dfields && en > 0) ADJ_CHECK(hipMemcpyAsync(d_dfields, mu, en * sizeof(T), hipMemcpyDeviceToDevice, s));
+    return passes;
+}
+
+template <typename T>
+void adj_gn(AdjTapeDev& t, const T* d_v, const T* d_rw, T* d_out, int schedule, int* passes_jvp, int* passes_vjp) {
+    T* w = (T*)t.w_tmp;
+    *passes_jvp = adj_jvp<T>(t, d_v, w, nullptr, schedule);
+    if (d_rw && t.n_rows > 0) {
+        tan_scale_rows_kernel<T><<<blocks_for(t.n_rows), ADJ_THREADS, 0, t.stream>>>(d_rw, w, t.n_rows);
+        ADJ_CHECK(hipGetLastError());
+    }
+    *passes_vjp = adj_vjp<T>(t, w, nullptr, d_out, schedule);
+}
+
 template void adj_copy_field<float>(const float*, int, float*, size_t, hipStream_t);
 template void adj_copy_field<double>(const double*, int, double*, size_t, hipStream_t);
 template void adj_finish<float>(AdjTapeDev&, const AdjSink&);
 template void adj_finish<double>(AdjTapeDev&, const AdjSink&);
 template int adj_vjp<float>(AdjTapeDev&, const float*, const float*, float*, int);
 template int adj_vjp<double>(AdjTapeDev&, const double*, const double*, double*, int);
+template void adj_jvp_prepare<float>(AdjTapeDev&);
+template void adj_jvp_prepare<double>(AdjTapeDev&);
+template int adj_jvp<float>(AdjTapeDev&, const float*, float*, float*, int);
+template int adj_jvp<double>(AdjTapeDev&, const double*, double*, double*, int);
+template void adj_gn<float>(AdjTapeDev&, const float*, const float*, float*, int, int*, int*);
+template void adj_gn<double>(AdjTapeDev&, const double*, const double*, double*, int, int*, int*);
 
 }  // namespace ttcr_amd

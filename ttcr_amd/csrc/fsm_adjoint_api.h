@@ -4,6 +4,8 @@
 //
 // Per tape, once:   frozen marks -> coupling pass (per node and event: D, the sum of the active upwind differences, and the 6-bit mask of the
 //                   neighbours that have this node as an active upwind neighbour).
+// Per JVP:          relaxation of mu = own term + gather(mu) over the at most three upwind neighbours (the same two schedules; the upwind
+//                   choice is recomputed from the field) -> receiver rows through the stencil, one thread per row.
 // Per VJP:          seed (g = field cotangent + receiver rows through the interpolation stencil, one serial chain per node in row order)
 //                   -> relaxation of lam = g + gather(lam) to its fixed point (tiled in LDS, or the global Jacobi baseline)
 //                   -> gradient (events summed in ascending order from +0 inside the thread).
@@ -59,7 +61,17 @@ struct AdjTapeDev {
     int* stamps = nullptr;            // per event and tile: the last pass that changed the tile
     int* err = nullptr;               // internal error flag of the coupling pass
     void* w_tmp = nullptr;            // n_rows (host w staged here)
-    void* grad_tmp = nullptr;         // nn (host grad staged here)
+    void* grad_tmp = nullptr;         // nn (host grad staged here; a host ds of the forward mode too)
+    // forward mode (allocated and uploaded by the first jvp): the stencil entries in row order, and a staging row for a host row_weight
+    int* rw_off = nullptr;            // n_rows + 1: entries of row r at rw_off[r] .. rw_off[r + 1]
+    long long* rw_key = nullptr;      // event * nn + node
+    void* rw_w = nullptr;
+    void* rw_tmp = nullptr;           // n_rows
+    int* tan_stamps = nullptr;        // per event and tangent tile: the last pass that changed the tile
+    size_t n_tan_tiles = 0;
+    std::vector<int> h_rw_off;        // host copies, kept from adj_finish on
+    std::vector<long long> h_rw_key;
+    std::vector<double> h_rw_w;
     size_t n_tiles = 0;
     size_t total_bytes = 0;
     hipStream_t stream = nullptr;
@@ -69,6 +81,7 @@ struct AdjTapeDev {
 
 // edge of a relaxation tile (interior nodes) for an element size
 int adj_tile_edge(size_t elem);
+int adj_tan_tile_edge(size_t elem);   // the forward mode's
 // allocates fields and slowness (what the solves write into); throws AdjDeviceError naming the byte count
 void adj_alloc_fields(AdjTapeDev& t);
 // strided field (element n at src[n * ts]) -> contiguous dst, both on the current device
@@ -80,5 +93,16 @@ void adj_finish(AdjTapeDev& t, const AdjSink& sink);
 // d_w (n_rows, may be null), d_fc (n_events * nn, may be null), d_grad (nn): all on the tape's device; returns the passes launched
 template <typename T>
 int adj_vjp(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, int schedule);
+// forward mode (tests/tangent_reference.py restates it): d_ds (nn), d_dtt (n_rows, may be null), d_dfields (n_events * nn, may be
+// null); relaxes mu = dT/ds . ds in lam / lam2 to its fixed point (the same two schedules), then one thread per receiver row; returns the
+// passes launched.  The first call allocates adj_jvp_extra_bytes(t) more (AdjDeviceError naming the byte count if that fails).
+size_t adj_jvp_extra_bytes(const AdjTapeDev& t);
+template <typename T>
+void adj_jvp_prepare(AdjTapeDev& t);   // that allocation and the upload of the row-order stencil; a no-op from the second call on
+template <typename T>
+int adj_jvp(AdjTapeDev& t, const T* d_ds, T* d_dtt, T* d_dfields, int schedule);
+// Gauss-Newton product: jvp into w_tmp -> w_tmp *= d_rw (may be null) -> vjp into d_out (nn), all on the tape's stream
+template <typename T>
+void adj_gn(AdjTapeDev& t, const T* d_v, const T* d_rw, T* d_out, int schedule, int* passes_jvp, int* passes_vjp);
 
 }  // namespace ttcr_amd

@@ -3901,6 +3901,83 @@ int ttcr_fsm_adjoint_vjp(const ttcr_fsm_adjoint* t, const void* w, int w_on_devi
         });
     });
 }
+int ttcr_fsm_adjoint_jvp(const ttcr_fsm_adjoint* t, const void* ds, int ds_on_device, void* dtt, int dtt_on_device, void* dfields,
+                         int df_on_device, int schedule, int* passes) {
+    if (!t || !ds || (!dtt && !dfields)) {
+        g_last_error = !t ? "null tape" : (!ds ? "null ds" : "dtt and dfields are both null: nothing to compute");
+        return TTCR_ERR_VALUE;
+    }
+    if (schedule != 0 && schedule != 1) {
+        g_last_error = "schedule: 0 (tiled) or 1 (global Jacobi)";
+        return TTCR_ERR_VALUE;
+    }
+    ttcr_fsm_adjoint* tm = const_cast<ttcr_fsm_adjoint*>(t);
+    std::lock_guard<std::mutex> lock(tm->mu);
+    return guarded([&] {
+        ttcr_amd::AdjTapeDev& d = tm->t;
+        adj_device_errors([&] {
+            HIP_CHECK(hipSetDevice(d.device));
+            const size_t en = d.n_events * d.nn;
+            const void* dds = ds;
+            if (!ds_on_device) {   // (staged where a host gradient is staged: not in use during a jvp)
+                if (d.nn > 0) HIP_CHECK(hipMemcpyAsync(d.grad_tmp, ds, d.nn * d.elem, hipMemcpyHostToDevice, d.stream));
+                dds = d.grad_tmp;
+            }
+            void* ddtt = dtt ? (dtt_on_device ? dtt : d.w_tmp) : nullptr;
+            void* ddf = dfields && df_on_device ? dfields : nullptr;   // (a host copy is read from the relaxed buffer itself)
+            int np = 0;
+            if (tm->dtype == TTCR_F32) np = ttcr_amd::adj_jvp<float>(d, (const float*)dds, (float*)ddtt, (float*)ddf, schedule);
+            else np = ttcr_amd::adj_jvp<double>(d, (const double*)dds, (double*)ddtt, (double*)ddf, schedule);
+            if (dtt && !dtt_on_device && d.n_rows > 0)
+                HIP_CHECK(hipMemcpyAsync(dtt, d.w_tmp, d.n_rows * d.elem, hipMemcpyDeviceToHost, d.stream));
+            if (dfields && !df_on_device && en > 0) {
+                const void* mu = (schedule != 0 && np % 2 == 1) ? d.lam2 : d.lam;   // (the Jacobi baseline alternates lam -> lam2 -> lam)
+                HIP_CHECK(hipMemcpyAsync(dfields, mu, en * d.elem, hipMemcpyDeviceToHost, d.stream));
+            }
+            HIP_CHECK(hipStreamSynchronize(d.stream));
+            if (passes) *passes = np;
+        });
+    });
+}
+int ttcr_fsm_adjoint_gn(const ttcr_fsm_adjoint* t, const void* v, int v_on_device, const void* row_weight, int rw_on_device, void* out,
+                        int out_on_device, int schedule, int* passes_jvp, int* passes_vjp) {
+    if (!t || !v || !out) {
+        g_last_error = !t ? "null tape" : (!v ? "null v" : "null out");
+        return TTCR_ERR_VALUE;
+    }
+    if (schedule != 0 && schedule != 1) {
+        g_last_error = "schedule: 0 (tiled) or 1 (global Jacobi)";
+        return TTCR_ERR_VALUE;
+    }
+    ttcr_fsm_adjoint* tm = const_cast<ttcr_fsm_adjoint*>(t);
+    std::lock_guard<std::mutex> lock(tm->mu);
+    return guarded([&] {
+        ttcr_amd::AdjTapeDev& d = tm->t;
+        adj_device_errors([&] {
+            HIP_CHECK(hipSetDevice(d.device));
+            const void* dv = v;
+            if (!v_on_device) {   // (consumed by the jvp before the vjp writes a host gradient to the same place)
+                if (d.nn > 0) HIP_CHECK(hipMemcpyAsync(d.grad_tmp, v, d.nn * d.elem, hipMemcpyHostToDevice, d.stream));
+                dv = d.grad_tmp;
+            }
+            void* dout = out_on_device ? out : d.grad_tmp;
+            const bool stage_rw = row_weight && !rw_on_device;
+            int pj = 0, pv = 0;
+            if (stage_rw) {   // (the staging row is part of what the first jvp allocates)
+                if (tm->dtype == TTCR_F32) ttcr_amd::adj_jvp_prepare<float>(d);
+                else ttcr_amd::adj_jvp_prepare<double>(d);
+                if (d.n_rows > 0) HIP_CHECK(hipMemcpyAsync(d.rw_tmp, row_weight, d.n_rows * d.elem, hipMemcpyHostToDevice, d.stream));
+            }
+            const void* drw = row_weight ? (rw_on_device ? row_weight : d.rw_tmp) : nullptr;
+            if (tm->dtype == TTCR_F32) ttcr_amd::adj_gn<float>(d, (const float*)dv, (const float*)drw, (float*)dout, schedule, &pj, &pv);
+            else ttcr_amd::adj_gn<double>(d, (const double*)dv, (const double*)drw, (double*)dout, schedule, &pj, &pv);
+            if (!out_on_device) HIP_CHECK(hipMemcpyAsync(out, d.grad_tmp, d.nn * d.elem, hipMemcpyDeviceToHost, d.stream));
+            HIP_CHECK(hipStreamSynchronize(d.stream));
+            if (passes_jvp) *passes_jvp = pj;
+            if (passes_vjp) *passes_vjp = pv;
+        });
+    });
+}
 int ttcr_fsm_adjoint_free(ttcr_fsm_adjoint* t) {
     if (!t) return TTCR_OK;
     return guarded([&] { delete t; });

@@ -537,7 +537,8 @@ class FieldTape:
     """The traveltime fields of a raytrace_adjoint call kept on the device (ttcr_fsm_raytrace_multi_adjoint, include/ttcr_amd.h), with
     what the exact discrete adjoint of the first-order update needs besides them: the node slowness, the nodes each source froze and
     the interpolation stencil of every (event, receiver) row.  Events are in the order raytrace takes them.  The tape does not depend
-    on the grid any more: later calls, set_slowness and deleting the grid leave it as it is."""
+    on the grid any more: later calls, set_slowness and deleting the grid leave it as it is.  vjp applies J^T (reverse mode), jvp
+    applies J (forward mode) and gauss_newton J^T W J of the same linearisation, all on the device."""
 
     SCHEDULES = {'tiled': 0, 'jacobi': 1}
 
@@ -554,7 +555,7 @@ class FieldTape:
         _lib.check(lib.ttcr_fsm_adjoint_device(handle, C.byref(d)))
         _lib.check(lib.ttcr_fsm_adjoint_bytes(handle, C.byref(b)))
         self.device, self.nbytes = d.value, b.value
-        self.passes = 0            # relaxation passes of the last vjp
+        self.passes = 0            # relaxation passes of the last vjp or jvp; (jvp, vjp) after gauss_newton
         self._rows_dev = None
 
     def _handle(self):
@@ -632,6 +633,123 @@ class FieldTape:
                                                   sch, C.byref(np_)))
         self.passes = np_.value
         return g[:self.n_cols].to(ref.device)
+
+    def jvp(self, ds, return_fields=False, schedule='tiled'):
+        """J ds: the change of the receiver traveltimes for the node-slowness perturbation ds (n_cols values, x fastest), the forward
+        mode of the linearisation vjp is the reverse mode of.  Returns dtt, n_data values in rcv order (grid dtype); with
+        return_fields=True (dtt, dfields), dfields the (n_events, n_cols) tangents of the traveltime fields.  schedule as in vjp.
+        numpy in gives numpy out; a torch tensor in gives torch tensors out, and a tensor on the tape's device is used in place (torch's
+        current stream is synchronised first, the result is ready when the call returns).  The first jvp or gauss_newton of a tape
+        allocates the stencil in row order (nbytes grows by it once)."""
+        self._handle()
+        sch = self._schedule(schedule)
+        if type(ds).__module__.startswith('torch'):
+            return self._jvp_torch(ds, return_fields, sch)
+        ds = np.ascontiguousarray(ds, dtype=self.dtype)
+        if ds.size != self.n_cols:
+            raise ValueError('ds should hold %d values (one per node), got shape %s' % (self.n_cols, ds.shape))
+        rows = np.empty(max(self.n_rows, 1), dtype=self.dtype)
+        df = np.empty((self.n_events, self.n_cols), dtype=self.dtype) if return_fields else None
+        np_ = C.c_int(0)
+        _lib.check(self._lib.ttcr_fsm_adjoint_jvp(self._h, _ptr(ds), 0, _ptr(rows), 0, _ptr(df) if df is not None and df.size else None, 0,
+                                                  sch, C.byref(np_)))
+        self.passes = np_.value
+        self._refresh_nbytes()
+        dtt = np.zeros(self.n_data, dtype=self.dtype)
+        dtt[self._rows] = rows[:self.n_rows]
+        return (dtt, df) if return_fields else dtt
+
+    def _jvp_torch(self, ds, return_fields, sch):
+        import torch
+
+        tdt = torch.float32 if self.dtype == np.float32 else torch.float64
+        if ds.device.type != 'cuda':
+            out = self.jvp(ds.detach().numpy(), return_fields, 'jacobi' if sch else 'tiled')
+            return tuple(torch.from_numpy(o) for o in out) if return_fields else torch.from_numpy(out)
+        if ds.numel() != self.n_cols:
+            raise ValueError('ds should hold %d values (one per node), got shape %s' % (self.n_cols, tuple(ds.shape)))
+        dev = torch.device('cuda', self.device)
+        if self._rows_dev is None:
+            self._rows_dev = torch.as_tensor(self._rows, device=dev)
+        dst = ds.detach().to(device=dev, dtype=tdt).contiguous()
+        rows = torch.empty(max(self.n_rows, 1), dtype=tdt, device=dev)
+        df = torch.empty((self.n_events, self.n_cols), dtype=tdt, device=dev) if return_fields else None
+        torch.cuda.current_stream(dev).synchronize()
+        np_ = C.c_int(0)
+        _lib.check(self._lib.ttcr_fsm_adjoint_jvp(self._h, C.c_void_p(dst.data_ptr()), 1, C.c_void_p(rows.data_ptr()), 1,
+                                                  C.c_void_p(df.data_ptr()) if df is not None and df.numel() else None, 1, sch,
+                                                  C.byref(np_)))
+        self.passes = np_.value
+        self._refresh_nbytes()
+        dtt = torch.zeros(self.n_data, dtype=tdt, device=dev)
+        dtt[self._rows_dev] = rows[:self.n_rows]
+        return (dtt.to(ds.device), df.to(ds.device)) if return_fields else dtt.to(ds.device)
+
+    def gauss_newton(self, v, row_weight=None, schedule='tiled'):
+        """J^T (row_weight * (J v)): the Gauss-Newton Hessian product (n_cols values, x fastest, grid dtype), with the bits of
+        vjp(row_weight * jvp(v)), the product formed in the grid dtype, and no host round trip in between.  v: n_cols values;
+        row_weight: one value per data row (rcv order) or None.  Array handling and schedule as in jvp; passes becomes the pair
+        (passes of the jvp, passes of the vjp)."""
+        self._handle()
+        sch = self._schedule(schedule)
+        if any(type(a).__module__.startswith('torch') for a in (v, row_weight) if a is not None):
+            return self._gn_torch(v, row_weight, sch)
+        v = np.ascontiguousarray(v, dtype=self.dtype)
+        if v.size != self.n_cols:
+            raise ValueError('v should hold %d values (one per node), got shape %s' % (self.n_cols, v.shape))
+        rw = None
+        if row_weight is not None:
+            row_weight = np.asarray(row_weight)
+            if row_weight.ndim != 1 or row_weight.shape[0] != self.n_data:
+                raise ValueError('row_weight should hold %d values (one per data row), got shape %s' % (self.n_data, row_weight.shape))
+            rw = np.ascontiguousarray(row_weight[self._rows], dtype=self.dtype)
+            if rw.size == 0:
+                rw = np.zeros(1, dtype=self.dtype)
+        g = np.empty(max(self.n_cols, 1), dtype=self.dtype)
+        pj, pv = C.c_int(0), C.c_int(0)
+        _lib.check(self._lib.ttcr_fsm_adjoint_gn(self._h, _ptr(v), 0, _ptr(rw) if rw is not None else None, 0, _ptr(g), 0, sch,
+                                                 C.byref(pj), C.byref(pv)))
+        self.passes = (pj.value, pv.value)
+        self._refresh_nbytes()
+        return g[:self.n_cols]
+
+    def _gn_torch(self, v, row_weight, sch):
+        import torch
+
+        tdt = torch.float32 if self.dtype == np.float32 else torch.float64
+        ref = v if type(v).__module__.startswith('torch') else row_weight
+        if ref.device.type != 'cuda':
+            host = [a.detach().numpy() if hasattr(a, 'detach') else a for a in (v, row_weight)]
+            return torch.from_numpy(self.gauss_newton(host[0], host[1], 'jacobi' if sch else 'tiled')).to(ref.device)
+        dev = torch.device('cuda', self.device)
+        v = torch.as_tensor(v)
+        if v.numel() != self.n_cols:
+            raise ValueError('v should hold %d values (one per node), got shape %s' % (self.n_cols, tuple(v.shape)))
+        vt = v.detach().to(device=dev, dtype=tdt).contiguous()
+        rw = None
+        if row_weight is not None:
+            row_weight = torch.as_tensor(row_weight)
+            if row_weight.dim() != 1 or row_weight.shape[0] != self.n_data:
+                raise ValueError('row_weight should hold %d values (one per data row), got shape %s'
+                                 % (self.n_data, tuple(row_weight.shape)))
+            if self._rows_dev is None:
+                self._rows_dev = torch.as_tensor(self._rows, device=dev)
+            rw = row_weight.detach().to(device=dev, dtype=tdt).index_select(0, self._rows_dev).contiguous()
+            if rw.numel() == 0:
+                rw = torch.zeros(1, dtype=tdt, device=dev)
+        g = torch.empty(max(self.n_cols, 1), dtype=tdt, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        pj, pv = C.c_int(0), C.c_int(0)
+        _lib.check(self._lib.ttcr_fsm_adjoint_gn(self._h, C.c_void_p(vt.data_ptr()), 1, C.c_void_p(rw.data_ptr()) if rw is not None else None,
+                                                 1, C.c_void_p(g.data_ptr()), 1, sch, C.byref(pj), C.byref(pv)))
+        self.passes = (pj.value, pv.value)
+        self._refresh_nbytes()
+        return g[:self.n_cols].to(ref.device)
+
+    def _refresh_nbytes(self):
+        b = C.c_size_t(0)
+        _lib.check(self._lib.ttcr_fsm_adjoint_bytes(self._h, C.byref(b)))
+        self.nbytes = b.value
 
     def free(self):
         """Release the device memory now (also done when the tape is collected)."""
