@@ -182,7 +182,7 @@ __global__ __launch_bounds__(ADJ_THREADS) void adj_tiled_kernel(const T* __restr
         if (ty < nty - 1) run |= st[tile + ntx] >= since;
         if (tz > 0) run |= st[tile - ntx * nty] >= since;
         if (tz < ntz - 1) run |= st[tile + ntx * nty] >= since;
-        if (!run) return;
+        if (!__syncthreads_or(run)) return;   // (one decision for the workgroup: neighbours stamp during this pass, so the threads' own reads may differ)
     }
     const size_t base = (size_t)e * geo.nn;
     const int x0 = tx * TI - 1, y0 = ty * TI - 1, z0 = tz * TI - 1;
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(ADJ_THREADS) void tan_tiled_kernel(const T* __restr
         if (ty < nty - 1) run |= st[tile + ntx] >= since;
         if (tz > 0) run |= st[tile - ntx * nty] >= since;
         if (tz < ntz - 1) run |= st[tile + ntx * nty] >= since;
-        if (!run) return;
+        if (!__syncthreads_or(run)) return;   // (one decision for the workgroup: neighbours stamp during this pass, so the threads' own reads may differ)
     }
     const T inf = std::numeric_limits<T>::infinity();
     const size_t base = (size_t)e * geo.nn;
