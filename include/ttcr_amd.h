@@ -398,8 +398,28 @@ int ttcr_fsm_tape_free(ttcr_fsm_tape* t);
  * ttcr_fsm_adjoint_gn: the Gauss-Newton product out = J^T (row_weight * (J v)) (n_nodes values): the jvp of v, every row multiplied by
  *   row_weight[row] (n_rows values in tape row order; NULL: no weight), the vjp of the result -- with the bits of the two calls composed,
  *   and no host copy in between.  *passes_jvp, *passes_vjp (may be NULL): the passes of the two relaxations.
- * Argument errors (a NULL tape or pointer, w and field_cot both NULL, dtt and dfields both NULL) return TTCR_ERR_VALUE before any device
- * call. */
+ * Derivatives with respect to the source points.  The points of a tape are the source points of its events in call order
+ *   (tx order); the parameters of a point are (t0, x, y, z), the column order of a ttcrpy source row.  A frozen node m belongs to the
+ *   point q(m) that wrote it last, T[m] = t0 + d_m s[m]; c[m][a] = fl(fl(p_a - x_a(m)) / d_m) for a = x, y, z, +0 where d_m = 0 (p the point
+ *   as the solver sees it, after the origin shift of a translated grid), computed on the host in the grid dtype when the tape is made.
+ *   The map has a kink where a point crosses a cell face or enters the 1e-4 on-node tolerance; the formula is returned there too.
+ * ttcr_fsm_adjoint_points: *n_points, and the event of every point (event_of_point: n_points ints, may be NULL).
+ * ttcr_fsm_adjoint_jvp_source: n_cols (1 to 4) perturbations at once; dsrc: n_cols x n_points x 4 values.  Per column and event
+ *   mu[m] = dsrc[q(m)][0], then for a = x, y, z: acc = fl(acc + fl(fl(s[m] * c[m][a]) * dsrc[q(m)][1 + a]))  for m in F, and otherwise
+ *   mu[m] = fl(acc / D_m), acc = +0, then for the active axes x, y, z: acc = fl(acc + fl(mu[u_axis] * fl(T[m] - a_axis)))  -- the jvp above
+ *   with ds = +0.  dtt: n_cols x n_rows values (rows as in the jvp); dfields: n_cols x n_events x n_nodes values; either may be NULL, not
+ *   both.  n_cols = 1 relaxes one column in the lam buffers; n_cols > 1 relaxes four columns at once, the four values of a node adjacent
+ *   in memory (upwind choice, D and differences computed once per node), the columns past n_cols being +0.  Every column has the bits
+ *   of the one-column call.  The first jvp_source or vjp_source allocates the frozen entries by point, 4 (n_points + 1) + n_frozen (16 + 3
+ *   elem) bytes, and two staging arrays, (16 n_points + 4 n_rows) elem bytes; the first jvp_source what the first jvp allocates; the first
+ *   call with n_cols > 1 a work array of 4 n_events n_nodes elem bytes, the first such call with schedule 1 a second one.
+ *   ttcr_fsm_adjoint_bytes reports all of it from then on; TTCR_ERR_DEVICE with the byte count if an allocation fails.
+ * ttcr_fsm_adjoint_vjp_source: the vjp above and, from the same lam, gsrc (n_points x 4 values):  gsrc[q][0] = from +0, over the frozen
+ *   nodes m with q(m) = q in ascending node index, acc = fl(acc + lam[m]);  gsrc[q][1 + a] = the same chain of
+ *   fl(lam[m] * fl(s[m] * c[m][a])).  A point all of whose nodes a later point overwrote gets four +0.  grad may be NULL (no slowness
+ *   gradient is formed); otherwise it has the bits of ttcr_fsm_adjoint_vjp.  One thread per point, no floating-point atomics.
+ * Argument errors (a NULL tape or pointer, w and field_cot both NULL, dtt and dfields both NULL, n_cols outside 1 to 4, an unknown
+ * schedule) return TTCR_ERR_VALUE before any device call. */
 typedef struct ttcr_fsm_adjoint ttcr_fsm_adjoint; /* opaque */
 int ttcr_fsm_raytrace_multi_adjoint(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off,
                                     const void* rx, void* tt_out, ttcr_fsm_adjoint** tape);
@@ -413,6 +433,11 @@ int ttcr_fsm_adjoint_jvp(const ttcr_fsm_adjoint* t, const void* ds, int ds_on_de
                          int df_on_device, int schedule, int* passes);
 int ttcr_fsm_adjoint_gn(const ttcr_fsm_adjoint* t, const void* v, int v_on_device, const void* row_weight, int rw_on_device, void* out,
                         int out_on_device, int schedule, int* passes_jvp, int* passes_vjp);
+int ttcr_fsm_adjoint_points(const ttcr_fsm_adjoint* t, size_t* n_points, int* event_of_point);
+int ttcr_fsm_adjoint_jvp_source(const ttcr_fsm_adjoint* t, const void* dsrc, int dsrc_on_device, int n_cols, void* dtt, int dtt_on_device,
+                                void* dfields, int df_on_device, int schedule, int* passes);
+int ttcr_fsm_adjoint_vjp_source(const ttcr_fsm_adjoint* t, const void* w, int w_on_device, const void* field_cot, int fc_on_device, void* grad,
+                                int grad_on_device, void* gsrc, int gsrc_on_device, int schedule, int* passes);
 int ttcr_fsm_adjoint_free(ttcr_fsm_adjoint* t);
 
 /* Replaces: Grid2D::raytrace(Tx, t0, Rx, traveltimes, l_data, threadNo) (ttcr/Grid2D.h:616-640) and the overload with r_data

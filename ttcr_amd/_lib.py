@@ -84,6 +84,9 @@ SYMBOLS = {
     "ttcr_fsm_adjoint_vjp": (_I, [_P, _P, _I, _P, _I, _P, _I, _I, C.POINTER(_I)]),
     "ttcr_fsm_adjoint_jvp": (_I, [_P, _P, _I, _P, _I, _P, _I, _I, C.POINTER(_I)]),
     "ttcr_fsm_adjoint_gn": (_I, [_P, _P, _I, _P, _I, _P, _I, _I, C.POINTER(_I), C.POINTER(_I)]),
+    "ttcr_fsm_adjoint_points": (_I, [_P, C.POINTER(C.c_size_t), _P]),
+    "ttcr_fsm_adjoint_jvp_source": (_I, [_P, _P, _I, _I, _P, _I, _P, _I, _I, C.POINTER(_I)]),
+    "ttcr_fsm_adjoint_vjp_source": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _I, _I, C.POINTER(_I)]),
     "ttcr_fsm_adjoint_free": (_I, [_P]),
     "ttcr_fsm_raytrace_multi_l": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I]),
     "ttcr_fsm_multi_l_size": (_I, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),

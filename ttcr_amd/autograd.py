@@ -18,12 +18,22 @@ With return_fields=True it returns (tt, fields), fields the (n_events, nx, ny, n
 grid traveltimes has a gradient.  Forward mode works as well (torch.autograd.forward_ad): the tangent of the outputs for a velocity
 tangent tv is FieldTape.jvp(-(tv / velocity**2)), J v of the same linearisation, in the layout of the outputs.
 
+    tt = ttcr_amd.autograd.raytrace_events(grid, velocity, events, event_of_row, rcv, return_fields=False)
+
+is raytrace_adjoint for events that are themselves unknowns: `events` is an (n_events, 4) tensor of (t0, x, y, z), one source point
+per event, `event_of_row` names the event of every rcv row (every event needs a row), and the operator is differentiable with respect
+to velocity AND events.  The backward is one FieldTape.vjp(..., return_source_grad=True): the slowness gradient as above and the exact
+derivative with respect to the origin time and the position of every event, through the nodes the source initialisation froze.  Forward
+mode adds FieldTape.jvp and FieldTape.jvp_source.  The derivative with respect to a position has a kink where the point crosses a cell
+face or comes within 1e-4 of a node: the formula of the side the point is on is returned.
+
 torch is imported when this module is used, never by `import ttcr_amd`.
 """
 import numpy as np
 
 _Fn = None
 _AdjFn = None
+_EvFn = None
 
 
 def _function():
@@ -126,3 +136,79 @@ def raytrace_adjoint(grid, velocity, source, rcv, aggregate_src=False, return_fi
     source = np.asarray(source)
     rcv = np.asarray(rcv)
     return _adjoint_function().apply(velocity, grid, source, rcv, bool(aggregate_src), bool(return_fields))
+
+
+def _events_function():
+    global _EvFn
+    if _EvFn is not None:
+        return _EvFn
+    import torch
+
+    class RaytraceEventsFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, velocity, events, grid, event_of_row, rcv, return_fields):
+            grid.set_velocity(velocity.detach().cpu().numpy())
+            ev = events.detach().cpu().numpy().astype(np.float64)
+            # the 5-column source form of _split_sources: (event number, t0, x, y, z) per rcv row; events are taken in ascending number
+            source = np.column_stack([event_of_row.astype(np.float64), ev[event_of_row]])
+            tt, tape = grid.raytrace_adjoint(source, rcv)
+            nx, ny, nz = grid.x.size, grid.y.size, grid.z.size
+            ctx.tape = tape
+            ctx.layout = (tuple(velocity.shape), (nx, ny, nz))
+            ctx.save_for_backward(velocity, events)
+            ctx.save_for_forward(velocity)
+            ctx.return_fields = return_fields
+            out = torch.from_numpy(tt).to(velocity.device)
+            if not return_fields:
+                return out
+            f = np.stack([tape.field(e).reshape(nz, ny, nx).transpose(2, 1, 0) for e in range(tape.n_events)])
+            return out, torch.from_numpy(np.ascontiguousarray(f)).to(velocity.device)
+
+        @staticmethod
+        def backward(ctx, g, gf=None):
+            shape, (nx, ny, nz) = ctx.layout
+            velocity, events = ctx.saved_tensors
+            fc = None
+            if gf is not None:   # (n_events, nx, ny, nz) in C order -> node order x fastest
+                fc = gf.permute(0, 3, 2, 1).contiguous().reshape(gf.shape[0], -1)
+            gn, gs = ctx.tape.vjp(g.contiguous(), fc, return_source_grad=True)
+            gs_v = gn.reshape(nz, ny, nx).permute(2, 1, 0).contiguous().reshape(shape).to(velocity.dtype)
+            return -gs_v / (velocity * velocity), gs.to(device=events.device, dtype=events.dtype), None, None, None, None
+
+        @staticmethod
+        def jvp(ctx, tv, te, *_):
+            shape, (nx, ny, nz) = ctx.layout
+            (velocity,) = ctx.saved_tensors
+            parts = []
+            if tv is not None:
+                ds = (-(tv / (velocity * velocity))).reshape(nx, ny, nz).permute(2, 1, 0).contiguous().reshape(-1)
+                parts.append(ctx.tape.jvp(ds, return_fields=ctx.return_fields))
+            if te is not None:
+                parts.append(ctx.tape.jvp_source(te.to(velocity.device), return_fields=ctx.return_fields))
+            if not ctx.return_fields:
+                return parts[0] if len(parts) == 1 else parts[0] + parts[1]
+            dtt, df = parts[0] if len(parts) == 1 else (parts[0][0] + parts[1][0], parts[0][1] + parts[1][1])
+            return dtt, df.reshape(df.shape[0], nz, ny, nx).permute(0, 3, 2, 1).contiguous()
+
+    _EvFn = RaytraceEventsFn
+    return _EvFn
+
+
+def raytrace_events(grid, velocity, events, event_of_row, rcv, return_fields=False):
+    """Traveltimes at `rcv` (interpolated, as with tt_from_rp=0) of row r for the event event_of_row[r] of `events`, an (n_events, 4)
+    torch tensor of (t0, x, y, z); differentiable with respect to `velocity` (as raytrace_adjoint) and `events` (d tt / d origin time
+    and position, exact, FieldTape.vjp(..., return_source_grad=True)).  return_fields=True: (tt, fields) with the (n_events, nx, ny, nz)
+    traveltime fields, differentiable as well."""
+    if grid._ndim != 3:
+        raise NotImplementedError('the adjoint-state gradient is implemented for 3-D grids only')
+    if grid.cell_slowness:
+        raise NotImplementedError('the adjoint-state gradient is not implemented for grids with slowness defined for cells')
+    rcv = np.asarray(rcv)
+    event_of_row = np.asarray(event_of_row)
+    if events.dim() != 2 or events.shape[1] != 4:
+        raise ValueError('events should be (n_events, 4): t0, x, y, z; got shape %s' % (tuple(events.shape),))
+    if event_of_row.ndim != 1 or rcv.ndim != 2 or event_of_row.shape[0] != rcv.shape[0] or event_of_row.dtype.kind not in 'iu':
+        raise ValueError('event_of_row should hold one integer per rcv row')
+    if not np.array_equal(np.unique(event_of_row), np.arange(events.shape[0])):
+        raise ValueError('event_of_row should name events 0 .. %d, every one of them at least once' % (events.shape[0] - 1))
+    return _events_function().apply(velocity, events, grid, event_of_row.astype(np.int64), rcv, bool(return_fields))

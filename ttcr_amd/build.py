@@ -9,7 +9,7 @@ Two translation units, compiled to objects under ttcr_amd/csrc/_obj and linked:
   fsm_fast.hip    the sweep kernels with tolerance-grade arithmetic (option "arith" = 1)
   fsm_tape.hip    the M tape: compute_M's rows merged on the device, node index, M^T w (hipCUB sorts)
   fsm_adjoint.hip the field tape: discrete adjoint of the first-order 3-D update (coupling, seeds, relaxation, gradient)
-                  and its forward mode (tangent relaxation, receiver rows)
+                  and its forward mode (tangent relaxation, receiver rows); the source derivative (K-column relaxation, source gradient)
 """
 import os
 import shutil

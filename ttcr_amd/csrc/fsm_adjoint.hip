@@ -435,6 +435,258 @@ __global__ void tan_scale_rows_kernel(const T* __restrict__ rw, T* __restrict__ 
     if (r < n_rows) w[r] = rw[r] * w[r];
 }
 
+// ---- derivatives with respect to the source points: mu = dT/d(t0, x, y, z) . dsrc per event, K columns at once.  A source
+// enters the scheme through its frozen nodes only, T[m] = t0 + d_m s[m]: there mu is set by src_seed_kernel and left alone by the
+// relaxation; everywhere else mu obeys the tangent's triangular system with the slowness term switched off.  The K values of a node are
+// adjacent in memory and in LDS: one 16-byte access per node for fp32, K = 4 (two for fp64).
+template <typename T, int K>
+struct alignas(sizeof(T) * K) SrcVec {
+    T v[K];
+};
+
+// mu[m][k] = dsrc[k][q][0], then for a = x, y, z: acc = fl(acc + fl(fl(s[m] * c[m][a]) * dsrc[k][q][1 + a])), q the point that wrote m last;
+// +0 in the columns past n_cols.  One thread per frozen entry.
+template <typename T, int K>
+__global__ void src_seed_kernel(const long long* __restrict__ key, const int* __restrict__ node, const int* __restrict__ pt,
+                                const T* __restrict__ c, size_t n, const T* __restrict__ s, const T* __restrict__ dsrc, int n_cols,
+                                size_t n_points, SrcVec<T, K>* __restrict__ mu) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const T sm = s[node[i]];
+    const T sc0 = sm * c[3 * i], sc1 = sm * c[3 * i + 1], sc2 = sm * c[3 * i + 2];
+    SrcVec<T, K> v;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        T acc = 0;
+        if (k < n_cols) {
+            const T* d = dsrc + ((size_t)k * n_points + pt[i]) * 4;
+            acc = d[0];
+            acc = acc + sc0 * d[1];
+            acc = acc + sc1 * d[2];
+            acc = acc + sc2 * d[3];
+        }
+        v.v[k] = acc;
+    }
+    mu[key[i]] = v;
+}
+
+// Global Jacobi pass of the K-column relaxation (the correctness baseline): for a node that is not frozen
+//   mu[m][k] = fl(acc / D_m), acc = +0, then per active axis x, y, z: acc = fl(acc + fl(mu[u][k] * fl(T[m] - a)))
+// with the upwind choice recomputed from the field once for the K columns.  Frozen nodes keep what src_seed_kernel wrote (in both buffers).
+template <typename T, int K>
+__global__ void src_jacobi_kernel(const T* __restrict__ fields, const T* __restrict__ D, const unsigned char* __restrict__ frozen,
+                                  const SrcVec<T, K>* __restrict__ mu_in, SrcVec<T, K>* __restrict__ mu_out, AdjGeom<T> geo,
+                                  const int* __restrict__ prev, int* __restrict__ cur) {
+    const int e = blockIdx.y;
+    if (prev && prev[e] == 0) return;   // (both buffers of the event hold the fixed point already)
+    const size_t m = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    int changed = 0;
+    if (m < geo.nn && !frozen[(size_t)e * geo.nn + m]) {
+        const size_t idx = (size_t)e * geo.nn + m;
+        const T inf = std::numeric_limits<T>::infinity();
+        const int pos[3] = {(int)(m % geo.nnx), (int)((m / geo.nnx) % geo.nny), (int)(m / ((size_t)geo.nnx * geo.nny))};
+        const int ext[3] = {geo.nnx, geo.nny, geo.nnz};
+        const long long st[3] = {1, (long long)geo.nnx, (long long)geo.nnx * geo.nny};
+        const T* F = fields + idx;
+        const SrcVec<T, K>* L = mu_in + idx;
+        const T t = F[0];
+        SrcVec<T, K> acc;
+#pragma unroll
+        for (int k = 0; k < K; ++k) acc.v[k] = 0;
+        for (int ax = 0; ax < 3; ++ax) {
+            const T lo = pos[ax] > 0 ? F[-st[ax]] : inf;
+            const T hi = pos[ax] < ext[ax] - 1 ? F[st[ax]] : inf;
+            const bool up = hi < lo;
+            const T a = up ? hi : lo;
+            if (a < t) {
+                const T d = t - a;
+                const SrcVec<T, K> u = up ? L[st[ax]] : L[-st[ax]];
+#pragma unroll
+                for (int k = 0; k < K; ++k) acc.v[k] = acc.v[k] + u.v[k] * d;
+            }
+        }
+        const T Dm = D[idx];
+        const SrcVec<T, K> old = L[0];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            acc.v[k] = acc.v[k] / Dm;
+            changed |= !same_bits(acc.v[k], old.v[k]);
+        }
+        mu_out[idx] = acc;
+    }
+    if (__syncthreads_or(changed) && threadIdx.x == 0) cur[e] = 1;
+}
+
+// Tiled K-column relaxation: tan_tiled_kernel's tiles, stamps and passes.  T of the tile and its halo is staged once (+inf outside the grid),
+// the upwind choice, D and the differences T[m] - a are computed once per node and kept in registers for the K columns; a Jacobi step reads
+// the K adjacent values of each upwind neighbour in one access.  LDS: (K + 1) (edge + 2)^3 elements -- 34.5 KiB (fp32) and 39 KiB (fp64)
+// for K = 4.  Frozen nodes are staged like halo nodes: read, never written.
+template <typename T, int K, int TI>
+__global__ __launch_bounds__(ADJ_THREADS) void src_tiled_kernel(const T* __restrict__ fields, const T* __restrict__ D,
+                                                                 const unsigned char* __restrict__ frozen, SrcVec<T, K>* mu, AdjGeom<T> geo,
+                                                                 int ntx, int nty, int ntz, int* stamps, int pass, int* __restrict__ cur) {
+    constexpr int TH = TI + 2, NH = TH * TH * TH, NI = TI * TI * TI, NPT = (NI + ADJ_THREADS - 1) / ADJ_THREADS;
+    __shared__ SrcVec<T, K> sL[NH];
+    __shared__ T sF[NH];
+    const int e = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
+    const int tx = tile % ntx, ty = (tile / ntx) % nty, tz = tile / (ntx * nty);
+    int* st = stamps + (size_t)e * ntx * nty * ntz;
+    if (pass > 0) {
+        const int since = pass - 1;
+        bool run = false;
+        if (tx > 0) run |= st[tile - 1] >= since;
+        if (tx < ntx - 1) run |= st[tile + 1] >= since;
+        if (ty > 0) run |= st[tile - ntx] >= since;
+        if (ty < nty - 1) run |= st[tile + ntx] >= since;
+        if (tz > 0) run |= st[tile - ntx * nty] >= since;
+        if (tz < ntz - 1) run |= st[tile + ntx * nty] >= since;
+        if (!__syncthreads_or(run)) return;   // (one decision for the workgroup, as in tan_tiled_kernel)
+    }
+    const T inf = std::numeric_limits<T>::infinity();
+    const size_t base = (size_t)e * geo.nn;
+    const int x0 = tx * TI - 1, y0 = ty * TI - 1, z0 = tz * TI - 1;
+    SrcVec<T, K> zero;
+#pragma unroll
+    for (int k = 0; k < K; ++k) zero.v[k] = 0;
+    for (int h = tid; h < NH; h += ADJ_THREADS) {
+        const int x = x0 + h % TH, y = y0 + (h / TH) % TH, z = z0 + h / (TH * TH);
+        const bool inside = x >= 0 && x < geo.nnx && y >= 0 && y < geo.nny && z >= 0 && z < geo.nnz;
+        const size_t idx = base + ((size_t)(inside ? z : 0) * geo.nny + (inside ? y : 0)) * geo.nnx + (inside ? x : 0);
+        SrcVec<T, K> v = zero;
+        if (inside) v = mu[idx];
+        sL[h] = v;
+        sF[h] = inside ? fields[idx] : inf;
+    }
+    __syncthreads();
+    // the interior nodes of this thread that the relaxation owns (hq < 0: outside the grid, or frozen)
+    int hq[NPT];
+    unsigned cq[NPT];
+    T dq[NPT], c0[NPT], c1[NPT], c2[NPT];
+    for (int q = 0; q < NPT; ++q) {
+        const int n = tid + q * ADJ_THREADS;
+        hq[q] = -1; cq[q] = 0; dq[q] = 1; c0[q] = 0; c1[q] = 0; c2[q] = 0;
+        if (n >= NI) continue;
+        const int lx = n % TI, ly = (n / TI) % TI, lz = n / (TI * TI);
+        const int x = x0 + 1 + lx, y = y0 + 1 + ly, z = z0 + 1 + lz;
+        if (x >= geo.nnx || y >= geo.nny || z >= geo.nnz) continue;
+        const int h = ((lz + 1) * TH + ly + 1) * TH + lx + 1;
+        const size_t m = ((size_t)z * geo.nny + y) * geo.nnx + x;
+        if (frozen[base + m]) continue;
+        hq[q] = h;
+        dq[q] = D[base + m];
+        const T t = sF[h];
+        unsigned code = 0;
+        {
+            const T lo = sF[h - 1], hi = sF[h + 1];
+            const bool up = hi < lo;
+            const T a = up ? hi : lo;
+            if (a < t) { code |= up ? 3u : 1u; c0[q] = t - a; }
+        }
+        {
+            const T lo = sF[h - TH], hi = sF[h + TH];
+            const bool up = hi < lo;
+            const T a = up ? hi : lo;
+            if (a < t) { code |= up ? 12u : 4u; c1[q] = t - a; }
+        }
+        {
+            const T lo = sF[h - TH * TH], hi = sF[h + TH * TH];
+            const bool up = hi < lo;
+            const T a = up ? hi : lo;
+            if (a < t) { code |= up ? 48u : 16u; c2[q] = t - a; }
+        }
+        cq[q] = code;
+    }
+    bool tile_changed = false;
+    for (int it = 0; it <= NI; ++it) {
+        SrcVec<T, K> nv[NPT];
+        for (int q = 0; q < NPT; ++q) {
+            if (hq[q] < 0) continue;
+            const SrcVec<T, K>* L = sL + hq[q];
+            const unsigned code = cq[q];
+            SrcVec<T, K> acc = zero;
+            if (code & 1u) {
+                const SrcVec<T, K> u = L[(code & 2u) ? 1 : -1];
+#pragma unroll
+                for (int k = 0; k < K; ++k) acc.v[k] = acc.v[k] + u.v[k] * c0[q];
+            }
+            if (code & 4u) {
+                const SrcVec<T, K> u = L[(code & 8u) ? TH : -TH];
+#pragma unroll
+                for (int k = 0; k < K; ++k) acc.v[k] = acc.v[k] + u.v[k] * c1[q];
+            }
+            if (code & 16u) {
+                const SrcVec<T, K> u = L[(code & 32u) ? TH * TH : -TH * TH];
+#pragma unroll
+                for (int k = 0; k < K; ++k) acc.v[k] = acc.v[k] + u.v[k] * c2[q];
+            }
+#pragma unroll
+            for (int k = 0; k < K; ++k) nv[q].v[k] = acc.v[k] / dq[q];
+        }
+        __syncthreads();   // every read of this step is done
+        int ch = 0;
+        for (int q = 0; q < NPT; ++q) {
+            if (hq[q] < 0) continue;
+            const SrcVec<T, K> old = sL[hq[q]];
+            bool diff = false;
+#pragma unroll
+            for (int k = 0; k < K; ++k) diff |= !same_bits(nv[q].v[k], old.v[k]);
+            if (diff) { sL[hq[q]] = nv[q]; ch = 1; }
+        }
+        if (!__syncthreads_or(ch)) break;
+        tile_changed = true;
+    }
+    if (!tile_changed) return;
+    for (int q = 0; q < NPT; ++q) {
+        if (hq[q] < 0) continue;
+        const int n = tid + q * ADJ_THREADS;
+        const int x = x0 + 1 + n % TI, y = y0 + 1 + (n / TI) % TI, z = z0 + 1 + n / (TI * TI);
+        mu[base + ((size_t)z * geo.nny + y) * geo.nnx + x] = sL[hq[q]];
+    }
+    if (tid == 0) { st[tile] = pass; cur[e] = 1; }
+}
+
+// dtt[k][row] = from +0, over the row's stencil entries in interp3d_stencil order: acc = fl(acc + fl(weight * mu[node][k])); one thread per
+// (row, column)
+template <typename T, int K>
+__global__ void src_rows_kernel(const int* __restrict__ off, const long long* __restrict__ key, const T* __restrict__ wt, size_t n_rows,
+                                int n_cols, const T* __restrict__ mu, T* __restrict__ dtt) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n_rows * (size_t)n_cols) return;
+    const size_t r = i % n_rows;
+    const int k = (int)(i / n_rows);
+    T acc = 0;
+    for (int c = off[r]; c < off[r + 1]; ++c) acc = acc + wt[c] * mu[(size_t)key[c] * K + k];
+    dtt[i] = acc;
+}
+
+// dfields[k][i] = mu[i][k]
+template <typename T, int K>
+__global__ void src_unpack_kernel(const T* __restrict__ mu, size_t en, int n_cols, T* __restrict__ out) {
+    const size_t n = en * (size_t)n_cols;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        out[i] = mu[(i % en) * K + i / en];
+}
+
+// gsrc[q][0] = from +0, over the frozen nodes of point q in ascending node index: acc = fl(acc + lam[m]);
+// gsrc[q][1 + a] = the same chain of fl(lam[m] * fl(s[m] * c[m][a])).  One thread per point; no atomics.
+template <typename T>
+__global__ void src_grad_kernel(const int* __restrict__ off, const long long* __restrict__ key, const int* __restrict__ node,
+                                const T* __restrict__ c, size_t n_points, const T* __restrict__ s, const T* __restrict__ lam,
+                                T* __restrict__ gsrc) {
+    const size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (q >= n_points) return;
+    T a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+    for (int i = off[q]; i < off[q + 1]; ++i) {
+        const T l = lam[key[i]];
+        const T sm = s[node[i]];
+        a0 = a0 + l;
+        a1 = a1 + l * (sm * c[3 * (size_t)i]);
+        a2 = a2 + l * (sm * c[3 * (size_t)i + 1]);
+        a3 = a3 + l * (sm * c[3 * (size_t)i + 2]);
+    }
+    gsrc[4 * q] = a0; gsrc[4 * q + 1] = a1; gsrc[4 * q + 2] = a2; gsrc[4 * q + 3] = a3;
+}
+
 struct Alloc {
     AdjTapeDev& t;
     size_t planned;
@@ -483,6 +735,8 @@ void AdjTapeDev::release() {
     dev_free(fields); dev_free(slowness); dev_free(D); dev_free(inmask); dev_free(frozen); dev_free(g); dev_free(lam); dev_free(lam2);
     dev_free(sd_key); dev_free(sd_row); dev_free(sd_w); dev_free(flags); dev_free(stamps); dev_free(err); dev_free(w_tmp); dev_free(grad_tmp);
     dev_free(rw_off); dev_free(rw_key); dev_free(rw_w); dev_free(rw_tmp); dev_free(tan_stamps);
+    dev_free(src_off); dev_free(src_pt); dev_free(src_key); dev_free(src_node); dev_free(src_c); dev_free(src_io); dev_free(src_rows);
+    dev_free(mu4); dev_free(mu4b);
     if (stream) (void)hipStreamDestroy(stream);
     stream = nullptr;
     total_bytes = 0;
@@ -539,6 +793,28 @@ void adj_finish(AdjTapeDev& t, const AdjSink& sink) {
     for (size_t r = 0; r < t.n_rows; ++r) t.h_rw_off[r + 1] = t.h_rw_off[r] + sink.st_cnt[r];
     t.h_rw_key = key;
     t.h_rw_w.assign(wt.begin(), wt.end());
+    // the frozen entries by (point, node), for the source derivative: kept on the host until the first call that needs them
+    {
+        t.n_points = sink.pt_off.empty() ? 0 : (size_t)sink.pt_off[t.n_events];
+        t.h_pt_event.assign(t.n_points, 0);
+        struct Ent { int pt; long long key; const double* c; };
+        std::vector<Ent> ent;
+        for (size_t e = 0; e < t.n_events; ++e) {
+            for (int q = sink.pt_off[e]; q < sink.pt_off[e + 1]; ++q) t.h_pt_event[q] = (int)e;
+            for (size_t q = 0; q < sink.fr_node[e].size(); ++q)
+                ent.push_back({sink.pt_off[e] + sink.fr_pt[e][q], (long long)(e * t.nn) + sink.fr_node[e][q], &sink.fr_c[e][3 * q]});
+        }
+        std::sort(ent.begin(), ent.end(), [](const Ent& a, const Ent& b) { return a.pt != b.pt ? a.pt < b.pt : a.key < b.key; });
+        t.h_src_off.assign(t.n_points + 1, 0);
+        t.h_src_key.clear();
+        t.h_src_c.clear();
+        for (const Ent& en_ : ent) {
+            t.h_src_off[en_.pt + 1] += 1;
+            t.h_src_key.push_back(en_.key);
+            t.h_src_c.insert(t.h_src_c.end(), en_.c, en_.c + 3);
+        }
+        for (size_t q = 0; q < t.n_points; ++q) t.h_src_off[q + 1] += t.h_src_off[q];
+    }
 
     Alloc alloc{t, planned_bytes(t)};
     alloc(t.D, en * t.elem);
@@ -622,8 +898,9 @@ int relax_to_fixed_point(AdjTapeDev& t, const char* what, Launch launch) {
     }
 }
 
+// the vjp; d_grad may be null (no gradient kernel); *lam_final (may be null) receives the buffer that holds the fixed point
 template <typename T>
-int adj_vjp(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, int schedule) {
+static int adj_vjp_impl(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, int schedule, const T** lam_final) {
     ADJ_CHECK(hipSetDevice(t.device));
     hipStream_t s = t.stream;
     const size_t E = t.n_events, en = E * t.nn;
@@ -656,11 +933,17 @@ int adj_vjp(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, int schedule)
         });
         if (schedule != 0) lam = in;   // (the buffer the last pass wrote; both hold the fixed point)
     }
-    if (t.nn > 0) {
+    if (d_grad && t.nn > 0) {
         adj_grad_kernel<T><<<blocks_for(t.nn), ADJ_THREADS, 0, s>>>(lam, (const T*)t.D, t.frozen, (const T*)t.slowness, geo, E, d_grad);
         ADJ_CHECK(hipGetLastError());
     }
+    if (lam_final) *lam_final = lam;
     return passes;
+}
+
+template <typename T>
+int adj_vjp(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, int schedule) {
+    return adj_vjp_impl<T>(t, d_w, d_fc, d_grad, schedule, nullptr);
 }
 
 // what the first jvp adds to the tape: the stencil in row order (offsets, keys, weights), a staging row for a host row_weight and the
@@ -746,6 +1029,137 @@ void adj_gn(AdjTapeDev& t, const T* d_v, const T* d_rw, T* d_out, int schedule, 
     *passes_vjp = adj_vjp<T>(t, w, nullptr, d_out, schedule);
 }
 
+// ---- derivatives with respect to the source points
+size_t adj_src_extra_bytes(const AdjTapeDev& t) {
+    const size_t n_ent = t.h_src_key.size();
+    return (t.n_points + 1) * sizeof(int) + n_ent * (2 * sizeof(int) + sizeof(long long) + 3 * t.elem) + 16 * t.n_points * t.elem +
+           4 * t.n_rows * t.elem;
+}
+size_t adj_src_column_bytes(const AdjTapeDev& t) { return 4 * t.n_events * t.nn * t.elem; }
+
+template <typename T>
+void adj_src_prepare(AdjTapeDev& t) {
+    if (t.src_off) return;
+    ADJ_CHECK(hipSetDevice(t.device));
+    Alloc alloc{t, adj_src_extra_bytes(t)};
+    const size_t before = t.total_bytes;
+    const size_t n_ent = t.h_src_key.size();
+    try {
+        alloc(t.src_off, (t.n_points + 1) * sizeof(int));
+        alloc(t.src_pt, n_ent * sizeof(int));
+        alloc(t.src_key, n_ent * sizeof(long long));
+        alloc(t.src_node, n_ent * sizeof(int));
+        alloc(t.src_c, 3 * n_ent * sizeof(T));
+        alloc(t.src_io, 16 * t.n_points * sizeof(T));
+        alloc(t.src_rows, 4 * t.n_rows * sizeof(T));
+        std::vector<int> pt(n_ent), node(n_ent);
+        for (size_t q = 0; q < t.n_points; ++q)
+            for (int i = t.h_src_off[q]; i < t.h_src_off[q + 1]; ++i) {
+                pt[i] = (int)q;
+                node[i] = (int)(t.h_src_key[i] - (long long)((size_t)t.h_pt_event[q] * t.nn));
+            }
+        const std::vector<T> c(t.h_src_c.begin(), t.h_src_c.end());
+        ADJ_CHECK(hipMemcpyAsync(t.src_off, t.h_src_off.data(), (t.n_points + 1) * sizeof(int), hipMemcpyHostToDevice, t.stream));
+        if (n_ent > 0) {
+            ADJ_CHECK(hipMemcpyAsync(t.src_pt, pt.data(), n_ent * sizeof(int), hipMemcpyHostToDevice, t.stream));
+            ADJ_CHECK(hipMemcpyAsync(t.src_key, t.h_src_key.data(), n_ent * sizeof(long long), hipMemcpyHostToDevice, t.stream));
+            ADJ_CHECK(hipMemcpyAsync(t.src_node, node.data(), n_ent * sizeof(int), hipMemcpyHostToDevice, t.stream));
+            ADJ_CHECK(hipMemcpyAsync(t.src_c, c.data(), 3 * n_ent * sizeof(T), hipMemcpyHostToDevice, t.stream));
+        }
+        ADJ_CHECK(hipStreamSynchronize(t.stream));   // (the host vectors leave scope)
+    } catch (...) {
+        dev_free(t.src_off); dev_free(t.src_pt); dev_free(t.src_key); dev_free(t.src_node); dev_free(t.src_c); dev_free(t.src_io);
+        dev_free(t.src_rows);
+        t.total_bytes = before;
+        throw;
+    }
+}
+
+template <typename T, int K>
+static int adj_jvp_source_k(AdjTapeDev& t, const T* d_dsrc, int n_cols, T* d_dtt, T* d_dfields, int schedule, const T** mu_out) {
+    using V = SrcVec<T, K>;
+    hipStream_t s = t.stream;
+    const size_t E = t.n_events, en = E * t.nn, n_ent = t.h_src_key.size();
+    const AdjGeom<T> geo{t.nnx, t.nny, t.nnz, t.nn, (T)t.dx};
+    V* mu = (V*)(K == 1 ? t.lam : t.mu4);
+    V* mu2 = (V*)(K == 1 ? t.lam2 : t.mu4b);
+    const V* fin = mu;
+    int passes = 0;
+    if (en > 0) {
+        ADJ_CHECK(hipMemsetAsync(mu, 0, en * sizeof(V), s));   // (+0: any start reaches the fixed point)
+        if (schedule != 0) ADJ_CHECK(hipMemsetAsync(mu2, 0, en * sizeof(V), s));
+        if (n_ent > 0)
+            for (V* buf : {mu, schedule != 0 ? mu2 : (V*)nullptr}) {
+                if (!buf) continue;
+                src_seed_kernel<T, K><<<blocks_for(n_ent), ADJ_THREADS, 0, s>>>(t.src_key, t.src_node, t.src_pt, (const T*)t.src_c, n_ent,
+                                                                               (const T*)t.slowness, d_dsrc, n_cols, t.n_points, buf);
+                ADJ_CHECK(hipGetLastError());
+            }
+        if (schedule == 0) ADJ_CHECK(hipMemsetAsync(t.tan_stamps, 0xFF, E * t.n_tan_tiles * sizeof(int), s));
+        constexpr int ed = TanTile<T>::edge;
+        const int ntx = (t.nnx + ed - 1) / ed, nty = (t.nny + ed - 1) / ed, ntz = (t.nnz + ed - 1) / ed;
+        const unsigned tiles = (unsigned)t.n_tan_tiles;
+        V* in = mu;
+        V* out = mu2;
+        passes = relax_to_fixed_point(t, "source tangent", [&](int pass, const int* prev, int* cur) {
+            if (schedule == 0) {
+                src_tiled_kernel<T, K, ed><<<dim3(tiles, (unsigned)E), ADJ_THREADS, 0, s>>>((const T*)t.fields, (const T*)t.D, t.frozen, mu, geo,
+                                                                                           ntx, nty, ntz, t.tan_stamps, pass, cur);
+            } else {
+                src_jacobi_kernel<T, K><<<dim3(blocks_for(t.nn), (unsigned)E), ADJ_THREADS, 0, s>>>((const T*)t.fields, (const T*)t.D, t.frozen,
+                                                                                                   in, out, geo, prev, cur);
+                std::swap(in, out);
+            }
+        });
+        if (schedule != 0) fin = in;   // (the buffer the last pass wrote; both hold the fixed point)
+    }
+    if (d_dtt && t.n_rows > 0) {
+        src_rows_kernel<T, K><<<blocks_for(t.n_rows * (size_t)n_cols), ADJ_THREADS, 0, s>>>(t.rw_off, t.rw_key, (const T*)t.rw_w, t.n_rows,
+                                                                                           n_cols, (const T*)fin, d_dtt);
+        ADJ_CHECK(hipGetLastError());
+    }
+    if (d_dfields && en > 0) {
+        src_unpack_kernel<T, K><<<std::min(blocks_for(en * (size_t)n_cols), 65536u), ADJ_THREADS, 0, s>>>((const T*)fin, en, n_cols, d_dfields);
+        ADJ_CHECK(hipGetLastError());
+    }
+    if (mu_out) *mu_out = (const T*)fin;
+    return passes;
+}
+
+template <typename T>
+int adj_jvp_source(AdjTapeDev& t, const T* d_dsrc, int n_cols, T* d_dtt, T* d_dfields, int schedule, const T** mu_out, int* k_out) {
+    ADJ_CHECK(hipSetDevice(t.device));
+    adj_jvp_prepare<T>(t);   // (the stencil in row order and the stamps of the tangent tiles)
+    adj_src_prepare<T>(t);
+    const int K = n_cols > 1 ? 4 : 1;
+    if (k_out) *k_out = K;
+    if (K == 1) return adj_jvp_source_k<T, 1>(t, d_dsrc, n_cols, d_dtt, d_dfields, schedule, mu_out);
+    for (void** buf : {&t.mu4, schedule != 0 ? &t.mu4b : (void**)nullptr}) {
+        if (!buf || *buf) continue;
+        Alloc alloc{t, adj_src_column_bytes(t)};
+        alloc(*buf, adj_src_column_bytes(t));
+    }
+    return adj_jvp_source_k<T, 4>(t, d_dsrc, n_cols, d_dtt, d_dfields, schedule, mu_out);
+}
+
+template <typename T>
+int adj_vjp_source(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, T* d_gsrc, int schedule) {
+    ADJ_CHECK(hipSetDevice(t.device));
+    adj_src_prepare<T>(t);
+    const T* lam = nullptr;
+    const int passes = adj_vjp_impl<T>(t, d_w, d_fc, d_grad, schedule, &lam);
+    if (t.n_points > 0) {
+        if (t.n_events * t.nn == 0) {
+            ADJ_CHECK(hipMemsetAsync(d_gsrc, 0, 4 * t.n_points * sizeof(T), t.stream));
+        } else {
+            src_grad_kernel<T><<<blocks_for(t.n_points), ADJ_THREADS, 0, t.stream>>>(t.src_off, t.src_key, t.src_node, (const T*)t.src_c,
+                                                                                    t.n_points, (const T*)t.slowness, lam, d_gsrc);
+            ADJ_CHECK(hipGetLastError());
+        }
+    }
+    return passes;
+}
+
 template void adj_copy_field<float>(const float*, int, float*, size_t, hipStream_t);
 template void adj_copy_field<double>(const double*, int, double*, size_t, hipStream_t);
 template void adj_finish<float>(AdjTapeDev&, const AdjSink&);
@@ -758,5 +1172,12 @@ template int adj_jvp<float>(AdjTapeDev&, const float*, float*, float*, int);
 template int adj_jvp<double>(AdjTapeDev&, const double*, double*, double*, int);
 template void adj_gn<float>(AdjTapeDev&, const float*, const float*, float*, int, int*, int*);
 template void adj_gn<double>(AdjTapeDev&, const double*, const double*, double*, int, int*, int*);
+
+template void adj_src_prepare<float>(AdjTapeDev&);
+template void adj_src_prepare<double>(AdjTapeDev&);
+template int adj_jvp_source<float>(AdjTapeDev&, const float*, int, float*, float*, int, const float**, int*);
+template int adj_jvp_source<double>(AdjTapeDev&, const double*, int, double*, double*, int, const double**, int*);
+template int adj_vjp_source<float>(AdjTapeDev&, const float*, const float*, float*, float*, int);
+template int adj_vjp_source<double>(AdjTapeDev&, const double*, const double*, double*, double*, int);
 
 }  // namespace ttcr_amd

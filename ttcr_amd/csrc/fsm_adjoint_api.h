@@ -34,6 +34,11 @@ struct AdjSink {
     // frozen nodes of every event (fsm_init_source): node and distance d of the point that wrote it last (a T value, held exactly)
     std::vector<std::vector<int>> fr_node;
     std::vector<std::vector<double>> fr_d;
+    // ... and, for the source derivative: the point that wrote the node last (index within the event, tx order) and
+    // c[a] = fl(fl(p_a - x_a) / d) for a = x, y, z (+0 where d = 0), computed in T and held exactly; 3 values per node
+    std::vector<std::vector<int>> fr_pt;
+    std::vector<std::vector<double>> fr_c;
+    std::vector<int> pt_off;    // n_events + 1: first point of every event among the points of the call
     // interpolation stencil of every receiver row (interp3d_stencil): 8 slots per row, st_cnt[row] of them used
     std::vector<int> st_cnt, st_event;
     std::vector<long long> st_node;
@@ -72,6 +77,22 @@ struct AdjTapeDev {
     std::vector<int> h_rw_off;        // host copies, kept from adj_finish on
     std::vector<long long> h_rw_key;
     std::vector<double> h_rw_w;
+    // source derivative.  Host lists, kept from adj_finish on: the frozen entries sorted by (point, node) -- a node belongs
+    // to the point that wrote it last --, uploaded by the first jvp_source / vjp_source
+    size_t n_points = 0;
+    std::vector<int> h_pt_event;      // n_points: event of every point
+    std::vector<int> h_src_off;       // n_points + 1: entries of point q at h_src_off[q] .. h_src_off[q + 1]
+    std::vector<long long> h_src_key; // event * nn + node
+    std::vector<double> h_src_c;      // 3 per entry
+    int* src_off = nullptr;
+    int* src_pt = nullptr;            // point of every entry
+    long long* src_key = nullptr;
+    int* src_node = nullptr;
+    void* src_c = nullptr;
+    void* src_io = nullptr;           // 16 n_points values: a host dsrc / gsrc is staged here
+    void* src_rows = nullptr;         // 4 n_rows values: the dtt of a K-column call before it goes to the host
+    void* mu4 = nullptr;              // 4 n_events * nn: the four columns of a node adjacent (allocated by the first call with n_cols > 1)
+    void* mu4b = nullptr;             // second buffer of the Jacobi baseline (allocated by the first such call with that schedule)
     size_t n_tiles = 0;
     size_t total_bytes = 0;
     hipStream_t stream = nullptr;
@@ -104,5 +125,21 @@ int adj_jvp(AdjTapeDev& t, const T* d_ds, T* d_dtt, T* d_dfields, int schedule);
 // Gauss-Newton product: jvp into w_tmp -> w_tmp *= d_rw (may be null) -> vjp into d_out (nn), all on the tape's stream
 template <typename T>
 void adj_gn(AdjTapeDev& t, const T* d_v, const T* d_rw, T* d_out, int schedule, int* passes_jvp, int* passes_vjp);
+
+// ---- derivatives with respect to the source points (tests/source_reference.py restates them)
+// what the first jvp_source / vjp_source adds to the tape (the lists above and the two staging arrays), and what the first call with
+// n_cols > 1 adds per K-column buffer
+size_t adj_src_extra_bytes(const AdjTapeDev& t);
+size_t adj_src_column_bytes(const AdjTapeDev& t);
+template <typename T>
+void adj_src_prepare(AdjTapeDev& t);   // a no-op from the second call on
+// d_dsrc (n_cols * n_points * 4), d_dtt (n_cols * n_rows, may be null), d_dfields (n_cols * n_events * nn, may be null): on the tape's
+// device.  One relaxation of K = 1 (n_cols = 1) or K = 4 columns (the columns past n_cols are +0); returns the passes launched.
+// *mu_out (may be null) receives the relaxed buffer: n_events * nn * K values, the K columns of a node adjacent; *k_out its K.
+template <typename T>
+int adj_jvp_source(AdjTapeDev& t, const T* d_dsrc, int n_cols, T* d_dtt, T* d_dfields, int schedule, const T** mu_out, int* k_out);
+// the vjp (d_grad may be null here) and, from the same lam, d_gsrc (n_points * 4)
+template <typename T>
+int adj_vjp_source(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, T* d_gsrc, int schedule);
 
 }  // namespace ttcr_amd

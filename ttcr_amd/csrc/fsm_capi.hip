@@ -2415,17 +2415,26 @@ class GridT : public GridBase {
             }
             if (e == 0) HIP_CHECK(hipMemcpyAsync(sk.slowness, d_s.p, n_nodes * sizeof(T), hipMemcpyDefault, stream));
             // frozen nodes: the points in order, the later writer wins (fsm_init_source, 3-D branch, first order)
+            // (with each node the point that wrote it, counted within the event, and c = (p - x) / d in T, +0 where d = 0: DESIGN.md 6d)
             std::vector<int>& fn = sk.fr_node[e];
             std::vector<double>& fd = sk.fr_d[e];
-            fn.clear(); fd.clear();
+            std::vector<int>& fp = sk.fr_pt[e];
+            std::vector<double>& fc = sk.fr_c[e];
+            fn.clear(); fd.clear(); fp.clear(); fc.clear();
+            int pt = 0;
+            T cx = 0, cy = 0, cz = 0;
             auto put = [&](long long m, T d) {
-                for (size_t q = 0; q < fn.size(); ++q)
-                    if (fn[q] == (int)m) { fd[q] = (double)d; return; }
-                fn.push_back((int)m); fd.push_back((double)d);
+                size_t q = 0;
+                while (q < fn.size() && fn[q] != (int)m) ++q;
+                if (q == fn.size()) { fn.push_back((int)m); fd.push_back(0.0); fp.push_back(0); fc.insert(fc.end(), 3, 0.0); }
+                fd[q] = (double)d; fp[q] = pt;
+                fc[3 * q] = (double)cx; fc[3 * q + 1] = (double)cy; fc[3 * q + 2] = (double)cz;
             };
             for (int q = tx_off[n]; q < tx_off[n + 1]; ++q) {
                 const InitPoint<T> p = locate(tx + (size_t)3 * q, t0[q]);
                 const int b0 = p.on_node ? -1 : 0;
+                pt = q - tx_off[n];
+                cx = 0; cy = 0; cz = 0;
                 if (p.on_node) put(((long long)p.k * nny + p.j) * nnx + p.i, (T)0);
                 for (int kk = p.k + b0; kk <= p.k + 1; ++kk)
                     for (int jj = p.j + b0; jj <= p.j + 1; ++jj)
@@ -2434,7 +2443,12 @@ class GridT : public GridBase {
                             if (ii == p.i && jj == p.j && kk == p.k) continue;
                             const T x = node_coord_h(xmin, (uint32_t)ii, dx), y = node_coord_h(ymin, (uint32_t)jj, dx), z = node_coord_h(zmin, (uint32_t)kk, dx);
                             const T d2 = (x - p.x) * (x - p.x) + (y - p.y) * (y - p.y) + (z - p.z) * (z - p.z);
-                            put(((long long)kk * nny + jj) * nnx + ii, (T)std::sqrt((double)d2));
+                            const T d = (T)std::sqrt((double)d2);
+                            const bool zero = d == (T)0;
+                            cx = zero ? (T)0 : (T)((T)(p.x - x) / d);
+                            cy = zero ? (T)0 : (T)((T)(p.y - y) / d);
+                            cz = zero ? (T)0 : (T)((T)(p.z - z) / d);
+                            put(((long long)kk * nny + jj) * nnx + ii, d);
                         }
             }
             for (int r = rx_off[n]; r < rx_off[n + 1]; ++r) {
@@ -3809,6 +3823,8 @@ int ttcr_fsm_raytrace_multi_adjoint(ttcr_fsm_grid* g, int n_src, const int* tx_o
             sink.device = t.device; sink.elem = t.elem; sink.nn = t.nn;
             sink.fields = t.fields; sink.slowness = t.slowness;
             sink.fr_node.resize(t.n_events); sink.fr_d.resize(t.n_events);
+            sink.fr_pt.resize(t.n_events); sink.fr_c.resize(t.n_events);
+            sink.pt_off.assign(tx_off ? tx_off : &n_src, tx_off ? tx_off + n_src + 1 : &n_src + 1);   // (n_src = 0: the one offset 0)
             sink.st_cnt.assign(t.n_rows, 0); sink.st_event.assign(t.n_rows, 0);
             sink.st_node.assign(8 * t.n_rows, 0); sink.st_w.assign(8 * t.n_rows, 0.0);
             G.raytrace_multi_adjoint(n_src, tx_off, tx, t0, rx_off, rx, tt_out, sink);
@@ -3975,6 +3991,114 @@ int ttcr_fsm_adjoint_gn(const ttcr_fsm_adjoint* t, const void* v, int v_on_devic
             HIP_CHECK(hipStreamSynchronize(d.stream));
             if (passes_jvp) *passes_jvp = pj;
             if (passes_vjp) *passes_vjp = pv;
+        });
+    });
+}
+int ttcr_fsm_adjoint_points(const ttcr_fsm_adjoint* t, size_t* n_points, int* event_of_point) {
+    if (!t || !n_points) {
+        g_last_error = !t ? "null tape" : "null n_points";
+        return TTCR_ERR_VALUE;
+    }
+    *n_points = t->t.n_points;
+    if (event_of_point) std::copy(t->t.h_pt_event.begin(), t->t.h_pt_event.end(), event_of_point);
+    return TTCR_OK;
+}
+int ttcr_fsm_adjoint_jvp_source(const ttcr_fsm_adjoint* t, const void* dsrc, int dsrc_on_device, int n_cols, void* dtt, int dtt_on_device,
+                                void* dfields, int df_on_device, int schedule, int* passes) {
+    if (!t || !dsrc || (!dtt && !dfields)) {
+        g_last_error = !t ? "null tape" : (!dsrc ? "null dsrc" : "dtt and dfields are both null: nothing to compute");
+        return TTCR_ERR_VALUE;
+    }
+    if (n_cols < 1 || n_cols > 4) {
+        g_last_error = "n_cols: 1 to 4 columns per call";
+        return TTCR_ERR_VALUE;
+    }
+    if (schedule != 0 && schedule != 1) {
+        g_last_error = "schedule: 0 (tiled) or 1 (global Jacobi)";
+        return TTCR_ERR_VALUE;
+    }
+    ttcr_fsm_adjoint* tm = const_cast<ttcr_fsm_adjoint*>(t);
+    std::lock_guard<std::mutex> lock(tm->mu);
+    return guarded([&] {
+        ttcr_amd::AdjTapeDev& d = tm->t;
+        adj_device_errors([&] {
+            HIP_CHECK(hipSetDevice(d.device));
+            const size_t en = d.n_events * d.nn, nc = (size_t)n_cols;
+            if (tm->dtype == TTCR_F32) ttcr_amd::adj_src_prepare<float>(d);   // (the staging arrays are part of what the first call allocates)
+            else ttcr_amd::adj_src_prepare<double>(d);
+            const void* dd = dsrc;
+            if (!dsrc_on_device) {
+                if (d.n_points > 0) HIP_CHECK(hipMemcpyAsync(d.src_io, dsrc, nc * d.n_points * 4 * d.elem, hipMemcpyHostToDevice, d.stream));
+                dd = d.src_io;
+            }
+            void* ddtt = dtt ? (dtt_on_device ? dtt : d.src_rows) : nullptr;
+            void* ddf = dfields && df_on_device ? dfields : nullptr;
+            int np = 0, K = 1;
+            const void* mu = nullptr;
+            if (tm->dtype == TTCR_F32)
+                np = ttcr_amd::adj_jvp_source<float>(d, (const float*)dd, n_cols, (float*)ddtt, (float*)ddf, schedule, (const float**)&mu, &K);
+            else
+                np = ttcr_amd::adj_jvp_source<double>(d, (const double*)dd, n_cols, (double*)ddtt, (double*)ddf, schedule, (const double**)&mu, &K);
+            if (dtt && !dtt_on_device && d.n_rows > 0)
+                HIP_CHECK(hipMemcpyAsync(dtt, d.src_rows, nc * d.n_rows * d.elem, hipMemcpyDeviceToHost, d.stream));
+            if (dfields && !df_on_device && en > 0) {   // (a host copy: the relaxed buffer as it is, the columns of a node parted here)
+                if (K == 1) {
+                    HIP_CHECK(hipMemcpyAsync(dfields, mu, en * d.elem, hipMemcpyDeviceToHost, d.stream));
+                } else {
+                    std::vector<char> tmp(en * K * d.elem);
+                    HIP_CHECK(hipMemcpyAsync(tmp.data(), mu, tmp.size(), hipMemcpyDeviceToHost, d.stream));
+                    HIP_CHECK(hipStreamSynchronize(d.stream));
+                    char* out = (char*)dfields;
+                    for (size_t k = 0; k < nc; ++k)
+                        for (size_t i = 0; i < en; ++i) std::memcpy(out + (k * en + i) * d.elem, tmp.data() + (i * K + k) * d.elem, d.elem);
+                }
+            }
+            HIP_CHECK(hipStreamSynchronize(d.stream));
+            if (passes) *passes = np;
+        });
+    });
+}
+int ttcr_fsm_adjoint_vjp_source(const ttcr_fsm_adjoint* t, const void* w, int w_on_device, const void* field_cot, int fc_on_device, void* grad,
+                                int grad_on_device, void* gsrc, int gsrc_on_device, int schedule, int* passes) {
+    if (!t || !gsrc || (!w && !field_cot)) {
+        g_last_error = !t ? "null tape" : (!gsrc ? "null gsrc" : "w and field_cot are both null: nothing to back-propagate");
+        return TTCR_ERR_VALUE;
+    }
+    if (schedule != 0 && schedule != 1) {
+        g_last_error = "schedule: 0 (tiled) or 1 (global Jacobi)";
+        return TTCR_ERR_VALUE;
+    }
+    ttcr_fsm_adjoint* tm = const_cast<ttcr_fsm_adjoint*>(t);
+    std::lock_guard<std::mutex> lock(tm->mu);
+    return guarded([&] {
+        ttcr_amd::AdjTapeDev& d = tm->t;
+        adj_device_errors([&] {
+            HIP_CHECK(hipSetDevice(d.device));
+            if (tm->dtype == TTCR_F32) ttcr_amd::adj_src_prepare<float>(d);
+            else ttcr_amd::adj_src_prepare<double>(d);
+            const void* dw = w;
+            const void* dfc = field_cot;
+            void* dg = grad ? (grad_on_device ? grad : d.grad_tmp) : nullptr;
+            void* dgs = gsrc_on_device ? gsrc : d.src_io;
+            if (w && !w_on_device) {
+                if (d.n_rows > 0) HIP_CHECK(hipMemcpyAsync(d.w_tmp, w, d.n_rows * d.elem, hipMemcpyHostToDevice, d.stream));
+                dw = d.w_tmp;
+            }
+            if (field_cot && !fc_on_device) {   // (staged as ttcr_fsm_adjoint_vjp stages it)
+                if (d.n_events * d.nn > 0)
+                    HIP_CHECK(hipMemcpyAsync(d.lam2, field_cot, d.n_events * d.nn * d.elem, hipMemcpyHostToDevice, d.stream));
+                dfc = d.lam2;
+            }
+            int np = 0;
+            if (tm->dtype == TTCR_F32)
+                np = ttcr_amd::adj_vjp_source<float>(d, (const float*)dw, (const float*)dfc, (float*)dg, (float*)dgs, schedule);
+            else
+                np = ttcr_amd::adj_vjp_source<double>(d, (const double*)dw, (const double*)dfc, (double*)dg, (double*)dgs, schedule);
+            if (grad && !grad_on_device) HIP_CHECK(hipMemcpyAsync(grad, d.grad_tmp, d.nn * d.elem, hipMemcpyDeviceToHost, d.stream));
+            if (!gsrc_on_device && d.n_points > 0)
+                HIP_CHECK(hipMemcpyAsync(gsrc, d.src_io, 4 * d.n_points * d.elem, hipMemcpyDeviceToHost, d.stream));
+            HIP_CHECK(hipStreamSynchronize(d.stream));
+            if (passes) *passes = np;
         });
     });
 }

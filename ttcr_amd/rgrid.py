@@ -538,7 +538,9 @@ class FieldTape:
     what the exact discrete adjoint of the first-order update needs besides them: the node slowness, the nodes each source froze and
     the interpolation stencil of every (event, receiver) row.  Events are in the order raytrace takes them.  The tape does not depend
     on the grid any more: later calls, set_slowness and deleting the grid leave it as it is.  vjp applies J^T (reverse mode), jvp
-    applies J (forward mode) and gauss_newton J^T W J of the same linearisation, all on the device."""
+    applies J (forward mode) and gauss_newton J^T W J of the same linearisation, all on the device.  The same linearisation with respect
+    to the source points, parameters (t0, x, y, z) each: jvp_source, source_jacobian and vjp(..., return_source_grad=True); n_points
+    points in call order, point_event their events."""
 
     SCHEDULES = {'tiled': 0, 'jacobi': 1}
 
@@ -557,6 +559,12 @@ class FieldTape:
         self.device, self.nbytes = d.value, b.value
         self.passes = 0            # relaxation passes of the last vjp or jvp; (jvp, vjp) after gauss_newton
         self._rows_dev = None
+        npt = C.c_size_t(0)
+        _lib.check(lib.ttcr_fsm_adjoint_points(handle, C.byref(npt), None))
+        self.n_points = npt.value  # source points of all events, in call order
+        ev = np.zeros(max(self.n_points, 1), dtype=np.int32)
+        _lib.check(lib.ttcr_fsm_adjoint_points(handle, C.byref(npt), _ptr(ev)))
+        self.point_event = ev[:self.n_points].astype(np.int64)   # event of every point
 
     def _handle(self):
         if not self._h:
@@ -574,8 +582,10 @@ class FieldTape:
             raise ValueError("schedule should be 'tiled' or 'jacobi', got %r" % (schedule,))
         return self.SCHEDULES[schedule]
 
-    def vjp(self, w=None, field_cotangent=None, schedule='tiled'):
+    def vjp(self, w=None, field_cotangent=None, schedule='tiled', return_source_grad=False):
         """d loss / d node slowness (n_cols values, x fastest, grid dtype) for  loss = w . tt + field_cotangent . fields.
+        return_source_grad=True: (grad, gsrc) with gsrc (n_points, 4) = d loss / d (t0, x, y, z) of every source point, from the same
+        relaxation (a point whose frozen nodes a later point of its event all overwrote gets zeros).
         w: one value per data row of the raytrace_adjoint call (rcv order); field_cotangent: (n_events, n_cols) values, node order x
         fastest; either may be None, not both.  schedule: 'tiled' (default) or 'jacobi', the bit-equal baseline.  Torch tensors in give
         a torch tensor out; tensors on the tape's device are used in place (torch's current stream is synchronised first, the result is
@@ -585,7 +595,7 @@ class FieldTape:
         if w is None and field_cotangent is None:
             raise ValueError('w and field_cotangent are both None: nothing to back-propagate')
         if any(type(a).__module__.startswith('torch') for a in (w, field_cotangent) if a is not None):
-            return self._vjp_torch(w, field_cotangent, sch)
+            return self._vjp_torch(w, field_cotangent, sch, return_source_grad)
         wt = fc = None
         if w is not None:
             w = np.asarray(w)
@@ -598,19 +608,30 @@ class FieldTape:
                 raise ValueError('field_cotangent should hold %d x %d values, got shape %s' % (self.n_events, self.n_cols, fc.shape))
         g = np.empty(max(self.n_cols, 1), dtype=self.dtype)
         np_ = C.c_int(0)
+        if return_source_grad:
+            gs = np.zeros((max(self.n_points, 1), 4), dtype=self.dtype)
+            _lib.check(self._lib.ttcr_fsm_adjoint_vjp_source(self._h, _ptr(wt) if wt is not None else None, 0,
+                                                             _ptr(fc) if fc is not None else None, 0, _ptr(g), 0, _ptr(gs), 0, sch,
+                                                             C.byref(np_)))
+            self.passes = np_.value
+            self._refresh_nbytes()
+            return g[:self.n_cols], gs[:self.n_points]
         _lib.check(self._lib.ttcr_fsm_adjoint_vjp(self._h, _ptr(wt) if wt is not None else None, 0, _ptr(fc) if fc is not None else None, 0,
                                                   _ptr(g), 0, sch, C.byref(np_)))
         self.passes = np_.value
         return g[:self.n_cols]
 
-    def _vjp_torch(self, w, fc, sch):
+    def _vjp_torch(self, w, fc, sch, source_grad=False):
         import torch
 
         tdt = torch.float32 if self.dtype == np.float32 else torch.float64
         ref = w if (w is not None and type(w).__module__.startswith('torch')) else fc
         if ref.device.type != 'cuda':
             host = [a.detach().numpy() if hasattr(a, 'detach') else a for a in (w, fc)]
-            return torch.from_numpy(self.vjp(host[0], host[1], 'jacobi' if sch else 'tiled')).to(ref.device)
+            out = self.vjp(host[0], host[1], 'jacobi' if sch else 'tiled', source_grad)
+            if source_grad:
+                return tuple(torch.from_numpy(o).to(ref.device) for o in out)
+            return torch.from_numpy(out).to(ref.device)
         dev = torch.device('cuda', self.device)
         wt = fct = None
         if w is not None:
@@ -628,6 +649,15 @@ class FieldTape:
         g = torch.empty(max(self.n_cols, 1), dtype=tdt, device=dev)
         torch.cuda.current_stream(dev).synchronize()
         np_ = C.c_int(0)
+        if source_grad:
+            gs = torch.zeros((max(self.n_points, 1), 4), dtype=tdt, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            _lib.check(self._lib.ttcr_fsm_adjoint_vjp_source(self._h, C.c_void_p(wt.data_ptr()) if wt is not None else None, 1,
+                                                             C.c_void_p(fct.data_ptr()) if fct is not None else None, 1,
+                                                             C.c_void_p(g.data_ptr()), 1, C.c_void_p(gs.data_ptr()), 1, sch, C.byref(np_)))
+            self.passes = np_.value
+            self._refresh_nbytes()
+            return g[:self.n_cols].to(ref.device), gs[:self.n_points].to(ref.device)
         _lib.check(self._lib.ttcr_fsm_adjoint_vjp(self._h, C.c_void_p(wt.data_ptr()) if wt is not None else None, 1,
                                                   C.c_void_p(fct.data_ptr()) if fct is not None else None, 1, C.c_void_p(g.data_ptr()), 1,
                                                   sch, C.byref(np_)))
@@ -684,6 +714,75 @@ class FieldTape:
         dtt = torch.zeros(self.n_data, dtype=tdt, device=dev)
         dtt[self._rows_dev] = rows[:self.n_rows]
         return (dtt.to(ds.device), df.to(ds.device)) if return_fields else dtt.to(ds.device)
+
+    def jvp_source(self, dsrc, return_fields=False, schedule='tiled'):
+        """J_src dsrc: the change of the receiver traveltimes for a perturbation of the source points, dsrc (n_points, 4) holding
+        (dt0, dx, dy, dz) of every point in call order (point_event names their events) -- the exact derivative of the returned tt
+        through the nodes the source initialisation froze and the solver's own update.  dsrc (K, n_points, 4), K <= 4, applies K
+        perturbations in one relaxation; the results then carry a leading K axis, each column with the bits of its own call.  Returns
+        dtt in rcv order; with return_fields=True (dtt, dfields), dfields (n_events, n_cols) per perturbation.  The map has a kink where
+        a point crosses a cell face or enters the 1e-4 on-node tolerance: the formula of the side the point is on is returned.  Array
+        handling and schedule as in jvp; the first call allocates its lists, a call with K > 1 a four-column work array (nbytes)."""
+        self._handle()
+        sch = self._schedule(schedule)
+        is_torch = type(dsrc).__module__.startswith('torch')
+        if is_torch:
+            import torch
+        shape = tuple(dsrc.shape)
+        batched = len(shape) == 3
+        if len(shape) not in (2, 3) or shape[-2:] != (self.n_points, 4) or (batched and not 1 <= shape[0] <= 4):
+            raise ValueError('dsrc should be (%d, 4) or (K, %d, 4) with K from 1 to 4, got shape %s' % (self.n_points, self.n_points, shape))
+        K = shape[0] if batched else 1
+        np_ = C.c_int(0)
+        if is_torch and dsrc.device.type == 'cuda':
+            tdt = torch.float32 if self.dtype == np.float32 else torch.float64
+            dev = torch.device('cuda', self.device)
+            if self._rows_dev is None:
+                self._rows_dev = torch.as_tensor(self._rows, device=dev)
+            dd = dsrc.detach().to(device=dev, dtype=tdt).contiguous()
+            rows = torch.zeros((K, self.n_rows), dtype=tdt, device=dev)
+            df = torch.empty((K, self.n_events, self.n_cols), dtype=tdt, device=dev) if return_fields else None
+            torch.cuda.current_stream(dev).synchronize()
+            want_rows, want_df = rows.numel() > 0, df is not None and df.numel() > 0
+            if want_rows or want_df:
+                _lib.check(self._lib.ttcr_fsm_adjoint_jvp_source(self._h, C.c_void_p(dd.data_ptr()), 1, K,
+                                                                 C.c_void_p(rows.data_ptr()) if want_rows else None, 1,
+                                                                 C.c_void_p(df.data_ptr()) if want_df else None, 1, sch, C.byref(np_)))
+            dtt = torch.zeros((K, self.n_data), dtype=tdt, device=dev)
+            dtt[:, self._rows_dev] = rows
+            out = [dtt.to(dsrc.device), df.to(dsrc.device) if df is not None else None]
+        else:
+            host = dsrc.detach().numpy() if is_torch else dsrc
+            dd = np.ascontiguousarray(host, dtype=self.dtype)
+            if dd.size == 0:
+                dd = np.zeros(4, dtype=self.dtype)
+            rows = np.zeros((K, self.n_rows), dtype=self.dtype)
+            df = np.empty((K, self.n_events, self.n_cols), dtype=self.dtype) if return_fields else None
+            if rows.size or (df is not None and df.size):
+                _lib.check(self._lib.ttcr_fsm_adjoint_jvp_source(self._h, _ptr(dd), 0, K, _ptr(rows) if rows.size else None, 0,
+                                                                 _ptr(df) if df is not None and df.size else None, 0, sch, C.byref(np_)))
+            dtt = np.zeros((K, self.n_data), dtype=self.dtype)
+            dtt[:, self._rows] = rows
+            out = [dtt, df]
+            if is_torch:
+                out = [torch.from_numpy(o) if o is not None else None for o in out]
+        self.passes = np_.value
+        self._refresh_nbytes()
+        if not batched:
+            out = [o[0] if o is not None else None for o in out]
+        return (out[0], out[1]) if return_fields else out[0]
+
+    def source_jacobian(self, schedule='tiled'):
+        """(n_data, 4): d tt[row] / d (t0, x, y, z) of the source point of the row's event, rows in rcv order -- one jvp_source call of
+        four columns, column k perturbing parameter k of every point by 1.  Events with one point each only: with several points per
+        event a row depends on all of them, which jvp_source handles (ValueError here)."""
+        self._handle()
+        if self.n_points != self.n_events or np.any(self.point_event != np.arange(self.n_events)):
+            raise ValueError('source_jacobian needs one source point per event; an event of this tape has several: use jvp_source')
+        dsrc = np.zeros((4, self.n_points, 4), dtype=self.dtype)
+        for k in range(4):
+            dsrc[k, :, k] = 1
+        return np.ascontiguousarray(self.jvp_source(dsrc, schedule=schedule).T)
 
     def gauss_newton(self, v, row_weight=None, schedule='tiled'):
         """J^T (row_weight * (J v)): the Gauss-Newton Hessian product (n_cols values, x fastest, grid dtype), with the bits of
