@@ -258,6 +258,12 @@ size_t ttcr_fsm_n_cells(const ttcr_fsm_grid* g);
  *                     Grid3Drn::getRaypath(Tx,t0,Rx,r_data,tt,threadNo) (ttcr/Grid3Drn.h:1339-1500); the rays
  *                     stay in the grid until the next raytrace call, see ttcr_fsm_get_rays (2-D: Grid2Drn::
  *                     getRaypath, ttcr/Grid2Drn.h:1663-1850, points are (x, z) pairs).
+ *   "walk_records" room of one row of the recording ray walks (return_rays, compute_M, the M tape, compute_L), in records: it takes
+ *                     the place of 8 * (ncx + ncy + ncz + 3) (2-D: 8 * (ncx + ncz + 3)) in the row length; the rows of a launch share
+ *                     a fixed budget, so a larger value also means fewer receivers per launch.  A walk that needs more than a row is
+ *                     walked again alone with the room it asked for.  A buffer size, not arithmetic: no result depends on it (tests
+ *                     reach the second walk and the seams between launches with it on small grids).  0 (default): that formula;
+ *                     1 ... 1 000 000 (the step limit of a walk); anything else is refused.
  *   "skip"         1: the persistent kernels step over chunks, work units and whole sweeps that cannot change a node:
  *                     a chunk whose read set (bricks of 16^3 nodes stamped with the sweep of their last change; the
  *                     change flags its upwind patches publish with their progress) holds no change since its nodes

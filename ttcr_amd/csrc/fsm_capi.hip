@@ -224,6 +224,10 @@ class GridBase {
     Timing timing;
     std::string last_kernel;   // instantiation of the sweep kernel the last solve launched (ttcr_fsm_last_kernel)
     virtual std::string kernel_name() const { return last_kernel; }
+    long walk_step_limit = 1000000;   // steps after which a ray walk is declared endless (the oracle uses the same number)
+    long walk_records = 0;   // option "walk_records": records per row of the recording ray walks (rays, compute_M, the M tape, compute_L) in place
+                             // of eight per node of the grid's extent (0, default); a walk that needs more is walked again alone with room
+    long walk_room(long extent) const { return std::min<long>(walk_step_limit, walk_records > 0 ? walk_records : extent); }
     // ttcr_fsm_set_option (a multi-device grid forwards it to its replicas)
     virtual void apply_option(const std::string& k, double value) {
         if (k == "fixed_iters") fixed_iters = (int)value;
@@ -253,6 +257,11 @@ class GridBase {
             if (value != 0 && value != 1 && value != 2)
                 throw ValueError("option 'arith': 0 (the reference's arithmetic), 1 (tolerance-grade fp32 where it stays within 1e-5 s RMS) or 2 (the WENO stage as well)");
             arith = (int)value;
+        }
+        else if (k == "walk_records") {
+            if (value != 0 && !(value >= 1 && value <= (double)walk_step_limit && value == (double)(long)value))
+                throw ValueError("option 'walk_records': 0 (default) or a whole number from 1 to the step limit of a walk");
+            walk_records = (long)value;
         }
         else throw ValueError("unknown option '" + k + "'");
     }
@@ -2080,7 +2089,7 @@ class GridT : public GridBase {
         // of steps before it drifts away (41 512 points for a receiver 1.7e-4 inside the far corner of a 2-D cell grid,
         // tests/test_parity_gpu.py).  The limit only turns a walk that would never end into an error.
         const long max_steps = walk_step_limit;
-        const long cap = std::min<long>(max_steps, 8L * ((long)ncx + ncy + ncz + 3)) + 3;   // Rx, one point per step, <= two per source point
+        const long cap = walk_room(8L * ((long)ncx + ncy + ncz + 3)) + 3;   // Rx, one point per step, <= two per source point
         // (the recording rows of a launch: at most rays_buffer_bytes, and at most a quarter of what the device has free -- a replica that is
         // full of slots, or a smaller device, records in more launches instead of failing its allocation)
         size_t rays_budget = rays_buffer_bytes, free_b = 0, total_b = 0;
@@ -2164,7 +2173,6 @@ class GridT : public GridBase {
     std::vector<T> rays_pts;
     DevBuf<T> d_raypts, d_raydense, d_raylong;
     DevBuf<long long> d_rayoff2;
-    long walk_step_limit = 1000000;   // steps after which a ray walk is declared endless (the oracle uses the same number)
     DevBuf<int> d_raynp;
     DevBuf<long long> d_rayoff;
 
@@ -2201,7 +2209,7 @@ class GridT : public GridBase {
         rg.interp_vel = interp_vel;
         const long max_steps = walk_step_limit;
         // one record per step, up to two per source point at the end; a longer walk is done again with the room it asked for
-        const long cap = std::min<long>(max_steps, 8L * ((long)ncx + ncy + ncz + 3)) + 2L * n_tx + 1;
+        const long cap = walk_room(8L * ((long)ncx + ncy + ncz + 3)) + 2L * n_tx + 1;
         const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)256 << 20) / (sizeof(T) * 5 * cap)));
         std::vector<int> st(chunk), ns(chunk);
         std::vector<T> rows;
@@ -2549,7 +2557,7 @@ class GridT : public GridBase {
         rg2.nnx = ncx + 1; rg2.nnz = ncz + 1;
         rg2.dx = dx; rg2.dz = dz; rg2.xmin = xmin; rg2.zmin = zmin; rg2.xmax = xmax; rg2.zmax = zmax;
         const long max_steps = walk_step_limit;
-        long cap = std::min<long>(max_steps, 8L * ((long)ncx + ncz + 3)) + 4;
+        long cap = walk_room(8L * ((long)ncx + ncz + 3)) + 4;
         const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_rx, ((size_t)256 << 20) / (sizeof(T) * 4 * cap)));
         std::vector<int> st(chunk), np(chunk), nl(chunk);
         std::vector<uint32_t> hc;
