@@ -424,11 +424,29 @@ int ttcr_fsm_tape_free(ttcr_fsm_tape* t);
  *   nodes m with q(m) = q in ascending node index, acc = fl(acc + lam[m]);  gsrc[q][1 + a] = the same chain of
  *   fl(lam[m] * fl(s[m] * c[m][a])).  A point all of whose nodes a later point overwrote gets four +0.  grad may be NULL (no slowness
  *   gradient is formed); otherwise it has the bits of ttcr_fsm_adjoint_vjp.  One thread per point, no floating-point atomics.
+ * Cell tapes.  ttcr_fsm_raytrace_multi_adjoint_cells: the same call for a 3-D grid with slowness defined for CELLS and
+ *   without the WENO stage (a node grid: TTCR_ERR_VALUE, the message names ttcr_fsm_raytrace_multi_adjoint; 2-D and WENO grids:
+ *   TTCR_ERR_UNSUPPORTED; ttcr_fsm_raytrace_multi_adjoint itself keeps refusing cell grids).  The solver works on the node slowness
+ *   s = A sc, A the averaging of Grid3Drcfs::setSlowness (the mean of the cells that touch a node); the tape holds that s and is the tape
+ *   above in everything but its model vector, which has n_cells = ncx ncy ncz values, cell (ck * ncy + cj) * ncx + ci, x fastest -- the
+ *   order ttcr_fsm_set_slowness takes.  On such a tape grad of ttcr_fsm_adjoint_vjp and ttcr_fsm_adjoint_vjp_source, ds of
+ *   ttcr_fsm_adjoint_jvp, v and out of ttcr_fsm_adjoint_gn hold n_cells values:  jvp(ds) = node jvp(A ds), A ds with the arithmetic and
+ *   summation order of ttcr_fsm_set_slowness (its kernel);  vjp = A^T (node vjp), with  (A^T g)[c] = the eight products fl(f(n) * g[n]) over
+ *   the corner nodes n = (ci + a, cj + b, ck + d) of the cell, f(n) = 1 / (number of cells that touch n), added left to right from the
+ *   first product, a innermost, d outermost, lower index first, in the grid dtype, without fused multiply-add; one thread per cell, no
+ *   atomics;  gn(v) = A^T J^T W J A v, on the tape's stream without a host copy in between.  field_cot, dfields, the field of
+ *   ttcr_fsm_adjoint_get_field and the third output of ttcr_fsm_adjoint_size stay n_nodes; the source-point calls are unchanged.  A cell
+ *   tape holds n_cells elem bytes more (a staging vector for host arrays), which ttcr_fsm_adjoint_bytes reports.
+ * ttcr_fsm_adjoint_model: *cells = 1 for a cell tape, 0 for a node tape; *n_params the length of its model vector (n_cells or n_nodes);
+ *   *n_nodes the nodes of a field.
  * Argument errors (a NULL tape or pointer, w and field_cot both NULL, dtt and dfields both NULL, n_cols outside 1 to 4, an unknown
  * schedule) return TTCR_ERR_VALUE before any device call. */
 typedef struct ttcr_fsm_adjoint ttcr_fsm_adjoint; /* opaque */
 int ttcr_fsm_raytrace_multi_adjoint(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off,
                                     const void* rx, void* tt_out, ttcr_fsm_adjoint** tape);
+int ttcr_fsm_raytrace_multi_adjoint_cells(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off,
+                                          const void* rx, void* tt_out, ttcr_fsm_adjoint** tape);
+int ttcr_fsm_adjoint_model(const ttcr_fsm_adjoint* t, int* cells, size_t* n_params, size_t* n_nodes);
 int ttcr_fsm_adjoint_size(const ttcr_fsm_adjoint* t, size_t* n_events, size_t* n_rows, size_t* n_nodes);
 int ttcr_fsm_adjoint_bytes(const ttcr_fsm_adjoint* t, size_t* bytes);
 int ttcr_fsm_adjoint_device(const ttcr_fsm_adjoint* t, int* device);

@@ -72,6 +72,10 @@ cdef extern from "ttcr_amd.h" nogil:
         pass
     int ttcr_fsm_raytrace_multi_adjoint(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0,
                                         const int* rx_off, const void* rx, void* tt_out, ttcr_fsm_adjoint** tape)
+    # the same for a 3-D cell grid: the model vector of vjp / jvp / gn then holds n_cells values (ttcr_fsm_adjoint_model tells which)
+    int ttcr_fsm_raytrace_multi_adjoint_cells(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0,
+                                              const int* rx_off, const void* rx, void* tt_out, ttcr_fsm_adjoint** tape)
+    int ttcr_fsm_adjoint_model(const ttcr_fsm_adjoint* t, int* cells, size_t* n_params, size_t* n_nodes)
     int ttcr_fsm_adjoint_size(const ttcr_fsm_adjoint* t, size_t* n_events, size_t* n_rows, size_t* n_nodes)
     int ttcr_fsm_adjoint_bytes(const ttcr_fsm_adjoint* t, size_t* bytes)
     int ttcr_fsm_adjoint_device(const ttcr_fsm_adjoint* t, int* device)

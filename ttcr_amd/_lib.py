@@ -77,6 +77,8 @@ SYMBOLS = {
     "ttcr_fsm_tape_vjp": (_I, [_P, _P, _I, _P, _I]),
     "ttcr_fsm_tape_free": (_I, [_P]),
     "ttcr_fsm_raytrace_multi_adjoint": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, C.POINTER(_P)]),
+    "ttcr_fsm_raytrace_multi_adjoint_cells": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, C.POINTER(_P)]),
+    "ttcr_fsm_adjoint_model": (_I, [_P, C.POINTER(_I), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "ttcr_fsm_adjoint_size": (_I, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "ttcr_fsm_adjoint_bytes": (_I, [_P, C.POINTER(C.c_size_t)]),
     "ttcr_fsm_adjoint_device": (_I, [_P, C.POINTER(_I)]),

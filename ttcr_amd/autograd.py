@@ -27,6 +27,11 @@ derivative with respect to the origin time and the position of every event, thro
 mode adds FieldTape.jvp and FieldTape.jvp_source.  The derivative with respect to a position has a kink where the point crosses a cell
 face or comes within 1e-4 of a node: the formula of the side the point is on is returned.
 
+Both take wrt='nodes' (default) or wrt='cells'.  With wrt='cells' `grid` is a 3-D cell grid (Grid3d(..., cell_slowness=1, weno=0)),
+`velocity` holds one value per cell, shape (ncx, ncy, ncz) or flat in C order, and the derivative is the one with respect to the cell
+velocities (FieldTape of raytrace_adjoint(..., wrt='cells'): the node tape composed with the cell-to-node averaging of set_slowness);
+fields and their cotangents stay (n_events, nx, ny, nz) node arrays.
+
 torch is imported when this module is used, never by `import ttcr_amd`.
 """
 import numpy as np
@@ -83,12 +88,12 @@ def _adjoint_function():
 
     class RaytraceAdjointFn(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, velocity, grid, source, rcv, aggregate_src, return_fields):
+        def forward(ctx, velocity, grid, source, rcv, aggregate_src, return_fields, wrt):
             grid.set_velocity(velocity.detach().cpu().numpy())
-            tt, tape = grid.raytrace_adjoint(source, rcv, aggregate_src=aggregate_src)
+            tt, tape = grid.raytrace_adjoint(source, rcv, aggregate_src=aggregate_src, wrt=wrt)
             nx, ny, nz = grid.x.size, grid.y.size, grid.z.size
             ctx.tape = tape
-            ctx.layout = (tuple(velocity.shape), (nx, ny, nz))
+            ctx.layout = (tuple(velocity.shape), (nx, ny, nz), _model_dims(grid, wrt))
             ctx.save_for_backward(velocity)
             ctx.save_for_forward(velocity)
             ctx.return_fields = return_fields
@@ -100,22 +105,22 @@ def _adjoint_function():
 
         @staticmethod
         def backward(ctx, g, gf=None):
-            shape, (nx, ny, nz) = ctx.layout
+            shape, (nx, ny, nz), (mx, my, mz) = ctx.layout
             (velocity,) = ctx.saved_tensors
             fc = None
             if gf is not None:   # (n_events, nx, ny, nz) in C order -> node order x fastest
                 fc = gf.permute(0, 3, 2, 1).contiguous().reshape(gf.shape[0], -1)
             gn = ctx.tape.vjp(g.contiguous(), fc)
-            # node order x fastest -> (nx, ny, nz) in C order -> velocity's layout; d slowness / d velocity = -1 / velocity^2
-            gs = gn.reshape(nz, ny, nx).permute(2, 1, 0).contiguous().reshape(shape).to(velocity.dtype)
-            return -gs / (velocity * velocity), None, None, None, None, None
+            # model order x fastest -> (mx, my, mz) in C order -> velocity's layout; d slowness / d velocity = -1 / velocity^2
+            gs = gn.reshape(mz, my, mx).permute(2, 1, 0).contiguous().reshape(shape).to(velocity.dtype)
+            return -gs / (velocity * velocity), None, None, None, None, None, None
 
         @staticmethod
         def jvp(ctx, tv, *_):
-            shape, (nx, ny, nz) = ctx.layout
+            shape, (nx, ny, nz), (mx, my, mz) = ctx.layout
             (velocity,) = ctx.saved_tensors
-            # d slowness = -(tv / velocity^2), velocity's layout -> (nx, ny, nz) in C order -> node order x fastest
-            ds = (-(tv / (velocity * velocity))).reshape(nx, ny, nz).permute(2, 1, 0).contiguous().reshape(-1)
+            # d slowness = -(tv / velocity^2), velocity's layout -> (mx, my, mz) in C order -> model order x fastest
+            ds = (-(tv / (velocity * velocity))).reshape(mx, my, mz).permute(2, 1, 0).contiguous().reshape(-1)
             if not ctx.return_fields:
                 return ctx.tape.jvp(ds)
             dtt, df = ctx.tape.jvp(ds, return_fields=True)
@@ -125,17 +130,34 @@ def _adjoint_function():
     return _AdjFn
 
 
-def raytrace_adjoint(grid, velocity, source, rcv, aggregate_src=False, return_fields=False):
-    """Traveltimes at `rcv` (interpolated, as with tt_from_rp=0) for the model `velocity` (torch tensor, node grid layout), differentiable
-    with respect to velocity by the adjoint-state method: backward = -(FieldTape.vjp) / velocity**2, the exact derivative of the returned
-    values.  return_fields=True: (tt, fields) with the (n_events, nx, ny, nz) traveltime fields, differentiable as well."""
+def _check_wrt(grid, wrt):
+    """the refusals of Grid3d.raytrace_adjoint, before the model is set"""
+    if wrt not in ('nodes', 'cells'):
+        raise ValueError("wrt should be 'nodes' or 'cells', got %r" % (wrt,))
     if grid._ndim != 3:
         raise NotImplementedError('the adjoint-state gradient is implemented for 3-D grids only')
-    if grid.cell_slowness:
-        raise NotImplementedError('the adjoint-state gradient is not implemented for grids with slowness defined for cells')
+    if grid.cell_slowness and wrt == 'nodes':
+        raise NotImplementedError("the adjoint-state gradient with respect to node slowness is not implemented for grids with slowness "
+                                  "defined for cells: wrt='cells' gives the gradient with respect to the cells")
+    if not grid.cell_slowness and wrt == 'cells':
+        raise ValueError("wrt='cells' needs a grid with slowness defined for cells (cell_slowness=1); this grid has it at the nodes")
+
+
+def _model_dims(grid, wrt):
+    """extents of the model array velocity is laid out in: the nodes, or the cells"""
+    nx, ny, nz = grid.x.size, grid.y.size, grid.z.size
+    return (nx - 1, ny - 1, nz - 1) if wrt == 'cells' else (nx, ny, nz)
+
+
+def raytrace_adjoint(grid, velocity, source, rcv, aggregate_src=False, return_fields=False, wrt='nodes'):
+    """Traveltimes at `rcv` (interpolated, as with tt_from_rp=0) for the model `velocity` (torch tensor, node grid layout; cell layout
+    with wrt='cells' on a cell grid), differentiable with respect to velocity by the adjoint-state method: backward =
+    -(FieldTape.vjp) / velocity**2, the exact derivative of the returned values.  return_fields=True: (tt, fields) with the
+    (n_events, nx, ny, nz) traveltime fields, differentiable as well."""
+    _check_wrt(grid, wrt)
     source = np.asarray(source)
     rcv = np.asarray(rcv)
-    return _adjoint_function().apply(velocity, grid, source, rcv, bool(aggregate_src), bool(return_fields))
+    return _adjoint_function().apply(velocity, grid, source, rcv, bool(aggregate_src), bool(return_fields), wrt)
 
 
 def _events_function():
@@ -146,15 +168,15 @@ def _events_function():
 
     class RaytraceEventsFn(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, velocity, events, grid, event_of_row, rcv, return_fields):
+        def forward(ctx, velocity, events, grid, event_of_row, rcv, return_fields, wrt):
             grid.set_velocity(velocity.detach().cpu().numpy())
             ev = events.detach().cpu().numpy().astype(np.float64)
             # the 5-column source form of _split_sources: (event number, t0, x, y, z) per rcv row; events are taken in ascending number
             source = np.column_stack([event_of_row.astype(np.float64), ev[event_of_row]])
-            tt, tape = grid.raytrace_adjoint(source, rcv)
+            tt, tape = grid.raytrace_adjoint(source, rcv, wrt=wrt)
             nx, ny, nz = grid.x.size, grid.y.size, grid.z.size
             ctx.tape = tape
-            ctx.layout = (tuple(velocity.shape), (nx, ny, nz))
+            ctx.layout = (tuple(velocity.shape), (nx, ny, nz), _model_dims(grid, wrt))
             ctx.save_for_backward(velocity, events)
             ctx.save_for_forward(velocity)
             ctx.return_fields = return_fields
@@ -166,22 +188,22 @@ def _events_function():
 
         @staticmethod
         def backward(ctx, g, gf=None):
-            shape, (nx, ny, nz) = ctx.layout
+            shape, (nx, ny, nz), (mx, my, mz) = ctx.layout
             velocity, events = ctx.saved_tensors
             fc = None
             if gf is not None:   # (n_events, nx, ny, nz) in C order -> node order x fastest
                 fc = gf.permute(0, 3, 2, 1).contiguous().reshape(gf.shape[0], -1)
             gn, gs = ctx.tape.vjp(g.contiguous(), fc, return_source_grad=True)
-            gs_v = gn.reshape(nz, ny, nx).permute(2, 1, 0).contiguous().reshape(shape).to(velocity.dtype)
-            return -gs_v / (velocity * velocity), gs.to(device=events.device, dtype=events.dtype), None, None, None, None
+            gs_v = gn.reshape(mz, my, mx).permute(2, 1, 0).contiguous().reshape(shape).to(velocity.dtype)
+            return -gs_v / (velocity * velocity), gs.to(device=events.device, dtype=events.dtype), None, None, None, None, None
 
         @staticmethod
         def jvp(ctx, tv, te, *_):
-            shape, (nx, ny, nz) = ctx.layout
+            shape, (nx, ny, nz), (mx, my, mz) = ctx.layout
             (velocity,) = ctx.saved_tensors
             parts = []
             if tv is not None:
-                ds = (-(tv / (velocity * velocity))).reshape(nx, ny, nz).permute(2, 1, 0).contiguous().reshape(-1)
+                ds = (-(tv / (velocity * velocity))).reshape(mx, my, mz).permute(2, 1, 0).contiguous().reshape(-1)
                 parts.append(ctx.tape.jvp(ds, return_fields=ctx.return_fields))
             if te is not None:
                 parts.append(ctx.tape.jvp_source(te.to(velocity.device), return_fields=ctx.return_fields))
@@ -194,15 +216,12 @@ def _events_function():
     return _EvFn
 
 
-def raytrace_events(grid, velocity, events, event_of_row, rcv, return_fields=False):
+def raytrace_events(grid, velocity, events, event_of_row, rcv, return_fields=False, wrt='nodes'):
     """Traveltimes at `rcv` (interpolated, as with tt_from_rp=0) of row r for the event event_of_row[r] of `events`, an (n_events, 4)
     torch tensor of (t0, x, y, z); differentiable with respect to `velocity` (as raytrace_adjoint) and `events` (d tt / d origin time
     and position, exact, FieldTape.vjp(..., return_source_grad=True)).  return_fields=True: (tt, fields) with the (n_events, nx, ny, nz)
-    traveltime fields, differentiable as well."""
-    if grid._ndim != 3:
-        raise NotImplementedError('the adjoint-state gradient is implemented for 3-D grids only')
-    if grid.cell_slowness:
-        raise NotImplementedError('the adjoint-state gradient is not implemented for grids with slowness defined for cells')
+    traveltime fields, differentiable as well.  wrt='cells': a cell grid, velocity in the cell layout."""
+    _check_wrt(grid, wrt)
     rcv = np.asarray(rcv)
     event_of_row = np.asarray(event_of_row)
     if events.dim() != 2 or events.shape[1] != 4:
@@ -211,4 +230,4 @@ def raytrace_events(grid, velocity, events, event_of_row, rcv, return_fields=Fal
         raise ValueError('event_of_row should hold one integer per rcv row')
     if not np.array_equal(np.unique(event_of_row), np.arange(events.shape[0])):
         raise ValueError('event_of_row should name events 0 .. %d, every one of them at least once' % (events.shape[0] - 1))
-    return _events_function().apply(velocity, events, grid, event_of_row.astype(np.int64), rcv, bool(return_fields))
+    return _events_function().apply(velocity, events, grid, event_of_row.astype(np.int64), rcv, bool(return_fields), wrt)

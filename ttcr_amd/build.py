@@ -9,7 +9,8 @@ Two translation units, compiled to objects under ttcr_amd/csrc/_obj and linked:
   fsm_fast.hip    the sweep kernels with tolerance-grade arithmetic (option "arith" = 1)
   fsm_tape.hip    the M tape: compute_M's rows merged on the device, node index, M^T w (hipCUB sorts)
   fsm_adjoint.hip the field tape: discrete adjoint of the first-order 3-D update (coupling, seeds, relaxation, gradient)
-                  and its forward mode (tangent relaxation, receiver rows); the source derivative (K-column relaxation, source gradient)
+                  and its forward mode (tangent relaxation, receiver rows); the source derivative (K-column relaxation, source gradient);
+                  cell tapes (the transpose of the cell-to-node averaging)
 """
 import os
 import shutil
@@ -26,7 +27,7 @@ UNITS = {
                           "fsm_tape.hip", "fsm_adjoint_api.h", "fsm_adjoint.hip", INC]),
     "fsm_fast.hip": ([], ["fsm_fast.hip", "fsm_fast_api.h", "fsm_kernels.h", "fsm_march_levels.inc"]),
     "fsm_tape.hip": ([], ["fsm_tape.hip", "fsm_tape_api.h"]),
-    "fsm_adjoint.hip": ([], ["fsm_adjoint.hip", "fsm_adjoint_api.h"]),
+    "fsm_adjoint.hip": ([], ["fsm_adjoint.hip", "fsm_adjoint_api.h", "fsm_kernels.h", "fsm_march_levels.inc"]),
 }
 SOURCES = list(UNITS)
 DEPS = sorted({d for _, ds in UNITS.values() for d in ds})

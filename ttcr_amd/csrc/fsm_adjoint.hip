@@ -1,7 +1,8 @@
 // ttcr_amd/csrc/fsm_adjoint.hip -- translation unit of the field tape's kernels (coupling, seeds, relaxation, gradient; the forward-mode
-// tangent: relaxation, receiver rows); see fsm_adjoint_api.h and DESIGN.md 6b, 6c.  Compiled with -ffp-contract=off like every other unit: each product, difference, quotient and sum
+// tangent: relaxation, receiver rows; cell tapes: the transpose of the cell-to-node averaging); see fsm_adjoint_api.h and DESIGN.md 6b, 6c, 6e.  Compiled with -ffp-contract=off like every other unit: each product, difference, quotient and sum
 // below is rounded on its own, in the order the definition writes them.
 #include "fsm_adjoint_api.h"
+#include "fsm_kernels.h"   // fsm_cells_to_nodes3d: the forward direction of a cell tape is set_slowness's own kernel
 
 #include <algorithm>
 #include <cstdint>
@@ -687,6 +688,34 @@ __global__ void src_grad_kernel(const int* __restrict__ off, const long long* __
     gsrc[4 * q] = a0; gsrc[4 * q + 1] = a1; gsrc[4 * q + 2] = a2; gsrc[4 * q + 3] = a3;
 }
 
+// ---- cell tapes: gc = A^T g, A the averaging of fsm_cells_to_nodes3d.  One thread per cell c = (ck * ncy + cj) * ncx + ci:
+// the eight products fl(f(n) * g[n]) over the corner nodes n = (ci + a, cj + b, ck + d), f(n) = 1 / (cells touching n) = 1, 1/2, 1/4 or 1/8
+// (a product of exact per-axis factors), added left to right from the first product, a innermost, d outermost.  No atomics.
+template <typename T>
+__global__ void adj_nodes_to_cells_kernel(const T* __restrict__ g, T* __restrict__ gc, int ncx, int ncy, int ncz) {
+    const size_t nc = (size_t)ncx * ncy * ncz;
+    const size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (c >= nc) return;
+    const int ci = (int)(c % ncx), cj = (int)((c / ncx) % ncy), ck = (int)(c / ((size_t)ncx * ncy));
+    const size_t nnx = (size_t)ncx + 1, nny = (size_t)ncy + 1;
+    T acc = 0;
+    for (int d = 0; d < 2; ++d) {
+        const int k = ck + d;
+        const T fz = (k == 0 || k == ncz) ? (T)1 : (T)0.5;
+        for (int b = 0; b < 2; ++b) {
+            const int j = cj + b;
+            const T fy = (j == 0 || j == ncy) ? fz : fz * (T)0.5;
+            for (int a = 0; a < 2; ++a) {
+                const int i = ci + a;
+                const T f = (i == 0 || i == ncx) ? fy : fy * (T)0.5;
+                const T p = f * g[((size_t)k * nny + j) * nnx + i];
+                acc = (a | b | d) == 0 ? p : acc + p;
+            }
+        }
+    }
+    gc[c] = acc;
+}
+
 struct Alloc {
     AdjTapeDev& t;
     size_t planned;
@@ -716,10 +745,10 @@ size_t tiles_of(const AdjTapeDev& t, int ed) { return (size_t)((t.nnx + ed - 1) 
 size_t tiles_of(const AdjTapeDev& t) { return tiles_of(t, adj_tile_edge(t.elem)); }
 
 // every byte the finished tape holds (the figure an allocation failure names): fields, D, g, lam, lam2; inmask, frozen; slowness and the
-// staged gradient; the staged w; the seed entries (8 per row at most); flags, stamps, error flag
+// staged gradient; the staged w; the seed entries (8 per row at most); flags, stamps, error flag; a cell tape's staged cell vector
 size_t planned_bytes(const AdjTapeDev& t) {
     const size_t en = t.n_events * t.nn;
-    return 5 * en * t.elem + 2 * en + 2 * t.nn * t.elem + t.n_rows * t.elem + 8 * t.n_rows * (8 + 4 + t.elem) +
+    return 5 * en * t.elem + 2 * en + 2 * t.nn * t.elem + t.n_rows * t.elem + 8 * t.n_rows * (8 + 4 + t.elem) + (t.cells ? t.nc * t.elem : 0) +
            (ADJ_RING * t.n_events + t.n_events * tiles_of(t) + 1) * sizeof(int);
 }
 
@@ -736,7 +765,7 @@ void AdjTapeDev::release() {
     dev_free(sd_key); dev_free(sd_row); dev_free(sd_w); dev_free(flags); dev_free(stamps); dev_free(err); dev_free(w_tmp); dev_free(grad_tmp);
     dev_free(rw_off); dev_free(rw_key); dev_free(rw_w); dev_free(rw_tmp); dev_free(tan_stamps);
     dev_free(src_off); dev_free(src_pt); dev_free(src_key); dev_free(src_node); dev_free(src_c); dev_free(src_io); dev_free(src_rows);
-    dev_free(mu4); dev_free(mu4b);
+    dev_free(mu4); dev_free(mu4b); dev_free(cell_tmp);
     if (stream) (void)hipStreamDestroy(stream);
     stream = nullptr;
     total_bytes = 0;
@@ -831,6 +860,7 @@ void adj_finish(AdjTapeDev& t, const AdjSink& sink) {
     alloc(t.err, sizeof(int));
     alloc(t.w_tmp, t.n_rows * t.elem);
     alloc(t.grad_tmp, t.nn * t.elem);
+    if (t.cells) alloc(t.cell_tmp, t.nc * t.elem);
     long long* d_fk = nullptr;
     T* d_fd = nullptr;
     hipStream_t s = t.stream;
@@ -941,9 +971,34 @@ static int adj_vjp_impl(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, i
     return passes;
 }
 
+// cell tape: d_nodes = A d_cells (fsm_cells_to_nodes3d) and d_cells = A^T d_nodes (one thread per cell), on the tape's stream
+template <typename T>
+static void adj_cells_to_nodes(AdjTapeDev& t, const T* d_cells, T* d_nodes) {
+    if (t.nn == 0) return;
+    const unsigned blocks = std::min(blocks_for(t.nn), 4096u);   // (the launch of set_slowness)
+    fsm_cells_to_nodes3d<T><<<blocks, ADJ_THREADS, 0, t.stream>>>(d_cells, d_nodes, t.nnx - 1, t.nny - 1, t.nnz - 1);
+    ADJ_CHECK(hipGetLastError());
+}
+
+template <typename T>
+static void adj_nodes_to_cells(AdjTapeDev& t, const T* d_nodes, T* d_cells) {
+    if (t.nc == 0) return;
+    adj_nodes_to_cells_kernel<T><<<blocks_for(t.nc), ADJ_THREADS, 0, t.stream>>>(d_nodes, d_cells, t.nnx - 1, t.nny - 1, t.nnz - 1);
+    ADJ_CHECK(hipGetLastError());
+}
+
+// the vjp with respect to the model vector: on a cell tape the node gradient of 6b is formed in grad_tmp, then d_grad = A^T grad_tmp
+template <typename T>
+static int adj_vjp_model(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, int schedule, const T** lam_final) {
+    if (!t.cells || !d_grad) return adj_vjp_impl<T>(t, d_w, d_fc, d_grad, schedule, lam_final);
+    const int passes = adj_vjp_impl<T>(t, d_w, d_fc, (T*)t.grad_tmp, schedule, lam_final);
+    adj_nodes_to_cells<T>(t, (const T*)t.grad_tmp, d_grad);
+    return passes;
+}
+
 template <typename T>
 int adj_vjp(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, int schedule) {
-    return adj_vjp_impl<T>(t, d_w, d_fc, d_grad, schedule, nullptr);
+    return adj_vjp_model<T>(t, d_w, d_fc, d_grad, schedule, nullptr);
 }
 
 // what the first jvp adds to the tape: the stencil in row order (offsets, keys, weights), a staging row for a host row_weight and the
@@ -987,6 +1042,10 @@ int adj_jvp(AdjTapeDev& t, const T* d_ds, T* d_dtt, T* d_dfields, int schedule) 
     hipStream_t s = t.stream;
     const size_t E = t.n_events, en = E * t.nn;
     const AdjGeom<T> geo{t.nnx, t.nny, t.nnz, t.nn, (T)t.dx};
+    if (t.cells) {   // the node perturbation set_slowness would compute from the cell perturbation
+        adj_cells_to_nodes<T>(t, d_ds, (T*)t.grad_tmp);
+        d_ds = (const T*)t.grad_tmp;
+    }
     T* mu = (T*)t.lam;
     int passes = 0;
     if (en > 0) {
@@ -1147,7 +1206,7 @@ int adj_vjp_source(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, T* d_g
     ADJ_CHECK(hipSetDevice(t.device));
     adj_src_prepare<T>(t);
     const T* lam = nullptr;
-    const int passes = adj_vjp_impl<T>(t, d_w, d_fc, d_grad, schedule, &lam);
+    const int passes = adj_vjp_model<T>(t, d_w, d_fc, d_grad, schedule, &lam);
     if (t.n_points > 0) {
         if (t.n_events * t.nn == 0) {
             ADJ_CHECK(hipMemsetAsync(d_gsrc, 0, 4 * t.n_points * sizeof(T), t.stream));

@@ -10,6 +10,8 @@
 //                   -> relaxation of lam = g + gather(lam) to its fixed point (tiled in LDS, or the global Jacobi baseline)
 //                   -> gradient (events summed in ascending order from +0 inside the thread).
 // No floating-point atomics anywhere: every value is one fixed expression of final values, so the bits do not depend on the schedule.
+// Cell tapes (ttcr_fsm_raytrace_multi_adjoint_cells): the model vector holds one slowness per cell and the node slowness is
+// A times it (fsm_cells_to_nodes3d); a jvp first applies A to ds, a vjp ends with A^T on the node gradient (one thread per cell).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -39,6 +41,7 @@ struct AdjSink {
     std::vector<std::vector<int>> fr_pt;
     std::vector<std::vector<double>> fr_c;
     std::vector<int> pt_off;    // n_events + 1: first point of every event among the points of the call
+    bool cells = false;         // the call came through the cell entry: the grid has to be a cell grid (a node grid otherwise)
     // interpolation stencil of every receiver row (interp3d_stencil): 8 slots per row, st_cnt[row] of them used
     std::vector<int> st_cnt, st_event;
     std::vector<long long> st_node;
@@ -50,6 +53,12 @@ struct AdjTapeDev {
     size_t elem = 0, n_events = 0, n_rows = 0, nn = 0;
     int nnx = 0, nny = 0, nnz = 0;
     double dx = 0;
+    // cell tape: the model vector of vjp / jvp / gn holds nc = (nnx - 1) (nny - 1) (nnz - 1) cell values (x fastest) instead of nn node values
+    bool cells = false;
+    size_t nc = 0;
+    void* cell_tmp = nullptr;         // nc (cell tape only: a host grad / ds / v / out is staged here; grad_tmp holds the node vector)
+    size_t n_model() const { return cells ? nc : nn; }
+    void* model_tmp() const { return cells ? cell_tmp : grad_tmp; }
     void* fields = nullptr;           // n_events * nn
     void* slowness = nullptr;         // nn
     void* D = nullptr;                // n_events * nn: D of a non-frozen node, d of a frozen one
@@ -111,18 +120,19 @@ void adj_copy_field(const T* src, int ts, T* dst, size_t n, hipStream_t stream);
 // uploads the lists of the sink, allocates the work arrays, marks the frozen nodes and runs the coupling pass
 template <typename T>
 void adj_finish(AdjTapeDev& t, const AdjSink& sink);
-// d_w (n_rows, may be null), d_fc (n_events * nn, may be null), d_grad (nn): all on the tape's device; returns the passes launched
+// d_w (n_rows, may be null), d_fc (n_events * nn, may be null), d_grad (n_model()): all on the tape's device; returns the passes launched.
+// On a cell tape the node gradient is formed in grad_tmp and d_grad = A^T grad_tmp.
 template <typename T>
 int adj_vjp(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, int schedule);
-// forward mode (tests/tangent_reference.py restates it): d_ds (nn), d_dtt (n_rows, may be null), d_dfields (n_events * nn, may be
-// null); relaxes mu = dT/ds . ds in lam / lam2 to its fixed point (the same two schedules), then one thread per receiver row; returns the
+// forward mode (tests/tangent_reference.py restates it): d_ds (n_model(); a cell tape relaxes with grad_tmp = A d_ds), d_dtt
+// (n_rows, may be null), d_dfields (n_events * nn, may be null); relaxes mu = dT/ds . ds in lam / lam2 to its fixed point (the same two schedules), then one thread per receiver row; returns the
 // passes launched.  The first call allocates adj_jvp_extra_bytes(t) more (AdjDeviceError naming the byte count if that fails).
 size_t adj_jvp_extra_bytes(const AdjTapeDev& t);
 template <typename T>
 void adj_jvp_prepare(AdjTapeDev& t);   // that allocation and the upload of the row-order stencil; a no-op from the second call on
 template <typename T>
 int adj_jvp(AdjTapeDev& t, const T* d_ds, T* d_dtt, T* d_dfields, int schedule);
-// Gauss-Newton product: jvp into w_tmp -> w_tmp *= d_rw (may be null) -> vjp into d_out (nn), all on the tape's stream
+// Gauss-Newton product: jvp into w_tmp -> w_tmp *= d_rw (may be null) -> vjp into d_out (n_model()), all on the tape's stream
 template <typename T>
 void adj_gn(AdjTapeDev& t, const T* d_v, const T* d_rw, T* d_out, int schedule, int* passes_jvp, int* passes_vjp);
 

@@ -120,8 +120,9 @@ class GridBase {
     // (whatever tt_from_rp says); after each batch every event's field, frozen nodes and receiver stencils go to `sink`
     virtual void raytrace_multi_adjoint(int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off, const void* rx,
                                         void* tt_out, AdjSink& sink) = 0;
-    // node counts and spacing of a grid the adjoint is defined for; Unsupported (with the reason) for every other grid
-    virtual void adjoint_geometry(int* nn3, double* spacing) const = 0;
+    // node counts and spacing of a grid the adjoint is defined for; Unsupported (with the reason) for every other grid.  wrt_cells: the
+    // call came through the cell entry, which takes cell grids only (ValueError on a node grid); the node entry keeps refusing cell grids
+    virtual void adjoint_geometry(int* nn3, double* spacing, bool wrt_cells) const = 0;
     AdjSink* adj_sink = nullptr;          // set for the duration of such a call
     std::vector<int> adj_src, adj_row;    // a replica of a multi-device grid: event and first row, in the call, of each source of ITS call
     // the raytrace overloads with l_data (2-D cell grids): ray-projection matrix L, one CSR row per receiver
@@ -2384,9 +2385,13 @@ class GridT : public GridBase {
         for (auto& v : m_seg_off) std::vector<long long>().swap(v);
     }
     // ---- the field tape (fsm_adjoint_api.h)
-    void adjoint_geometry(int* nn3, double* spacing) const override {
+    void adjoint_geometry(int* nn3, double* spacing, bool wrt_cells) const override {
         if (dim != 3) throw Unsupported("the adjoint-state gradient is implemented for 3-D grids only");
-        if (cell) throw Unsupported("the adjoint-state gradient is not implemented for grids with slowness defined for cells");
+        if (cell && !wrt_cells)
+            throw Unsupported("the adjoint-state gradient with respect to node slowness is not implemented for grids with slowness defined for "
+                              "cells: ttcr_fsm_raytrace_multi_adjoint_cells gives the gradient with respect to the cells");
+        if (!cell && wrt_cells)
+            throw ValueError("raytrace_multi_adjoint_cells: the grid has slowness defined at the nodes: use ttcr_fsm_raytrace_multi_adjoint");
         if (weno) throw Unsupported("the adjoint-state gradient is implemented for the first-order solver only (weno = 0)");
         nn3[0] = (int)ncx + 1; nn3[1] = (int)ncy + 1; nn3[2] = (int)ncz + 1;
         *spacing = (double)dx;
@@ -2395,7 +2400,7 @@ class GridT : public GridBase {
                                 void* tt_out_v, AdjSink& sink) override {
         int nn3[3];
         double sp;
-        adjoint_geometry(nn3, &sp);
+        adjoint_geometry(nn3, &sp, sink.cells);
         adj_sink = &sink;
         try {
             raytrace_multi(n_src, tx_off, tx_v, t0_v, rx_off, rx_v, tt_out_v, -1, nullptr, false);
@@ -3155,12 +3160,12 @@ class MultiGrid : public GridBase {
         timing.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
     }
     // The field tape: the sources go to the replicas like raytrace_multi sends them; every replica copies its fields to the sink's device.
-    void adjoint_geometry(int* nn3, double* spacing) const override { rep[0]->adjoint_geometry(nn3, spacing); }
+    void adjoint_geometry(int* nn3, double* spacing, bool wrt_cells) const override { rep[0]->adjoint_geometry(nn3, spacing, wrt_cells); }
     void raytrace_multi_adjoint(int n_src, const int* tx_off, const void* tx_v, const void* t0_v, const int* rx_off, const void* rx_v,
                                 void* tt_out_v, AdjSink& sink) override {
         int nn3[3];
         double sp;
-        adjoint_geometry(nn3, &sp);
+        adjoint_geometry(nn3, &sp, sink.cells);
         for (auto& r : rep) r->adj_sink = &sink;
         auto clear = [&] { for (auto& r : rep) { r->adj_sink = nullptr; r->adj_src.clear(); r->adj_row.clear(); } };
         try {
@@ -3797,22 +3802,24 @@ struct ttcr_fsm_adjoint {
     ~ttcr_fsm_adjoint() { t.release(); }
 };
 
-int ttcr_fsm_raytrace_multi_adjoint(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off,
-                                    const void* rx, void* tt_out, ttcr_fsm_adjoint** tape) {
+// the two entries that make a field tape: wrt_cells = the cell entry (a cell grid, model vector = cell slowness)
+static int raytrace_multi_adjoint_entry(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off,
+                                        const void* rx, void* tt_out, ttcr_fsm_adjoint** tape, bool wrt_cells) {
     if (!tape) {
         g_last_error = "null tape output pointer";
         return TTCR_ERR_VALUE;
     }
     *tape = nullptr;
     if (n_src < 0 || (n_src > 0 && (!tx_off || !tx || !t0 || !rx_off || !rx || !tt_out))) {
-        g_last_error = "raytrace_multi_adjoint: null array or negative source count";
+        g_last_error = wrt_cells ? "raytrace_multi_adjoint_cells: null array or negative source count"
+                                 : "raytrace_multi_adjoint: null array or negative source count";
         return TTCR_ERR_VALUE;
     }
     return guarded_on(g, [&] {
         GridBase& G = *g->impl;
         int nn3[3];
         double spacing = 0;
-        G.adjoint_geometry(nn3, &spacing);
+        G.adjoint_geometry(nn3, &spacing, wrt_cells);
         std::unique_ptr<ttcr_fsm_adjoint> tp(new ttcr_fsm_adjoint());
         ttcr_amd::AdjTapeDev& t = tp->t;
         tp->dtype = G.dtype;
@@ -3823,12 +3830,14 @@ int ttcr_fsm_raytrace_multi_adjoint(ttcr_fsm_grid* g, int n_src, const int* tx_o
         t.nn = G.n_nodes;
         t.nnx = nn3[0]; t.nny = nn3[1]; t.nnz = nn3[2];
         t.dx = spacing;
+        t.cells = wrt_cells;
+        t.nc = wrt_cells ? (size_t)(nn3[0] - 1) * (size_t)(nn3[1] - 1) * (size_t)(nn3[2] - 1) : 0;
         adj_device_errors([&] {
             HIP_CHECK(hipSetDevice(t.device));
             HIP_CHECK(hipStreamCreateWithFlags(&t.stream, hipStreamNonBlocking));
             ttcr_amd::adj_alloc_fields(t);
             ttcr_amd::AdjSink sink;
-            sink.device = t.device; sink.elem = t.elem; sink.nn = t.nn;
+            sink.device = t.device; sink.elem = t.elem; sink.nn = t.nn; sink.cells = wrt_cells;
             sink.fields = t.fields; sink.slowness = t.slowness;
             sink.fr_node.resize(t.n_events); sink.fr_d.resize(t.n_events);
             sink.fr_pt.resize(t.n_events); sink.fr_c.resize(t.n_events);
@@ -3843,6 +3852,24 @@ int ttcr_fsm_raytrace_multi_adjoint(ttcr_fsm_grid* g, int n_src, const int* tx_o
         });
         *tape = tp.release();
     });
+}
+int ttcr_fsm_raytrace_multi_adjoint(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off,
+                                    const void* rx, void* tt_out, ttcr_fsm_adjoint** tape) {
+    return raytrace_multi_adjoint_entry(g, n_src, tx_off, tx, t0, rx_off, rx, tt_out, tape, false);
+}
+int ttcr_fsm_raytrace_multi_adjoint_cells(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off,
+                                          const void* rx, void* tt_out, ttcr_fsm_adjoint** tape) {
+    return raytrace_multi_adjoint_entry(g, n_src, tx_off, tx, t0, rx_off, rx, tt_out, tape, true);
+}
+int ttcr_fsm_adjoint_model(const ttcr_fsm_adjoint* t, int* cells, size_t* n_params, size_t* n_nodes) {
+    if (!t || !cells || !n_params || !n_nodes) {
+        g_last_error = "null tape or output pointer";
+        return TTCR_ERR_VALUE;
+    }
+    *cells = t->t.cells ? 1 : 0;
+    *n_params = t->t.n_model();
+    *n_nodes = t->t.nn;
+    return TTCR_OK;
 }
 int ttcr_fsm_adjoint_size(const ttcr_fsm_adjoint* t, size_t* n_events, size_t* n_rows, size_t* n_nodes) {
     if (!t || !n_events || !n_rows || !n_nodes) {
@@ -3906,7 +3933,7 @@ int ttcr_fsm_adjoint_vjp(const ttcr_fsm_adjoint* t, const void* w, int w_on_devi
             HIP_CHECK(hipSetDevice(d.device));
             const void* dw = w;
             const void* dfc = field_cot;
-            void* dg = grad_on_device ? grad : d.grad_tmp;
+            void* dg = grad_on_device ? grad : d.model_tmp();   // (a cell tape forms the node gradient in grad_tmp, then A^T into dg)
             if (w && !w_on_device) {
                 if (d.n_rows > 0) HIP_CHECK(hipMemcpyAsync(d.w_tmp, w, d.n_rows * d.elem, hipMemcpyHostToDevice, d.stream));
                 dw = d.w_tmp;
@@ -3919,7 +3946,8 @@ int ttcr_fsm_adjoint_vjp(const ttcr_fsm_adjoint* t, const void* w, int w_on_devi
             int np = 0;
             if (tm->dtype == TTCR_F32) np = ttcr_amd::adj_vjp<float>(d, (const float*)dw, (const float*)dfc, (float*)dg, schedule);
             else np = ttcr_amd::adj_vjp<double>(d, (const double*)dw, (const double*)dfc, (double*)dg, schedule);
-            if (!grad_on_device) HIP_CHECK(hipMemcpyAsync(grad, d.grad_tmp, d.nn * d.elem, hipMemcpyDeviceToHost, d.stream));
+            if (!grad_on_device && d.n_model() > 0)
+                HIP_CHECK(hipMemcpyAsync(grad, d.model_tmp(), d.n_model() * d.elem, hipMemcpyDeviceToHost, d.stream));
             HIP_CHECK(hipStreamSynchronize(d.stream));
             if (passes) *passes = np;
         });
@@ -3944,8 +3972,8 @@ int ttcr_fsm_adjoint_jvp(const ttcr_fsm_adjoint* t, const void* ds, int ds_on_de
             const size_t en = d.n_events * d.nn;
             const void* dds = ds;
             if (!ds_on_device) {   // (staged where a host gradient is staged: not in use during a jvp)
-                if (d.nn > 0) HIP_CHECK(hipMemcpyAsync(d.grad_tmp, ds, d.nn * d.elem, hipMemcpyHostToDevice, d.stream));
-                dds = d.grad_tmp;
+                if (d.n_model() > 0) HIP_CHECK(hipMemcpyAsync(d.model_tmp(), ds, d.n_model() * d.elem, hipMemcpyHostToDevice, d.stream));
+                dds = d.model_tmp();
             }
             void* ddtt = dtt ? (dtt_on_device ? dtt : d.w_tmp) : nullptr;
             void* ddf = dfields && df_on_device ? dfields : nullptr;   // (a host copy is read from the relaxed buffer itself)
@@ -3981,10 +4009,10 @@ int ttcr_fsm_adjoint_gn(const ttcr_fsm_adjoint* t, const void* v, int v_on_devic
             HIP_CHECK(hipSetDevice(d.device));
             const void* dv = v;
             if (!v_on_device) {   // (consumed by the jvp before the vjp writes a host gradient to the same place)
-                if (d.nn > 0) HIP_CHECK(hipMemcpyAsync(d.grad_tmp, v, d.nn * d.elem, hipMemcpyHostToDevice, d.stream));
-                dv = d.grad_tmp;
+                if (d.n_model() > 0) HIP_CHECK(hipMemcpyAsync(d.model_tmp(), v, d.n_model() * d.elem, hipMemcpyHostToDevice, d.stream));
+                dv = d.model_tmp();
             }
-            void* dout = out_on_device ? out : d.grad_tmp;
+            void* dout = out_on_device ? out : d.model_tmp();
             const bool stage_rw = row_weight && !rw_on_device;
             int pj = 0, pv = 0;
             if (stage_rw) {   // (the staging row is part of what the first jvp allocates)
@@ -3995,7 +4023,8 @@ int ttcr_fsm_adjoint_gn(const ttcr_fsm_adjoint* t, const void* v, int v_on_devic
             const void* drw = row_weight ? (rw_on_device ? row_weight : d.rw_tmp) : nullptr;
             if (tm->dtype == TTCR_F32) ttcr_amd::adj_gn<float>(d, (const float*)dv, (const float*)drw, (float*)dout, schedule, &pj, &pv);
             else ttcr_amd::adj_gn<double>(d, (const double*)dv, (const double*)drw, (double*)dout, schedule, &pj, &pv);
-            if (!out_on_device) HIP_CHECK(hipMemcpyAsync(out, d.grad_tmp, d.nn * d.elem, hipMemcpyDeviceToHost, d.stream));
+            if (!out_on_device && d.n_model() > 0)
+                HIP_CHECK(hipMemcpyAsync(out, d.model_tmp(), d.n_model() * d.elem, hipMemcpyDeviceToHost, d.stream));
             HIP_CHECK(hipStreamSynchronize(d.stream));
             if (passes_jvp) *passes_jvp = pj;
             if (passes_vjp) *passes_vjp = pv;
@@ -4086,7 +4115,7 @@ int ttcr_fsm_adjoint_vjp_source(const ttcr_fsm_adjoint* t, const void* w, int w_
             else ttcr_amd::adj_src_prepare<double>(d);
             const void* dw = w;
             const void* dfc = field_cot;
-            void* dg = grad ? (grad_on_device ? grad : d.grad_tmp) : nullptr;
+            void* dg = grad ? (grad_on_device ? grad : d.model_tmp()) : nullptr;
             void* dgs = gsrc_on_device ? gsrc : d.src_io;
             if (w && !w_on_device) {
                 if (d.n_rows > 0) HIP_CHECK(hipMemcpyAsync(d.w_tmp, w, d.n_rows * d.elem, hipMemcpyHostToDevice, d.stream));
@@ -4102,7 +4131,8 @@ int ttcr_fsm_adjoint_vjp_source(const ttcr_fsm_adjoint* t, const void* w, int w_
                 np = ttcr_amd::adj_vjp_source<float>(d, (const float*)dw, (const float*)dfc, (float*)dg, (float*)dgs, schedule);
             else
                 np = ttcr_amd::adj_vjp_source<double>(d, (const double*)dw, (const double*)dfc, (double*)dg, (double*)dgs, schedule);
-            if (grad && !grad_on_device) HIP_CHECK(hipMemcpyAsync(grad, d.grad_tmp, d.nn * d.elem, hipMemcpyDeviceToHost, d.stream));
+            if (grad && !grad_on_device && d.n_model() > 0)
+                HIP_CHECK(hipMemcpyAsync(grad, d.model_tmp(), d.n_model() * d.elem, hipMemcpyDeviceToHost, d.stream));
             if (!gsrc_on_device && d.n_points > 0)
                 HIP_CHECK(hipMemcpyAsync(gsrc, d.src_io, 4 * d.n_points * d.elem, hipMemcpyDeviceToHost, d.stream));
             HIP_CHECK(hipStreamSynchronize(d.stream));

@@ -376,30 +376,39 @@ class _GridBase:
         rx_off[1:] = np.cumsum([len(r) for r in vRx])
         return tx_off, tx, t0, rx_off, rx, np.empty(max(rx.shape[0], 1), dtype=dt)
 
-    def raytrace_adjoint(self, source, rcv, slowness=None, aggregate_src=False):
-        """raytrace_adjoint(source, rcv, slowness=None, aggregate_src=False) -> (tt, tape)
+    def raytrace_adjoint(self, source, rcv, slowness=None, aggregate_src=False, wrt='nodes'):
+        """raytrace_adjoint(source, rcv, slowness=None, aggregate_src=False, wrt='nodes') -> (tt, tape)
 
         Traveltimes at the receivers (same source / receiver handling as raytrace_tape) and a FieldTape that keeps every event's
         traveltime field on the device for the adjoint-state gradient: tape.vjp(w, field_cotangent) is the exact derivative, with
         respect to node slowness, of  w . tt + field_cotangent . fields  through the first-order solver's own update.  The receiver
         traveltimes of this call are the INTERPOLATED ones (what a grid with tt_from_rp=0 returns, bit for bit): the call forces that
-        for its own solves whatever the grid's tt_from_rp setting.  3-D node grids with weno=0 only (NotImplementedError otherwise)."""
+        for its own solves whatever the grid's tt_from_rp setting.  3-D grids with weno=0 only (NotImplementedError otherwise).
+        wrt='nodes' (default): a node grid, the model vector of the tape is the node slowness.  wrt='cells': a grid with slowness defined
+        for cells; the tape differentiates with respect to the cell slowness (tape.n_cols = number of cells, the flat order of
+        set_slowness, x fastest) through the cell-to-node averaging of set_slowness; its fields stay node-sized (tape.n_nodes).  A
+        cell grid with wrt='nodes' raises NotImplementedError, a node grid with wrt='cells' ValueError."""
         source = np.asarray(source)
         rcv = np.asarray(rcv)
         if source.ndim != 2 or rcv.ndim != 2:
             raise ValueError('source and rcv should be 2D arrays')
+        if wrt not in ('nodes', 'cells'):
+            raise ValueError("wrt should be 'nodes' or 'cells', got %r" % (wrt,))
         if self._ndim != 3:
             raise NotImplementedError('the adjoint-state gradient is implemented for 3-D grids only')
-        if self.cell_slowness:
-            raise NotImplementedError('the adjoint-state gradient is not implemented for grids with slowness defined for cells')
+        if self.cell_slowness and wrt == 'nodes':
+            raise NotImplementedError("the adjoint-state gradient with respect to node slowness is not implemented for grids with "
+                                      "slowness defined for cells: wrt='cells' gives the gradient with respect to the cells")
+        if not self.cell_slowness and wrt == 'cells':
+            raise ValueError("wrt='cells' needs a grid with slowness defined for cells (cell_slowness=1); this grid has it at the nodes")
         vTx, vt0, vRx, iRx = self._split_sources(source, rcv, aggregate_src)
         if slowness is not None:
             self.set_slowness(slowness)
         dt = self._dtype
         tx_off, tx, t0, rx_off, rx, out = self._event_arrays(vTx, vt0, vRx)
         h = C.c_void_p()
-        _lib.check(self._lib.ttcr_fsm_raytrace_multi_adjoint(self._h, len(vTx), _ptr(tx_off), _ptr(tx), _ptr(t0), _ptr(rx_off), _ptr(rx),
-                                                             _ptr(out), C.byref(h)))
+        entry = self._lib.ttcr_fsm_raytrace_multi_adjoint_cells if wrt == 'cells' else self._lib.ttcr_fsm_raytrace_multi_adjoint
+        _lib.check(entry(self._h, len(vTx), _ptr(tx_off), _ptr(tx), _ptr(t0), _ptr(rx_off), _ptr(rx), _ptr(out), C.byref(h)))
         tape = FieldTape(self._lib, h, dt, np.concatenate(iRx).astype(np.int64), rcv.shape[0])
         tt = np.zeros((rcv.shape[0],), dtype=dt)
         for n in range(len(vTx)):
@@ -540,7 +549,10 @@ class FieldTape:
     on the grid any more: later calls, set_slowness and deleting the grid leave it as it is.  vjp applies J^T (reverse mode), jvp
     applies J (forward mode) and gauss_newton J^T W J of the same linearisation, all on the device.  The same linearisation with respect
     to the source points, parameters (t0, x, y, z) each: jvp_source, source_jacobian and vjp(..., return_source_grad=True); n_points
-    points in call order, point_event their events."""
+    points in call order, point_event their events.
+    wrt is 'nodes' or 'cells': what the model vector of vjp / jvp / gauss_newton holds, n_cols values -- the node slowness (n_cols =
+    n_nodes) or, for the tape of raytrace_adjoint(..., wrt='cells'), the cell slowness in set_slowness's flat order (n_cols = cells).
+    Fields, field cotangents and field tangents hold n_nodes values per event on either tape."""
 
     SCHEDULES = {'tiled': 0, 'jacobi': 1}
 
@@ -552,7 +564,12 @@ class FieldTape:
         self.n_data = int(n_data)
         ne, nr, nc = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
         _lib.check(lib.ttcr_fsm_adjoint_size(handle, C.byref(ne), C.byref(nr), C.byref(nc)))
-        self.n_events, self.n_rows, self.n_cols = ne.value, nr.value, nc.value
+        self.n_events, self.n_rows, self.n_nodes = ne.value, nr.value, nc.value
+        cells, npar = C.c_int(0), C.c_size_t(0)
+        _lib.check(lib.ttcr_fsm_adjoint_model(handle, C.byref(cells), C.byref(npar), C.byref(nc)))
+        self.wrt = 'cells' if cells.value else 'nodes'
+        self.n_cols = npar.value   # length of the model vector
+        self._per = 'cell' if cells.value else 'node'
         d, b = C.c_int(0), C.c_size_t(0)
         _lib.check(lib.ttcr_fsm_adjoint_device(handle, C.byref(d)))
         _lib.check(lib.ttcr_fsm_adjoint_bytes(handle, C.byref(b)))
@@ -572,10 +589,10 @@ class FieldTape:
         return self._h
 
     def field(self, event):
-        """Host copy of the traveltime field of one event: n_cols values of the grid dtype, node order (x fastest)."""
-        out = np.empty(max(self.n_cols, 1), dtype=self.dtype)
+        """Host copy of the traveltime field of one event: n_nodes values of the grid dtype, node order (x fastest)."""
+        out = np.empty(max(self.n_nodes, 1), dtype=self.dtype)
         _lib.check(self._lib.ttcr_fsm_adjoint_get_field(self._handle(), int(event), _ptr(out)))
-        return out[:self.n_cols]
+        return out[:self.n_nodes]
 
     def _schedule(self, schedule):
         if schedule not in self.SCHEDULES:
@@ -583,10 +600,11 @@ class FieldTape:
         return self.SCHEDULES[schedule]
 
     def vjp(self, w=None, field_cotangent=None, schedule='tiled', return_source_grad=False):
-        """d loss / d node slowness (n_cols values, x fastest, grid dtype) for  loss = w . tt + field_cotangent . fields.
+        """d loss / d slowness (n_cols values -- nodes, or cells on a cell tape --, x fastest, grid dtype) for  loss = w . tt +
+        field_cotangent . fields.
         return_source_grad=True: (grad, gsrc) with gsrc (n_points, 4) = d loss / d (t0, x, y, z) of every source point, from the same
         relaxation (a point whose frozen nodes a later point of its event all overwrote gets zeros).
-        w: one value per data row of the raytrace_adjoint call (rcv order); field_cotangent: (n_events, n_cols) values, node order x
+        w: one value per data row of the raytrace_adjoint call (rcv order); field_cotangent: (n_events, n_nodes) values, node order x
         fastest; either may be None, not both.  schedule: 'tiled' (default) or 'jacobi', the bit-equal baseline.  Torch tensors in give
         a torch tensor out; tensors on the tape's device are used in place (torch's current stream is synchronised first, the result is
         ready when the call returns)."""
@@ -604,8 +622,8 @@ class FieldTape:
             wt = np.ascontiguousarray(w[self._rows], dtype=self.dtype)
         if field_cotangent is not None:
             fc = np.ascontiguousarray(field_cotangent, dtype=self.dtype)
-            if fc.size != self.n_events * self.n_cols:
-                raise ValueError('field_cotangent should hold %d x %d values, got shape %s' % (self.n_events, self.n_cols, fc.shape))
+            if fc.size != self.n_events * self.n_nodes:
+                raise ValueError('field_cotangent should hold %d x %d values, got shape %s' % (self.n_events, self.n_nodes, fc.shape))
         g = np.empty(max(self.n_cols, 1), dtype=self.dtype)
         np_ = C.c_int(0)
         if return_source_grad:
@@ -643,8 +661,8 @@ class FieldTape:
             wt = w.detach().to(device=dev, dtype=tdt).index_select(0, self._rows_dev).contiguous()
         if fc is not None:
             fc = torch.as_tensor(fc)
-            if fc.numel() != self.n_events * self.n_cols:
-                raise ValueError('field_cotangent should hold %d x %d values, got shape %s' % (self.n_events, self.n_cols, tuple(fc.shape)))
+            if fc.numel() != self.n_events * self.n_nodes:
+                raise ValueError('field_cotangent should hold %d x %d values, got shape %s' % (self.n_events, self.n_nodes, tuple(fc.shape)))
             fct = fc.detach().to(device=dev, dtype=tdt).contiguous()
         g = torch.empty(max(self.n_cols, 1), dtype=tdt, device=dev)
         torch.cuda.current_stream(dev).synchronize()
@@ -665,9 +683,9 @@ class FieldTape:
         return g[:self.n_cols].to(ref.device)
 
     def jvp(self, ds, return_fields=False, schedule='tiled'):
-        """J ds: the change of the receiver traveltimes for the node-slowness perturbation ds (n_cols values, x fastest), the forward
-        mode of the linearisation vjp is the reverse mode of.  Returns dtt, n_data values in rcv order (grid dtype); with
-        return_fields=True (dtt, dfields), dfields the (n_events, n_cols) tangents of the traveltime fields.  schedule as in vjp.
+        """J ds: the change of the receiver traveltimes for the slowness perturbation ds (n_cols values -- nodes, or cells on a cell
+        tape --, x fastest), the forward mode of the linearisation vjp is the reverse mode of.  Returns dtt, n_data values in rcv order
+        (grid dtype); with return_fields=True (dtt, dfields), dfields the (n_events, n_nodes) tangents of the traveltime fields.  schedule as in vjp.
         numpy in gives numpy out; a torch tensor in gives torch tensors out, and a tensor on the tape's device is used in place (torch's
         current stream is synchronised first, the result is ready when the call returns).  The first jvp or gauss_newton of a tape
         allocates the stencil in row order (nbytes grows by it once)."""
@@ -677,9 +695,9 @@ class FieldTape:
             return self._jvp_torch(ds, return_fields, sch)
         ds = np.ascontiguousarray(ds, dtype=self.dtype)
         if ds.size != self.n_cols:
-            raise ValueError('ds should hold %d values (one per node), got shape %s' % (self.n_cols, ds.shape))
+            raise ValueError('ds should hold %d values (one per %s), got shape %s' % (self.n_cols, self._per, ds.shape))
         rows = np.empty(max(self.n_rows, 1), dtype=self.dtype)
-        df = np.empty((self.n_events, self.n_cols), dtype=self.dtype) if return_fields else None
+        df = np.empty((self.n_events, self.n_nodes), dtype=self.dtype) if return_fields else None
         np_ = C.c_int(0)
         _lib.check(self._lib.ttcr_fsm_adjoint_jvp(self._h, _ptr(ds), 0, _ptr(rows), 0, _ptr(df) if df is not None and df.size else None, 0,
                                                   sch, C.byref(np_)))
@@ -697,13 +715,13 @@ class FieldTape:
             out = self.jvp(ds.detach().numpy(), return_fields, 'jacobi' if sch else 'tiled')
             return tuple(torch.from_numpy(o) for o in out) if return_fields else torch.from_numpy(out)
         if ds.numel() != self.n_cols:
-            raise ValueError('ds should hold %d values (one per node), got shape %s' % (self.n_cols, tuple(ds.shape)))
+            raise ValueError('ds should hold %d values (one per %s), got shape %s' % (self.n_cols, self._per, tuple(ds.shape)))
         dev = torch.device('cuda', self.device)
         if self._rows_dev is None:
             self._rows_dev = torch.as_tensor(self._rows, device=dev)
         dst = ds.detach().to(device=dev, dtype=tdt).contiguous()
         rows = torch.empty(max(self.n_rows, 1), dtype=tdt, device=dev)
-        df = torch.empty((self.n_events, self.n_cols), dtype=tdt, device=dev) if return_fields else None
+        df = torch.empty((self.n_events, self.n_nodes), dtype=tdt, device=dev) if return_fields else None
         torch.cuda.current_stream(dev).synchronize()
         np_ = C.c_int(0)
         _lib.check(self._lib.ttcr_fsm_adjoint_jvp(self._h, C.c_void_p(dst.data_ptr()), 1, C.c_void_p(rows.data_ptr()), 1,
@@ -720,7 +738,7 @@ class FieldTape:
         (dt0, dx, dy, dz) of every point in call order (point_event names their events) -- the exact derivative of the returned tt
         through the nodes the source initialisation froze and the solver's own update.  dsrc (K, n_points, 4), K <= 4, applies K
         perturbations in one relaxation; the results then carry a leading K axis, each column with the bits of its own call.  Returns
-        dtt in rcv order; with return_fields=True (dtt, dfields), dfields (n_events, n_cols) per perturbation.  The map has a kink where
+        dtt in rcv order; with return_fields=True (dtt, dfields), dfields (n_events, n_nodes) per perturbation.  The map has a kink where
         a point crosses a cell face or enters the 1e-4 on-node tolerance: the formula of the side the point is on is returned.  Array
         handling and schedule as in jvp; the first call allocates its lists, a call with K > 1 a four-column work array (nbytes)."""
         self._handle()
@@ -741,7 +759,7 @@ class FieldTape:
                 self._rows_dev = torch.as_tensor(self._rows, device=dev)
             dd = dsrc.detach().to(device=dev, dtype=tdt).contiguous()
             rows = torch.zeros((K, self.n_rows), dtype=tdt, device=dev)
-            df = torch.empty((K, self.n_events, self.n_cols), dtype=tdt, device=dev) if return_fields else None
+            df = torch.empty((K, self.n_events, self.n_nodes), dtype=tdt, device=dev) if return_fields else None
             torch.cuda.current_stream(dev).synchronize()
             want_rows, want_df = rows.numel() > 0, df is not None and df.numel() > 0
             if want_rows or want_df:
@@ -757,7 +775,7 @@ class FieldTape:
             if dd.size == 0:
                 dd = np.zeros(4, dtype=self.dtype)
             rows = np.zeros((K, self.n_rows), dtype=self.dtype)
-            df = np.empty((K, self.n_events, self.n_cols), dtype=self.dtype) if return_fields else None
+            df = np.empty((K, self.n_events, self.n_nodes), dtype=self.dtype) if return_fields else None
             if rows.size or (df is not None and df.size):
                 _lib.check(self._lib.ttcr_fsm_adjoint_jvp_source(self._h, _ptr(dd), 0, K, _ptr(rows) if rows.size else None, 0,
                                                                  _ptr(df) if df is not None and df.size else None, 0, sch, C.byref(np_)))
@@ -795,7 +813,7 @@ class FieldTape:
             return self._gn_torch(v, row_weight, sch)
         v = np.ascontiguousarray(v, dtype=self.dtype)
         if v.size != self.n_cols:
-            raise ValueError('v should hold %d values (one per node), got shape %s' % (self.n_cols, v.shape))
+            raise ValueError('v should hold %d values (one per %s), got shape %s' % (self.n_cols, self._per, v.shape))
         rw = None
         if row_weight is not None:
             row_weight = np.asarray(row_weight)
@@ -823,7 +841,7 @@ class FieldTape:
         dev = torch.device('cuda', self.device)
         v = torch.as_tensor(v)
         if v.numel() != self.n_cols:
-            raise ValueError('v should hold %d values (one per node), got shape %s' % (self.n_cols, tuple(v.shape)))
+            raise ValueError('v should hold %d values (one per %s), got shape %s' % (self.n_cols, self._per, tuple(v.shape)))
         vt = v.detach().to(device=dev, dtype=tdt).contiguous()
         rw = None
         if row_weight is not None:
