@@ -424,6 +424,28 @@ int ttcr_fsm_tape_free(ttcr_fsm_tape* t);
  *   nodes m with q(m) = q in ascending node index, acc = fl(acc + lam[m]);  gsrc[q][1 + a] = the same chain of
  *   fl(lam[m] * fl(s[m] * c[m][a])).  A point all of whose nodes a later point overwrote gets four +0.  grad may be NULL (no slowness
  *   gradient is formed); otherwise it has the bits of ttcr_fsm_adjoint_vjp.  One thread per point, no floating-point atomics.
+ * Second-order products (tests/hessian_reference.py restates them).  For a cotangent (w, field_cot) the vjp is a function
+ *   of the slowness; its derivative in a direction v, with the cotangent held fixed, is  sum_r w_r (d2 tt_r / ds2) v  (and the same for
+ *   the field part): the term a Gauss-Newton product drops.
+ * ttcr_fsm_adjoint_hold: the vjp of (w, field_cot) -- grad (may be NULL) has the bits of ttcr_fsm_adjoint_vjp -- whose lam stays on the
+ *   tape.  The first hold allocates 2 n_events n_nodes elem bytes (lam and a work array), which ttcr_fsm_adjoint_bytes reports;
+ *   TTCR_ERR_DEVICE with the byte count if that fails.  A later hold replaces the held lam.  ttcr_fsm_adjoint_release frees both arrays
+ *   (ttcr_fsm_adjoint_bytes falls by the same figure); ttcr_fsm_adjoint_free releases too.
+ * ttcr_fsm_adjoint_hvp: out (n_nodes values) for a direction v (n_nodes values).  Per event, mu the jvp field tangent of v, lam the held one:
+ *     dD[n]    = over the active axes x, y, z, the first term assigned:  fl(mu[n] - mu[u_axis(n)])                         n not in F
+ *     q[j]     = +0, then over the neighbours n that have j as an active upwind neighbour, order x-, x+, y-, y+, z-, z+:
+ *                q[j] = fl(q[j] + fl(lam[n] * fl(fl(fl(mu[n] - mu[j]) - fl(fl(fl(T[n] - T[j]) / D_n) * dD[n])) / D_n)))
+ *     lam2     = the fixed point of the vjp for the field cotangent q (and no rows)
+ *     r[m]     = fl(fl(lam[m] * fl(fl(dx * fl(v[m] * dx)) - fl(fl(fl(dx * fl(s[m] * dx)) / D_m) * dD[m]))) / D_m)           m not in F
+ *     out_e[m] = fl(fl(fl(lam2[m] * fl(dx * fl(s[m] * dx))) / D_m) + r[m])  for m not in F,   fl(d_m * lam2[m])  for m in F
+ *     out[m]   = the events summed ascending from +0
+ *   One tangent and one adjoint relaxation (the kernels of jvp and vjp) and three streaming kernels, on the tape's stream without a host
+ *   copy in between; no floating-point atomics; the bits depend on no schedule.  *passes_jvp, *passes_vjp as for ttcr_fsm_adjoint_gn.
+ * ttcr_fsm_adjoint_newton: the same with the rows fl(row_weight[row] * (J v)[row]) (row_weight NULL: (J v)[row]) added to the seeds of lam2
+ *   exactly as the vjp adds w:  out = J^T W J v + hvp(v)  from ONE adjoint relaxation, the cost of ttcr_fsm_adjoint_gn plus the three
+ *   streaming kernels.  The first hvp or newton allocates what the first jvp allocates.
+ *   On a cell tape v and out hold n_cells values:  hvp(v) = A^T (node hvp(A v)), likewise newton, A and A^T as for jvp and vjp.
+ *   Without a held cotangent both return TTCR_ERR_VALUE (the message says so) before any device call.
  * Cell tapes.  ttcr_fsm_raytrace_multi_adjoint_cells: the same call for a 3-D grid with slowness defined for CELLS and
  *   without the WENO stage (a node grid: TTCR_ERR_VALUE, the message names ttcr_fsm_raytrace_multi_adjoint; 2-D and WENO grids:
  *   TTCR_ERR_UNSUPPORTED; ttcr_fsm_raytrace_multi_adjoint itself keeps refusing cell grids).  The solver works on the node slowness
@@ -462,6 +484,13 @@ int ttcr_fsm_adjoint_jvp_source(const ttcr_fsm_adjoint* t, const void* dsrc, int
                                 void* dfields, int df_on_device, int schedule, int* passes);
 int ttcr_fsm_adjoint_vjp_source(const ttcr_fsm_adjoint* t, const void* w, int w_on_device, const void* field_cot, int fc_on_device, void* grad,
                                 int grad_on_device, void* gsrc, int gsrc_on_device, int schedule, int* passes);
+int ttcr_fsm_adjoint_hold(ttcr_fsm_adjoint* t, const void* w, int w_on_device, const void* field_cot, int fc_on_device, void* grad,
+                          int grad_on_device, int schedule, int* passes);
+int ttcr_fsm_adjoint_release(ttcr_fsm_adjoint* t);
+int ttcr_fsm_adjoint_hvp(ttcr_fsm_adjoint* t, const void* v, int v_on_device, void* out, int out_on_device, int schedule, int* passes_jvp,
+                         int* passes_vjp);
+int ttcr_fsm_adjoint_newton(ttcr_fsm_adjoint* t, const void* v, int v_on_device, const void* row_weight, int rw_on_device, void* out,
+                            int out_on_device, int schedule, int* passes_jvp, int* passes_vjp);
 int ttcr_fsm_adjoint_free(ttcr_fsm_adjoint* t);
 
 /* Replaces: Grid2D::raytrace(Tx, t0, Rx, traveltimes, l_data, threadNo) (ttcr/Grid2D.h:616-640) and the overload with r_data

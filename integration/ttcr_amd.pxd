@@ -92,6 +92,14 @@ cdef extern from "ttcr_amd.h" nogil:
                                     int dtt_on_device, void* dfields, int df_on_device, int schedule, int* passes)
     int ttcr_fsm_adjoint_vjp_source(const ttcr_fsm_adjoint* t, const void* w, int w_on_device, const void* field_cot, int fc_on_device,
                                     void* grad, int grad_on_device, void* gsrc, int gsrc_on_device, int schedule, int* passes)
+    # second-order products: hold keeps lam of a cotangent on the tape, hvp is the derivative of its vjp in a direction, newton adds J^T W J v
+    int ttcr_fsm_adjoint_hold(ttcr_fsm_adjoint* t, const void* w, int w_on_device, const void* field_cot, int fc_on_device, void* grad,
+                              int grad_on_device, int schedule, int* passes)
+    int ttcr_fsm_adjoint_release(ttcr_fsm_adjoint* t)
+    int ttcr_fsm_adjoint_hvp(ttcr_fsm_adjoint* t, const void* v, int v_on_device, void* out, int out_on_device, int schedule,
+                             int* passes_jvp, int* passes_vjp)
+    int ttcr_fsm_adjoint_newton(ttcr_fsm_adjoint* t, const void* v, int v_on_device, const void* row_weight, int rw_on_device,
+                                void* out, int out_on_device, int schedule, int* passes_jvp, int* passes_vjp)
     int ttcr_fsm_adjoint_free(ttcr_fsm_adjoint* t)
     int ttcr_fsm_slot_m_size(const ttcr_fsm_grid* g, int slot, size_t* n_rows, size_t* nnz)
     int ttcr_fsm_get_slot_m(const ttcr_fsm_grid* g, int slot, long long* row_off, long long* j, void* v)

@@ -7,7 +7,8 @@ C order (what Grid3d.set_velocity reads).  The forward sets the model as set_vel
 then the grid dtype) and runs grid.raytrace_tape; tt is a tensor of the grid dtype on velocity's device, bit-equal to
 raytrace(..., compute_M=True)[0].  The backward is M^T g (MTape.vjp, on the device) permuted to velocity's layout, where M is the
 reference's matrix of d tt / d velocity with the rays held fixed: the gradient of the ray-frozen (linearised) problem, not the exact
-derivative of the returned tt.  A model in slowness composes in torch: raytrace(grid, 1 / s, ...).
+derivative of the returned tt.  A model in slowness composes in torch: raytrace(grid, 1 / s, ...).  A second derivative through this
+operator raises (its backward is marked once_differentiable).
 
     tt = ttcr_amd.autograd.raytrace_adjoint(grid, velocity, source, rcv, aggregate_src=False, return_fields=False)
 
@@ -15,7 +16,11 @@ is the same operator with the EXACT derivative: the forward runs grid.raytrace_a
 with tt_from_rp=0 returns them; 3-D node grids with weno=0), the backward is the adjoint-state gradient FieldTape.vjp -- the derivative
 of the returned tt through the solver's own first-order update -- times d slowness / d velocity = -1 / velocity**2, in velocity's layout.
 With return_fields=True it returns (tt, fields), fields the (n_events, nx, ny, nz) traveltime fields, differentiable too: a loss on the
-grid traveltimes has a gradient.  Forward mode works as well (torch.autograd.forward_ad): the tangent of the outputs for a velocity
+grid traveltimes has a gradient.  The backward is itself differentiable (create_graph=True, torch.autograd.functional.hvp, gradient
+penalties): the second derivative with respect to velocity is exact -- FieldTape.jvp for the part through the cotangent, FieldTape.hvp
+(the second-order term of the solver's own linearisation) for the part through the model, and the derivative of the factor
+-1 / velocity**2 --, on node and cell grids, with and without return_fields.  The double backward is linear in its own cotangent
+and differentiable in it (torch.autograd.functional.hvp's double-backward trick works); a third derivative raises.  Forward mode works as well (torch.autograd.forward_ad): the tangent of the outputs for a velocity
 tangent tv is FieldTape.jvp(-(tv / velocity**2)), J v of the same linearisation, in the layout of the outputs.
 
     tt = ttcr_amd.autograd.raytrace_events(grid, velocity, events, event_of_row, rcv, return_fields=False)
@@ -25,7 +30,8 @@ per event, `event_of_row` names the event of every rcv row (every event needs a 
 to velocity AND events.  The backward is one FieldTape.vjp(..., return_source_grad=True): the slowness gradient as above and the exact
 derivative with respect to the origin time and the position of every event, through the nodes the source initialisation froze.  Forward
 mode adds FieldTape.jvp and FieldTape.jvp_source.  The derivative with respect to a position has a kink where the point crosses a cell
-face or comes within 1e-4 of a node: the formula of the side the point is on is returned.
+face or comes within 1e-4 of a node: the formula of the side the point is on is returned.  Second derivatives through raytrace_events
+(with respect to the source points, and mixed ones) are not implemented: a double backward raises instead of returning a part.
 
 Both take wrt='nodes' (default) or wrt='cells'.  With wrt='cells' `grid` is a 3-D cell grid (Grid3d(..., cell_slowness=1, weno=0)),
 `velocity` holds one value per cell, shape (ncx, ncy, ncz) or flat in C order, and the derivative is the one with respect to the cell
@@ -46,6 +52,7 @@ def _function():
     if _Fn is not None:
         return _Fn
     import torch
+    from torch.autograd.function import once_differentiable
 
     class RaytraceFn(torch.autograd.Function):
         @staticmethod
@@ -57,6 +64,7 @@ def _function():
             return torch.from_numpy(tt).to(velocity.device)
 
         @staticmethod
+        @once_differentiable   # (M is the ray-frozen matrix: a second derivative through it would be a partial one)
         def backward(ctx, g):
             shape, vdt, (nx, ny, nz) = ctx.layout
             gn = ctx.tape.vjp(g.contiguous())
@@ -85,6 +93,112 @@ def _adjoint_function():
     if _AdjFn is not None:
         return _AdjFn
     import torch
+    from torch.autograd.function import once_differentiable
+
+    def to_model(a, layout):
+        """velocity's layout -> (mx, my, mz) in C order -> model order x fastest"""
+        (mx, my, mz) = layout[2]
+        return a.reshape(mx, my, mz).permute(2, 1, 0).contiguous().reshape(-1)
+
+    def from_model(a, layout):
+        """model order x fastest -> (mx, my, mz) in C order -> velocity's layout"""
+        (mx, my, mz) = layout[2]
+        return a.reshape(mz, my, mx).permute(2, 1, 0).contiguous().reshape(layout[0])
+
+    def field_cot(gf):
+        """(n_events, nx, ny, nz) in C order -> node order x fastest"""
+        return None if gf is None else gf.permute(0, 3, 2, 1).contiguous().reshape(gf.shape[0], -1)
+
+    def fields_out(df, layout):
+        """(n_events, n_nodes) node order x fastest -> (n_events, nx, ny, nz) in C order"""
+        nx, ny, nz = layout[1]
+        return df.reshape(df.shape[0], nz, ny, nx).permute(0, 3, 2, 1).contiguous()
+
+    class _NoThirdFn(torch.autograd.Function):
+        """identity whose backward raises: put on the inputs the second derivative depends on beyond what is implemented, so that a
+        third derivative raises where autograd would otherwise return a part of it"""
+
+        @staticmethod
+        def forward(ctx, a):
+            return a.view_as(a)
+
+        @staticmethod
+        def backward(ctx, c):
+            raise RuntimeError('raytrace_adjoint is differentiable twice: third derivatives are not implemented')
+
+    def no_third(a):
+        return a if a is None or not a.requires_grad else _NoThirdFn.apply(a)
+
+    def second_order(gg, g, gf, velocity, tape, layout, need):
+        """(grad_g, grad_gf, grad_v) of y = -P vjp(g, gf) / v^2 for the cotangent gg of y (P: model order -> velocity's layout):
+        y is linear in (g, gf) -- the transpose is the jvp of ds = P^T(-gg / v^2) --; through the slowness its derivative is the hvp for
+        the held cotangent (g, gf) between the two factors -1 / v^2, plus the derivative of the outer factor, 2 h gg / v^3, h = P vjp"""
+        v2 = velocity * velocity
+        ds = to_model(-(gg / v2), layout)
+        grad_g = grad_gf = grad_v = None
+        if need[0] or need[1]:
+            if gf is not None and need[1]:
+                dtt, df = tape.jvp(ds, return_fields=True)
+                grad_gf = fields_out(df, layout).to(gf.dtype)
+            else:
+                dtt = tape.jvp(ds)
+            grad_g = dtt.to(g.dtype)
+        if need[2]:
+            h = from_model(tape.hold(g.contiguous(), field_cot(gf), return_grad=True), layout).to(velocity.dtype)
+            hv = from_model(tape.hvp(ds), layout).to(velocity.dtype)
+            grad_v = -hv / v2 + 2 * h * gg / (v2 * velocity)
+        return grad_g, grad_gf, grad_v
+
+    class _AdjDoubleBackwardFn(torch.autograd.Function):
+        """The double backward as a function of its cotangent gg, in which it is linear: differentiable with respect to gg (what
+        torch.autograd.functional.hvp's double-backward trick needs); g, gf and velocity come in behind _NoThirdFn."""
+
+        @staticmethod
+        def forward(ctx, gg, g, gf, velocity, tape, layout, need):
+            ctx.tape, ctx.layout, ctx.has_gf = tape, layout, gf is not None
+            ctx.save_for_backward(g, gf, velocity)
+            ctx.set_materialize_grads(False)
+            outs = second_order(gg, g, gf, velocity, tape, layout, need)
+            ctx.mark_non_differentiable(*[o for o, n in zip(outs, need) if o is not None and not n])
+            return outs
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, c_g, c_gf, c_v):
+            # the transpose of a map that is symmetric up to the layout: gg -> (J ds, H ds + ...) has the transpose
+            # (c_g, c_gf, c_v) -> -P vjp(c_g, c_gf) / v^2 + second_order(c_v)[2]
+            g, gf, velocity = ctx.saved_tensors
+            tape, layout = ctx.tape, ctx.layout
+            out = None
+            if c_g is not None or c_gf is not None:
+                if c_g is None:
+                    c_g = torch.zeros_like(g)
+                out = -from_model(tape.vjp(c_g.contiguous(), field_cot(c_gf)), layout).to(velocity.dtype) / (velocity * velocity)
+            if c_v is not None:
+                part = second_order(c_v, g, gf, velocity, tape, layout, (False, False, True))[2]
+                out = part if out is None else out + part
+            zero = lambda a: None if a is None else torch.zeros_like(a)   # noqa: E731  (behind _NoThirdFn: raises if it is ever used)
+            return out, zero(g), zero(gf), zero(velocity), None, None, None
+
+    class _AdjBackwardFn(torch.autograd.Function):
+        """The backward of RaytraceAdjointFn as a function of (g, gf, velocity), differentiable once more: see second_order."""
+
+        @staticmethod
+        def forward(ctx, g, gf, velocity, tape, layout):
+            ctx.tape, ctx.layout = tape, layout
+            ctx.save_for_backward(g, gf, velocity)
+            gn = tape.vjp(g.contiguous(), field_cot(gf))
+            # d slowness / d velocity = -1 / velocity^2
+            return -from_model(gn, layout).to(velocity.dtype) / (velocity * velocity)
+
+        @staticmethod
+        def backward(ctx, gg):
+            g, gf, velocity = ctx.saved_tensors
+            need = (ctx.needs_input_grad[0], gf is not None and ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+            if not torch.is_grad_enabled():
+                return second_order(gg, g, gf, velocity, ctx.tape, ctx.layout, need) + (None, None)
+            outs = _AdjDoubleBackwardFn.apply(gg, no_third(g), no_third(gf), no_third(velocity), ctx.tape, ctx.layout, need)
+            return tuple(outs) + (None, None)
 
     class RaytraceAdjointFn(torch.autograd.Function):
         @staticmethod
@@ -105,15 +219,8 @@ def _adjoint_function():
 
         @staticmethod
         def backward(ctx, g, gf=None):
-            shape, (nx, ny, nz), (mx, my, mz) = ctx.layout
             (velocity,) = ctx.saved_tensors
-            fc = None
-            if gf is not None:   # (n_events, nx, ny, nz) in C order -> node order x fastest
-                fc = gf.permute(0, 3, 2, 1).contiguous().reshape(gf.shape[0], -1)
-            gn = ctx.tape.vjp(g.contiguous(), fc)
-            # model order x fastest -> (mx, my, mz) in C order -> velocity's layout; d slowness / d velocity = -1 / velocity^2
-            gs = gn.reshape(mz, my, mx).permute(2, 1, 0).contiguous().reshape(shape).to(velocity.dtype)
-            return -gs / (velocity * velocity), None, None, None, None, None, None
+            return _AdjBackwardFn.apply(g, gf, velocity, ctx.tape, ctx.layout), None, None, None, None, None, None
 
         @staticmethod
         def jvp(ctx, tv, *_):
@@ -165,6 +272,7 @@ def _events_function():
     if _EvFn is not None:
         return _EvFn
     import torch
+    from torch.autograd.function import once_differentiable
 
     class RaytraceEventsFn(torch.autograd.Function):
         @staticmethod
@@ -187,6 +295,7 @@ def _events_function():
             return out, torch.from_numpy(np.ascontiguousarray(f)).to(velocity.device)
 
         @staticmethod
+        @once_differentiable   # (second derivatives with respect to the source points, and mixed ones, are not implemented: raise, not a part)
         def backward(ctx, g, gf=None):
             shape, (nx, ny, nz), (mx, my, mz) = ctx.layout
             velocity, events = ctx.saved_tensors

@@ -688,6 +688,99 @@ __global__ void src_grad_kernel(const int* __restrict__ off, const long long* __
     gsrc[4 * q] = a0; gsrc[4 * q + 1] = a1; gsrc[4 * q + 2] = a2; gsrc[4 * q + 3] = a3;
 }
 
+// ---- second-order products: the derivative of the vjp in a direction v, for a cotangent whose lam is held on the tape.
+// Three streaming passes around the relaxations above; every value is one fixed expression of final values.
+// dD[n] = sum over the active axes, order x, y, z, the first term assigned, of fl(mu[n] - mu[u_axis(n)]); +0 for a frozen node.  One thread
+// per node, events in blockIdx.y; the upwind choice is recomputed from the field as tan_jacobi_kernel does.
+template <typename T>
+__global__ void hess_dd_kernel(const T* __restrict__ fields, const unsigned char* __restrict__ frozen, const T* __restrict__ mu,
+                               AdjGeom<T> geo, T* __restrict__ dD) {
+    const size_t m = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (m >= geo.nn) return;
+    const size_t idx = (size_t)blockIdx.y * geo.nn + m;
+    T acc = 0;
+    if (!frozen[idx]) {
+        const T inf = std::numeric_limits<T>::infinity();
+        const int pos[3] = {(int)(m % geo.nnx), (int)((m / geo.nnx) % geo.nny), (int)(m / ((size_t)geo.nnx * geo.nny))};
+        const int ext[3] = {geo.nnx, geo.nny, geo.nnz};
+        const long long st[3] = {1, (long long)geo.nnx, (long long)geo.nnx * geo.nny};
+        const T* F = fields + idx;
+        const T* M = mu + idx;
+        const T t = F[0], mm = M[0];
+        bool any = false;
+        for (int ax = 0; ax < 3; ++ax) {
+            const T lo = pos[ax] > 0 ? F[-st[ax]] : inf;
+            const T hi = pos[ax] < ext[ax] - 1 ? F[st[ax]] : inf;
+            const bool up = hi < lo;
+            const T a = up ? hi : lo;
+            if (a < t) {
+                const T p = mm - (up ? M[st[ax]] : M[-st[ax]]);
+                acc = any ? acc + p : p;
+                any = true;
+            }
+        }
+    }
+    dD[idx] = acc;
+}
+
+// q[j] = +0, then over the neighbours n flagged in j's in-mask, order x-, x+, y-, y+, z-, z+:
+//   q[j] = fl(q[j] + fl(lam[n] * fl(fl(fl(mu[n] - mu[j]) - fl(fl(fl(T[n] - T[j]) / D[n]) * dD[n])) / D[n])))
+#define HESS_TERM(bit, off)                                                                          \
+    if (in & (1u << (bit))) {                                                                         \
+        const T dn = Dn[(off)];                                                                       \
+        acc = acc + L[(off)] * (((M[(off)] - mj) - ((F[(off)] - tj) / dn) * dDn[(off)]) / dn);        \
+    }
+template <typename T>
+__global__ void hess_q_kernel(const T* __restrict__ fields, const T* __restrict__ D, const unsigned char* __restrict__ inmask,
+                              const T* __restrict__ lam, const T* __restrict__ mu, const T* __restrict__ dD, AdjGeom<T> geo,
+                              T* __restrict__ q) {
+    const size_t m = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (m >= geo.nn) return;
+    const size_t idx = (size_t)blockIdx.y * geo.nn + m;
+    const long long sy = geo.nnx, sz = (long long)geo.nnx * geo.nny;
+    const unsigned in = inmask[idx];
+    T acc = 0;
+    if (in) {
+        const T* L = lam + idx;
+        const T* F = fields + idx;
+        const T* M = mu + idx;
+        const T* Dn = D + idx;
+        const T* dDn = dD + idx;
+        const T tj = F[0], mj = M[0];
+        HESS_TERM(0, -1) HESS_TERM(1, 1) HESS_TERM(2, -sy) HESS_TERM(3, sy) HESS_TERM(4, -sz) HESS_TERM(5, sz)
+    }
+    q[idx] = acc;
+}
+#undef HESS_TERM
+
+// out[m] = sum over the events, ascending, from +0, of  fl(d * lam2) (frozen)  or  fl(fl(fl(lam2 * c) / D) + r),
+//   c = fl(dx * fl(s * dx)),  r = fl(fl(lam * fl(fl(dx * fl(v * dx)) - fl(fl(c / D) * dD))) / D)
+// adj_grad_kernel with the direct term added.  v and out may be the same array (a thread reads v[m] before it writes out[m]).
+template <typename T>
+__global__ void hess_grad_kernel(const T* __restrict__ lam2, const T* __restrict__ lam, const T* __restrict__ D, const T* __restrict__ dD,
+                                 const unsigned char* __restrict__ frozen, const T* __restrict__ s, const T* v, AdjGeom<T> geo,
+                                 size_t n_events, T* out) {
+    const size_t m = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (m >= geo.nn) return;
+    const T c = geo.dx * (s[m] * geo.dx);
+    const T cv = geo.dx * (v[m] * geo.dx);
+    T acc = 0;
+    for (size_t e = 0; e < n_events; ++e) {
+        const size_t idx = e * geo.nn + m;
+        const T l2 = lam2[idx];
+        const T d = D[idx];
+        T o;
+        if (frozen[idx]) {
+            o = d * l2;
+        } else {
+            const T r = (lam[idx] * (cv - (c / d) * dD[idx])) / d;
+            o = (l2 * c) / d + r;
+        }
+        acc = acc + o;
+    }
+    out[m] = acc;
+}
+
 // ---- cell tapes: gc = A^T g, A the averaging of fsm_cells_to_nodes3d.  One thread per cell c = (ck * ncy + cj) * ncx + ci:
 // the eight products fl(f(n) * g[n]) over the corner nodes n = (ci + a, cj + b, ck + d), f(n) = 1 / (cells touching n) = 1, 1/2, 1/4 or 1/8
 // (a product of exact per-axis factors), added left to right from the first product, a innermost, d outermost.  No atomics.
@@ -765,7 +858,8 @@ void AdjTapeDev::release() {
     dev_free(sd_key); dev_free(sd_row); dev_free(sd_w); dev_free(flags); dev_free(stamps); dev_free(err); dev_free(w_tmp); dev_free(grad_tmp);
     dev_free(rw_off); dev_free(rw_key); dev_free(rw_w); dev_free(rw_tmp); dev_free(tan_stamps);
     dev_free(src_off); dev_free(src_pt); dev_free(src_key); dev_free(src_node); dev_free(src_c); dev_free(src_io); dev_free(src_rows);
-    dev_free(mu4); dev_free(mu4b); dev_free(cell_tmp);
+    dev_free(mu4); dev_free(mu4b); dev_free(cell_tmp); dev_free(hold_lam); dev_free(hess_dd);
+    held = false;
     if (stream) (void)hipStreamDestroy(stream);
     stream = nullptr;
     total_bytes = 0;
@@ -939,8 +1033,10 @@ static int adj_vjp_impl(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, i
     T* lam = (T*)t.lam;
     int passes = 0;
     if (en > 0) {
-        adj_seed_fill_kernel<T><<<std::min(blocks_for(en), 65536u), ADJ_THREADS, 0, s>>>(d_fc, g, en);
-        ADJ_CHECK(hipGetLastError());
+        if (d_fc != g) {   // (a caller that formed the field cotangent in g itself: hess_q_kernel)
+            adj_seed_fill_kernel<T><<<std::min(blocks_for(en), 65536u), ADJ_THREADS, 0, s>>>(d_fc, g, en);
+            ADJ_CHECK(hipGetLastError());
+        }
         if (d_w && t.n_seed > 0) {
             adj_seed_rows_kernel<T><<<blocks_for(t.n_seed), ADJ_THREADS, 0, s>>>(t.sd_key, t.sd_row, (const T*)t.sd_w, t.n_seed, d_w, g);
             ADJ_CHECK(hipGetLastError());
@@ -1035,8 +1131,9 @@ void adj_jvp_prepare(AdjTapeDev& t) {
     }
 }
 
+// the jvp; *mu_final (may be null) receives the buffer that holds the relaxed tangent, *ds_nodes (may be null) the node perturbation
 template <typename T>
-int adj_jvp(AdjTapeDev& t, const T* d_ds, T* d_dtt, T* d_dfields, int schedule) {
+static int adj_jvp_impl(AdjTapeDev& t, const T* d_ds, T* d_dtt, T* d_dfields, int schedule, const T** mu_final, const T** ds_nodes) {
     ADJ_CHECK(hipSetDevice(t.device));
     adj_jvp_prepare<T>(t);
     hipStream_t s = t.stream;
@@ -1074,7 +1171,14 @@ int adj_jvp(AdjTapeDev& t, const T* d_ds, T* d_dtt, T* d_dfields, int schedule) 
         ADJ_CHECK(hipGetLastError());
     }
     if (d_dfields && en > 0) ADJ_CHECK(hipMemcpyAsync(d_dfields, mu, en * sizeof(T), hipMemcpyDeviceToDevice, s));
+    if (mu_final) *mu_final = mu;
+    if (ds_nodes) *ds_nodes = d_ds;
     return passes;
+}
+
+template <typename T>
+int adj_jvp(AdjTapeDev& t, const T* d_ds, T* d_dtt, T* d_dfields, int schedule) {
+    return adj_jvp_impl<T>(t, d_ds, d_dtt, d_dfields, schedule, nullptr, nullptr);
 }
 
 template <typename T>
@@ -1086,6 +1190,76 @@ void adj_gn(AdjTapeDev& t, const T* d_v, const T* d_rw, T* d_out, int schedule, 
         ADJ_CHECK(hipGetLastError());
     }
     *passes_vjp = adj_vjp<T>(t, w, nullptr, d_out, schedule);
+}
+
+// ---- second-order products
+size_t adj_hold_bytes(const AdjTapeDev& t) { return 2 * t.n_events * t.nn * t.elem; }
+
+void adj_release_hold(AdjTapeDev& t) {
+    if (!t.hold_lam && !t.hess_dd) return;
+    (void)hipSetDevice(t.device);
+    if (t.stream) (void)hipStreamSynchronize(t.stream);
+    const size_t each = std::max<size_t>(t.n_events * t.nn * t.elem, 1);
+    if (t.hold_lam) { dev_free(t.hold_lam); t.total_bytes -= each; }
+    if (t.hess_dd) { dev_free(t.hess_dd); t.total_bytes -= each; }
+    t.held = false;
+}
+
+template <typename T>
+int adj_hold(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, int schedule) {
+    ADJ_CHECK(hipSetDevice(t.device));
+    const size_t en = t.n_events * t.nn;
+    t.held = false;
+    if (!t.hold_lam || !t.hess_dd) {
+        Alloc alloc{t, adj_hold_bytes(t)};
+        try {
+            if (!t.hold_lam) alloc(t.hold_lam, en * sizeof(T));
+            if (!t.hess_dd) alloc(t.hess_dd, en * sizeof(T));
+        } catch (...) {
+            adj_release_hold(t);
+            throw;
+        }
+    }
+    const T* lam = nullptr;
+    const int passes = adj_vjp_model<T>(t, d_w, d_fc, d_grad, schedule, &lam);
+    if (en > 0) ADJ_CHECK(hipMemcpyAsync(t.hold_lam, lam, en * sizeof(T), hipMemcpyDeviceToDevice, t.stream));
+    t.held = true;
+    return passes;
+}
+
+// tangent relaxation of v -> dD and q from final values (q written into g, the seeds of the relaxation that follows) -> adjoint relaxation
+// of lam2 for the field cotangent q (newton: and the rows rw * J v) -> gradient with the direct term; a cell tape ends with A^T
+template <typename T>
+void adj_hess(AdjTapeDev& t, const T* d_v, const T* d_rw, bool newton, T* d_out, int schedule, int* passes_jvp, int* passes_vjp) {
+    if (!t.held) throw std::invalid_argument("no held cotangent: call hold first");
+    hipStream_t s = t.stream;
+    const size_t E = t.n_events, en = E * t.nn;
+    const AdjGeom<T> geo{t.nnx, t.nny, t.nnz, t.nn, (T)t.dx};
+    T* w = (T*)t.w_tmp;
+    const T* mu = nullptr;
+    const T* v_nodes = nullptr;
+    *passes_jvp = adj_jvp_impl<T>(t, d_v, newton ? w : nullptr, nullptr, schedule, &mu, &v_nodes);
+    if (newton && d_rw && t.n_rows > 0) {
+        tan_scale_rows_kernel<T><<<blocks_for(t.n_rows), ADJ_THREADS, 0, s>>>(d_rw, w, t.n_rows);
+        ADJ_CHECK(hipGetLastError());
+    }
+    if (en > 0) {
+        const dim3 grid(blocks_for(t.nn), (unsigned)E);
+        hess_dd_kernel<T><<<grid, ADJ_THREADS, 0, s>>>((const T*)t.fields, t.frozen, mu, geo, (T*)t.hess_dd);
+        ADJ_CHECK(hipGetLastError());
+        hess_q_kernel<T><<<grid, ADJ_THREADS, 0, s>>>((const T*)t.fields, (const T*)t.D, t.inmask, (const T*)t.hold_lam, mu,
+                                                     (const T*)t.hess_dd, geo, (T*)t.g);
+        ADJ_CHECK(hipGetLastError());
+    }
+    const T* lam2 = nullptr;
+    *passes_vjp = adj_vjp_impl<T>(t, newton ? w : nullptr, (const T*)t.g, nullptr, schedule, &lam2);
+    if (t.nn > 0) {
+        T* out_nodes = t.cells ? (T*)t.grad_tmp : d_out;   // (a cell tape: v_nodes is grad_tmp, overwritten in place)
+        hess_grad_kernel<T><<<blocks_for(t.nn), ADJ_THREADS, 0, s>>>(lam2, (const T*)t.hold_lam, (const T*)t.D, (const T*)t.hess_dd, t.frozen,
+                                                                    (const T*)t.slowness, v_nodes, geo, E, out_nodes);
+        ADJ_CHECK(hipGetLastError());
+        if (t.cells) adj_nodes_to_cells<T>(t, (const T*)t.grad_tmp, d_out);
+    }
 }
 
 // ---- derivatives with respect to the source points
@@ -1231,6 +1405,10 @@ template int adj_jvp<float>(AdjTapeDev&, const float*, float*, float*, int);
 template int adj_jvp<double>(AdjTapeDev&, const double*, double*, double*, int);
 template void adj_gn<float>(AdjTapeDev&, const float*, const float*, float*, int, int*, int*);
 template void adj_gn<double>(AdjTapeDev&, const double*, const double*, double*, int, int*, int*);
+template int adj_hold<float>(AdjTapeDev&, const float*, const float*, float*, int);
+template int adj_hold<double>(AdjTapeDev&, const double*, const double*, double*, int);
+template void adj_hess<float>(AdjTapeDev&, const float*, const float*, bool, float*, int, int*, int*);
+template void adj_hess<double>(AdjTapeDev&, const double*, const double*, bool, double*, int, int*, int*);
 
 template void adj_src_prepare<float>(AdjTapeDev&);
 template void adj_src_prepare<double>(AdjTapeDev&);

@@ -6,6 +6,8 @@
 //                   neighbours that have this node as an active upwind neighbour).
 // Per JVP:          relaxation of mu = own term + gather(mu) over the at most three upwind neighbours (the same two schedules; the upwind
 //                   choice is recomputed from the field) -> receiver rows through the stencil, one thread per row.
+// Per HVP / Newton product: JVP relaxation -> dD (per node) -> q (gather through the in-mask, lam of the held cotangent)
+//                   -> VJP relaxation seeded with q (and the weighted rows of J v) -> gradient with the direct term added.
 // Per VJP:          seed (g = field cotangent + receiver rows through the interpolation stencil, one serial chain per node in row order)
 //                   -> relaxation of lam = g + gather(lam) to its fixed point (tiled in LDS, or the global Jacobi baseline)
 //                   -> gradient (events summed in ascending order from +0 inside the thread).
@@ -102,6 +104,10 @@ struct AdjTapeDev {
     void* src_rows = nullptr;         // 4 n_rows values: the dtt of a K-column call before it goes to the host
     void* mu4 = nullptr;              // 4 n_events * nn: the four columns of a node adjacent (allocated by the first call with n_cols > 1)
     void* mu4b = nullptr;             // second buffer of the Jacobi baseline (allocated by the first such call with that schedule)
+    // second-order products: allocated by hold, returned by release_hold
+    void* hold_lam = nullptr;         // n_events * nn: lam of the held cotangent
+    void* hess_dd = nullptr;          // n_events * nn: dD of the running product
+    bool held = false;                // hold_lam holds a solved lam
     size_t n_tiles = 0;
     size_t total_bytes = 0;
     hipStream_t stream = nullptr;
@@ -135,6 +141,20 @@ int adj_jvp(AdjTapeDev& t, const T* d_ds, T* d_dtt, T* d_dfields, int schedule);
 // Gauss-Newton product: jvp into w_tmp -> w_tmp *= d_rw (may be null) -> vjp into d_out (n_model()), all on the tape's stream
 template <typename T>
 void adj_gn(AdjTapeDev& t, const T* d_v, const T* d_rw, T* d_out, int schedule, int* passes_jvp, int* passes_vjp);
+
+// ---- second-order products (tests/hessian_reference.py restates them)
+// hold: the vjp of (d_w, d_fc) -- d_grad (n_model(), may be null) with the bits of adj_vjp -- whose lam stays on the tape in hold_lam; the
+// first hold allocates adj_hold_bytes(t) (hold_lam and the dD workspace; AdjDeviceError naming the byte count if that fails), a later one
+// replaces the held lam.  adj_release_hold frees both and takes them off bytes().
+size_t adj_hold_bytes(const AdjTapeDev& t);
+template <typename T>
+int adj_hold(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, int schedule);
+void adj_release_hold(AdjTapeDev& t);
+// d_out (n_model()) = the derivative in direction d_v (n_model()) of the held vjp with (w, field_cot) fixed; newton: plus J^T (d_rw * J v)
+// (d_rw n_rows, may be null) from the same adjoint relaxation.  d_v and d_out may be the same array.  Throws std::invalid_argument
+// without a held cotangent.  Uses g, lam, lam2, w_tmp (and grad_tmp on a cell tape) as jvp and vjp do.
+template <typename T>
+void adj_hess(AdjTapeDev& t, const T* d_v, const T* d_rw, bool newton, T* d_out, int schedule, int* passes_jvp, int* passes_vjp);
 
 // ---- derivatives with respect to the source points (tests/source_reference.py restates them)
 // what the first jvp_source / vjp_source adds to the tape (the lists above and the two staging arrays), and what the first call with

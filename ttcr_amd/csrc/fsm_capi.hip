@@ -4140,6 +4140,107 @@ int ttcr_fsm_adjoint_vjp_source(const ttcr_fsm_adjoint* t, const void* w, int w_
         });
     });
 }
+// ---- second-order products of the field tape
+int ttcr_fsm_adjoint_hold(ttcr_fsm_adjoint* t, const void* w, int w_on_device, const void* field_cot, int fc_on_device, void* grad,
+                          int grad_on_device, int schedule, int* passes) {
+    if (!t || (!w && !field_cot)) {
+        g_last_error = !t ? "null tape" : "w and field_cot are both null: no cotangent to hold";
+        return TTCR_ERR_VALUE;
+    }
+    if (schedule != 0 && schedule != 1) {
+        g_last_error = "schedule: 0 (tiled) or 1 (global Jacobi)";
+        return TTCR_ERR_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(t->mu);
+    return guarded([&] {
+        ttcr_amd::AdjTapeDev& d = t->t;
+        adj_device_errors([&] {
+            HIP_CHECK(hipSetDevice(d.device));
+            const void* dw = w;
+            const void* dfc = field_cot;
+            void* dg = grad ? (grad_on_device ? grad : d.model_tmp()) : nullptr;
+            if (w && !w_on_device) {
+                if (d.n_rows > 0) HIP_CHECK(hipMemcpyAsync(d.w_tmp, w, d.n_rows * d.elem, hipMemcpyHostToDevice, d.stream));
+                dw = d.w_tmp;
+            }
+            if (field_cot && !fc_on_device) {   // (staged as ttcr_fsm_adjoint_vjp stages it)
+                if (d.n_events * d.nn > 0)
+                    HIP_CHECK(hipMemcpyAsync(d.lam2, field_cot, d.n_events * d.nn * d.elem, hipMemcpyHostToDevice, d.stream));
+                dfc = d.lam2;
+            }
+            int np = 0;
+            if (t->dtype == TTCR_F32) np = ttcr_amd::adj_hold<float>(d, (const float*)dw, (const float*)dfc, (float*)dg, schedule);
+            else np = ttcr_amd::adj_hold<double>(d, (const double*)dw, (const double*)dfc, (double*)dg, schedule);
+            if (grad && !grad_on_device && d.n_model() > 0)
+                HIP_CHECK(hipMemcpyAsync(grad, d.model_tmp(), d.n_model() * d.elem, hipMemcpyDeviceToHost, d.stream));
+            HIP_CHECK(hipStreamSynchronize(d.stream));
+            if (passes) *passes = np;
+        });
+    });
+}
+int ttcr_fsm_adjoint_release(ttcr_fsm_adjoint* t) {
+    if (!t) {
+        g_last_error = "null tape";
+        return TTCR_ERR_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(t->mu);
+    return guarded([&] { ttcr_amd::adj_release_hold(t->t); });
+}
+// hvp and newton: one body (row_weight is NULL for the hvp)
+static int adjoint_second_order(ttcr_fsm_adjoint* t, const char* what, const void* v, int v_on_device, const void* row_weight,
+                                int rw_on_device, bool newton, void* out, int out_on_device, int schedule, int* passes_jvp,
+                                int* passes_vjp) {
+    if (!t || !v || !out) {
+        g_last_error = !t ? "null tape" : (!v ? "null v" : "null out");
+        return TTCR_ERR_VALUE;
+    }
+    if (schedule != 0 && schedule != 1) {
+        g_last_error = "schedule: 0 (tiled) or 1 (global Jacobi)";
+        return TTCR_ERR_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(t->mu);
+    if (!t->t.held) {
+        g_last_error = std::string(what) + ": the tape holds no cotangent (call ttcr_fsm_adjoint_hold first)";
+        return TTCR_ERR_VALUE;
+    }
+    return guarded([&] {
+        ttcr_amd::AdjTapeDev& d = t->t;
+        adj_device_errors([&] {
+            HIP_CHECK(hipSetDevice(d.device));
+            const void* dv = v;
+            if (!v_on_device) {   // (read by the tangent relaxation and by the last kernel, which writes the host result to the same place)
+                if (d.n_model() > 0) HIP_CHECK(hipMemcpyAsync(d.model_tmp(), v, d.n_model() * d.elem, hipMemcpyHostToDevice, d.stream));
+                dv = d.model_tmp();
+            }
+            void* dout = out_on_device ? out : d.model_tmp();
+            const bool stage_rw = row_weight && !rw_on_device;
+            int pj = 0, pv = 0;
+            if (stage_rw) {   // (the staging row is part of what the first jvp allocates)
+                if (t->dtype == TTCR_F32) ttcr_amd::adj_jvp_prepare<float>(d);
+                else ttcr_amd::adj_jvp_prepare<double>(d);
+                if (d.n_rows > 0) HIP_CHECK(hipMemcpyAsync(d.rw_tmp, row_weight, d.n_rows * d.elem, hipMemcpyHostToDevice, d.stream));
+            }
+            const void* drw = row_weight ? (rw_on_device ? row_weight : d.rw_tmp) : nullptr;
+            if (t->dtype == TTCR_F32)
+                ttcr_amd::adj_hess<float>(d, (const float*)dv, (const float*)drw, newton, (float*)dout, schedule, &pj, &pv);
+            else ttcr_amd::adj_hess<double>(d, (const double*)dv, (const double*)drw, newton, (double*)dout, schedule, &pj, &pv);
+            if (!out_on_device && d.n_model() > 0)
+                HIP_CHECK(hipMemcpyAsync(out, d.model_tmp(), d.n_model() * d.elem, hipMemcpyDeviceToHost, d.stream));
+            HIP_CHECK(hipStreamSynchronize(d.stream));
+            if (passes_jvp) *passes_jvp = pj;
+            if (passes_vjp) *passes_vjp = pv;
+        });
+    });
+}
+int ttcr_fsm_adjoint_hvp(ttcr_fsm_adjoint* t, const void* v, int v_on_device, void* out, int out_on_device, int schedule, int* passes_jvp,
+                         int* passes_vjp) {
+    return adjoint_second_order(t, "hvp", v, v_on_device, nullptr, 0, false, out, out_on_device, schedule, passes_jvp, passes_vjp);
+}
+int ttcr_fsm_adjoint_newton(ttcr_fsm_adjoint* t, const void* v, int v_on_device, const void* row_weight, int rw_on_device, void* out,
+                            int out_on_device, int schedule, int* passes_jvp, int* passes_vjp) {
+    return adjoint_second_order(t, "newton", v, v_on_device, row_weight, rw_on_device, true, out, out_on_device, schedule, passes_jvp,
+                                passes_vjp);
+}
 int ttcr_fsm_adjoint_free(ttcr_fsm_adjoint* t) {
     if (!t) return TTCR_OK;
     return guarded([&] { delete t; });

@@ -547,7 +547,9 @@ class FieldTape:
     what the exact discrete adjoint of the first-order update needs besides them: the node slowness, the nodes each source froze and
     the interpolation stencil of every (event, receiver) row.  Events are in the order raytrace takes them.  The tape does not depend
     on the grid any more: later calls, set_slowness and deleting the grid leave it as it is.  vjp applies J^T (reverse mode), jvp
-    applies J (forward mode) and gauss_newton J^T W J of the same linearisation, all on the device.  The same linearisation with respect
+    applies J (forward mode) and gauss_newton J^T W J of the same linearisation, all on the device; hold keeps the adjoint of a cotangent
+    on the tape, hvp then applies the second-order term sum_r w_r d2 tt_r / ds2 and newton the full Hessian J^T W J + that term (release
+    frees the held adjoint).  The same linearisation with respect
     to the source points, parameters (t0, x, y, z) each: jvp_source, source_jacobian and vjp(..., return_source_grad=True); n_points
     points in call order, point_event their events.
     wrt is 'nodes' or 'cells': what the model vector of vjp / jvp / gauss_newton holds, n_cols values -- the node slowness (n_cols =
@@ -862,6 +864,140 @@ class FieldTape:
         self.passes = (pj.value, pv.value)
         self._refresh_nbytes()
         return g[:self.n_cols].to(ref.device)
+
+    # ---- second-order products
+    def _model_arg(self, v, name):
+        """(array, pointer, on_device) of a model vector, numpy or torch"""
+        if type(v).__module__.startswith('torch') and v.device.type == 'cuda':
+            import torch
+
+            tdt = torch.float32 if self.dtype == np.float32 else torch.float64
+            if v.numel() != self.n_cols:
+                raise ValueError('%s should hold %d values (one per %s), got shape %s' % (name, self.n_cols, self._per, tuple(v.shape)))
+            a = v.detach().to(device=torch.device('cuda', self.device), dtype=tdt).contiguous().reshape(-1)
+            return a, C.c_void_p(a.data_ptr()), 1
+        a = np.ascontiguousarray(v.detach().numpy() if hasattr(v, 'detach') else v, dtype=self.dtype).reshape(-1)
+        if a.size != self.n_cols:
+            raise ValueError('%s should hold %d values (one per %s), got shape %s' % (name, self.n_cols, self._per, a.shape))
+        if a.size == 0:
+            a = np.zeros(1, dtype=self.dtype)
+        return a, _ptr(a), 0
+
+    def _row_arg(self, w, name):
+        """a per-data-row vector in tape row order: (array, pointer, on_device)"""
+        if type(w).__module__.startswith('torch') and w.device.type == 'cuda':
+            import torch
+
+            tdt = torch.float32 if self.dtype == np.float32 else torch.float64
+            dev = torch.device('cuda', self.device)
+            if w.dim() != 1 or w.shape[0] != self.n_data:
+                raise ValueError('%s should hold %d values (one per data row), got shape %s' % (name, self.n_data, tuple(w.shape)))
+            if self._rows_dev is None:
+                self._rows_dev = torch.as_tensor(self._rows, device=dev)
+            a = w.detach().to(device=dev, dtype=tdt).index_select(0, self._rows_dev).contiguous()
+            if a.numel() == 0:
+                a = torch.zeros(1, dtype=tdt, device=dev)
+            return a, C.c_void_p(a.data_ptr()), 1
+        w = np.asarray(w.detach().numpy() if hasattr(w, 'detach') else w)
+        if w.ndim != 1 or w.shape[0] != self.n_data:
+            raise ValueError('%s should hold %d values (one per data row), got shape %s' % (name, self.n_data, w.shape))
+        a = np.ascontiguousarray(w[self._rows], dtype=self.dtype)
+        if a.size == 0:
+            a = np.zeros(1, dtype=self.dtype)
+        return a, _ptr(a), 0
+
+    def _model_out(self, like):
+        """an output model vector where `like` (numpy or torch) lives: (array, pointer, on_device, finish)"""
+        if type(like).__module__.startswith('torch'):
+            import torch
+
+            tdt = torch.float32 if self.dtype == np.float32 else torch.float64
+            if like.device.type == 'cuda':
+                dev = torch.device('cuda', self.device)
+                g = torch.empty(max(self.n_cols, 1), dtype=tdt, device=dev)
+                torch.cuda.current_stream(dev).synchronize()
+                return C.c_void_p(g.data_ptr()), 1, lambda: g[:self.n_cols].to(like.device)
+            g = np.empty(max(self.n_cols, 1), dtype=self.dtype)
+            return _ptr(g), 0, lambda: torch.from_numpy(g[:self.n_cols])
+        g = np.empty(max(self.n_cols, 1), dtype=self.dtype)
+        return _ptr(g), 0, lambda: g[:self.n_cols]
+
+    def hold(self, w=None, field_cotangent=None, return_grad=False, schedule='tiled'):
+        """Solve the adjoint of the cotangent (w, field_cotangent) -- the arguments of vjp -- and keep it on the tape for hvp and newton.
+        return_grad=True returns the gradient as well, with the bits of vjp(w, field_cotangent).  The first hold allocates two
+        (n_events, n_nodes) arrays (nbytes grows by them); a later hold replaces the held cotangent; release() returns the memory."""
+        self._handle()
+        sch = self._schedule(schedule)
+        if w is None and field_cotangent is None:
+            raise ValueError('w and field_cotangent are both None: no cotangent to hold')
+        keep = []
+        pw = pf = None
+        dw = df = 0
+        if w is not None:
+            a, pw, dw = self._row_arg(w, 'w')
+            keep.append(a)
+        if field_cotangent is not None:
+            fc = field_cotangent
+            if type(fc).__module__.startswith('torch') and fc.device.type == 'cuda':
+                import torch
+
+                tdt = torch.float32 if self.dtype == np.float32 else torch.float64
+                a = fc.detach().to(device=torch.device('cuda', self.device), dtype=tdt).contiguous()
+                n, pf, df = a.numel(), C.c_void_p(a.data_ptr()), 1
+            else:
+                a = np.ascontiguousarray(fc.detach().numpy() if hasattr(fc, 'detach') else fc, dtype=self.dtype)
+                n, pf, df = a.size, _ptr(a), 0
+            if n != self.n_events * self.n_nodes:
+                raise ValueError('field_cotangent should hold %d x %d values, got shape %s' % (self.n_events, self.n_nodes, tuple(a.shape)))
+            keep.append(a)
+        like = w if w is not None else field_cotangent
+        pg, dg, finish = self._model_out(like) if return_grad else (None, 0, None)
+        if any(type(a).__module__.startswith('torch') and a.device.type == 'cuda' for a in keep):
+            import torch
+
+            torch.cuda.current_stream(torch.device('cuda', self.device)).synchronize()
+        np_ = C.c_int(0)
+        _lib.check(self._lib.ttcr_fsm_adjoint_hold(self._h, pw, dw, pf, df, pg, dg, sch, C.byref(np_)))
+        self.passes = np_.value
+        self._refresh_nbytes()
+        return finish() if return_grad else None
+
+    def release(self):
+        """Free the held cotangent and its work array (nbytes falls by what the first hold added); hvp and newton then raise until the
+        next hold."""
+        _lib.check(self._lib.ttcr_fsm_adjoint_release(self._handle()))
+        self._refresh_nbytes()
+
+    def _second_order(self, v, row_weight, newton, schedule):
+        self._handle()
+        sch = self._schedule(schedule)
+        va, pv, dv = self._model_arg(v, 'v')
+        ra, pr, dr = self._row_arg(row_weight, 'row_weight') if row_weight is not None else (None, None, 0)
+        pg, dg, finish = self._model_out(v)
+        if dv or dr:
+            import torch
+
+            torch.cuda.current_stream(torch.device('cuda', self.device)).synchronize()
+        pj, pa = C.c_int(0), C.c_int(0)
+        if newton:
+            _lib.check(self._lib.ttcr_fsm_adjoint_newton(self._h, pv, dv, pr, dr, pg, dg, sch, C.byref(pj), C.byref(pa)))
+        else:
+            _lib.check(self._lib.ttcr_fsm_adjoint_hvp(self._h, pv, dv, pg, dg, sch, C.byref(pj), C.byref(pa)))
+        self.passes = (pj.value, pa.value)
+        self._refresh_nbytes()
+        return finish()
+
+    def hvp(self, v, schedule='tiled'):
+        """The second-order term of the held cotangent applied to v:  d/dv of vjp(w, field_cotangent) with the cotangent fixed, i.e.
+        sum_r w_r (d2 tt_r / ds2) v -- what gauss_newton drops from the Hessian of a misfit (w the weighted residual).  n_cols values in,
+        n_cols values out (nodes, or cells on a cell tape), grid dtype.  One tangent and one adjoint relaxation.  Needs hold() first
+        (ValueError otherwise).  Array handling and schedule as in jvp; passes becomes (passes of the jvp, passes of the vjp)."""
+        return self._second_order(v, None, False, schedule)
+
+    def newton(self, v, row_weight=None, schedule='tiled'):
+        """J^T (row_weight * (J v)) + hvp(v) from ONE adjoint relaxation: the full Hessian product of a least-squares misfit whose weighted
+        residual is the held w, at the cost of gauss_newton plus three streaming kernels.  Arguments as gauss_newton; needs hold()."""
+        return self._second_order(v, row_weight, True, schedule)
 
     def _refresh_nbytes(self):
         b = C.c_size_t(0)
