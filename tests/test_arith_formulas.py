@@ -4,25 +4,9 @@ error of ONE update is a few ulp of the increment t - a1 plus the final rounding
 ~1e-6 s RMS over a field.  No device needed: this pins the formulas, the GPU tests pin the kernels."""
 import numpy as np
 
+from arith_reference import update2_fast, update3_fast   # (the restated solvers live with the restated solve)
+
 f32 = np.float32
-
-
-def update3_fast(ax, ay, az, s, dx):
-    a = np.sort(np.stack([ax, ay, az]), axis=0)
-    a1, a2, a3 = a[0], a[1], a[2]
-    fh = (s * dx).astype(f32)
-    rfh = (f32(1) / fh).astype(f32)
-    p2 = ((a2 - a1) * rfh).astype(f32); p3 = ((a3 - a1) * rfh).astype(f32)
-    e = (p3 - p2).astype(f32)
-    q = (p3.astype(np.float64) * p3 + (e * e).astype(f32)).astype(f32)               # fma(p3, p3, e*e)
-    n2 = (f32(2) - p2.astype(np.float64) * p2).astype(f32)                          # fma(-p2, p2, 2)
-    s3 = q < 1
-    disc = np.where(s3, ((n2 + f32(1)).astype(f32) - q).astype(f32), n2)
-    root = np.sqrt(np.maximum(disc, 0).astype(f32)).astype(f32)
-    psum = np.where(s3, (p2 + p3).astype(f32), p2)
-    w = (fh * np.where(s3, f32(1.0 / 3.0), f32(0.5))).astype(f32)
-    t = (w.astype(np.float64) * (psum + root).astype(f32) + a1).astype(f32)           # fma(w, psum + root, a1)
-    return np.where(p2 < 1, t, (a1 + fh).astype(f32))
 
 
 def update3_ref64(ax, ay, az, s, dx):
@@ -33,16 +17,6 @@ def update3_ref64(ax, ay, az, s, dx):
     t2 = 0.5 * (a1 + a2 + np.sqrt(np.maximum(2 * fh * fh - (a1 - a2) ** 2, 0)))
     t3 = (a1 + a2 + a3 + np.sqrt(np.maximum(3 * fh * fh - (a1 - a2) ** 2 - (a1 - a3) ** 2 - (a2 - a3) ** 2, 0))) / 3
     return np.where(t1 > a2, np.where(t2 > a3, t3, t2), t1), fh
-
-
-def update2_fast(a, b, s, dx):
-    fh = (s * dx).astype(f32)
-    d = (a - b).astype(f32)
-    t1 = (np.minimum(a, b) + fh).astype(f32)
-    disc = ((f32(2) * fh).astype(np.float64) * fh - (d * d).astype(f32)).astype(f32)   # fma(2 fh, fh, -(d*d))
-    root = np.sqrt(np.maximum(disc, 0)).astype(f32)
-    t2 = (f32(0.5) * ((a + b).astype(f32) + root).astype(f32)).astype(f32)
-    return np.where(np.abs(d) >= fh, t1, t2)
 
 
 def test_update3_fast_is_a_few_ulp_of_the_increment_off():

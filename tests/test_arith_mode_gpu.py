@@ -15,6 +15,11 @@ opt-in mode to the contract, at the same sizes:
 RMS over ALL nodes of a field, in float64; the tolerance is TOL = 1e-5 s as the contract states it.  Iteration counts are reported next to the
 oracle's and must agree on these models (the stopping rule sees changes of ~1e-7 relative).  The mode must also leave the default path alone:
 switching it off again gives the bit-identical default fields.
+
+An RMS over 1e8 nodes cannot see a local fault (a halo column, a chunk seam, a thin axis), and these sizes launch only half of the AR = 1
+kernels: tests/test_arith_small_gpu.py holds the mode to a PER-NODE bar on grids of 30 - 70 nodes per axis (patch remainders, thin grids,
+cell grids, batches, dx != dz, units), launches every instantiation of fsm_fast.hip once and runs a seeded sweep; the bar is calibrated on
+the CPU by tests/test_arith_reference.py (tests/arith_reference.py restates a whole tolerance-mode solve in numpy).
 """
 import os
 from concurrent.futures import ThreadPoolExecutor
