@@ -446,6 +446,26 @@ int ttcr_fsm_tape_free(ttcr_fsm_tape* t);
  *   streaming kernels.  The first hvp or newton allocates what the first jvp allocates.
  *   On a cell tape v and out hold n_cells values:  hvp(v) = A^T (node hvp(A v)), likewise newton, A and A^T as for jvp and vjp.
  *   Without a held cotangent both return TTCR_ERR_VALUE (the message says so) before any device call.
+ * Block products: the three products above for n_cols >= 1 model vectors per call.  ds, v, grad and out hold n_cols x
+ *   n_params values (n_params of ttcr_fsm_adjoint_model), w and dtt n_cols x n_rows values in tape row order, dfields n_cols x n_events x
+ *   n_nodes values, column k at k times the length of one column; row_weight holds rw_cols x n_rows values, rw_cols = 0 (none, row_weight
+ *   is ignored), 1 (one set shared by the columns) or n_cols (one set per column).  Under schedule 0 the columns are relaxed in groups of
+ *   four, the four values of a node adjacent in memory and in LDS: masks, upwind choice, differences, D and the tile stamps are read and
+ *   formed once per node, and per column the expressions of the one-column calls are evaluated in their order -- the jvp chain starts from
+ *   the own term, the seeds and the gradient from +0, the vjp chain from the seed.  The last group is padded with +0 columns.  Schedule 1
+ *   runs the columns one by one through the Jacobi baseline.  Column k of every output has the bits of the one-column call
+ *   (ttcr_fsm_adjoint_jvp, _vjp with field_cot NULL, _gn) on column k, whatever n_cols, the position of the column, the schedule, the slots
+ *   and the devices of the grid the tape came from.  *passes: the passes of all groups summed.  No floating-point atomics.  On a cell tape
+ *   A and A^T are applied column by column with the kernels of the one-column calls.
+ *   The first block call allocates the work arrays: the seeds of four columns, 4 n_events n_nodes elem bytes; lam / mu of four columns, as
+ *   much again unless a ttcr_fsm_adjoint_jvp_source call with n_cols > 1 allocated that array before; staging for one group, (4 n_params +
+ *   8 n_rows) elem bytes and, on a cell tape, 4 n_nodes elem bytes; and what the first jvp allocates if no jvp came before.
+ *   ttcr_fsm_adjoint_bytes reports them from then on; TTCR_ERR_DEVICE with the byte count if an allocation fails.
+ *   ttcr_fsm_adjoint_block_release frees them (ttcr_fsm_adjoint_bytes falls by the figure the block call added; the next block call
+ *   allocates again), ttcr_fsm_adjoint_free too; ttcr_fsm_adjoint_release and a held lam are left alone, and a block call leaves them alone.
+ *   Not offered per block: hvp / newton, field cotangents, source-point gradients.
+ *   Argument errors -- n_cols < 1, an unknown schedule, a NULL input (ds, w, v) or output (dtt and dfields both NULL, grad, out), rw_cols
+ *   not 0, 1 or n_cols, a NULL row_weight with rw_cols != 0, a NULL tape -- return TTCR_ERR_VALUE before any device call.
  * Cell tapes.  ttcr_fsm_raytrace_multi_adjoint_cells: the same call for a 3-D grid with slowness defined for CELLS and
  *   without the WENO stage (a node grid: TTCR_ERR_VALUE, the message names ttcr_fsm_raytrace_multi_adjoint; 2-D and WENO grids:
  *   TTCR_ERR_UNSUPPORTED; ttcr_fsm_raytrace_multi_adjoint itself keeps refusing cell grids).  The solver works on the node slowness
@@ -491,6 +511,13 @@ int ttcr_fsm_adjoint_hvp(ttcr_fsm_adjoint* t, const void* v, int v_on_device, vo
                          int* passes_vjp);
 int ttcr_fsm_adjoint_newton(ttcr_fsm_adjoint* t, const void* v, int v_on_device, const void* row_weight, int rw_on_device, void* out,
                             int out_on_device, int schedule, int* passes_jvp, int* passes_vjp);
+int ttcr_fsm_adjoint_jvp_block(const ttcr_fsm_adjoint* t, int n_cols, const void* ds, int ds_on_device, void* dtt, int dtt_on_device,
+                               void* dfields, int df_on_device, int schedule, int* passes);
+int ttcr_fsm_adjoint_vjp_block(const ttcr_fsm_adjoint* t, int n_cols, const void* w, int w_on_device, void* grad, int grad_on_device,
+                               int schedule, int* passes);
+int ttcr_fsm_adjoint_gn_block(const ttcr_fsm_adjoint* t, int n_cols, const void* v, int v_on_device, const void* row_weight,
+                              int rw_cols, int rw_on_device, void* out, int out_on_device, int schedule, int* passes_jvp, int* passes_vjp);
+int ttcr_fsm_adjoint_block_release(ttcr_fsm_adjoint* t);
 int ttcr_fsm_adjoint_free(ttcr_fsm_adjoint* t);
 
 /* Replaces: Grid2D::raytrace(Tx, t0, Rx, traveltimes, l_data, threadNo) (ttcr/Grid2D.h:616-640) and the overload with r_data

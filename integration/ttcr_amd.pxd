@@ -100,6 +100,15 @@ cdef extern from "ttcr_amd.h" nogil:
                              int* passes_jvp, int* passes_vjp)
     int ttcr_fsm_adjoint_newton(ttcr_fsm_adjoint* t, const void* v, int v_on_device, const void* row_weight, int rw_on_device,
                                 void* out, int out_on_device, int schedule, int* passes_jvp, int* passes_vjp)
+    # block products: n_cols model vectors per call, relaxed in groups of four; column k has the bits of the one-column call
+    int ttcr_fsm_adjoint_jvp_block(const ttcr_fsm_adjoint* t, int n_cols, const void* ds, int ds_on_device, void* dtt, int dtt_on_device,
+                                   void* dfields, int df_on_device, int schedule, int* passes)
+    int ttcr_fsm_adjoint_vjp_block(const ttcr_fsm_adjoint* t, int n_cols, const void* w, int w_on_device, void* grad, int grad_on_device,
+                                   int schedule, int* passes)
+    int ttcr_fsm_adjoint_gn_block(const ttcr_fsm_adjoint* t, int n_cols, const void* v, int v_on_device, const void* row_weight,
+                                  int rw_cols, int rw_on_device, void* out, int out_on_device, int schedule, int* passes_jvp,
+                                  int* passes_vjp)
+    int ttcr_fsm_adjoint_block_release(ttcr_fsm_adjoint* t)
     int ttcr_fsm_adjoint_free(ttcr_fsm_adjoint* t)
     int ttcr_fsm_slot_m_size(const ttcr_fsm_grid* g, int slot, size_t* n_rows, size_t* nnz)
     int ttcr_fsm_get_slot_m(const ttcr_fsm_grid* g, int slot, long long* row_off, long long* j, void* v)

@@ -93,6 +93,10 @@ SYMBOLS = {
     "ttcr_fsm_adjoint_release": (_I, [_P]),
     "ttcr_fsm_adjoint_hvp": (_I, [_P, _P, _I, _P, _I, _I, C.POINTER(_I), C.POINTER(_I)]),
     "ttcr_fsm_adjoint_newton": (_I, [_P, _P, _I, _P, _I, _P, _I, _I, C.POINTER(_I), C.POINTER(_I)]),
+    "ttcr_fsm_adjoint_jvp_block": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, C.POINTER(_I)]),
+    "ttcr_fsm_adjoint_vjp_block": (_I, [_P, _I, _P, _I, _P, _I, _I, C.POINTER(_I)]),
+    "ttcr_fsm_adjoint_gn_block": (_I, [_P, _I, _P, _I, _P, _I, _I, _P, _I, _I, C.POINTER(_I), C.POINTER(_I)]),
+    "ttcr_fsm_adjoint_block_release": (_I, [_P]),
     "ttcr_fsm_adjoint_free": (_I, [_P]),
     "ttcr_fsm_raytrace_multi_l": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I]),
     "ttcr_fsm_multi_l_size": (_I, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),

@@ -1,5 +1,6 @@
 // ttcr_amd/csrc/fsm_adjoint.hip -- translation unit of the field tape's kernels (coupling, seeds, relaxation, gradient; the forward-mode
-// tangent: relaxation, receiver rows; cell tapes: the transpose of the cell-to-node averaging); see fsm_adjoint_api.h and DESIGN.md 6b, 6c, 6e.  Compiled with -ffp-contract=off like every other unit: each product, difference, quotient and sum
+// tangent: relaxation, receiver rows; cell tapes: the transpose of the cell-to-node averaging; block products: both relaxations, seeds and gradient
+// for four columns at once); see fsm_adjoint_api.h and DESIGN.md 6b, 6c, 6e, 6g.  Compiled with -ffp-contract=off like every other unit: each product, difference, quotient and sum
 // below is rounded on its own, in the order the definition writes them.
 #include "fsm_adjoint_api.h"
 #include "fsm_kernels.h"   // fsm_cells_to_nodes3d: the forward direction of a cell tape is set_slowness's own kernel
@@ -668,6 +669,294 @@ __global__ void src_unpack_kernel(const T* __restrict__ mu, size_t en, int n_col
         out[i] = mu[(i % en) * K + i / en];
 }
 
+// ---- block products: K model vectors per relaxation, the K values of a node adjacent (SrcVec) in memory and in LDS.  What a
+// step computes once per node -- masks, upwind choice, differences, D -- serves the K columns; per column the expressions and their order are
+// those of the one-column kernels above, so every column has the bits of the one-column call.
+
+// g[j][k] = from +0, over the stencil entries of node j in row order: acc = fl(acc + fl(w[k][row] * weight)): adj_seed_rows_kernel's serial
+// chain, K chains per thread (+0 in the columns past n_cols).  g is +0 everywhere before the launch.
+template <typename T, int K>
+__global__ void adjk_seed_rows_kernel(const long long* __restrict__ key, const int* __restrict__ row, const T* __restrict__ wt, size_t n,
+                                      const T* __restrict__ w, size_t n_rows, int n_cols, SrcVec<T, K>* __restrict__ g) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long long j = key[i];
+    if (i > 0 && key[i - 1] == j) return;
+    SrcVec<T, K> a;
+#pragma unroll
+    for (int k = 0; k < K; ++k) a.v[k] = 0;
+    for (size_t r = i; r < n && key[r] == j; ++r) {
+        const T wr = wt[r];
+        const size_t rr = (size_t)row[r];
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            if (k < n_cols) a.v[k] = a.v[k] + w[(size_t)k * n_rows + rr] * wr;
+    }
+    g[j] = a;
+}
+
+// lam[j][k] = g[j][k] + sum over the flagged neighbours, order x-, x+, y-, y+, z-, z+, of fl(fl(lam[n][k] * (T[n] - T[j])) / D[n])
+#define ADJK_TERM(bit, off)                                                  \
+    if (in & (1u << (bit))) {                                                \
+        const T c = F[(off)] - tj;                                           \
+        const T dn = Dn[(off)];                                              \
+        const SrcVec<T, K> u = L[(off)];                                     \
+        _Pragma("unroll") for (int k = 0; k < K; ++k) acc.v[k] = acc.v[k] + (u.v[k] * c) / dn; \
+    }
+
+// Tiled K-column relaxation of the adjoint: adj_tiled_kernel with the tangent's tile edge (lam of K columns, T and D of a tile with its
+// halo take (K + 2) (edge + 2)^3 elements of LDS: 40.5 KiB fp32, 46.9 KiB fp64 for K = 4), its stamps, run decision and passes.  The
+// in-mask, T[n] - T[j] and D[n] are read and formed once per coupling, the K values of lam[n] come in one access.
+template <typename T, int K, int TI>
+__global__ __launch_bounds__(ADJ_THREADS) void adjk_tiled_kernel(const T* __restrict__ fields, const T* __restrict__ D,
+                                                                  const unsigned char* __restrict__ inmask,
+                                                                  const SrcVec<T, K>* __restrict__ g, SrcVec<T, K>* lam, AdjGeom<T> geo, int ntx,
+                                                                  int nty, int ntz, int* stamps, int pass, int* __restrict__ cur) {
+    constexpr int TH = TI + 2, NH = TH * TH * TH, NI = TI * TI * TI, NPT = (NI + ADJ_THREADS - 1) / ADJ_THREADS;
+    __shared__ SrcVec<T, K> sL[NH];
+    __shared__ T sF[NH], sD[NH];
+    const int e = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
+    const int tx = tile % ntx, ty = (tile / ntx) % nty, tz = tile / (ntx * nty);
+    int* st = stamps + (size_t)e * ntx * nty * ntz;
+    if (pass > 0) {
+        const int since = pass - 1;
+        bool run = false;
+        if (tx > 0) run |= st[tile - 1] >= since;
+        if (tx < ntx - 1) run |= st[tile + 1] >= since;
+        if (ty > 0) run |= st[tile - ntx] >= since;
+        if (ty < nty - 1) run |= st[tile + ntx] >= since;
+        if (tz > 0) run |= st[tile - ntx * nty] >= since;
+        if (tz < ntz - 1) run |= st[tile + ntx * nty] >= since;
+        if (!__syncthreads_or(run)) return;   // (one decision for the workgroup, as in adj_tiled_kernel)
+    }
+    const size_t base = (size_t)e * geo.nn;
+    const int x0 = tx * TI - 1, y0 = ty * TI - 1, z0 = tz * TI - 1;
+    SrcVec<T, K> zero;
+#pragma unroll
+    for (int k = 0; k < K; ++k) zero.v[k] = 0;
+    for (int h = tid; h < NH; h += ADJ_THREADS) {
+        const int x = x0 + h % TH, y = y0 + (h / TH) % TH, z = z0 + h / (TH * TH);
+        const bool inside = x >= 0 && x < geo.nnx && y >= 0 && y < geo.nny && z >= 0 && z < geo.nnz;
+        const size_t idx = base + ((size_t)(inside ? z : 0) * geo.nny + (inside ? y : 0)) * geo.nnx + (inside ? x : 0);
+        SrcVec<T, K> v = zero;
+        if (inside) v = lam[idx];
+        sL[h] = v;
+        sF[h] = inside ? fields[idx] : (T)0;
+        sD[h] = inside ? D[idx] : (T)1;
+    }
+    // the interior nodes of this thread: LDS index, seeds, inflow mask (hq < 0: outside the grid)
+    int hq[NPT];
+    SrcVec<T, K> gq[NPT];
+    unsigned inq[NPT];
+    size_t mq[NPT];
+    for (int q = 0; q < NPT; ++q) {
+        const int n = tid + q * ADJ_THREADS;
+        hq[q] = -1; gq[q] = zero; inq[q] = 0; mq[q] = 0;
+        if (n >= NI) continue;
+        const int lx = n % TI, ly = (n / TI) % TI, lz = n / (TI * TI);
+        const int x = x0 + 1 + lx, y = y0 + 1 + ly, z = z0 + 1 + lz;
+        if (x >= geo.nnx || y >= geo.nny || z >= geo.nnz) continue;
+        hq[q] = ((lz + 1) * TH + ly + 1) * TH + lx + 1;
+        mq[q] = base + ((size_t)z * geo.nny + y) * geo.nnx + x;
+        gq[q] = g[mq[q]];
+        inq[q] = inmask[mq[q]];
+    }
+    __syncthreads();
+    bool tile_changed = false;
+    for (int it = 0; it <= NI; ++it) {
+        SrcVec<T, K> nv[NPT];
+        for (int q = 0; q < NPT; ++q) {
+            if (hq[q] < 0) continue;
+            const SrcVec<T, K>* L = sL + hq[q];
+            const T* F = sF + hq[q];
+            const T* Dn = sD + hq[q];
+            const unsigned in = inq[q];
+            const T tj = F[0];
+            SrcVec<T, K> acc = gq[q];
+            ADJK_TERM(0, -1) ADJK_TERM(1, 1) ADJK_TERM(2, -TH) ADJK_TERM(3, TH) ADJK_TERM(4, -TH * TH) ADJK_TERM(5, TH * TH)
+            nv[q] = acc;
+        }
+        __syncthreads();   // every read of this step is done
+        int ch = 0;
+        for (int q = 0; q < NPT; ++q) {
+            if (hq[q] < 0) continue;
+            const SrcVec<T, K> old = sL[hq[q]];
+            bool diff = false;
+#pragma unroll
+            for (int k = 0; k < K; ++k) diff |= !same_bits(nv[q].v[k], old.v[k]);
+            if (diff) { sL[hq[q]] = nv[q]; ch = 1; }
+        }
+        if (!__syncthreads_or(ch)) break;
+        tile_changed = true;
+    }
+    if (!tile_changed) return;
+    for (int q = 0; q < NPT; ++q)
+        if (hq[q] >= 0) lam[mq[q]] = sL[hq[q]];
+    if (tid == 0) { st[tile] = pass; cur[e] = 1; }
+}
+#undef ADJK_TERM
+
+// grad[k][m] = sum over the events, ascending, from +0, of  d * lam[.][k] (frozen)  or  fl(fl(lam[.][k] * fl(dx * fl(s * dx))) / D):
+// adj_grad_kernel per column, D, the frozen mark and the own factor read once
+template <typename T, int K>
+__global__ void adjk_grad_kernel(const SrcVec<T, K>* __restrict__ lam, const T* __restrict__ D, const unsigned char* __restrict__ frozen,
+                                 const T* __restrict__ s, AdjGeom<T> geo, size_t n_events, int n_cols, T* __restrict__ grad) {
+    const size_t m = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (m >= geo.nn) return;
+    const T c = geo.dx * (s[m] * geo.dx);
+    SrcVec<T, K> acc;
+#pragma unroll
+    for (int k = 0; k < K; ++k) acc.v[k] = 0;
+    for (size_t e = 0; e < n_events; ++e) {
+        const size_t idx = e * geo.nn + m;
+        const SrcVec<T, K> l = lam[idx];
+        const T d = D[idx];
+        const bool fz = frozen[idx] != 0;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const T v = fz ? d * l.v[k] : (l.v[k] * c) / d;
+            acc.v[k] = acc.v[k] + v;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+        if (k < n_cols) grad[(size_t)k * geo.nn + m] = acc.v[k];
+}
+
+// Tiled K-column relaxation of the tangent with its slowness term: src_tiled_kernel's tiles, staging and registers plus tan_tiled_kernel's
+// own term per column -- fl(d_m * ds[k][m]) for a frozen node (no axis, divisor 1: exact), fl(fl(dx * fl(s[m] * dx)) * ds[k][m]) for every
+// other one, the start of the chain over the active axes (never +0: +0 + (-0) is +0).  ds holds n_cols columns of nn values; the columns
+// past n_cols are +0.
+template <typename T, int K, int TI>
+__global__ __launch_bounds__(ADJ_THREADS) void tank_tiled_kernel(const T* __restrict__ fields, const T* __restrict__ D,
+                                                                  const unsigned char* __restrict__ frozen, const T* __restrict__ s,
+                                                                  const T* __restrict__ ds, int n_cols, SrcVec<T, K>* mu, AdjGeom<T> geo,
+                                                                  int ntx, int nty, int ntz, int* stamps, int pass, int* __restrict__ cur) {
+    constexpr int TH = TI + 2, NH = TH * TH * TH, NI = TI * TI * TI, NPT = (NI + ADJ_THREADS - 1) / ADJ_THREADS;
+    __shared__ SrcVec<T, K> sL[NH];
+    __shared__ T sF[NH];
+    const int e = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
+    const int tx = tile % ntx, ty = (tile / ntx) % nty, tz = tile / (ntx * nty);
+    int* st = stamps + (size_t)e * ntx * nty * ntz;
+    if (pass > 0) {
+        const int since = pass - 1;
+        bool run = false;
+        if (tx > 0) run |= st[tile - 1] >= since;
+        if (tx < ntx - 1) run |= st[tile + 1] >= since;
+        if (ty > 0) run |= st[tile - ntx] >= since;
+        if (ty < nty - 1) run |= st[tile + ntx] >= since;
+        if (tz > 0) run |= st[tile - ntx * nty] >= since;
+        if (tz < ntz - 1) run |= st[tile + ntx * nty] >= since;
+        if (!__syncthreads_or(run)) return;   // (one decision for the workgroup, as in tan_tiled_kernel)
+    }
+    const T inf = std::numeric_limits<T>::infinity();
+    const size_t base = (size_t)e * geo.nn;
+    const int x0 = tx * TI - 1, y0 = ty * TI - 1, z0 = tz * TI - 1;
+    SrcVec<T, K> zero;
+#pragma unroll
+    for (int k = 0; k < K; ++k) zero.v[k] = 0;
+    for (int h = tid; h < NH; h += ADJ_THREADS) {
+        const int x = x0 + h % TH, y = y0 + (h / TH) % TH, z = z0 + h / (TH * TH);
+        const bool inside = x >= 0 && x < geo.nnx && y >= 0 && y < geo.nny && z >= 0 && z < geo.nnz;
+        const size_t idx = base + ((size_t)(inside ? z : 0) * geo.nny + (inside ? y : 0)) * geo.nnx + (inside ? x : 0);
+        SrcVec<T, K> v = zero;
+        if (inside) v = mu[idx];
+        sL[h] = v;
+        sF[h] = inside ? fields[idx] : inf;
+    }
+    __syncthreads();
+    // the interior nodes of this thread (hq < 0: outside the grid)
+    int hq[NPT];
+    unsigned cq[NPT];
+    SrcVec<T, K> bq[NPT];
+    T dq[NPT], c0[NPT], c1[NPT], c2[NPT];
+    for (int q = 0; q < NPT; ++q) {
+        const int n = tid + q * ADJ_THREADS;
+        hq[q] = -1; cq[q] = 0; bq[q] = zero; dq[q] = 1; c0[q] = 0; c1[q] = 0; c2[q] = 0;
+        if (n >= NI) continue;
+        const int lx = n % TI, ly = (n / TI) % TI, lz = n / (TI * TI);
+        const int x = x0 + 1 + lx, y = y0 + 1 + ly, z = z0 + 1 + lz;
+        if (x >= geo.nnx || y >= geo.nny || z >= geo.nnz) continue;
+        const int h = ((lz + 1) * TH + ly + 1) * TH + lx + 1;
+        const size_t m = ((size_t)z * geo.nny + y) * geo.nnx + x;
+        hq[q] = h;
+        const bool fz = frozen[base + m] != 0;
+        const T own = fz ? D[base + m] : geo.dx * (s[m] * geo.dx);
+#pragma unroll
+        for (int k = 0; k < K; ++k) bq[q].v[k] = own * (k < n_cols ? ds[(size_t)k * geo.nn + m] : (T)0);
+        if (fz) continue;
+        dq[q] = D[base + m];
+        const T t = sF[h];
+        unsigned code = 0;
+        {
+            const T lo = sF[h - 1], hi = sF[h + 1];
+            const bool up = hi < lo;
+            const T a = up ? hi : lo;
+            if (a < t) { code |= up ? 3u : 1u; c0[q] = t - a; }
+        }
+        {
+            const T lo = sF[h - TH], hi = sF[h + TH];
+            const bool up = hi < lo;
+            const T a = up ? hi : lo;
+            if (a < t) { code |= up ? 12u : 4u; c1[q] = t - a; }
+        }
+        {
+            const T lo = sF[h - TH * TH], hi = sF[h + TH * TH];
+            const bool up = hi < lo;
+            const T a = up ? hi : lo;
+            if (a < t) { code |= up ? 48u : 16u; c2[q] = t - a; }
+        }
+        cq[q] = code;
+    }
+    bool tile_changed = false;
+    for (int it = 0; it <= NI; ++it) {
+        SrcVec<T, K> nv[NPT];
+        for (int q = 0; q < NPT; ++q) {
+            if (hq[q] < 0) continue;
+            const SrcVec<T, K>* L = sL + hq[q];
+            const unsigned code = cq[q];
+            SrcVec<T, K> acc = bq[q];
+            if (code & 1u) {
+                const SrcVec<T, K> u = L[(code & 2u) ? 1 : -1];
+#pragma unroll
+                for (int k = 0; k < K; ++k) acc.v[k] = acc.v[k] + u.v[k] * c0[q];
+            }
+            if (code & 4u) {
+                const SrcVec<T, K> u = L[(code & 8u) ? TH : -TH];
+#pragma unroll
+                for (int k = 0; k < K; ++k) acc.v[k] = acc.v[k] + u.v[k] * c1[q];
+            }
+            if (code & 16u) {
+                const SrcVec<T, K> u = L[(code & 32u) ? TH * TH : -TH * TH];
+#pragma unroll
+                for (int k = 0; k < K; ++k) acc.v[k] = acc.v[k] + u.v[k] * c2[q];
+            }
+#pragma unroll
+            for (int k = 0; k < K; ++k) nv[q].v[k] = acc.v[k] / dq[q];
+        }
+        __syncthreads();   // every read of this step is done
+        int ch = 0;
+        for (int q = 0; q < NPT; ++q) {
+            if (hq[q] < 0) continue;
+            const SrcVec<T, K> old = sL[hq[q]];
+            bool diff = false;
+#pragma unroll
+            for (int k = 0; k < K; ++k) diff |= !same_bits(nv[q].v[k], old.v[k]);
+            if (diff) { sL[hq[q]] = nv[q]; ch = 1; }
+        }
+        if (!__syncthreads_or(ch)) break;
+        tile_changed = true;
+    }
+    if (!tile_changed) return;
+    for (int q = 0; q < NPT; ++q) {
+        if (hq[q] < 0) continue;
+        const int n = tid + q * ADJ_THREADS;
+        const int x = x0 + 1 + n % TI, y = y0 + 1 + (n / TI) % TI, z = z0 + 1 + n / (TI * TI);
+        mu[base + ((size_t)z * geo.nny + y) * geo.nnx + x] = sL[hq[q]];
+    }
+    if (tid == 0) { st[tile] = pass; cur[e] = 1; }
+}
+
 // gsrc[q][0] = from +0, over the frozen nodes of point q in ascending node index: acc = fl(acc + lam[m]);
 // gsrc[q][1 + a] = the same chain of fl(lam[m] * fl(s[m] * c[m][a])).  One thread per point; no atomics.
 template <typename T>
@@ -859,6 +1148,9 @@ void AdjTapeDev::release() {
     dev_free(rw_off); dev_free(rw_key); dev_free(rw_w); dev_free(rw_tmp); dev_free(tan_stamps);
     dev_free(src_off); dev_free(src_pt); dev_free(src_key); dev_free(src_node); dev_free(src_c); dev_free(src_io); dev_free(src_rows);
     dev_free(mu4); dev_free(mu4b); dev_free(cell_tmp); dev_free(hold_lam); dev_free(hess_dd);
+    dev_free(g4); dev_free(blk_model); dev_free(blk_nodes); dev_free(blk_rows); dev_free(blk_rw);
+    blk_owns_mu4 = false;
+    blk_bytes = 0;
     held = false;
     if (stream) (void)hipStreamDestroy(stream);
     stream = nullptr;
@@ -1393,6 +1685,156 @@ int adj_vjp_source(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, T* d_g
     return passes;
 }
 
+
+// ---- block products
+size_t adj_block_bytes(const AdjTapeDev& t) {
+    return (t.mu4 ? 1 : 2) * adj_src_column_bytes(t) + 4 * t.n_model() * t.elem + (t.cells ? 4 * t.nn * t.elem : 0) + 8 * t.n_rows * t.elem;
+}
+
+template <typename T>
+void adj_block_prepare(AdjTapeDev& t) {
+    ADJ_CHECK(hipSetDevice(t.device));
+    adj_jvp_prepare<T>(t);   // (the stencil in row order and the stamps of the tangent tiles)
+    if (t.g4) return;
+    Alloc alloc{t, adj_block_bytes(t)};
+    const size_t before = t.total_bytes;
+    const bool had_mu4 = t.mu4 != nullptr;
+    try {
+        alloc(t.g4, adj_src_column_bytes(t));
+        if (!had_mu4) alloc(t.mu4, adj_src_column_bytes(t));
+        alloc(t.blk_model, 4 * t.n_model() * t.elem);
+        if (t.cells) alloc(t.blk_nodes, 4 * t.nn * t.elem);
+        alloc(t.blk_rows, 4 * t.n_rows * t.elem);
+        alloc(t.blk_rw, 4 * t.n_rows * t.elem);
+    } catch (...) {
+        dev_free(t.g4); dev_free(t.blk_model); dev_free(t.blk_nodes); dev_free(t.blk_rows); dev_free(t.blk_rw);
+        if (!had_mu4) dev_free(t.mu4);
+        t.total_bytes = before;
+        throw;
+    }
+    t.blk_owns_mu4 = !had_mu4;
+    t.blk_bytes = t.total_bytes - before;
+}
+
+void adj_block_release(AdjTapeDev& t) {
+    if (!t.g4) return;
+    (void)hipSetDevice(t.device);
+    if (t.stream) (void)hipStreamSynchronize(t.stream);
+    dev_free(t.g4); dev_free(t.blk_model); dev_free(t.blk_nodes); dev_free(t.blk_rows); dev_free(t.blk_rw);
+    if (t.blk_owns_mu4) dev_free(t.mu4);
+    t.blk_owns_mu4 = false;
+    t.total_bytes -= t.blk_bytes;
+    t.blk_bytes = 0;
+}
+
+template <typename T>
+int adj_jvp_block(AdjTapeDev& t, const T* d_ds, int n_cols, T* d_dtt, T* d_dfields, int schedule) {
+    ADJ_CHECK(hipSetDevice(t.device));
+    adj_block_prepare<T>(t);
+    const size_t E = t.n_events, en = E * t.nn;
+    if (schedule != 0) {   // the Jacobi baseline, column by column
+        int passes = 0;
+        for (int k = 0; k < n_cols; ++k)
+            passes += adj_jvp<T>(t, d_ds + (size_t)k * t.n_model(), d_dtt ? d_dtt + (size_t)k * t.n_rows : nullptr,
+                                 d_dfields ? d_dfields + (size_t)k * en : nullptr, schedule);
+        return passes;
+    }
+    constexpr int K = 4;
+    using V = SrcVec<T, K>;
+    hipStream_t s = t.stream;
+    const AdjGeom<T> geo{t.nnx, t.nny, t.nnz, t.nn, (T)t.dx};
+    if (t.cells) {   // column by column, the node perturbation set_slowness would compute from the cell perturbation
+        for (int k = 0; k < n_cols; ++k) adj_cells_to_nodes<T>(t, d_ds + (size_t)k * t.nc, (T*)t.blk_nodes + (size_t)k * t.nn);
+        d_ds = (const T*)t.blk_nodes;
+    }
+    V* mu = (V*)t.mu4;
+    int passes = 0;
+    if (en > 0) {
+        ADJ_CHECK(hipMemsetAsync(mu, 0, en * sizeof(V), s));   // (+0: any start reaches the fixed point)
+        ADJ_CHECK(hipMemsetAsync(t.tan_stamps, 0xFF, E * t.n_tan_tiles * sizeof(int), s));
+        constexpr int ed = TanTile<T>::edge;
+        const int ntx = (t.nnx + ed - 1) / ed, nty = (t.nny + ed - 1) / ed, ntz = (t.nnz + ed - 1) / ed;
+        const unsigned tiles = (unsigned)t.n_tan_tiles;
+        passes = relax_to_fixed_point(t, "block tangent", [&](int pass, const int*, int* cur) {
+            tank_tiled_kernel<T, K, ed><<<dim3(tiles, (unsigned)E), ADJ_THREADS, 0, s>>>((const T*)t.fields, (const T*)t.D, t.frozen,
+                                                                                        (const T*)t.slowness, d_ds, n_cols, mu, geo, ntx, nty,
+                                                                                        ntz, t.tan_stamps, pass, cur);
+        });
+    }
+    if (d_dtt && t.n_rows > 0) {
+        src_rows_kernel<T, K><<<blocks_for(t.n_rows * (size_t)n_cols), ADJ_THREADS, 0, s>>>(t.rw_off, t.rw_key, (const T*)t.rw_w, t.n_rows,
+                                                                                           n_cols, (const T*)mu, d_dtt);
+        ADJ_CHECK(hipGetLastError());
+    }
+    if (d_dfields && en > 0) {
+        src_unpack_kernel<T, K><<<std::min(blocks_for(en * (size_t)n_cols), 65536u), ADJ_THREADS, 0, s>>>((const T*)mu, en, n_cols, d_dfields);
+        ADJ_CHECK(hipGetLastError());
+    }
+    return passes;
+}
+
+template <typename T>
+int adj_vjp_block(AdjTapeDev& t, const T* d_w, int n_cols, T* d_grad, int schedule) {
+    ADJ_CHECK(hipSetDevice(t.device));
+    adj_block_prepare<T>(t);
+    const size_t E = t.n_events, en = E * t.nn;
+    if (schedule != 0) {   // the Jacobi baseline, column by column
+        int passes = 0;
+        for (int k = 0; k < n_cols; ++k)
+            passes += adj_vjp<T>(t, d_w + (size_t)k * t.n_rows, nullptr, d_grad + (size_t)k * t.n_model(), schedule);
+        return passes;
+    }
+    constexpr int K = 4;
+    using V = SrcVec<T, K>;
+    hipStream_t s = t.stream;
+    const AdjGeom<T> geo{t.nnx, t.nny, t.nnz, t.nn, (T)t.dx};
+    V* g = (V*)t.g4;
+    V* lam = (V*)t.mu4;
+    int passes = 0;
+    if (en > 0) {
+        ADJ_CHECK(hipMemsetAsync(g, 0, en * sizeof(V), s));
+        if (t.n_seed > 0) {
+            adjk_seed_rows_kernel<T, K><<<blocks_for(t.n_seed), ADJ_THREADS, 0, s>>>(t.sd_key, t.sd_row, (const T*)t.sd_w, t.n_seed, d_w,
+                                                                                    t.n_rows, n_cols, g);
+            ADJ_CHECK(hipGetLastError());
+        }
+        ADJ_CHECK(hipMemcpyAsync(lam, g, en * sizeof(V), hipMemcpyDeviceToDevice, s));
+        ADJ_CHECK(hipMemsetAsync(t.tan_stamps, 0xFF, E * t.n_tan_tiles * sizeof(int), s));
+        constexpr int ed = TanTile<T>::edge;
+        const int ntx = (t.nnx + ed - 1) / ed, nty = (t.nny + ed - 1) / ed, ntz = (t.nnz + ed - 1) / ed;
+        const unsigned tiles = (unsigned)t.n_tan_tiles;
+        passes = relax_to_fixed_point(t, "block adjoint", [&](int pass, const int*, int* cur) {
+            adjk_tiled_kernel<T, K, ed><<<dim3(tiles, (unsigned)E), ADJ_THREADS, 0, s>>>((const T*)t.fields, (const T*)t.D, t.inmask, g, lam, geo,
+                                                                                        ntx, nty, ntz, t.tan_stamps, pass, cur);
+        });
+    }
+    if (t.nn > 0) {
+        // a cell tape forms the node gradients of the group in blk_nodes, then d_grad = A^T of each
+        T* gn = t.cells ? (T*)t.blk_nodes : d_grad;
+        adjk_grad_kernel<T, K><<<blocks_for(t.nn), ADJ_THREADS, 0, s>>>(lam, (const T*)t.D, t.frozen, (const T*)t.slowness, geo, E, n_cols, gn);
+        ADJ_CHECK(hipGetLastError());
+        if (t.cells)
+            for (int k = 0; k < n_cols; ++k) adj_nodes_to_cells<T>(t, gn + (size_t)k * t.nn, d_grad + (size_t)k * t.nc);
+    }
+    return passes;
+}
+
+template <typename T>
+void adj_gn_block(AdjTapeDev& t, const T* d_v, const T* d_rw, size_t rw_stride, int n_cols, T* d_out, int schedule, int* passes_jvp,
+                  int* passes_vjp) {
+    ADJ_CHECK(hipSetDevice(t.device));
+    adj_block_prepare<T>(t);
+    T* w = (T*)t.blk_rows;
+    *passes_jvp = adj_jvp_block<T>(t, d_v, n_cols, w, nullptr, schedule);
+    if (d_rw && t.n_rows > 0)
+        for (int k = 0; k < n_cols; ++k) {
+            tan_scale_rows_kernel<T><<<blocks_for(t.n_rows), ADJ_THREADS, 0, t.stream>>>(d_rw + (size_t)k * rw_stride, w + (size_t)k * t.n_rows,
+                                                                                        t.n_rows);
+            ADJ_CHECK(hipGetLastError());
+        }
+    *passes_vjp = adj_vjp_block<T>(t, w, n_cols, d_out, schedule);
+}
+
 template void adj_copy_field<float>(const float*, int, float*, size_t, hipStream_t);
 template void adj_copy_field<double>(const double*, int, double*, size_t, hipStream_t);
 template void adj_finish<float>(AdjTapeDev&, const AdjSink&);
@@ -1416,5 +1858,14 @@ template int adj_jvp_source<float>(AdjTapeDev&, const float*, int, float*, float
 template int adj_jvp_source<double>(AdjTapeDev&, const double*, int, double*, double*, int, const double**, int*);
 template int adj_vjp_source<float>(AdjTapeDev&, const float*, const float*, float*, float*, int);
 template int adj_vjp_source<double>(AdjTapeDev&, const double*, const double*, double*, double*, int);
+
+template void adj_block_prepare<float>(AdjTapeDev&);
+template void adj_block_prepare<double>(AdjTapeDev&);
+template int adj_jvp_block<float>(AdjTapeDev&, const float*, int, float*, float*, int);
+template int adj_jvp_block<double>(AdjTapeDev&, const double*, int, double*, double*, int);
+template int adj_vjp_block<float>(AdjTapeDev&, const float*, int, float*, int);
+template int adj_vjp_block<double>(AdjTapeDev&, const double*, int, double*, int);
+template void adj_gn_block<float>(AdjTapeDev&, const float*, const float*, size_t, int, float*, int, int*, int*);
+template void adj_gn_block<double>(AdjTapeDev&, const double*, const double*, size_t, int, double*, int, int*, int*);
 
 }  // namespace ttcr_amd

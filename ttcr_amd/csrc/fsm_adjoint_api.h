@@ -11,6 +11,8 @@
 // Per VJP:          seed (g = field cotangent + receiver rows through the interpolation stencil, one serial chain per node in row order)
 //                   -> relaxation of lam = g + gather(lam) to its fixed point (tiled in LDS, or the global Jacobi baseline)
 //                   -> gradient (events summed in ascending order from +0 inside the thread).
+// Per block product: the same steps for groups of four model vectors, the four values of a node adjacent: K-column seeds,
+//                   K-column relaxations (tiled; what a step needs of the field is read and formed once per node), K-column gradient.
 // No floating-point atomics anywhere: every value is one fixed expression of final values, so the bits do not depend on the schedule.
 // Cell tapes (ttcr_fsm_raytrace_multi_adjoint_cells): the model vector holds one slowness per cell and the node slowness is
 // A times it (fsm_cells_to_nodes3d); a jvp first applies A to ds, a vjp ends with A^T on the node gradient (one thread per cell).
@@ -108,6 +110,14 @@ struct AdjTapeDev {
     void* hold_lam = nullptr;         // n_events * nn: lam of the held cotangent
     void* hess_dd = nullptr;          // n_events * nn: dD of the running product
     bool held = false;                // hold_lam holds a solved lam
+    // block products: allocated by the first block call, returned by adj_block_release.  lam of K columns lives in mu4.
+    void* g4 = nullptr;               // 4 n_events * nn: the seeds of the running K-column vjp (a host dfields of jvp_block is staged here)
+    void* blk_model = nullptr;        // 4 n_model(): a group of host ds / v / grad / out columns
+    void* blk_nodes = nullptr;        // 4 nn (cell tape only): the node vectors of a group
+    void* blk_rows = nullptr;         // 4 n_rows: a group of host w / dtt columns; J v of a Gauss-Newton group
+    void* blk_rw = nullptr;           // 4 n_rows: a group of host row_weight columns
+    bool blk_owns_mu4 = false;        // mu4 came with the block arrays (no jvp_source had allocated it) and leaves with them
+    size_t blk_bytes = 0;             // what the block arrays added to total_bytes
     size_t n_tiles = 0;
     size_t total_bytes = 0;
     hipStream_t stream = nullptr;
@@ -171,5 +181,28 @@ int adj_jvp_source(AdjTapeDev& t, const T* d_dsrc, int n_cols, T* d_dtt, T* d_df
 // the vjp (d_grad may be null here) and, from the same lam, d_gsrc (n_points * 4)
 template <typename T>
 int adj_vjp_source(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, T* d_gsrc, int schedule);
+
+
+// ---- block products: groups of up to 4 model vectors per relaxation.  Column k of every result has the bits of the
+// one-column call (adj_jvp / adj_vjp / adj_gn) on column k.
+// What the first block call adds to the tape: the K-column seeds g4 (4 n_events nn), the K-column lam / mu buffer mu4 (as much again, unless
+// a jvp_source with n_cols > 1 allocated it before) and the staging arrays of a group (4 n_model(), 4 nn on a cell tape, 8 n_rows); the
+// first jvp's arrays too if no jvp came before.  AdjDeviceError naming the byte count if an allocation fails.
+size_t adj_block_bytes(const AdjTapeDev& t);
+template <typename T>
+void adj_block_prepare(AdjTapeDev& t);   // a no-op while the arrays are there
+void adj_block_release(AdjTapeDev& t);   // frees them (mu4 only if it came with them) and takes them off bytes()
+// one group, n_cols from 1 to 4, every array on the tape's device, column k at k * (length of one column): d_ds (n_cols x n_model()),
+// d_dtt (n_cols x n_rows, may be null), d_dfields (n_cols x n_events * nn, may be null; may be g4); d_w (n_cols x n_rows), d_grad (n_cols x
+// n_model()); d_rw: column k of the row weights at d_rw + k * rw_stride (null: none; rw_stride 0: one set shared by the columns).
+// schedule 0 relaxes the group at once (K = 4, the columns past n_cols +0), schedule 1 runs the columns one by one through the Jacobi
+// baseline.  Return the passes launched.
+template <typename T>
+int adj_jvp_block(AdjTapeDev& t, const T* d_ds, int n_cols, T* d_dtt, T* d_dfields, int schedule);
+template <typename T>
+int adj_vjp_block(AdjTapeDev& t, const T* d_w, int n_cols, T* d_grad, int schedule);
+template <typename T>
+void adj_gn_block(AdjTapeDev& t, const T* d_v, const T* d_rw, size_t rw_stride, int n_cols, T* d_out, int schedule, int* passes_jvp,
+                  int* passes_vjp);
 
 }  // namespace ttcr_amd

@@ -4241,6 +4241,167 @@ int ttcr_fsm_adjoint_newton(ttcr_fsm_adjoint* t, const void* v, int v_on_device,
     return adjoint_second_order(t, "newton", v, v_on_device, row_weight, rw_on_device, true, out, out_on_device, schedule, passes_jvp,
                                 passes_vjp);
 }
+// ---- block products of the field tape: n_cols model vectors per call, relaxed in groups of four
+// the argument checks the three products share: what needs no tape first, the tape last (null: no message)
+static const char* adjoint_block_args(const ttcr_fsm_adjoint* t, int n_cols, const void* in, const char* in_null, bool have_out,
+                                      const char* out_null, int schedule) {
+    if (n_cols < 1) return "n_cols: at least one column per call";
+    if (schedule != 0 && schedule != 1) return "schedule: 0 (tiled) or 1 (global Jacobi)";
+    if (!in) return in_null;
+    if (!have_out) return out_null;
+    if (!t) return "null tape";
+    return nullptr;
+}
+extern "C++" {
+template <typename T>
+static void adjoint_jvp_block_run(ttcr_amd::AdjTapeDev& d, int n_cols, const void* ds, int ds_on_device, void* dtt, int dtt_on_device,
+                                  void* dfields, int df_on_device, int schedule, int* passes) {
+    HIP_CHECK(hipSetDevice(d.device));
+    ttcr_amd::adj_block_prepare<T>(d);
+    const size_t en = d.n_events * d.nn, nm = d.n_model(), nr = d.n_rows;
+    int np = 0;
+    for (int c0 = 0; c0 < n_cols; c0 += 4) {
+        const size_t nc = (size_t)std::min(4, n_cols - c0);
+        const T* in = (const T*)ds + (size_t)c0 * nm;
+        if (!ds_on_device) {
+            if (nm > 0) HIP_CHECK(hipMemcpyAsync(d.blk_model, in, nc * nm * sizeof(T), hipMemcpyHostToDevice, d.stream));
+            in = (const T*)d.blk_model;
+        }
+        T* ddtt = dtt ? (dtt_on_device ? (T*)dtt + (size_t)c0 * nr : (T*)d.blk_rows) : nullptr;
+        T* ddf = dfields ? (df_on_device ? (T*)dfields + (size_t)c0 * en : (T*)d.g4) : nullptr;   // (g4 is idle during a jvp)
+        np += ttcr_amd::adj_jvp_block<T>(d, in, (int)nc, ddtt, ddf, schedule);
+        if (dtt && !dtt_on_device && nr > 0)
+            HIP_CHECK(hipMemcpyAsync((T*)dtt + (size_t)c0 * nr, d.blk_rows, nc * nr * sizeof(T), hipMemcpyDeviceToHost, d.stream));
+        if (dfields && !df_on_device && en > 0)
+            HIP_CHECK(hipMemcpyAsync((T*)dfields + (size_t)c0 * en, d.g4, nc * en * sizeof(T), hipMemcpyDeviceToHost, d.stream));
+    }
+    HIP_CHECK(hipStreamSynchronize(d.stream));
+    if (passes) *passes = np;
+}
+template <typename T>
+static void adjoint_vjp_block_run(ttcr_amd::AdjTapeDev& d, int n_cols, const void* w, int w_on_device, void* grad, int grad_on_device,
+                                  int schedule, int* passes) {
+    HIP_CHECK(hipSetDevice(d.device));
+    ttcr_amd::adj_block_prepare<T>(d);
+    const size_t nm = d.n_model(), nr = d.n_rows;
+    int np = 0;
+    for (int c0 = 0; c0 < n_cols; c0 += 4) {
+        const size_t nc = (size_t)std::min(4, n_cols - c0);
+        const T* in = (const T*)w + (size_t)c0 * nr;
+        if (!w_on_device) {
+            if (nr > 0) HIP_CHECK(hipMemcpyAsync(d.blk_rows, in, nc * nr * sizeof(T), hipMemcpyHostToDevice, d.stream));
+            in = (const T*)d.blk_rows;
+        }
+        T* dg = grad_on_device ? (T*)grad + (size_t)c0 * nm : (T*)d.blk_model;
+        np += ttcr_amd::adj_vjp_block<T>(d, in, (int)nc, dg, schedule);
+        if (!grad_on_device && nm > 0)
+            HIP_CHECK(hipMemcpyAsync((T*)grad + (size_t)c0 * nm, d.blk_model, nc * nm * sizeof(T), hipMemcpyDeviceToHost, d.stream));
+    }
+    HIP_CHECK(hipStreamSynchronize(d.stream));
+    if (passes) *passes = np;
+}
+template <typename T>
+static void adjoint_gn_block_run(ttcr_amd::AdjTapeDev& d, int n_cols, const void* v, int v_on_device, const void* row_weight, int rw_cols,
+                                 int rw_on_device, void* out, int out_on_device, int schedule, int* passes_jvp, int* passes_vjp) {
+    HIP_CHECK(hipSetDevice(d.device));
+    ttcr_amd::adj_block_prepare<T>(d);
+    const size_t nm = d.n_model(), nr = d.n_rows;
+    const bool shared = rw_cols == 1;
+    if (rw_cols > 0 && !rw_on_device && shared && nr > 0)
+        HIP_CHECK(hipMemcpyAsync(d.blk_rw, row_weight, nr * sizeof(T), hipMemcpyHostToDevice, d.stream));
+    int pj = 0, pv = 0;
+    for (int c0 = 0; c0 < n_cols; c0 += 4) {
+        const size_t nc = (size_t)std::min(4, n_cols - c0);
+        const T* in = (const T*)v + (size_t)c0 * nm;
+        if (!v_on_device) {   // (consumed by the jvp before the vjp writes the host columns to the same place)
+            if (nm > 0) HIP_CHECK(hipMemcpyAsync(d.blk_model, in, nc * nm * sizeof(T), hipMemcpyHostToDevice, d.stream));
+            in = (const T*)d.blk_model;
+        }
+        const T* drw = nullptr;
+        if (rw_cols > 0) {
+            const T* src = (const T*)row_weight + (shared ? 0 : (size_t)c0 * nr);
+            if (!rw_on_device) {
+                if (!shared && nr > 0) HIP_CHECK(hipMemcpyAsync(d.blk_rw, src, nc * nr * sizeof(T), hipMemcpyHostToDevice, d.stream));
+                src = (const T*)d.blk_rw;
+            }
+            drw = src;
+        }
+        T* dout = out_on_device ? (T*)out + (size_t)c0 * nm : (T*)d.blk_model;
+        int gj = 0, gv = 0;
+        ttcr_amd::adj_gn_block<T>(d, in, drw, shared ? 0 : nr, (int)nc, dout, schedule, &gj, &gv);
+        pj += gj;
+        pv += gv;
+        if (!out_on_device && nm > 0)
+            HIP_CHECK(hipMemcpyAsync((T*)out + (size_t)c0 * nm, d.blk_model, nc * nm * sizeof(T), hipMemcpyDeviceToHost, d.stream));
+    }
+    HIP_CHECK(hipStreamSynchronize(d.stream));
+    if (passes_jvp) *passes_jvp = pj;
+    if (passes_vjp) *passes_vjp = pv;
+}
+}  // extern "C++"
+int ttcr_fsm_adjoint_jvp_block(const ttcr_fsm_adjoint* t, int n_cols, const void* ds, int ds_on_device, void* dtt, int dtt_on_device,
+                               void* dfields, int df_on_device, int schedule, int* passes) {
+    if (const char* bad = adjoint_block_args(t, n_cols, ds, "null ds", dtt || dfields, "dtt and dfields are both null: nothing to compute",
+                                             schedule)) {
+        g_last_error = bad;
+        return TTCR_ERR_VALUE;
+    }
+    ttcr_fsm_adjoint* tm = const_cast<ttcr_fsm_adjoint*>(t);
+    std::lock_guard<std::mutex> lock(tm->mu);
+    return guarded([&] {
+        adj_device_errors([&] {
+            if (tm->dtype == TTCR_F32)
+                adjoint_jvp_block_run<float>(tm->t, n_cols, ds, ds_on_device, dtt, dtt_on_device, dfields, df_on_device, schedule, passes);
+            else adjoint_jvp_block_run<double>(tm->t, n_cols, ds, ds_on_device, dtt, dtt_on_device, dfields, df_on_device, schedule, passes);
+        });
+    });
+}
+int ttcr_fsm_adjoint_vjp_block(const ttcr_fsm_adjoint* t, int n_cols, const void* w, int w_on_device, void* grad, int grad_on_device,
+                               int schedule, int* passes) {
+    if (const char* bad = adjoint_block_args(t, n_cols, w, "null w", grad != nullptr, "null grad", schedule)) {
+        g_last_error = bad;
+        return TTCR_ERR_VALUE;
+    }
+    ttcr_fsm_adjoint* tm = const_cast<ttcr_fsm_adjoint*>(t);
+    std::lock_guard<std::mutex> lock(tm->mu);
+    return guarded([&] {
+        adj_device_errors([&] {
+            if (tm->dtype == TTCR_F32) adjoint_vjp_block_run<float>(tm->t, n_cols, w, w_on_device, grad, grad_on_device, schedule, passes);
+            else adjoint_vjp_block_run<double>(tm->t, n_cols, w, w_on_device, grad, grad_on_device, schedule, passes);
+        });
+    });
+}
+int ttcr_fsm_adjoint_gn_block(const ttcr_fsm_adjoint* t, int n_cols, const void* v, int v_on_device, const void* row_weight, int rw_cols,
+                              int rw_on_device, void* out, int out_on_device, int schedule, int* passes_jvp, int* passes_vjp) {
+    const char* bad = nullptr;
+    if (n_cols >= 1 && rw_cols != 0 && rw_cols != 1 && rw_cols != n_cols) bad = "rw_cols: 0 (no row_weight), 1 (one set for every column) or n_cols";
+    else if (n_cols >= 1 && rw_cols != 0 && !row_weight) bad = "null row_weight with rw_cols != 0";
+    else bad = adjoint_block_args(t, n_cols, v, "null v", out != nullptr, "null out", schedule);
+    if (bad) {
+        g_last_error = bad;
+        return TTCR_ERR_VALUE;
+    }
+    ttcr_fsm_adjoint* tm = const_cast<ttcr_fsm_adjoint*>(t);
+    std::lock_guard<std::mutex> lock(tm->mu);
+    return guarded([&] {
+        adj_device_errors([&] {
+            if (tm->dtype == TTCR_F32)
+                adjoint_gn_block_run<float>(tm->t, n_cols, v, v_on_device, row_weight, rw_cols, rw_on_device, out, out_on_device, schedule,
+                                            passes_jvp, passes_vjp);
+            else
+                adjoint_gn_block_run<double>(tm->t, n_cols, v, v_on_device, row_weight, rw_cols, rw_on_device, out, out_on_device, schedule,
+                                             passes_jvp, passes_vjp);
+        });
+    });
+}
+int ttcr_fsm_adjoint_block_release(ttcr_fsm_adjoint* t) {
+    if (!t) {
+        g_last_error = "null tape";
+        return TTCR_ERR_VALUE;
+    }
+    std::lock_guard<std::mutex> lock(t->mu);
+    return guarded([&] { ttcr_amd::adj_block_release(t->t); });
+}
 int ttcr_fsm_adjoint_free(ttcr_fsm_adjoint* t) {
     if (!t) return TTCR_OK;
     return guarded([&] { delete t; });

@@ -999,6 +999,144 @@ class FieldTape:
         residual is the held w, at the cost of gauss_newton plus three streaming kernels.  Arguments as gauss_newton; needs hold()."""
         return self._second_order(v, row_weight, True, schedule)
 
+    # ---- block products (DESIGN.md 6g)
+    def _block_arg(self, a, name, n_last, rows, n_lead=None):
+        """a (K, n_last) array, numpy or torch, for a block call: (array, pointer, on_device, K).  rows=True: one value per data row,
+        permuted to tape row order.  n_lead: the K the array has to have (row weights)."""
+        on_dev = type(a).__module__.startswith('torch') and a.device.type == 'cuda'
+        if not on_dev:
+            a = np.asarray(a.detach().numpy() if hasattr(a, 'detach') else a)
+        shape = tuple(a.shape)
+        if len(shape) != 2 or shape[1] != n_last or shape[0] < 1 or (n_lead is not None and shape[0] != n_lead):
+            raise ValueError('%s should be (%s, %d) with K >= 1, got shape %s' % (name, 'K' if n_lead is None else n_lead, n_last, shape))
+        if on_dev:
+            import torch
+
+            tdt = torch.float32 if self.dtype == np.float32 else torch.float64
+            dev = torch.device('cuda', self.device)
+            a = a.detach().to(device=dev, dtype=tdt)
+            if rows:
+                if self._rows_dev is None:
+                    self._rows_dev = torch.as_tensor(self._rows, device=dev)
+                a = a.index_select(1, self._rows_dev)
+            a = a.contiguous()
+            if a.numel() == 0:
+                a = torch.zeros(1, dtype=tdt, device=dev)
+            return a, C.c_void_p(a.data_ptr()), 1, shape[0]
+        a = np.ascontiguousarray(a[:, self._rows] if rows else a, dtype=self.dtype)
+        if a.size == 0:
+            a = np.zeros(1, dtype=self.dtype)
+        return a, _ptr(a), 0, shape[0]
+
+    def _block_out(self, like, K, n_last, rows=False):
+        """a (K, n_last) output where `like` lives: (pointer, on_device, finish); rows=True: tape row order in, rcv order out"""
+        is_torch = type(like).__module__.startswith('torch')
+        if is_torch and like.device.type == 'cuda':
+            import torch
+
+            tdt = torch.float32 if self.dtype == np.float32 else torch.float64
+            dev = torch.device('cuda', self.device)
+            o = torch.empty(max(K * n_last, 1), dtype=tdt, device=dev)
+            if rows and self._rows_dev is None:
+                self._rows_dev = torch.as_tensor(self._rows, device=dev)
+
+            def finish():
+                r = o[:K * n_last].reshape(K, n_last)
+                if rows:
+                    d = torch.zeros((K, self.n_data), dtype=tdt, device=dev)
+                    d[:, self._rows_dev] = r
+                    r = d
+                return r.to(like.device)
+            return C.c_void_p(o.data_ptr()), 1, finish
+        o = np.empty(max(K * n_last, 1), dtype=self.dtype)
+
+        def finish():
+            r = o[:K * n_last].reshape(K, n_last)
+            if rows:
+                d = np.zeros((K, self.n_data), dtype=self.dtype)
+                d[:, self._rows] = r
+                r = d
+            if is_torch:
+                import torch
+
+                r = torch.from_numpy(r)
+            return r
+        return _ptr(o), 0, finish
+
+    def _block_sync(self, *on_device):
+        if any(on_device):
+            import torch
+
+            torch.cuda.current_stream(torch.device('cuda', self.device)).synchronize()
+
+    def jvp_block(self, ds, return_fields=False, schedule='tiled'):
+        """J applied to K perturbations at once: ds (K, n_cols), K >= 1; returns dtt (K, n_data) in rcv order, with return_fields=True
+        (dtt, dfields) with dfields (K, n_events, n_nodes).  Row k has the bits of jvp(ds[k]) whatever K and k are.  Under 'tiled' the
+        columns are relaxed four at a time (the last group padded with zeros); 'jacobi' runs them one by one through the baseline.
+        Array handling as in jvp.  The first block call of a tape allocates two arrays of 4 x n_events x n_nodes values and the staging of
+        a group (nbytes grows by them; release_block returns them).  Block forms of hvp / newton, of field cotangents and of the
+        source-point gradient, and a vmap rule for the torch Functions, are not offered."""
+        self._handle()
+        sch = self._schedule(schedule)
+        a, pa, da, K = self._block_arg(ds, 'ds', self.n_cols, False)
+        pr, dr, fin_r = self._block_out(ds, K, self.n_rows, rows=True)
+        pf, df, fin_f = self._block_out(ds, K, self.n_events * self.n_nodes) if return_fields else (None, 0, None)
+        self._block_sync(da, dr, df)
+        np_ = C.c_int(0)
+        want_f = return_fields and self.n_events * self.n_nodes > 0
+        if self.n_rows > 0 or want_f:
+            _lib.check(self._lib.ttcr_fsm_adjoint_jvp_block(self._h, K, pa, da, pr if self.n_rows > 0 else None, dr,
+                                                            pf if want_f else None, df, sch, C.byref(np_)))
+        self.passes = np_.value
+        self._refresh_nbytes()
+        dtt = fin_r()
+        return (dtt, fin_f().reshape(K, self.n_events, self.n_nodes)) if return_fields else dtt
+
+    def vjp_block(self, w, schedule='tiled'):
+        """J^T applied to K receiver cotangents at once: w (K, n_data) in rcv order, K >= 1; returns (K, n_cols) gradients, row k with
+        the bits of vjp(w[k]).  Grouping, schedules, array handling and memory as in jvp_block; no field cotangent and no source-point
+        gradient per block."""
+        self._handle()
+        sch = self._schedule(schedule)
+        a, pa, da, K = self._block_arg(w, 'w', self.n_data, True)
+        pg, dg, fin = self._block_out(w, K, self.n_cols)
+        self._block_sync(da, dg)
+        np_ = C.c_int(0)
+        _lib.check(self._lib.ttcr_fsm_adjoint_vjp_block(self._h, K, pa, da, pg, dg, sch, C.byref(np_)))
+        self.passes = np_.value
+        self._refresh_nbytes()
+        return fin()
+
+    def gauss_newton_block(self, v, row_weight=None, schedule='tiled'):
+        """J^T (row_weight * (J v)) for K vectors at once: v (K, n_cols), K >= 1; row_weight None, (n_data,) -- shared by the K vectors --
+        or (K, n_data), in rcv order; returns (K, n_cols), row k with the bits of gauss_newton(v[k], row_weight or row_weight[k]).
+        passes becomes (passes of the jvp, passes of the vjp), summed over the groups.  Everything else as in jvp_block."""
+        self._handle()
+        sch = self._schedule(schedule)
+        a, pa, da, K = self._block_arg(v, 'v', self.n_cols, False)
+        rw, prw, drw, rw_cols = None, None, 0, 0
+        if row_weight is not None:
+            if len(tuple(row_weight.shape)) == 1:
+                rw, prw, drw = self._row_arg(row_weight, 'row_weight')
+                rw_cols = 1
+            else:
+                rw, prw, drw, rw_cols = self._block_arg(row_weight, 'row_weight', self.n_data, True, n_lead=K)
+                if K == 1:
+                    rw_cols = 1
+        pg, dg, fin = self._block_out(v, K, self.n_cols)
+        self._block_sync(da, drw, dg)
+        pj, pv = C.c_int(0), C.c_int(0)
+        _lib.check(self._lib.ttcr_fsm_adjoint_gn_block(self._h, K, pa, da, prw, rw_cols, drw, pg, dg, sch, C.byref(pj), C.byref(pv)))
+        self.passes = (pj.value, pv.value)
+        self._refresh_nbytes()
+        return fin()
+
+    def release_block(self):
+        """Free the work arrays of the block products (nbytes falls by what the first block call added); the next block call allocates
+        them again.  A held cotangent (hold / release) is not touched."""
+        _lib.check(self._lib.ttcr_fsm_adjoint_block_release(self._handle()))
+        self._refresh_nbytes()
+
     def _refresh_nbytes(self):
         b = C.c_size_t(0)
         _lib.check(self._lib.ttcr_fsm_adjoint_bytes(self._h, C.byref(b)))
