@@ -4,7 +4,7 @@ hipcc cross-compiles without a GPU.  -ffp-contract=off is REQUIRED for parity: t
 solver must round a1 + s*dx (and every other product/sum pair) exactly like the reference,
 which a fused multiply-add would not (ttcr_amd/csrc/fsm_kernels.h header).
 
-Two translation units, compiled to objects under ttcr_amd/csrc/_obj and linked:
+Four translation units, compiled to objects under ttcr_amd/csrc/_obj and linked:
   fsm_capi.hip    the C ABI, the host side and every kernel but one
   fsm_fast.hip    the sweep kernels with tolerance-grade arithmetic (option "arith" = 1)
   fsm_tape.hip    the M tape: compute_M's rows merged on the device, node index, M^T w (hipCUB sorts)

@@ -3861,51 +3861,127 @@ int ttcr_fsm_raytrace_multi_adjoint_cells(ttcr_fsm_grid* g, int n_src, const int
                                           const void* rx, void* tt_out, ttcr_fsm_adjoint** tape) {
     return raytrace_multi_adjoint_entry(g, n_src, tx_off, tx, t0, rx_off, rx, tt_out, tape, true);
 }
-int ttcr_fsm_adjoint_model(const ttcr_fsm_adjoint* t, int* cells, size_t* n_params, size_t* n_nodes) {
-    if (!t || !cells || !n_params || !n_nodes) {
-        g_last_error = "null tape or output pointer";
+// ---- the host layer of the tape's entries: one frame, two staging helpers.
+//
+// An argument or a result of a product is used in place if it is on the tape's device; a host one goes through a work array of the tape,
+// asynchronously on the tape's stream, so that every copy is ordered with the kernels around it.  What is staged where, and why that
+// array is free at that moment:
+//
+//   product                      host argument      staged in     free because
+//   ---------------------------  -----------------  ------------  -----------------------------------------------------------------------
+//   vjp, hold, vjp_source        w                  w_tmp         nothing else of a vjp uses it (it holds J v in a jvp / Gauss-Newton product)
+//                                field_cot          lam2          the Jacobi baseline's second buffer: not in use before the seeds are formed,
+//                                                                 and the seeds have read it by then
+//                                grad (result)      model_tmp()   written by the last kernel (a cell tape forms the node gradient in
+//                                                                 grad_tmp, then A^T into cell_tmp)
+//                                gsrc (result)      src_io        allocated by adj_src_prepare, which therefore runs first; no dsrc in a vjp
+//   jvp                          ds                 model_tmp()   where a host gradient is staged: no gradient during a jvp
+//                                dtt (result)       w_tmp         a jvp has no w
+//                                dfields (result)   --            read from the relaxed buffer itself: lam, or lam2 after an odd number of
+//                                                                 passes of the Jacobi schedule, which alternates lam -> lam2 -> lam
+//   gn, hvp, newton              v and out          model_tmp()   both: v is consumed by the tangent relaxation before the vjp writes the
+//                                                                 result to the same place (hvp / newton: the last kernel reads v too;
+//                                                                 adj_hess allows d_v == d_out)
+//                                row_weight         rw_tmp        part of what the first jvp allocates: adj_jvp_prepare runs before the copy
+//   jvp_source                   dsrc               src_io        allocated by adj_src_prepare, which runs first; no gsrc in a jvp
+//                                dtt (result)       src_rows      the K-column rows, allocated with src_io
+//                                dfields (result)   --            read from the relaxed buffer adj_jvp_source names: as it is for K = 1,
+//                                                                 through a host vector that parts the K columns of a node for K = 4
+//   jvp_block (per group)        ds                 blk_model     the group's own staging, allocated by adj_block_prepare, which runs first
+//                                dtt (result)       blk_rows      a jvp group has no w
+//                                dfields (result)   g4            the seeds of a K-column vjp: idle during a jvp
+//   vjp_block (per group)        w                  blk_rows      no J v in a vjp group
+//                                grad (result)      blk_model     no ds in a vjp group
+//   gn_block (per group)         v and out          blk_model     both, as for gn
+//                                row_weight         blk_rw        one set shared by the columns: uploaded once, before the loop; a set per
+//                                                                 column: the group's columns, uploaded in the loop
+//
+// The groups of a block product run one after the other on the stream, so a group's staging is free again when the next group's copy is
+// enqueued behind it.  Nothing is copied for an empty array, and an argument that is null stays null.
+extern "C++" {
+// the device pointer to read a `count`-element argument from: `ptr` itself if it is null or on the device, else `staging` after the copy
+template <typename T>
+static const T* stage_in(ttcr_amd::AdjTapeDev& d, const void* ptr, int on_device, void* staging, size_t count) {
+    if (!ptr || on_device) return (const T*)ptr;
+    if (count > 0) HIP_CHECK(hipMemcpyAsync(staging, ptr, count * sizeof(T), hipMemcpyHostToDevice, d.stream));
+    return (const T*)staging;
+}
+// the device pointer the kernels write a result to (null if the caller does not want it) ...
+template <typename T>
+static T* stage_dst(void* dst, int on_device, void* staging) {
+    return (T*)(dst && !on_device ? staging : dst);
+}
+// ... and its way to a host `dst` afterwards
+template <typename T>
+static void stage_out(ttcr_amd::AdjTapeDev& d, void* dst, int on_device, const void* staging, size_t count) {
+    if (dst && !on_device && count > 0) HIP_CHECK(hipMemcpyAsync(dst, staging, count * sizeof(T), hipMemcpyDeviceToHost, d.stream));
+}
+}  // extern "C++"
+
+static int tape_arg_error(const char* msg) {
+    g_last_error = msg;
+    return TTCR_ERR_VALUE;
+}
+static const char* schedule_error(int schedule) {
+    return schedule == 0 || schedule == 1 ? nullptr : "schedule: 0 (tiled) or 1 (global Jacobi)";
+}
+
+// The frame of every product entry, called once the entry's own argument checks have passed: checks the schedule, locks the tape, turns
+// exceptions into a status (the kernel unit's device errors among them), selects the tape's device, calls body(d, T(), p1, p2) with T the
+// tape's element type, waits for the tape's stream and hands out the pass counts p1, p2 the body left.  need_held names a product that
+// needs a held cotangent.
+extern "C++" {
+template <typename Body>
+static int tape_call(const ttcr_fsm_adjoint* t, int schedule, int* passes1, int* passes2, Body&& body, const char* need_held = nullptr) {
+    if (const char* bad = schedule_error(schedule)) return tape_arg_error(bad);
+    ttcr_fsm_adjoint* tm = const_cast<ttcr_fsm_adjoint*>(t);
+    std::lock_guard<std::mutex> lock(tm->mu);
+    if (need_held && !tm->t.held) {
+        g_last_error = std::string(need_held) + ": the tape holds no cotangent (call ttcr_fsm_adjoint_hold first)";
         return TTCR_ERR_VALUE;
     }
+    return guarded([&] {
+        adj_device_errors([&] {
+            ttcr_amd::AdjTapeDev& d = tm->t;
+            HIP_CHECK(hipSetDevice(d.device));
+            int p1 = 0, p2 = 0;
+            if (tm->dtype == TTCR_F32) body(d, float(), p1, p2);
+            else body(d, double(), p1, p2);
+            HIP_CHECK(hipStreamSynchronize(d.stream));
+            if (passes1) *passes1 = p1;
+            if (passes2) *passes2 = p2;
+        });
+    });
+}
+}  // extern "C++"
+
+int ttcr_fsm_adjoint_model(const ttcr_fsm_adjoint* t, int* cells, size_t* n_params, size_t* n_nodes) {
+    if (!t || !cells || !n_params || !n_nodes) return tape_arg_error("null tape or output pointer");
     *cells = t->t.cells ? 1 : 0;
     *n_params = t->t.n_model();
     *n_nodes = t->t.nn;
     return TTCR_OK;
 }
 int ttcr_fsm_adjoint_size(const ttcr_fsm_adjoint* t, size_t* n_events, size_t* n_rows, size_t* n_nodes) {
-    if (!t || !n_events || !n_rows || !n_nodes) {
-        g_last_error = "null tape or output pointer";
-        return TTCR_ERR_VALUE;
-    }
+    if (!t || !n_events || !n_rows || !n_nodes) return tape_arg_error("null tape or output pointer");
     *n_events = t->t.n_events;
     *n_rows = t->t.n_rows;
     *n_nodes = t->t.nn;
     return TTCR_OK;
 }
 int ttcr_fsm_adjoint_bytes(const ttcr_fsm_adjoint* t, size_t* bytes) {
-    if (!t || !bytes) {
-        g_last_error = "null tape or output pointer";
-        return TTCR_ERR_VALUE;
-    }
+    if (!t || !bytes) return tape_arg_error("null tape or output pointer");
     *bytes = t->t.bytes();
     return TTCR_OK;
 }
 int ttcr_fsm_adjoint_device(const ttcr_fsm_adjoint* t, int* device) {
-    if (!t || !device) {
-        g_last_error = "null tape or output pointer";
-        return TTCR_ERR_VALUE;
-    }
+    if (!t || !device) return tape_arg_error("null tape or output pointer");
     *device = t->t.device;
     return TTCR_OK;
 }
 int ttcr_fsm_adjoint_get_field(const ttcr_fsm_adjoint* t, size_t event, void* out) {
-    if (!t || !out) {
-        g_last_error = "null tape or output pointer";
-        return TTCR_ERR_VALUE;
-    }
-    if (event >= t->t.n_events) {
-        g_last_error = "event index out of range";
-        return TTCR_ERR_VALUE;
-    }
+    if (!t || !out) return tape_arg_error("null tape or output pointer");
+    if (event >= t->t.n_events) return tape_arg_error("event index out of range");
     ttcr_fsm_adjoint* tm = const_cast<ttcr_fsm_adjoint*>(t);
     std::lock_guard<std::mutex> lock(tm->mu);
     return guarded([&] {
@@ -3915,460 +3991,169 @@ int ttcr_fsm_adjoint_get_field(const ttcr_fsm_adjoint* t, size_t event, void* ou
         HIP_CHECK(hipStreamSynchronize(d.stream));
     });
 }
-int ttcr_fsm_adjoint_vjp(const ttcr_fsm_adjoint* t, const void* w, int w_on_device, const void* field_cot, int fc_on_device, void* grad,
-                         int grad_on_device, int schedule, int* passes) {
-    if (!t || !grad || (!w && !field_cot)) {
-        g_last_error = !t ? "null tape" : (!grad ? "null grad" : "w and field_cot are both null: nothing to back-propagate");
-        return TTCR_ERR_VALUE;
-    }
-    if (schedule != 0 && schedule != 1) {
-        g_last_error = "schedule: 0 (tiled) or 1 (global Jacobi)";
-        return TTCR_ERR_VALUE;
-    }
-    ttcr_fsm_adjoint* tm = const_cast<ttcr_fsm_adjoint*>(t);
-    std::lock_guard<std::mutex> lock(tm->mu);
-    return guarded([&] {
-        ttcr_amd::AdjTapeDev& d = tm->t;
-        adj_device_errors([&] {
-            HIP_CHECK(hipSetDevice(d.device));
-            const void* dw = w;
-            const void* dfc = field_cot;
-            void* dg = grad_on_device ? grad : d.model_tmp();   // (a cell tape forms the node gradient in grad_tmp, then A^T into dg)
-            if (w && !w_on_device) {
-                if (d.n_rows > 0) HIP_CHECK(hipMemcpyAsync(d.w_tmp, w, d.n_rows * d.elem, hipMemcpyHostToDevice, d.stream));
-                dw = d.w_tmp;
-            }
-            if (field_cot && !fc_on_device) {   // (staged in the Jacobi baseline's second buffer, which is not in use before the seeds are formed)
-                if (d.n_events * d.nn > 0)
-                    HIP_CHECK(hipMemcpyAsync(d.lam2, field_cot, d.n_events * d.nn * d.elem, hipMemcpyHostToDevice, d.stream));
-                dfc = d.lam2;
-            }
-            int np = 0;
-            if (tm->dtype == TTCR_F32) np = ttcr_amd::adj_vjp<float>(d, (const float*)dw, (const float*)dfc, (float*)dg, schedule);
-            else np = ttcr_amd::adj_vjp<double>(d, (const double*)dw, (const double*)dfc, (double*)dg, schedule);
-            if (!grad_on_device && d.n_model() > 0)
-                HIP_CHECK(hipMemcpyAsync(grad, d.model_tmp(), d.n_model() * d.elem, hipMemcpyDeviceToHost, d.stream));
-            HIP_CHECK(hipStreamSynchronize(d.stream));
-            if (passes) *passes = np;
-        });
-    });
-}
-int ttcr_fsm_adjoint_jvp(const ttcr_fsm_adjoint* t, const void* ds, int ds_on_device, void* dtt, int dtt_on_device, void* dfields,
-                         int df_on_device, int schedule, int* passes) {
-    if (!t || !ds || (!dtt && !dfields)) {
-        g_last_error = !t ? "null tape" : (!ds ? "null ds" : "dtt and dfields are both null: nothing to compute");
-        return TTCR_ERR_VALUE;
-    }
-    if (schedule != 0 && schedule != 1) {
-        g_last_error = "schedule: 0 (tiled) or 1 (global Jacobi)";
-        return TTCR_ERR_VALUE;
-    }
-    ttcr_fsm_adjoint* tm = const_cast<ttcr_fsm_adjoint*>(t);
-    std::lock_guard<std::mutex> lock(tm->mu);
-    return guarded([&] {
-        ttcr_amd::AdjTapeDev& d = tm->t;
-        adj_device_errors([&] {
-            HIP_CHECK(hipSetDevice(d.device));
-            const size_t en = d.n_events * d.nn;
-            const void* dds = ds;
-            if (!ds_on_device) {   // (staged where a host gradient is staged: not in use during a jvp)
-                if (d.n_model() > 0) HIP_CHECK(hipMemcpyAsync(d.model_tmp(), ds, d.n_model() * d.elem, hipMemcpyHostToDevice, d.stream));
-                dds = d.model_tmp();
-            }
-            void* ddtt = dtt ? (dtt_on_device ? dtt : d.w_tmp) : nullptr;
-            void* ddf = dfields && df_on_device ? dfields : nullptr;   // (a host copy is read from the relaxed buffer itself)
-            int np = 0;
-            if (tm->dtype == TTCR_F32) np = ttcr_amd::adj_jvp<float>(d, (const float*)dds, (float*)ddtt, (float*)ddf, schedule);
-            else np = ttcr_amd::adj_jvp<double>(d, (const double*)dds, (double*)ddtt, (double*)ddf, schedule);
-            if (dtt && !dtt_on_device && d.n_rows > 0)
-                HIP_CHECK(hipMemcpyAsync(dtt, d.w_tmp, d.n_rows * d.elem, hipMemcpyDeviceToHost, d.stream));
-            if (dfields && !df_on_device && en > 0) {
-                const void* mu = (schedule != 0 && np % 2 == 1) ? d.lam2 : d.lam;   // (the Jacobi baseline alternates lam -> lam2 -> lam)
-                HIP_CHECK(hipMemcpyAsync(dfields, mu, en * d.elem, hipMemcpyDeviceToHost, d.stream));
-            }
-            HIP_CHECK(hipStreamSynchronize(d.stream));
-            if (passes) *passes = np;
-        });
-    });
-}
-int ttcr_fsm_adjoint_gn(const ttcr_fsm_adjoint* t, const void* v, int v_on_device, const void* row_weight, int rw_on_device, void* out,
-                        int out_on_device, int schedule, int* passes_jvp, int* passes_vjp) {
-    if (!t || !v || !out) {
-        g_last_error = !t ? "null tape" : (!v ? "null v" : "null out");
-        return TTCR_ERR_VALUE;
-    }
-    if (schedule != 0 && schedule != 1) {
-        g_last_error = "schedule: 0 (tiled) or 1 (global Jacobi)";
-        return TTCR_ERR_VALUE;
-    }
-    ttcr_fsm_adjoint* tm = const_cast<ttcr_fsm_adjoint*>(t);
-    std::lock_guard<std::mutex> lock(tm->mu);
-    return guarded([&] {
-        ttcr_amd::AdjTapeDev& d = tm->t;
-        adj_device_errors([&] {
-            HIP_CHECK(hipSetDevice(d.device));
-            const void* dv = v;
-            if (!v_on_device) {   // (consumed by the jvp before the vjp writes a host gradient to the same place)
-                if (d.n_model() > 0) HIP_CHECK(hipMemcpyAsync(d.model_tmp(), v, d.n_model() * d.elem, hipMemcpyHostToDevice, d.stream));
-                dv = d.model_tmp();
-            }
-            void* dout = out_on_device ? out : d.model_tmp();
-            const bool stage_rw = row_weight && !rw_on_device;
-            int pj = 0, pv = 0;
-            if (stage_rw) {   // (the staging row is part of what the first jvp allocates)
-                if (tm->dtype == TTCR_F32) ttcr_amd::adj_jvp_prepare<float>(d);
-                else ttcr_amd::adj_jvp_prepare<double>(d);
-                if (d.n_rows > 0) HIP_CHECK(hipMemcpyAsync(d.rw_tmp, row_weight, d.n_rows * d.elem, hipMemcpyHostToDevice, d.stream));
-            }
-            const void* drw = row_weight ? (rw_on_device ? row_weight : d.rw_tmp) : nullptr;
-            if (tm->dtype == TTCR_F32) ttcr_amd::adj_gn<float>(d, (const float*)dv, (const float*)drw, (float*)dout, schedule, &pj, &pv);
-            else ttcr_amd::adj_gn<double>(d, (const double*)dv, (const double*)drw, (double*)dout, schedule, &pj, &pv);
-            if (!out_on_device && d.n_model() > 0)
-                HIP_CHECK(hipMemcpyAsync(out, d.model_tmp(), d.n_model() * d.elem, hipMemcpyDeviceToHost, d.stream));
-            HIP_CHECK(hipStreamSynchronize(d.stream));
-            if (passes_jvp) *passes_jvp = pj;
-            if (passes_vjp) *passes_vjp = pv;
-        });
-    });
-}
 int ttcr_fsm_adjoint_points(const ttcr_fsm_adjoint* t, size_t* n_points, int* event_of_point) {
-    if (!t || !n_points) {
-        g_last_error = !t ? "null tape" : "null n_points";
-        return TTCR_ERR_VALUE;
-    }
+    if (!t || !n_points) return tape_arg_error(!t ? "null tape" : "null n_points");
     *n_points = t->t.n_points;
     if (event_of_point) std::copy(t->t.h_pt_event.begin(), t->t.h_pt_event.end(), event_of_point);
     return TTCR_OK;
 }
-int ttcr_fsm_adjoint_jvp_source(const ttcr_fsm_adjoint* t, const void* dsrc, int dsrc_on_device, int n_cols, void* dtt, int dtt_on_device,
-                                void* dfields, int df_on_device, int schedule, int* passes) {
-    if (!t || !dsrc || (!dtt && !dfields)) {
-        g_last_error = !t ? "null tape" : (!dsrc ? "null dsrc" : "dtt and dfields are both null: nothing to compute");
-        return TTCR_ERR_VALUE;
-    }
-    if (n_cols < 1 || n_cols > 4) {
-        g_last_error = "n_cols: 1 to 4 columns per call";
-        return TTCR_ERR_VALUE;
-    }
-    if (schedule != 0 && schedule != 1) {
-        g_last_error = "schedule: 0 (tiled) or 1 (global Jacobi)";
-        return TTCR_ERR_VALUE;
-    }
-    ttcr_fsm_adjoint* tm = const_cast<ttcr_fsm_adjoint*>(t);
-    std::lock_guard<std::mutex> lock(tm->mu);
-    return guarded([&] {
-        ttcr_amd::AdjTapeDev& d = tm->t;
-        adj_device_errors([&] {
-            HIP_CHECK(hipSetDevice(d.device));
-            const size_t en = d.n_events * d.nn, nc = (size_t)n_cols;
-            if (tm->dtype == TTCR_F32) ttcr_amd::adj_src_prepare<float>(d);   // (the staging arrays are part of what the first call allocates)
-            else ttcr_amd::adj_src_prepare<double>(d);
-            const void* dd = dsrc;
-            if (!dsrc_on_device) {
-                if (d.n_points > 0) HIP_CHECK(hipMemcpyAsync(d.src_io, dsrc, nc * d.n_points * 4 * d.elem, hipMemcpyHostToDevice, d.stream));
-                dd = d.src_io;
-            }
-            void* ddtt = dtt ? (dtt_on_device ? dtt : d.src_rows) : nullptr;
-            void* ddf = dfields && df_on_device ? dfields : nullptr;
-            int np = 0, K = 1;
-            const void* mu = nullptr;
-            if (tm->dtype == TTCR_F32)
-                np = ttcr_amd::adj_jvp_source<float>(d, (const float*)dd, n_cols, (float*)ddtt, (float*)ddf, schedule, (const float**)&mu, &K);
-            else
-                np = ttcr_amd::adj_jvp_source<double>(d, (const double*)dd, n_cols, (double*)ddtt, (double*)ddf, schedule, (const double**)&mu, &K);
-            if (dtt && !dtt_on_device && d.n_rows > 0)
-                HIP_CHECK(hipMemcpyAsync(dtt, d.src_rows, nc * d.n_rows * d.elem, hipMemcpyDeviceToHost, d.stream));
-            if (dfields && !df_on_device && en > 0) {   // (a host copy: the relaxed buffer as it is, the columns of a node parted here)
-                if (K == 1) {
-                    HIP_CHECK(hipMemcpyAsync(dfields, mu, en * d.elem, hipMemcpyDeviceToHost, d.stream));
-                } else {
-                    std::vector<char> tmp(en * K * d.elem);
-                    HIP_CHECK(hipMemcpyAsync(tmp.data(), mu, tmp.size(), hipMemcpyDeviceToHost, d.stream));
-                    HIP_CHECK(hipStreamSynchronize(d.stream));
-                    char* out = (char*)dfields;
-                    for (size_t k = 0; k < nc; ++k)
-                        for (size_t i = 0; i < en; ++i) std::memcpy(out + (k * en + i) * d.elem, tmp.data() + (i * K + k) * d.elem, d.elem);
-                }
-            }
-            HIP_CHECK(hipStreamSynchronize(d.stream));
-            if (passes) *passes = np;
-        });
+
+// vjp, hold and vjp_source: one body.  They differ in the adj_* that runs, in whether grad may be null (the entries check) and in gsrc.
+enum TapeBack { TAPE_VJP, TAPE_HOLD, TAPE_VJP_SOURCE };
+static int tape_back(const ttcr_fsm_adjoint* t, TapeBack which, const void* w, int w_on_device, const void* field_cot, int fc_on_device,
+                     void* grad, int grad_on_device, void* gsrc, int gsrc_on_device, int schedule, int* passes) {
+    return tape_call(t, schedule, passes, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int& np, int&) {
+        using T = decltype(tag);
+        if (which == TAPE_VJP_SOURCE) ttcr_amd::adj_src_prepare<T>(d);
+        const T* dw = stage_in<T>(d, w, w_on_device, d.w_tmp, d.n_rows);
+        const T* dfc = stage_in<T>(d, field_cot, fc_on_device, d.lam2, d.n_events * d.nn);
+        T* dg = stage_dst<T>(grad, grad_on_device, d.model_tmp());
+        T* dgs = stage_dst<T>(gsrc, gsrc_on_device, d.src_io);
+        if (which == TAPE_VJP) np = ttcr_amd::adj_vjp<T>(d, dw, dfc, dg, schedule);
+        else if (which == TAPE_HOLD) np = ttcr_amd::adj_hold<T>(d, dw, dfc, dg, schedule);
+        else np = ttcr_amd::adj_vjp_source<T>(d, dw, dfc, dg, dgs, schedule);
+        stage_out<T>(d, grad, grad_on_device, d.model_tmp(), d.n_model());
+        stage_out<T>(d, gsrc, gsrc_on_device, d.src_io, 4 * d.n_points);
     });
+}
+int ttcr_fsm_adjoint_vjp(const ttcr_fsm_adjoint* t, const void* w, int w_on_device, const void* field_cot, int fc_on_device, void* grad,
+                         int grad_on_device, int schedule, int* passes) {
+    if (!t || !grad || (!w && !field_cot))
+        return tape_arg_error(!t ? "null tape" : (!grad ? "null grad" : "w and field_cot are both null: nothing to back-propagate"));
+    return tape_back(t, TAPE_VJP, w, w_on_device, field_cot, fc_on_device, grad, grad_on_device, nullptr, 0, schedule, passes);
 }
 int ttcr_fsm_adjoint_vjp_source(const ttcr_fsm_adjoint* t, const void* w, int w_on_device, const void* field_cot, int fc_on_device, void* grad,
                                 int grad_on_device, void* gsrc, int gsrc_on_device, int schedule, int* passes) {
-    if (!t || !gsrc || (!w && !field_cot)) {
-        g_last_error = !t ? "null tape" : (!gsrc ? "null gsrc" : "w and field_cot are both null: nothing to back-propagate");
-        return TTCR_ERR_VALUE;
-    }
-    if (schedule != 0 && schedule != 1) {
-        g_last_error = "schedule: 0 (tiled) or 1 (global Jacobi)";
-        return TTCR_ERR_VALUE;
-    }
-    ttcr_fsm_adjoint* tm = const_cast<ttcr_fsm_adjoint*>(t);
-    std::lock_guard<std::mutex> lock(tm->mu);
-    return guarded([&] {
-        ttcr_amd::AdjTapeDev& d = tm->t;
-        adj_device_errors([&] {
-            HIP_CHECK(hipSetDevice(d.device));
-            if (tm->dtype == TTCR_F32) ttcr_amd::adj_src_prepare<float>(d);
-            else ttcr_amd::adj_src_prepare<double>(d);
-            const void* dw = w;
-            const void* dfc = field_cot;
-            void* dg = grad ? (grad_on_device ? grad : d.model_tmp()) : nullptr;
-            void* dgs = gsrc_on_device ? gsrc : d.src_io;
-            if (w && !w_on_device) {
-                if (d.n_rows > 0) HIP_CHECK(hipMemcpyAsync(d.w_tmp, w, d.n_rows * d.elem, hipMemcpyHostToDevice, d.stream));
-                dw = d.w_tmp;
-            }
-            if (field_cot && !fc_on_device) {   // (staged as ttcr_fsm_adjoint_vjp stages it)
-                if (d.n_events * d.nn > 0)
-                    HIP_CHECK(hipMemcpyAsync(d.lam2, field_cot, d.n_events * d.nn * d.elem, hipMemcpyHostToDevice, d.stream));
-                dfc = d.lam2;
-            }
-            int np = 0;
-            if (tm->dtype == TTCR_F32)
-                np = ttcr_amd::adj_vjp_source<float>(d, (const float*)dw, (const float*)dfc, (float*)dg, (float*)dgs, schedule);
-            else
-                np = ttcr_amd::adj_vjp_source<double>(d, (const double*)dw, (const double*)dfc, (double*)dg, (double*)dgs, schedule);
-            if (grad && !grad_on_device && d.n_model() > 0)
-                HIP_CHECK(hipMemcpyAsync(grad, d.model_tmp(), d.n_model() * d.elem, hipMemcpyDeviceToHost, d.stream));
-            if (!gsrc_on_device && d.n_points > 0)
-                HIP_CHECK(hipMemcpyAsync(gsrc, d.src_io, 4 * d.n_points * d.elem, hipMemcpyDeviceToHost, d.stream));
-            HIP_CHECK(hipStreamSynchronize(d.stream));
-            if (passes) *passes = np;
-        });
-    });
+    if (!t || !gsrc || (!w && !field_cot))
+        return tape_arg_error(!t ? "null tape" : (!gsrc ? "null gsrc" : "w and field_cot are both null: nothing to back-propagate"));
+    return tape_back(t, TAPE_VJP_SOURCE, w, w_on_device, field_cot, fc_on_device, grad, grad_on_device, gsrc, gsrc_on_device, schedule,
+                     passes);
 }
-// ---- second-order products of the field tape
+// (second-order products, DESIGN.md 6f: hold keeps the lam of this vjp on the tape)
 int ttcr_fsm_adjoint_hold(ttcr_fsm_adjoint* t, const void* w, int w_on_device, const void* field_cot, int fc_on_device, void* grad,
                           int grad_on_device, int schedule, int* passes) {
-    if (!t || (!w && !field_cot)) {
-        g_last_error = !t ? "null tape" : "w and field_cot are both null: no cotangent to hold";
-        return TTCR_ERR_VALUE;
-    }
-    if (schedule != 0 && schedule != 1) {
-        g_last_error = "schedule: 0 (tiled) or 1 (global Jacobi)";
-        return TTCR_ERR_VALUE;
-    }
-    std::lock_guard<std::mutex> lock(t->mu);
-    return guarded([&] {
-        ttcr_amd::AdjTapeDev& d = t->t;
-        adj_device_errors([&] {
-            HIP_CHECK(hipSetDevice(d.device));
-            const void* dw = w;
-            const void* dfc = field_cot;
-            void* dg = grad ? (grad_on_device ? grad : d.model_tmp()) : nullptr;
-            if (w && !w_on_device) {
-                if (d.n_rows > 0) HIP_CHECK(hipMemcpyAsync(d.w_tmp, w, d.n_rows * d.elem, hipMemcpyHostToDevice, d.stream));
-                dw = d.w_tmp;
-            }
-            if (field_cot && !fc_on_device) {   // (staged as ttcr_fsm_adjoint_vjp stages it)
-                if (d.n_events * d.nn > 0)
-                    HIP_CHECK(hipMemcpyAsync(d.lam2, field_cot, d.n_events * d.nn * d.elem, hipMemcpyHostToDevice, d.stream));
-                dfc = d.lam2;
-            }
-            int np = 0;
-            if (t->dtype == TTCR_F32) np = ttcr_amd::adj_hold<float>(d, (const float*)dw, (const float*)dfc, (float*)dg, schedule);
-            else np = ttcr_amd::adj_hold<double>(d, (const double*)dw, (const double*)dfc, (double*)dg, schedule);
-            if (grad && !grad_on_device && d.n_model() > 0)
-                HIP_CHECK(hipMemcpyAsync(grad, d.model_tmp(), d.n_model() * d.elem, hipMemcpyDeviceToHost, d.stream));
-            HIP_CHECK(hipStreamSynchronize(d.stream));
-            if (passes) *passes = np;
-        });
-    });
+    if (!t || (!w && !field_cot)) return tape_arg_error(!t ? "null tape" : "w and field_cot are both null: no cotangent to hold");
+    return tape_back(t, TAPE_HOLD, w, w_on_device, field_cot, fc_on_device, grad, grad_on_device, nullptr, 0, schedule, passes);
 }
 int ttcr_fsm_adjoint_release(ttcr_fsm_adjoint* t) {
-    if (!t) {
-        g_last_error = "null tape";
-        return TTCR_ERR_VALUE;
-    }
+    if (!t) return tape_arg_error("null tape");
     std::lock_guard<std::mutex> lock(t->mu);
     return guarded([&] { ttcr_amd::adj_release_hold(t->t); });
 }
-// hvp and newton: one body (row_weight is NULL for the hvp)
-static int adjoint_second_order(ttcr_fsm_adjoint* t, const char* what, const void* v, int v_on_device, const void* row_weight,
-                                int rw_on_device, bool newton, void* out, int out_on_device, int schedule, int* passes_jvp,
-                                int* passes_vjp) {
-    if (!t || !v || !out) {
-        g_last_error = !t ? "null tape" : (!v ? "null v" : "null out");
-        return TTCR_ERR_VALUE;
-    }
-    if (schedule != 0 && schedule != 1) {
-        g_last_error = "schedule: 0 (tiled) or 1 (global Jacobi)";
-        return TTCR_ERR_VALUE;
-    }
-    std::lock_guard<std::mutex> lock(t->mu);
-    if (!t->t.held) {
-        g_last_error = std::string(what) + ": the tape holds no cotangent (call ttcr_fsm_adjoint_hold first)";
-        return TTCR_ERR_VALUE;
-    }
-    return guarded([&] {
-        ttcr_amd::AdjTapeDev& d = t->t;
-        adj_device_errors([&] {
-            HIP_CHECK(hipSetDevice(d.device));
-            const void* dv = v;
-            if (!v_on_device) {   // (read by the tangent relaxation and by the last kernel, which writes the host result to the same place)
-                if (d.n_model() > 0) HIP_CHECK(hipMemcpyAsync(d.model_tmp(), v, d.n_model() * d.elem, hipMemcpyHostToDevice, d.stream));
-                dv = d.model_tmp();
-            }
-            void* dout = out_on_device ? out : d.model_tmp();
-            const bool stage_rw = row_weight && !rw_on_device;
-            int pj = 0, pv = 0;
-            if (stage_rw) {   // (the staging row is part of what the first jvp allocates)
-                if (t->dtype == TTCR_F32) ttcr_amd::adj_jvp_prepare<float>(d);
-                else ttcr_amd::adj_jvp_prepare<double>(d);
-                if (d.n_rows > 0) HIP_CHECK(hipMemcpyAsync(d.rw_tmp, row_weight, d.n_rows * d.elem, hipMemcpyHostToDevice, d.stream));
-            }
-            const void* drw = row_weight ? (rw_on_device ? row_weight : d.rw_tmp) : nullptr;
-            if (t->dtype == TTCR_F32)
-                ttcr_amd::adj_hess<float>(d, (const float*)dv, (const float*)drw, newton, (float*)dout, schedule, &pj, &pv);
-            else ttcr_amd::adj_hess<double>(d, (const double*)dv, (const double*)drw, newton, (double*)dout, schedule, &pj, &pv);
-            if (!out_on_device && d.n_model() > 0)
-                HIP_CHECK(hipMemcpyAsync(out, d.model_tmp(), d.n_model() * d.elem, hipMemcpyDeviceToHost, d.stream));
-            HIP_CHECK(hipStreamSynchronize(d.stream));
-            if (passes_jvp) *passes_jvp = pj;
-            if (passes_vjp) *passes_vjp = pv;
-        });
+
+int ttcr_fsm_adjoint_jvp(const ttcr_fsm_adjoint* t, const void* ds, int ds_on_device, void* dtt, int dtt_on_device, void* dfields,
+                         int df_on_device, int schedule, int* passes) {
+    if (!t || !ds || (!dtt && !dfields))
+        return tape_arg_error(!t ? "null tape" : (!ds ? "null ds" : "dtt and dfields are both null: nothing to compute"));
+    return tape_call(t, schedule, passes, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int& np, int&) {
+        using T = decltype(tag);
+        const T* dds = stage_in<T>(d, ds, ds_on_device, d.model_tmp(), d.n_model());
+        np = ttcr_amd::adj_jvp<T>(d, dds, stage_dst<T>(dtt, dtt_on_device, d.w_tmp), df_on_device ? (T*)dfields : nullptr, schedule);
+        stage_out<T>(d, dtt, dtt_on_device, d.w_tmp, d.n_rows);
+        stage_out<T>(d, dfields, df_on_device, (schedule != 0 && np % 2 == 1) ? d.lam2 : d.lam, d.n_events * d.nn);
     });
+}
+int ttcr_fsm_adjoint_jvp_source(const ttcr_fsm_adjoint* t, const void* dsrc, int dsrc_on_device, int n_cols, void* dtt, int dtt_on_device,
+                                void* dfields, int df_on_device, int schedule, int* passes) {
+    if (!t || !dsrc || (!dtt && !dfields))
+        return tape_arg_error(!t ? "null tape" : (!dsrc ? "null dsrc" : "dtt and dfields are both null: nothing to compute"));
+    if (n_cols < 1 || n_cols > 4) return tape_arg_error("n_cols: 1 to 4 columns per call");
+    return tape_call(t, schedule, passes, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int& np, int&) {
+        using T = decltype(tag);
+        const size_t en = d.n_events * d.nn, nc = (size_t)n_cols;
+        ttcr_amd::adj_src_prepare<T>(d);
+        const T* dd = stage_in<T>(d, dsrc, dsrc_on_device, d.src_io, nc * d.n_points * 4);
+        int K = 1;
+        const T* mu = nullptr;
+        np = ttcr_amd::adj_jvp_source<T>(d, dd, n_cols, stage_dst<T>(dtt, dtt_on_device, d.src_rows), df_on_device ? (T*)dfields : nullptr,
+                                         schedule, &mu, &K);
+        stage_out<T>(d, dtt, dtt_on_device, d.src_rows, nc * d.n_rows);
+        if (K == 1) {
+            stage_out<T>(d, dfields, df_on_device, mu, en);
+        } else if (dfields && !df_on_device && en > 0) {   // (the K columns of a node are adjacent in the relaxed buffer: parted here)
+            std::vector<T> tmp(en * K);
+            HIP_CHECK(hipMemcpyAsync(tmp.data(), mu, tmp.size() * sizeof(T), hipMemcpyDeviceToHost, d.stream));
+            HIP_CHECK(hipStreamSynchronize(d.stream));
+            for (size_t k = 0; k < nc; ++k)
+                for (size_t i = 0; i < en; ++i) ((T*)dfields)[k * en + i] = tmp[i * K + k];
+        }
+    });
+}
+
+// gn, hvp and newton: one body.  held_for names the product that reads the held cotangent (null: gn); row_weight is null for the hvp.
+static int tape_normal(const ttcr_fsm_adjoint* t, const char* held_for, bool newton, const void* v, int v_on_device, const void* row_weight,
+                       int rw_on_device, void* out, int out_on_device, int schedule, int* passes_jvp, int* passes_vjp) {
+    if (!t || !v || !out) return tape_arg_error(!t ? "null tape" : (!v ? "null v" : "null out"));
+    return tape_call(t, schedule, passes_jvp, passes_vjp, [&](ttcr_amd::AdjTapeDev& d, auto tag, int& pj, int& pv) {
+        using T = decltype(tag);
+        const T* dv = stage_in<T>(d, v, v_on_device, d.model_tmp(), d.n_model());
+        if (row_weight && !rw_on_device) ttcr_amd::adj_jvp_prepare<T>(d);
+        const T* drw = stage_in<T>(d, row_weight, rw_on_device, d.rw_tmp, d.n_rows);
+        T* dout = stage_dst<T>(out, out_on_device, d.model_tmp());
+        if (held_for) ttcr_amd::adj_hess<T>(d, dv, drw, newton, dout, schedule, &pj, &pv);
+        else ttcr_amd::adj_gn<T>(d, dv, drw, dout, schedule, &pj, &pv);
+        stage_out<T>(d, out, out_on_device, d.model_tmp(), d.n_model());
+    }, held_for);
+}
+int ttcr_fsm_adjoint_gn(const ttcr_fsm_adjoint* t, const void* v, int v_on_device, const void* row_weight, int rw_on_device, void* out,
+                        int out_on_device, int schedule, int* passes_jvp, int* passes_vjp) {
+    return tape_normal(t, nullptr, false, v, v_on_device, row_weight, rw_on_device, out, out_on_device, schedule, passes_jvp, passes_vjp);
 }
 int ttcr_fsm_adjoint_hvp(ttcr_fsm_adjoint* t, const void* v, int v_on_device, void* out, int out_on_device, int schedule, int* passes_jvp,
                          int* passes_vjp) {
-    return adjoint_second_order(t, "hvp", v, v_on_device, nullptr, 0, false, out, out_on_device, schedule, passes_jvp, passes_vjp);
+    return tape_normal(t, "hvp", false, v, v_on_device, nullptr, 0, out, out_on_device, schedule, passes_jvp, passes_vjp);
 }
 int ttcr_fsm_adjoint_newton(ttcr_fsm_adjoint* t, const void* v, int v_on_device, const void* row_weight, int rw_on_device, void* out,
                             int out_on_device, int schedule, int* passes_jvp, int* passes_vjp) {
-    return adjoint_second_order(t, "newton", v, v_on_device, row_weight, rw_on_device, true, out, out_on_device, schedule, passes_jvp,
-                                passes_vjp);
+    return tape_normal(t, "newton", true, v, v_on_device, row_weight, rw_on_device, out, out_on_device, schedule, passes_jvp, passes_vjp);
 }
+
 // ---- block products of the field tape: n_cols model vectors per call, relaxed in groups of four
 // the argument checks the three products share: what needs no tape first, the tape last (null: no message)
 static const char* adjoint_block_args(const ttcr_fsm_adjoint* t, int n_cols, const void* in, const char* in_null, bool have_out,
                                       const char* out_null, int schedule) {
     if (n_cols < 1) return "n_cols: at least one column per call";
-    if (schedule != 0 && schedule != 1) return "schedule: 0 (tiled) or 1 (global Jacobi)";
+    if (const char* bad = schedule_error(schedule)) return bad;
     if (!in) return in_null;
     if (!have_out) return out_null;
     if (!t) return "null tape";
     return nullptr;
 }
-extern "C++" {
-template <typename T>
-static void adjoint_jvp_block_run(ttcr_amd::AdjTapeDev& d, int n_cols, const void* ds, int ds_on_device, void* dtt, int dtt_on_device,
-                                  void* dfields, int df_on_device, int schedule, int* passes) {
-    HIP_CHECK(hipSetDevice(d.device));
-    ttcr_amd::adj_block_prepare<T>(d);
-    const size_t en = d.n_events * d.nn, nm = d.n_model(), nr = d.n_rows;
-    int np = 0;
-    for (int c0 = 0; c0 < n_cols; c0 += 4) {
-        const size_t nc = (size_t)std::min(4, n_cols - c0);
-        const T* in = (const T*)ds + (size_t)c0 * nm;
-        if (!ds_on_device) {
-            if (nm > 0) HIP_CHECK(hipMemcpyAsync(d.blk_model, in, nc * nm * sizeof(T), hipMemcpyHostToDevice, d.stream));
-            in = (const T*)d.blk_model;
-        }
-        T* ddtt = dtt ? (dtt_on_device ? (T*)dtt + (size_t)c0 * nr : (T*)d.blk_rows) : nullptr;
-        T* ddf = dfields ? (df_on_device ? (T*)dfields + (size_t)c0 * en : (T*)d.g4) : nullptr;   // (g4 is idle during a jvp)
-        np += ttcr_amd::adj_jvp_block<T>(d, in, (int)nc, ddtt, ddf, schedule);
-        if (dtt && !dtt_on_device && nr > 0)
-            HIP_CHECK(hipMemcpyAsync((T*)dtt + (size_t)c0 * nr, d.blk_rows, nc * nr * sizeof(T), hipMemcpyDeviceToHost, d.stream));
-        if (dfields && !df_on_device && en > 0)
-            HIP_CHECK(hipMemcpyAsync((T*)dfields + (size_t)c0 * en, d.g4, nc * en * sizeof(T), hipMemcpyDeviceToHost, d.stream));
-    }
-    HIP_CHECK(hipStreamSynchronize(d.stream));
-    if (passes) *passes = np;
-}
-template <typename T>
-static void adjoint_vjp_block_run(ttcr_amd::AdjTapeDev& d, int n_cols, const void* w, int w_on_device, void* grad, int grad_on_device,
-                                  int schedule, int* passes) {
-    HIP_CHECK(hipSetDevice(d.device));
-    ttcr_amd::adj_block_prepare<T>(d);
-    const size_t nm = d.n_model(), nr = d.n_rows;
-    int np = 0;
-    for (int c0 = 0; c0 < n_cols; c0 += 4) {
-        const size_t nc = (size_t)std::min(4, n_cols - c0);
-        const T* in = (const T*)w + (size_t)c0 * nr;
-        if (!w_on_device) {
-            if (nr > 0) HIP_CHECK(hipMemcpyAsync(d.blk_rows, in, nc * nr * sizeof(T), hipMemcpyHostToDevice, d.stream));
-            in = (const T*)d.blk_rows;
-        }
-        T* dg = grad_on_device ? (T*)grad + (size_t)c0 * nm : (T*)d.blk_model;
-        np += ttcr_amd::adj_vjp_block<T>(d, in, (int)nc, dg, schedule);
-        if (!grad_on_device && nm > 0)
-            HIP_CHECK(hipMemcpyAsync((T*)grad + (size_t)c0 * nm, d.blk_model, nc * nm * sizeof(T), hipMemcpyDeviceToHost, d.stream));
-    }
-    HIP_CHECK(hipStreamSynchronize(d.stream));
-    if (passes) *passes = np;
-}
-template <typename T>
-static void adjoint_gn_block_run(ttcr_amd::AdjTapeDev& d, int n_cols, const void* v, int v_on_device, const void* row_weight, int rw_cols,
-                                 int rw_on_device, void* out, int out_on_device, int schedule, int* passes_jvp, int* passes_vjp) {
-    HIP_CHECK(hipSetDevice(d.device));
-    ttcr_amd::adj_block_prepare<T>(d);
-    const size_t nm = d.n_model(), nr = d.n_rows;
-    const bool shared = rw_cols == 1;
-    if (rw_cols > 0 && !rw_on_device && shared && nr > 0)
-        HIP_CHECK(hipMemcpyAsync(d.blk_rw, row_weight, nr * sizeof(T), hipMemcpyHostToDevice, d.stream));
-    int pj = 0, pv = 0;
-    for (int c0 = 0; c0 < n_cols; c0 += 4) {
-        const size_t nc = (size_t)std::min(4, n_cols - c0);
-        const T* in = (const T*)v + (size_t)c0 * nm;
-        if (!v_on_device) {   // (consumed by the jvp before the vjp writes the host columns to the same place)
-            if (nm > 0) HIP_CHECK(hipMemcpyAsync(d.blk_model, in, nc * nm * sizeof(T), hipMemcpyHostToDevice, d.stream));
-            in = (const T*)d.blk_model;
-        }
-        const T* drw = nullptr;
-        if (rw_cols > 0) {
-            const T* src = (const T*)row_weight + (shared ? 0 : (size_t)c0 * nr);
-            if (!rw_on_device) {
-                if (!shared && nr > 0) HIP_CHECK(hipMemcpyAsync(d.blk_rw, src, nc * nr * sizeof(T), hipMemcpyHostToDevice, d.stream));
-                src = (const T*)d.blk_rw;
-            }
-            drw = src;
-        }
-        T* dout = out_on_device ? (T*)out + (size_t)c0 * nm : (T*)d.blk_model;
-        int gj = 0, gv = 0;
-        ttcr_amd::adj_gn_block<T>(d, in, drw, shared ? 0 : nr, (int)nc, dout, schedule, &gj, &gv);
-        pj += gj;
-        pv += gv;
-        if (!out_on_device && nm > 0)
-            HIP_CHECK(hipMemcpyAsync((T*)out + (size_t)c0 * nm, d.blk_model, nc * nm * sizeof(T), hipMemcpyDeviceToHost, d.stream));
-    }
-    HIP_CHECK(hipStreamSynchronize(d.stream));
-    if (passes_jvp) *passes_jvp = pj;
-    if (passes_vjp) *passes_vjp = pv;
-}
-}  // extern "C++"
 int ttcr_fsm_adjoint_jvp_block(const ttcr_fsm_adjoint* t, int n_cols, const void* ds, int ds_on_device, void* dtt, int dtt_on_device,
                                void* dfields, int df_on_device, int schedule, int* passes) {
     if (const char* bad = adjoint_block_args(t, n_cols, ds, "null ds", dtt || dfields, "dtt and dfields are both null: nothing to compute",
-                                             schedule)) {
-        g_last_error = bad;
-        return TTCR_ERR_VALUE;
-    }
-    ttcr_fsm_adjoint* tm = const_cast<ttcr_fsm_adjoint*>(t);
-    std::lock_guard<std::mutex> lock(tm->mu);
-    return guarded([&] {
-        adj_device_errors([&] {
-            if (tm->dtype == TTCR_F32)
-                adjoint_jvp_block_run<float>(tm->t, n_cols, ds, ds_on_device, dtt, dtt_on_device, dfields, df_on_device, schedule, passes);
-            else adjoint_jvp_block_run<double>(tm->t, n_cols, ds, ds_on_device, dtt, dtt_on_device, dfields, df_on_device, schedule, passes);
-        });
+                                             schedule))
+        return tape_arg_error(bad);
+    return tape_call(t, schedule, passes, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int& np, int&) {
+        using T = decltype(tag);
+        ttcr_amd::adj_block_prepare<T>(d);
+        const size_t en = d.n_events * d.nn, nm = d.n_model(), nr = d.n_rows;
+        for (int c0 = 0; c0 < n_cols; c0 += 4) {
+            const size_t nc = (size_t)std::min(4, n_cols - c0);
+            const T* in = stage_in<T>(d, (const T*)ds + (size_t)c0 * nm, ds_on_device, d.blk_model, nc * nm);
+            T* gdtt = dtt ? (T*)dtt + (size_t)c0 * nr : nullptr;   // (the group's columns of the caller's arrays)
+            T* gdf = dfields ? (T*)dfields + (size_t)c0 * en : nullptr;
+            np += ttcr_amd::adj_jvp_block<T>(d, in, (int)nc, stage_dst<T>(gdtt, dtt_on_device, d.blk_rows),
+                                             stage_dst<T>(gdf, df_on_device, d.g4), schedule);
+            stage_out<T>(d, gdtt, dtt_on_device, d.blk_rows, nc * nr);
+            stage_out<T>(d, gdf, df_on_device, d.g4, nc * en);
+        }
     });
 }
 int ttcr_fsm_adjoint_vjp_block(const ttcr_fsm_adjoint* t, int n_cols, const void* w, int w_on_device, void* grad, int grad_on_device,
                                int schedule, int* passes) {
-    if (const char* bad = adjoint_block_args(t, n_cols, w, "null w", grad != nullptr, "null grad", schedule)) {
-        g_last_error = bad;
-        return TTCR_ERR_VALUE;
-    }
-    ttcr_fsm_adjoint* tm = const_cast<ttcr_fsm_adjoint*>(t);
-    std::lock_guard<std::mutex> lock(tm->mu);
-    return guarded([&] {
-        adj_device_errors([&] {
-            if (tm->dtype == TTCR_F32) adjoint_vjp_block_run<float>(tm->t, n_cols, w, w_on_device, grad, grad_on_device, schedule, passes);
-            else adjoint_vjp_block_run<double>(tm->t, n_cols, w, w_on_device, grad, grad_on_device, schedule, passes);
-        });
+    if (const char* bad = adjoint_block_args(t, n_cols, w, "null w", grad != nullptr, "null grad", schedule)) return tape_arg_error(bad);
+    return tape_call(t, schedule, passes, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int& np, int&) {
+        using T = decltype(tag);
+        ttcr_amd::adj_block_prepare<T>(d);
+        const size_t nm = d.n_model(), nr = d.n_rows;
+        for (int c0 = 0; c0 < n_cols; c0 += 4) {
+            const size_t nc = (size_t)std::min(4, n_cols - c0);
+            const T* in = stage_in<T>(d, (const T*)w + (size_t)c0 * nr, w_on_device, d.blk_rows, nc * nr);
+            T* gg = (T*)grad + (size_t)c0 * nm;
+            np += ttcr_amd::adj_vjp_block<T>(d, in, (int)nc, stage_dst<T>(gg, grad_on_device, d.blk_model), schedule);
+            stage_out<T>(d, gg, grad_on_device, d.blk_model, nc * nm);
+        }
     });
 }
 int ttcr_fsm_adjoint_gn_block(const ttcr_fsm_adjoint* t, int n_cols, const void* v, int v_on_device, const void* row_weight, int rw_cols,
@@ -4377,28 +4162,28 @@ int ttcr_fsm_adjoint_gn_block(const ttcr_fsm_adjoint* t, int n_cols, const void*
     if (n_cols >= 1 && rw_cols != 0 && rw_cols != 1 && rw_cols != n_cols) bad = "rw_cols: 0 (no row_weight), 1 (one set for every column) or n_cols";
     else if (n_cols >= 1 && rw_cols != 0 && !row_weight) bad = "null row_weight with rw_cols != 0";
     else bad = adjoint_block_args(t, n_cols, v, "null v", out != nullptr, "null out", schedule);
-    if (bad) {
-        g_last_error = bad;
-        return TTCR_ERR_VALUE;
-    }
-    ttcr_fsm_adjoint* tm = const_cast<ttcr_fsm_adjoint*>(t);
-    std::lock_guard<std::mutex> lock(tm->mu);
-    return guarded([&] {
-        adj_device_errors([&] {
-            if (tm->dtype == TTCR_F32)
-                adjoint_gn_block_run<float>(tm->t, n_cols, v, v_on_device, row_weight, rw_cols, rw_on_device, out, out_on_device, schedule,
-                                            passes_jvp, passes_vjp);
-            else
-                adjoint_gn_block_run<double>(tm->t, n_cols, v, v_on_device, row_weight, rw_cols, rw_on_device, out, out_on_device, schedule,
-                                             passes_jvp, passes_vjp);
-        });
+    if (bad) return tape_arg_error(bad);
+    return tape_call(t, schedule, passes_jvp, passes_vjp, [&](ttcr_amd::AdjTapeDev& d, auto tag, int& pj, int& pv) {
+        using T = decltype(tag);
+        ttcr_amd::adj_block_prepare<T>(d);
+        const size_t nm = d.n_model(), nr = d.n_rows;
+        const bool shared = rw_cols == 1;
+        const T* drw = shared ? stage_in<T>(d, row_weight, rw_on_device, d.blk_rw, nr) : nullptr;
+        for (int c0 = 0; c0 < n_cols; c0 += 4) {
+            const size_t nc = (size_t)std::min(4, n_cols - c0);
+            const T* in = stage_in<T>(d, (const T*)v + (size_t)c0 * nm, v_on_device, d.blk_model, nc * nm);
+            if (rw_cols > 1) drw = stage_in<T>(d, (const T*)row_weight + (size_t)c0 * nr, rw_on_device, d.blk_rw, nc * nr);
+            T* gout = (T*)out + (size_t)c0 * nm;
+            int gj = 0, gv = 0;
+            ttcr_amd::adj_gn_block<T>(d, in, drw, shared ? 0 : nr, (int)nc, stage_dst<T>(gout, out_on_device, d.blk_model), schedule, &gj, &gv);
+            pj += gj;
+            pv += gv;
+            stage_out<T>(d, gout, out_on_device, d.blk_model, nc * nm);
+        }
     });
 }
 int ttcr_fsm_adjoint_block_release(ttcr_fsm_adjoint* t) {
-    if (!t) {
-        g_last_error = "null tape";
-        return TTCR_ERR_VALUE;
-    }
+    if (!t) return tape_arg_error("null tape");
     std::lock_guard<std::mutex> lock(t->mu);
     return guarded([&] { ttcr_amd::adj_block_release(t->t); });
 }

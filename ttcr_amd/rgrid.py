@@ -16,6 +16,7 @@ ray traced back through the field).  What is not on the FSM hot path raises NotI
 (SPM/DSPM, compute_L).  There is no CPU fallback.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -577,13 +578,13 @@ class FieldTape:
         _lib.check(lib.ttcr_fsm_adjoint_bytes(handle, C.byref(b)))
         self.device, self.nbytes = d.value, b.value
         self.passes = 0            # relaxation passes of the last vjp or jvp; (jvp, vjp) after gauss_newton
-        self._rows_dev = None
+        self._rows_dev_cache = None
         npt = C.c_size_t(0)
         _lib.check(lib.ttcr_fsm_adjoint_points(handle, C.byref(npt), None))
         self.n_points = npt.value  # source points of all events, in call order
-        ev = np.zeros(max(self.n_points, 1), dtype=np.int32)
-        _lib.check(lib.ttcr_fsm_adjoint_points(handle, C.byref(npt), _ptr(ev)))
-        self.point_event = ev[:self.n_points].astype(np.int64)   # event of every point
+        ev = (C.c_int * max(self.n_points, 1))()
+        _lib.check(lib.ttcr_fsm_adjoint_points(handle, C.byref(npt), ev))
+        self.point_event = np.array(ev[:self.n_points], dtype=np.int64)   # event of every point
 
     def _handle(self):
         if not self._h:
@@ -592,14 +593,161 @@ class FieldTape:
 
     def field(self, event):
         """Host copy of the traveltime field of one event: n_nodes values of the grid dtype, node order (x fastest)."""
-        out = np.empty(max(self.n_nodes, 1), dtype=self.dtype)
-        _lib.check(self._lib.ttcr_fsm_adjoint_get_field(self._handle(), int(event), _ptr(out)))
-        return out[:self.n_nodes]
+        p, _, finish = self._out(None, 1, self.n_nodes)
+        _lib.check(self._lib.ttcr_fsm_adjoint_get_field(self._handle(), int(event), p))
+        return finish()[0]
 
     def _schedule(self, schedule):
         if schedule not in self.SCHEDULES:
             raise ValueError("schedule should be 'tiled' or 'jacobi', got %r" % (schedule,))
         return self.SCHEDULES[schedule]
+
+    # ---- marshalling (DESIGN.md 6h).  Every product below is: check and convert the inputs (_*_arg), make the outputs where the result is
+    # to live (_out, _model_out), _sync, the C call, passes, _refresh_nbytes, finish().  A CUDA tensor is used in place on the tape's device;
+    # numpy arrays, CPU tensors and sequences go in as host pointers, which the C entry stages.  Only these helpers build pointers.
+    @property
+    def _tdt(self):
+        import torch
+
+        return torch.float32 if self.dtype == np.float32 else torch.float64
+
+    @property
+    def _dev(self):
+        import torch
+
+        return torch.device('cuda', self.device)
+
+    @property
+    def _rows_dev(self):
+        if self._rows_dev_cache is None:
+            import torch
+
+            self._rows_dev_cache = torch.as_tensor(self._rows, device=self._dev)
+        return self._rows_dev_cache
+
+    @staticmethod
+    def _is_torch(a):
+        return type(a).__module__.startswith('torch')
+
+    @staticmethod
+    def _on_device(a):
+        return type(a).__module__.startswith('torch') and a.device.type == 'cuda'
+
+    def _seen(self, a):
+        """an input as the checks look at it: a CUDA tensor as it is, anything else as a numpy array"""
+        return a if self._on_device(a) else np.asarray(a.detach().numpy() if hasattr(a, 'detach') else a)
+
+    def _arg(self, a, rows_axis=None):
+        """(array, pointer, on_device) of an input that _seen has looked at: grid dtype, contiguous, a one-element dummy if it is empty.
+        rows_axis: that axis holds one value per data row (rcv order) and is permuted to tape row order."""
+        if self._on_device(a):
+            import torch
+
+            a = a.detach().to(device=self._dev, dtype=self._tdt)
+            if rows_axis is not None:
+                a = a.index_select(rows_axis, self._rows_dev)
+            a = a.contiguous()
+            if a.numel() == 0:
+                a = torch.zeros(1, dtype=self._tdt, device=self._dev)
+            return a, C.c_void_p(a.data_ptr()), 1
+        a = np.ascontiguousarray(a if rows_axis is None else a.take(self._rows, axis=rows_axis), dtype=self.dtype)
+        if a.size == 0:
+            a = np.zeros(1, dtype=self.dtype)
+        return a, _ptr(a), 0
+
+    def _model_arg(self, v, name):
+        """a model vector: (array, pointer, on_device)"""
+        v = self._seen(v)
+        if math.prod(v.shape) != self.n_cols:
+            raise ValueError('%s should hold %d values (one per %s), got shape %s' % (name, self.n_cols, self._per, tuple(v.shape)))
+        return self._arg(v)
+
+    def _row_arg(self, w, name):
+        """a per-data-row vector, handed over in tape row order: (array, pointer, on_device)"""
+        w = self._seen(w)
+        if len(w.shape) != 1 or w.shape[0] != self.n_data:
+            raise ValueError('%s should hold %d values (one per data row), got shape %s' % (name, self.n_data, tuple(w.shape)))
+        return self._arg(w, rows_axis=0)
+
+    def _fields_arg(self, fc):
+        """a field cotangent, (n_events, n_nodes) values: (array, pointer, on_device)"""
+        fc = self._seen(fc)
+        if math.prod(fc.shape) != self.n_events * self.n_nodes:
+            raise ValueError('field_cotangent should hold %d x %d values, got shape %s' % (self.n_events, self.n_nodes, tuple(fc.shape)))
+        return self._arg(fc)
+
+    def _points_arg(self, dsrc):
+        """the source perturbations of jvp_source, (n_points, 4) or (K, n_points, 4): (array, pointer, on_device, K, batched)"""
+        dsrc = self._seen(dsrc)
+        shape = tuple(dsrc.shape)
+        batched = len(shape) == 3
+        if len(shape) not in (2, 3) or shape[-2:] != (self.n_points, 4) or (batched and not 1 <= shape[0] <= 4):
+            raise ValueError('dsrc should be (%d, 4) or (K, %d, 4) with K from 1 to 4, got shape %s' % (self.n_points, self.n_points, shape))
+        return self._arg(dsrc) + (shape[0] if batched else 1, batched)
+
+    def _block_arg(self, a, name, n_last, rows, n_lead=None):
+        """a (K, n_last) array for a block call: (array, pointer, on_device, K).  rows=True: one value per data row, handed over in tape
+        row order.  n_lead: the K the array has to have (row weights)."""
+        a = self._seen(a)
+        shape = tuple(a.shape)
+        if len(shape) != 2 or shape[1] != n_last or shape[0] < 1 or (n_lead is not None and shape[0] != n_lead):
+            raise ValueError('%s should be (%s, %d) with K >= 1, got shape %s' % (name, 'K' if n_lead is None else n_lead, n_last, shape))
+        return self._arg(a, rows_axis=1 if rows else None) + (shape[0],)
+
+    def _out(self, like, K, n_last, rows=False):
+        """a (K, n_last) output where `like` lives (numpy for numpy or None, a CPU tensor for a CPU tensor, a tensor on like's device
+        through one on the tape's device for a CUDA tensor): (pointer, on_device, finish).  rows=True: n_last = n_rows values in tape
+        row order come back as n_data values in rcv order, zeros for the rows that are not on the tape."""
+        if self._on_device(like):
+            import torch
+
+            o = torch.empty(max(K * n_last, 1), dtype=self._tdt, device=self._dev)
+
+            def finish():
+                r = o[:K * n_last].reshape(K, n_last)
+                if rows:
+                    d = torch.zeros((K, self.n_data), dtype=self._tdt, device=self._dev)
+                    d[:, self._rows_dev] = r
+                    r = d
+                return r.to(like.device)
+            return C.c_void_p(o.data_ptr()), 1, finish
+        o = np.empty(max(K * n_last, 1), dtype=self.dtype)
+
+        def finish():
+            r = o[:K * n_last].reshape(K, n_last)
+            if rows:
+                d = np.zeros((K, self.n_data), dtype=self.dtype)
+                d[:, self._rows] = r
+                r = d
+            if self._is_torch(like):
+                import torch
+
+                r = torch.from_numpy(r)
+            return r
+        return _ptr(o), 0, finish
+
+    def _model_out(self, like):
+        """an output model vector where `like` lives: (pointer, on_device, finish)"""
+        p, on_dev, finish = self._out(like, 1, self.n_cols)
+        return p, on_dev, lambda: finish()[0]
+
+    def _first_tensor(self, *args):
+        """the argument the result of vjp / gauss_newton lives with: the first torch tensor, else the first argument given"""
+        given = [a for a in args if a is not None]
+        return next((a for a in given if self._is_torch(a)), given[0])
+
+    def _sync(self, *on_device):
+        """before a device pointer is handed over: what torch has queued on its current stream of the tape's device is done"""
+        if any(on_device):
+            import torch
+
+            torch.cuda.current_stream(self._dev).synchronize()
+
+    def _cotangent(self, w, field_cotangent):
+        """the two cotangent arguments of vjp and hold, either may be None: (arrays kept alive, pw, dw, pf, df)"""
+        wa, pw, dw = self._row_arg(w, 'w') if w is not None else (None, None, 0)
+        fa, pf, df = self._fields_arg(field_cotangent) if field_cotangent is not None else (None, None, 0)
+        return (wa, fa), pw, dw, pf, df
 
     def vjp(self, w=None, field_cotangent=None, schedule='tiled', return_source_grad=False):
         """d loss / d slowness (n_cols values -- nodes, or cells on a cell tape --, x fastest, grid dtype) for  loss = w . tt +
@@ -608,81 +756,26 @@ class FieldTape:
         relaxation (a point whose frozen nodes a later point of its event all overwrote gets zeros).
         w: one value per data row of the raytrace_adjoint call (rcv order); field_cotangent: (n_events, n_nodes) values, node order x
         fastest; either may be None, not both.  schedule: 'tiled' (default) or 'jacobi', the bit-equal baseline.  Torch tensors in give
-        a torch tensor out; tensors on the tape's device are used in place (torch's current stream is synchronised first, the result is
-        ready when the call returns)."""
+        a torch tensor out, where the first of them lives; tensors on the tape's device are used in place (torch's current stream is
+        synchronised first, the result is ready when the call returns)."""
         self._handle()
         sch = self._schedule(schedule)
         if w is None and field_cotangent is None:
             raise ValueError('w and field_cotangent are both None: nothing to back-propagate')
-        if any(type(a).__module__.startswith('torch') for a in (w, field_cotangent) if a is not None):
-            return self._vjp_torch(w, field_cotangent, sch, return_source_grad)
-        wt = fc = None
-        if w is not None:
-            w = np.asarray(w)
-            if w.ndim != 1 or w.shape[0] != self.n_data:
-                raise ValueError('w should hold %d values (one per data row), got shape %s' % (self.n_data, w.shape))
-            wt = np.ascontiguousarray(w[self._rows], dtype=self.dtype)
-        if field_cotangent is not None:
-            fc = np.ascontiguousarray(field_cotangent, dtype=self.dtype)
-            if fc.size != self.n_events * self.n_nodes:
-                raise ValueError('field_cotangent should hold %d x %d values, got shape %s' % (self.n_events, self.n_nodes, fc.shape))
-        g = np.empty(max(self.n_cols, 1), dtype=self.dtype)
+        keep, pw, dw, pf, df = self._cotangent(w, field_cotangent)
+        like = self._first_tensor(w, field_cotangent)
+        pg, dg, fin_g = self._model_out(like)
         np_ = C.c_int(0)
         if return_source_grad:
-            gs = np.zeros((max(self.n_points, 1), 4), dtype=self.dtype)
-            _lib.check(self._lib.ttcr_fsm_adjoint_vjp_source(self._h, _ptr(wt) if wt is not None else None, 0,
-                                                             _ptr(fc) if fc is not None else None, 0, _ptr(g), 0, _ptr(gs), 0, sch,
-                                                             C.byref(np_)))
-            self.passes = np_.value
-            self._refresh_nbytes()
-            return g[:self.n_cols], gs[:self.n_points]
-        _lib.check(self._lib.ttcr_fsm_adjoint_vjp(self._h, _ptr(wt) if wt is not None else None, 0, _ptr(fc) if fc is not None else None, 0,
-                                                  _ptr(g), 0, sch, C.byref(np_)))
+            ps, dsrc, fin_s = self._out(like, self.n_points, 4)
+            self._sync(dw, df, dg, dsrc)
+            _lib.check(self._lib.ttcr_fsm_adjoint_vjp_source(self._h, pw, dw, pf, df, pg, dg, ps, dsrc, sch, C.byref(np_)))
+        else:
+            self._sync(dw, df, dg)
+            _lib.check(self._lib.ttcr_fsm_adjoint_vjp(self._h, pw, dw, pf, df, pg, dg, sch, C.byref(np_)))
         self.passes = np_.value
-        return g[:self.n_cols]
-
-    def _vjp_torch(self, w, fc, sch, source_grad=False):
-        import torch
-
-        tdt = torch.float32 if self.dtype == np.float32 else torch.float64
-        ref = w if (w is not None and type(w).__module__.startswith('torch')) else fc
-        if ref.device.type != 'cuda':
-            host = [a.detach().numpy() if hasattr(a, 'detach') else a for a in (w, fc)]
-            out = self.vjp(host[0], host[1], 'jacobi' if sch else 'tiled', source_grad)
-            if source_grad:
-                return tuple(torch.from_numpy(o).to(ref.device) for o in out)
-            return torch.from_numpy(out).to(ref.device)
-        dev = torch.device('cuda', self.device)
-        wt = fct = None
-        if w is not None:
-            w = torch.as_tensor(w)
-            if w.dim() != 1 or w.shape[0] != self.n_data:
-                raise ValueError('w should hold %d values (one per data row), got shape %s' % (self.n_data, tuple(w.shape)))
-            if self._rows_dev is None:
-                self._rows_dev = torch.as_tensor(self._rows, device=dev)
-            wt = w.detach().to(device=dev, dtype=tdt).index_select(0, self._rows_dev).contiguous()
-        if fc is not None:
-            fc = torch.as_tensor(fc)
-            if fc.numel() != self.n_events * self.n_nodes:
-                raise ValueError('field_cotangent should hold %d x %d values, got shape %s' % (self.n_events, self.n_nodes, tuple(fc.shape)))
-            fct = fc.detach().to(device=dev, dtype=tdt).contiguous()
-        g = torch.empty(max(self.n_cols, 1), dtype=tdt, device=dev)
-        torch.cuda.current_stream(dev).synchronize()
-        np_ = C.c_int(0)
-        if source_grad:
-            gs = torch.zeros((max(self.n_points, 1), 4), dtype=tdt, device=dev)
-            torch.cuda.current_stream(dev).synchronize()
-            _lib.check(self._lib.ttcr_fsm_adjoint_vjp_source(self._h, C.c_void_p(wt.data_ptr()) if wt is not None else None, 1,
-                                                             C.c_void_p(fct.data_ptr()) if fct is not None else None, 1,
-                                                             C.c_void_p(g.data_ptr()), 1, C.c_void_p(gs.data_ptr()), 1, sch, C.byref(np_)))
-            self.passes = np_.value
-            self._refresh_nbytes()
-            return g[:self.n_cols].to(ref.device), gs[:self.n_points].to(ref.device)
-        _lib.check(self._lib.ttcr_fsm_adjoint_vjp(self._h, C.c_void_p(wt.data_ptr()) if wt is not None else None, 1,
-                                                  C.c_void_p(fct.data_ptr()) if fct is not None else None, 1, C.c_void_p(g.data_ptr()), 1,
-                                                  sch, C.byref(np_)))
-        self.passes = np_.value
-        return g[:self.n_cols].to(ref.device)
+        self._refresh_nbytes()
+        return (fin_g(), fin_s()) if return_source_grad else fin_g()
 
     def jvp(self, ds, return_fields=False, schedule='tiled'):
         """J ds: the change of the receiver traveltimes for the slowness perturbation ds (n_cols values -- nodes, or cells on a cell
@@ -693,47 +786,17 @@ class FieldTape:
         allocates the stencil in row order (nbytes grows by it once)."""
         self._handle()
         sch = self._schedule(schedule)
-        if type(ds).__module__.startswith('torch'):
-            return self._jvp_torch(ds, return_fields, sch)
-        ds = np.ascontiguousarray(ds, dtype=self.dtype)
-        if ds.size != self.n_cols:
-            raise ValueError('ds should hold %d values (one per %s), got shape %s' % (self.n_cols, self._per, ds.shape))
-        rows = np.empty(max(self.n_rows, 1), dtype=self.dtype)
-        df = np.empty((self.n_events, self.n_nodes), dtype=self.dtype) if return_fields else None
+        a, pa, da = self._model_arg(ds, 'ds')
+        pr, dr, fin_r = self._out(ds, 1, self.n_rows, rows=True)
+        pf, df, fin_f = self._out(ds, self.n_events, self.n_nodes) if return_fields else (None, 0, None)
+        self._sync(da, dr, df)
         np_ = C.c_int(0)
-        _lib.check(self._lib.ttcr_fsm_adjoint_jvp(self._h, _ptr(ds), 0, _ptr(rows), 0, _ptr(df) if df is not None and df.size else None, 0,
-                                                  sch, C.byref(np_)))
+        want_f = return_fields and self.n_events * self.n_nodes > 0
+        _lib.check(self._lib.ttcr_fsm_adjoint_jvp(self._h, pa, da, pr, dr, pf if want_f else None, df, sch, C.byref(np_)))
         self.passes = np_.value
         self._refresh_nbytes()
-        dtt = np.zeros(self.n_data, dtype=self.dtype)
-        dtt[self._rows] = rows[:self.n_rows]
-        return (dtt, df) if return_fields else dtt
-
-    def _jvp_torch(self, ds, return_fields, sch):
-        import torch
-
-        tdt = torch.float32 if self.dtype == np.float32 else torch.float64
-        if ds.device.type != 'cuda':
-            out = self.jvp(ds.detach().numpy(), return_fields, 'jacobi' if sch else 'tiled')
-            return tuple(torch.from_numpy(o) for o in out) if return_fields else torch.from_numpy(out)
-        if ds.numel() != self.n_cols:
-            raise ValueError('ds should hold %d values (one per %s), got shape %s' % (self.n_cols, self._per, tuple(ds.shape)))
-        dev = torch.device('cuda', self.device)
-        if self._rows_dev is None:
-            self._rows_dev = torch.as_tensor(self._rows, device=dev)
-        dst = ds.detach().to(device=dev, dtype=tdt).contiguous()
-        rows = torch.empty(max(self.n_rows, 1), dtype=tdt, device=dev)
-        df = torch.empty((self.n_events, self.n_nodes), dtype=tdt, device=dev) if return_fields else None
-        torch.cuda.current_stream(dev).synchronize()
-        np_ = C.c_int(0)
-        _lib.check(self._lib.ttcr_fsm_adjoint_jvp(self._h, C.c_void_p(dst.data_ptr()), 1, C.c_void_p(rows.data_ptr()), 1,
-                                                  C.c_void_p(df.data_ptr()) if df is not None and df.numel() else None, 1, sch,
-                                                  C.byref(np_)))
-        self.passes = np_.value
-        self._refresh_nbytes()
-        dtt = torch.zeros(self.n_data, dtype=tdt, device=dev)
-        dtt[self._rows_dev] = rows[:self.n_rows]
-        return (dtt.to(ds.device), df.to(ds.device)) if return_fields else dtt.to(ds.device)
+        dtt = fin_r()[0]
+        return (dtt, fin_f()) if return_fields else dtt
 
     def jvp_source(self, dsrc, return_fields=False, schedule='tiled'):
         """J_src dsrc: the change of the receiver traveltimes for a perturbation of the source points, dsrc (n_points, 4) holding
@@ -745,49 +808,18 @@ class FieldTape:
         handling and schedule as in jvp; the first call allocates its lists, a call with K > 1 a four-column work array (nbytes)."""
         self._handle()
         sch = self._schedule(schedule)
-        is_torch = type(dsrc).__module__.startswith('torch')
-        if is_torch:
-            import torch
-        shape = tuple(dsrc.shape)
-        batched = len(shape) == 3
-        if len(shape) not in (2, 3) or shape[-2:] != (self.n_points, 4) or (batched and not 1 <= shape[0] <= 4):
-            raise ValueError('dsrc should be (%d, 4) or (K, %d, 4) with K from 1 to 4, got shape %s' % (self.n_points, self.n_points, shape))
-        K = shape[0] if batched else 1
+        a, pa, da, K, batched = self._points_arg(dsrc)
+        pr, dr, fin_r = self._out(dsrc, K, self.n_rows, rows=True)
+        pf, df, fin_f = self._out(dsrc, K, self.n_events * self.n_nodes) if return_fields else (None, 0, None)
+        self._sync(da, dr, df)
         np_ = C.c_int(0)
-        if is_torch and dsrc.device.type == 'cuda':
-            tdt = torch.float32 if self.dtype == np.float32 else torch.float64
-            dev = torch.device('cuda', self.device)
-            if self._rows_dev is None:
-                self._rows_dev = torch.as_tensor(self._rows, device=dev)
-            dd = dsrc.detach().to(device=dev, dtype=tdt).contiguous()
-            rows = torch.zeros((K, self.n_rows), dtype=tdt, device=dev)
-            df = torch.empty((K, self.n_events, self.n_nodes), dtype=tdt, device=dev) if return_fields else None
-            torch.cuda.current_stream(dev).synchronize()
-            want_rows, want_df = rows.numel() > 0, df is not None and df.numel() > 0
-            if want_rows or want_df:
-                _lib.check(self._lib.ttcr_fsm_adjoint_jvp_source(self._h, C.c_void_p(dd.data_ptr()), 1, K,
-                                                                 C.c_void_p(rows.data_ptr()) if want_rows else None, 1,
-                                                                 C.c_void_p(df.data_ptr()) if want_df else None, 1, sch, C.byref(np_)))
-            dtt = torch.zeros((K, self.n_data), dtype=tdt, device=dev)
-            dtt[:, self._rows_dev] = rows
-            out = [dtt.to(dsrc.device), df.to(dsrc.device) if df is not None else None]
-        else:
-            host = dsrc.detach().numpy() if is_torch else dsrc
-            dd = np.ascontiguousarray(host, dtype=self.dtype)
-            if dd.size == 0:
-                dd = np.zeros(4, dtype=self.dtype)
-            rows = np.zeros((K, self.n_rows), dtype=self.dtype)
-            df = np.empty((K, self.n_events, self.n_nodes), dtype=self.dtype) if return_fields else None
-            if rows.size or (df is not None and df.size):
-                _lib.check(self._lib.ttcr_fsm_adjoint_jvp_source(self._h, _ptr(dd), 0, K, _ptr(rows) if rows.size else None, 0,
-                                                                 _ptr(df) if df is not None and df.size else None, 0, sch, C.byref(np_)))
-            dtt = np.zeros((K, self.n_data), dtype=self.dtype)
-            dtt[:, self._rows] = rows
-            out = [dtt, df]
-            if is_torch:
-                out = [torch.from_numpy(o) if o is not None else None for o in out]
+        want_r, want_f = self.n_rows > 0, return_fields and self.n_events * self.n_nodes > 0
+        if want_r or want_f:
+            _lib.check(self._lib.ttcr_fsm_adjoint_jvp_source(self._h, pa, da, K, pr if want_r else None, dr, pf if want_f else None, df,
+                                                             sch, C.byref(np_)))
         self.passes = np_.value
         self._refresh_nbytes()
+        out = [fin_r(), fin_f().reshape(K, self.n_events, self.n_nodes) if return_fields else None]
         if not batched:
             out = [o[0] if o is not None else None for o in out]
         return (out[0], out[1]) if return_fields else out[0]
@@ -804,124 +836,29 @@ class FieldTape:
             dsrc[k, :, k] = 1
         return np.ascontiguousarray(self.jvp_source(dsrc, schedule=schedule).T)
 
+    def _normal_product(self, entry, v, row_weight, like, schedule):
+        """gauss_newton, hvp and newton: a model vector in, optional row weights, a model vector out where `like` lives"""
+        self._handle()
+        sch = self._schedule(schedule)
+        va, pv, dv = self._model_arg(v, 'v')
+        ra, pr, dr = self._row_arg(row_weight, 'row_weight') if row_weight is not None else (None, None, 0)
+        pg, dg, finish = self._model_out(like)
+        self._sync(dv, dr, dg)
+        pj, pa = C.c_int(0), C.c_int(0)
+        weights = () if entry == 'ttcr_fsm_adjoint_hvp' else (pr, dr)
+        _lib.check(getattr(self._lib, entry)(self._h, pv, dv, *weights, pg, dg, sch, C.byref(pj), C.byref(pa)))
+        self.passes = (pj.value, pa.value)
+        self._refresh_nbytes()
+        return finish()
+
     def gauss_newton(self, v, row_weight=None, schedule='tiled'):
         """J^T (row_weight * (J v)): the Gauss-Newton Hessian product (n_cols values, x fastest, grid dtype), with the bits of
         vjp(row_weight * jvp(v)), the product formed in the grid dtype, and no host round trip in between.  v: n_cols values;
-        row_weight: one value per data row (rcv order) or None.  Array handling and schedule as in jvp; passes becomes the pair
+        row_weight: one value per data row (rcv order) or None.  Array handling and schedule as in vjp; passes becomes the pair
         (passes of the jvp, passes of the vjp)."""
-        self._handle()
-        sch = self._schedule(schedule)
-        if any(type(a).__module__.startswith('torch') for a in (v, row_weight) if a is not None):
-            return self._gn_torch(v, row_weight, sch)
-        v = np.ascontiguousarray(v, dtype=self.dtype)
-        if v.size != self.n_cols:
-            raise ValueError('v should hold %d values (one per %s), got shape %s' % (self.n_cols, self._per, v.shape))
-        rw = None
-        if row_weight is not None:
-            row_weight = np.asarray(row_weight)
-            if row_weight.ndim != 1 or row_weight.shape[0] != self.n_data:
-                raise ValueError('row_weight should hold %d values (one per data row), got shape %s' % (self.n_data, row_weight.shape))
-            rw = np.ascontiguousarray(row_weight[self._rows], dtype=self.dtype)
-            if rw.size == 0:
-                rw = np.zeros(1, dtype=self.dtype)
-        g = np.empty(max(self.n_cols, 1), dtype=self.dtype)
-        pj, pv = C.c_int(0), C.c_int(0)
-        _lib.check(self._lib.ttcr_fsm_adjoint_gn(self._h, _ptr(v), 0, _ptr(rw) if rw is not None else None, 0, _ptr(g), 0, sch,
-                                                 C.byref(pj), C.byref(pv)))
-        self.passes = (pj.value, pv.value)
-        self._refresh_nbytes()
-        return g[:self.n_cols]
-
-    def _gn_torch(self, v, row_weight, sch):
-        import torch
-
-        tdt = torch.float32 if self.dtype == np.float32 else torch.float64
-        ref = v if type(v).__module__.startswith('torch') else row_weight
-        if ref.device.type != 'cuda':
-            host = [a.detach().numpy() if hasattr(a, 'detach') else a for a in (v, row_weight)]
-            return torch.from_numpy(self.gauss_newton(host[0], host[1], 'jacobi' if sch else 'tiled')).to(ref.device)
-        dev = torch.device('cuda', self.device)
-        v = torch.as_tensor(v)
-        if v.numel() != self.n_cols:
-            raise ValueError('v should hold %d values (one per %s), got shape %s' % (self.n_cols, self._per, tuple(v.shape)))
-        vt = v.detach().to(device=dev, dtype=tdt).contiguous()
-        rw = None
-        if row_weight is not None:
-            row_weight = torch.as_tensor(row_weight)
-            if row_weight.dim() != 1 or row_weight.shape[0] != self.n_data:
-                raise ValueError('row_weight should hold %d values (one per data row), got shape %s'
-                                 % (self.n_data, tuple(row_weight.shape)))
-            if self._rows_dev is None:
-                self._rows_dev = torch.as_tensor(self._rows, device=dev)
-            rw = row_weight.detach().to(device=dev, dtype=tdt).index_select(0, self._rows_dev).contiguous()
-            if rw.numel() == 0:
-                rw = torch.zeros(1, dtype=tdt, device=dev)
-        g = torch.empty(max(self.n_cols, 1), dtype=tdt, device=dev)
-        torch.cuda.current_stream(dev).synchronize()
-        pj, pv = C.c_int(0), C.c_int(0)
-        _lib.check(self._lib.ttcr_fsm_adjoint_gn(self._h, C.c_void_p(vt.data_ptr()), 1, C.c_void_p(rw.data_ptr()) if rw is not None else None,
-                                                 1, C.c_void_p(g.data_ptr()), 1, sch, C.byref(pj), C.byref(pv)))
-        self.passes = (pj.value, pv.value)
-        self._refresh_nbytes()
-        return g[:self.n_cols].to(ref.device)
+        return self._normal_product('ttcr_fsm_adjoint_gn', v, row_weight, self._first_tensor(v, row_weight), schedule)
 
     # ---- second-order products (DESIGN.md 6f)
-    def _model_arg(self, v, name):
-        """(array, pointer, on_device) of a model vector, numpy or torch"""
-        if type(v).__module__.startswith('torch') and v.device.type == 'cuda':
-            import torch
-
-            tdt = torch.float32 if self.dtype == np.float32 else torch.float64
-            if v.numel() != self.n_cols:
-                raise ValueError('%s should hold %d values (one per %s), got shape %s' % (name, self.n_cols, self._per, tuple(v.shape)))
-            a = v.detach().to(device=torch.device('cuda', self.device), dtype=tdt).contiguous().reshape(-1)
-            return a, C.c_void_p(a.data_ptr()), 1
-        a = np.ascontiguousarray(v.detach().numpy() if hasattr(v, 'detach') else v, dtype=self.dtype).reshape(-1)
-        if a.size != self.n_cols:
-            raise ValueError('%s should hold %d values (one per %s), got shape %s' % (name, self.n_cols, self._per, a.shape))
-        if a.size == 0:
-            a = np.zeros(1, dtype=self.dtype)
-        return a, _ptr(a), 0
-
-    def _row_arg(self, w, name):
-        """a per-data-row vector in tape row order: (array, pointer, on_device)"""
-        if type(w).__module__.startswith('torch') and w.device.type == 'cuda':
-            import torch
-
-            tdt = torch.float32 if self.dtype == np.float32 else torch.float64
-            dev = torch.device('cuda', self.device)
-            if w.dim() != 1 or w.shape[0] != self.n_data:
-                raise ValueError('%s should hold %d values (one per data row), got shape %s' % (name, self.n_data, tuple(w.shape)))
-            if self._rows_dev is None:
-                self._rows_dev = torch.as_tensor(self._rows, device=dev)
-            a = w.detach().to(device=dev, dtype=tdt).index_select(0, self._rows_dev).contiguous()
-            if a.numel() == 0:
-                a = torch.zeros(1, dtype=tdt, device=dev)
-            return a, C.c_void_p(a.data_ptr()), 1
-        w = np.asarray(w.detach().numpy() if hasattr(w, 'detach') else w)
-        if w.ndim != 1 or w.shape[0] != self.n_data:
-            raise ValueError('%s should hold %d values (one per data row), got shape %s' % (name, self.n_data, w.shape))
-        a = np.ascontiguousarray(w[self._rows], dtype=self.dtype)
-        if a.size == 0:
-            a = np.zeros(1, dtype=self.dtype)
-        return a, _ptr(a), 0
-
-    def _model_out(self, like):
-        """an output model vector where `like` (numpy or torch) lives: (array, pointer, on_device, finish)"""
-        if type(like).__module__.startswith('torch'):
-            import torch
-
-            tdt = torch.float32 if self.dtype == np.float32 else torch.float64
-            if like.device.type == 'cuda':
-                dev = torch.device('cuda', self.device)
-                g = torch.empty(max(self.n_cols, 1), dtype=tdt, device=dev)
-                torch.cuda.current_stream(dev).synchronize()
-                return C.c_void_p(g.data_ptr()), 1, lambda: g[:self.n_cols].to(like.device)
-            g = np.empty(max(self.n_cols, 1), dtype=self.dtype)
-            return _ptr(g), 0, lambda: torch.from_numpy(g[:self.n_cols])
-        g = np.empty(max(self.n_cols, 1), dtype=self.dtype)
-        return _ptr(g), 0, lambda: g[:self.n_cols]
-
     def hold(self, w=None, field_cotangent=None, return_grad=False, schedule='tiled'):
         """Solve the adjoint of the cotangent (w, field_cotangent) -- the arguments of vjp -- and keep it on the tape for hvp and newton.
         return_grad=True returns the gradient as well, with the bits of vjp(w, field_cotangent).  The first hold allocates two
@@ -930,32 +867,9 @@ class FieldTape:
         sch = self._schedule(schedule)
         if w is None and field_cotangent is None:
             raise ValueError('w and field_cotangent are both None: no cotangent to hold')
-        keep = []
-        pw = pf = None
-        dw = df = 0
-        if w is not None:
-            a, pw, dw = self._row_arg(w, 'w')
-            keep.append(a)
-        if field_cotangent is not None:
-            fc = field_cotangent
-            if type(fc).__module__.startswith('torch') and fc.device.type == 'cuda':
-                import torch
-
-                tdt = torch.float32 if self.dtype == np.float32 else torch.float64
-                a = fc.detach().to(device=torch.device('cuda', self.device), dtype=tdt).contiguous()
-                n, pf, df = a.numel(), C.c_void_p(a.data_ptr()), 1
-            else:
-                a = np.ascontiguousarray(fc.detach().numpy() if hasattr(fc, 'detach') else fc, dtype=self.dtype)
-                n, pf, df = a.size, _ptr(a), 0
-            if n != self.n_events * self.n_nodes:
-                raise ValueError('field_cotangent should hold %d x %d values, got shape %s' % (self.n_events, self.n_nodes, tuple(a.shape)))
-            keep.append(a)
-        like = w if w is not None else field_cotangent
-        pg, dg, finish = self._model_out(like) if return_grad else (None, 0, None)
-        if any(type(a).__module__.startswith('torch') and a.device.type == 'cuda' for a in keep):
-            import torch
-
-            torch.cuda.current_stream(torch.device('cuda', self.device)).synchronize()
+        keep, pw, dw, pf, df = self._cotangent(w, field_cotangent)
+        pg, dg, finish = self._model_out(w if w is not None else field_cotangent) if return_grad else (None, 0, None)
+        self._sync(dw, df, dg)
         np_ = C.c_int(0)
         _lib.check(self._lib.ttcr_fsm_adjoint_hold(self._h, pw, dw, pf, df, pg, dg, sch, C.byref(np_)))
         self.passes = np_.value
@@ -968,107 +882,20 @@ class FieldTape:
         _lib.check(self._lib.ttcr_fsm_adjoint_release(self._handle()))
         self._refresh_nbytes()
 
-    def _second_order(self, v, row_weight, newton, schedule):
-        self._handle()
-        sch = self._schedule(schedule)
-        va, pv, dv = self._model_arg(v, 'v')
-        ra, pr, dr = self._row_arg(row_weight, 'row_weight') if row_weight is not None else (None, None, 0)
-        pg, dg, finish = self._model_out(v)
-        if dv or dr:
-            import torch
-
-            torch.cuda.current_stream(torch.device('cuda', self.device)).synchronize()
-        pj, pa = C.c_int(0), C.c_int(0)
-        if newton:
-            _lib.check(self._lib.ttcr_fsm_adjoint_newton(self._h, pv, dv, pr, dr, pg, dg, sch, C.byref(pj), C.byref(pa)))
-        else:
-            _lib.check(self._lib.ttcr_fsm_adjoint_hvp(self._h, pv, dv, pg, dg, sch, C.byref(pj), C.byref(pa)))
-        self.passes = (pj.value, pa.value)
-        self._refresh_nbytes()
-        return finish()
-
     def hvp(self, v, schedule='tiled'):
         """The second-order term of the held cotangent applied to v:  d/dv of vjp(w, field_cotangent) with the cotangent fixed, i.e.
         sum_r w_r (d2 tt_r / ds2) v -- what gauss_newton drops from the Hessian of a misfit (w the weighted residual).  n_cols values in,
         n_cols values out (nodes, or cells on a cell tape), grid dtype.  One tangent and one adjoint relaxation.  Needs hold() first
         (ValueError otherwise).  Array handling and schedule as in jvp; passes becomes (passes of the jvp, passes of the vjp)."""
-        return self._second_order(v, None, False, schedule)
+        return self._normal_product('ttcr_fsm_adjoint_hvp', v, None, v, schedule)
 
     def newton(self, v, row_weight=None, schedule='tiled'):
         """J^T (row_weight * (J v)) + hvp(v) from ONE adjoint relaxation: the full Hessian product of a least-squares misfit whose weighted
-        residual is the held w, at the cost of gauss_newton plus three streaming kernels.  Arguments as gauss_newton; needs hold()."""
-        return self._second_order(v, row_weight, True, schedule)
+        residual is the held w, at the cost of gauss_newton plus three streaming kernels.  Arguments as gauss_newton, the result where v
+        lives; needs hold()."""
+        return self._normal_product('ttcr_fsm_adjoint_newton', v, row_weight, v, schedule)
 
     # ---- block products (DESIGN.md 6g)
-    def _block_arg(self, a, name, n_last, rows, n_lead=None):
-        """a (K, n_last) array, numpy or torch, for a block call: (array, pointer, on_device, K).  rows=True: one value per data row,
-        permuted to tape row order.  n_lead: the K the array has to have (row weights)."""
-        on_dev = type(a).__module__.startswith('torch') and a.device.type == 'cuda'
-        if not on_dev:
-            a = np.asarray(a.detach().numpy() if hasattr(a, 'detach') else a)
-        shape = tuple(a.shape)
-        if len(shape) != 2 or shape[1] != n_last or shape[0] < 1 or (n_lead is not None and shape[0] != n_lead):
-            raise ValueError('%s should be (%s, %d) with K >= 1, got shape %s' % (name, 'K' if n_lead is None else n_lead, n_last, shape))
-        if on_dev:
-            import torch
-
-            tdt = torch.float32 if self.dtype == np.float32 else torch.float64
-            dev = torch.device('cuda', self.device)
-            a = a.detach().to(device=dev, dtype=tdt)
-            if rows:
-                if self._rows_dev is None:
-                    self._rows_dev = torch.as_tensor(self._rows, device=dev)
-                a = a.index_select(1, self._rows_dev)
-            a = a.contiguous()
-            if a.numel() == 0:
-                a = torch.zeros(1, dtype=tdt, device=dev)
-            return a, C.c_void_p(a.data_ptr()), 1, shape[0]
-        a = np.ascontiguousarray(a[:, self._rows] if rows else a, dtype=self.dtype)
-        if a.size == 0:
-            a = np.zeros(1, dtype=self.dtype)
-        return a, _ptr(a), 0, shape[0]
-
-    def _block_out(self, like, K, n_last, rows=False):
-        """a (K, n_last) output where `like` lives: (pointer, on_device, finish); rows=True: tape row order in, rcv order out"""
-        is_torch = type(like).__module__.startswith('torch')
-        if is_torch and like.device.type == 'cuda':
-            import torch
-
-            tdt = torch.float32 if self.dtype == np.float32 else torch.float64
-            dev = torch.device('cuda', self.device)
-            o = torch.empty(max(K * n_last, 1), dtype=tdt, device=dev)
-            if rows and self._rows_dev is None:
-                self._rows_dev = torch.as_tensor(self._rows, device=dev)
-
-            def finish():
-                r = o[:K * n_last].reshape(K, n_last)
-                if rows:
-                    d = torch.zeros((K, self.n_data), dtype=tdt, device=dev)
-                    d[:, self._rows_dev] = r
-                    r = d
-                return r.to(like.device)
-            return C.c_void_p(o.data_ptr()), 1, finish
-        o = np.empty(max(K * n_last, 1), dtype=self.dtype)
-
-        def finish():
-            r = o[:K * n_last].reshape(K, n_last)
-            if rows:
-                d = np.zeros((K, self.n_data), dtype=self.dtype)
-                d[:, self._rows] = r
-                r = d
-            if is_torch:
-                import torch
-
-                r = torch.from_numpy(r)
-            return r
-        return _ptr(o), 0, finish
-
-    def _block_sync(self, *on_device):
-        if any(on_device):
-            import torch
-
-            torch.cuda.current_stream(torch.device('cuda', self.device)).synchronize()
-
     def jvp_block(self, ds, return_fields=False, schedule='tiled'):
         """J applied to K perturbations at once: ds (K, n_cols), K >= 1; returns dtt (K, n_data) in rcv order, with return_fields=True
         (dtt, dfields) with dfields (K, n_events, n_nodes).  Row k has the bits of jvp(ds[k]) whatever K and k are.  Under 'tiled' the
@@ -1079,9 +906,9 @@ class FieldTape:
         self._handle()
         sch = self._schedule(schedule)
         a, pa, da, K = self._block_arg(ds, 'ds', self.n_cols, False)
-        pr, dr, fin_r = self._block_out(ds, K, self.n_rows, rows=True)
-        pf, df, fin_f = self._block_out(ds, K, self.n_events * self.n_nodes) if return_fields else (None, 0, None)
-        self._block_sync(da, dr, df)
+        pr, dr, fin_r = self._out(ds, K, self.n_rows, rows=True)
+        pf, df, fin_f = self._out(ds, K, self.n_events * self.n_nodes) if return_fields else (None, 0, None)
+        self._sync(da, dr, df)
         np_ = C.c_int(0)
         want_f = return_fields and self.n_events * self.n_nodes > 0
         if self.n_rows > 0 or want_f:
@@ -1099,8 +926,8 @@ class FieldTape:
         self._handle()
         sch = self._schedule(schedule)
         a, pa, da, K = self._block_arg(w, 'w', self.n_data, True)
-        pg, dg, fin = self._block_out(w, K, self.n_cols)
-        self._block_sync(da, dg)
+        pg, dg, fin = self._out(w, K, self.n_cols)
+        self._sync(da, dg)
         np_ = C.c_int(0)
         _lib.check(self._lib.ttcr_fsm_adjoint_vjp_block(self._h, K, pa, da, pg, dg, sch, C.byref(np_)))
         self.passes = np_.value
@@ -1123,8 +950,8 @@ class FieldTape:
                 rw, prw, drw, rw_cols = self._block_arg(row_weight, 'row_weight', self.n_data, True, n_lead=K)
                 if K == 1:
                     rw_cols = 1
-        pg, dg, fin = self._block_out(v, K, self.n_cols)
-        self._block_sync(da, drw, dg)
+        pg, dg, fin = self._out(v, K, self.n_cols)
+        self._sync(da, drw, dg)
         pj, pv = C.c_int(0), C.c_int(0)
         _lib.check(self._lib.ttcr_fsm_adjoint_gn_block(self._h, K, pa, da, prw, rw_cols, drw, pg, dg, sch, C.byref(pj), C.byref(pv)))
         self.passes = (pj.value, pv.value)
