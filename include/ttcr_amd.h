@@ -572,6 +572,14 @@ int ttcr_fsm_reference_change(ttcr_fsm_grid* g, const void* times, const void* f
 /* Name of the sweep-kernel instantiation the last solve launched (first-order stage of the last batch; no reference
  * equivalent: bench.py reports it beside the roofline figures).  Written into buf (n bytes, NUL terminated). */
 int ttcr_fsm_last_kernel(const ttcr_fsm_grid* g, char* buf, size_t n);
+/* Test infrastructure, device free: the ticket order of the whole-iteration sweep launch of a grid with nnx x nny x nnz NODES (dim = 2:
+ * nny is ignored), exactly the words the kernel reads -- one per work unit (sweep direction d, patch), TJ | TK << 14 | d << 28, with the
+ * patch and chunk sizes the library uses for that dimension and dtype.  stage 0: first-order sweeps, 1: WENO sweeps (wider halo);
+ * by_time 0: sweep by sweep, 1: by expected start time (the default of every launch).  The kernels are deadlock free with any number of
+ * resident workgroups only if every unit comes after the units it waits for: tests/test_unit_order.py checks that.  *n_units: words
+ * of the list; out may be NULL (size query), else capacity (in words) must be >= *n_units.  No reference equivalent. */
+int ttcr_fsm_unit_order(int dim, int dtype, int stage, int by_time, uint32_t nnx, uint32_t nny, uint32_t nnz, uint32_t* out,
+                        size_t capacity, size_t* n_units);
 /* Build provenance: the 16-hex-digit hash of the kernel sources and compiler flags this library was compiled from (ttcr_amd/build.py,
  * source_hash(), baked in at compile time).  The Python layer refuses a library whose id is not the hash of the sources beside it, and
  * bench.py / the tests print it: a measured binary is provably the committed code.  "unknown" for a build that did not pass the id. */

@@ -2,7 +2,8 @@
 longer chunk is faster -- fp32 first-order sweeps at any batch size below the pairing threshold, fp64 first-order sweeps of up to four
 sources, the WENO stage of one or two sources: the partial order of the node updates is the same (Grid3Drn::sweep /
 update_node, ttcr/Grid3Drn.h:2816-2959), so fields, iteration counts and the change history are those of the 8-level kernels bit
-for bit (which test_parity_gpu.py pins to the oracle) -- with and without exact skipping, for one source and for a batch."""
+for bit (which test_parity_gpu.py pins to the oracle, one unit per workgroup, and test_few_workgroups_gpu.py looped: a workgroup taking
+unit after unit, both chunk lengths, both precisions) -- with and without exact skipping, for one source and for a batch."""
 import numpy as np
 import pytest
 

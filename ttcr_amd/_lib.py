@@ -56,6 +56,7 @@ SYMBOLS = {
     "ttcr_fsm_last_timing": (_I, [_P, C.POINTER(Timing)]),
     "ttcr_fsm_last_kernel": (_I, [_P, C.c_char_p, C.c_size_t]),
     "ttcr_fsm_build_id": (C.c_char_p, []),
+    "ttcr_fsm_unit_order": (_I, [_I, _I, _I, _I, _U32, _U32, _U32, C.POINTER(_U32), C.c_size_t, C.POINTER(C.c_size_t)]),
     "ttcr_fsm_stopping_stats": (_I, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "ttcr_fsm_prefill_swaps": (_I, [_P, C.POINTER(C.c_longlong)]),
     "ttcr_fsm_reference_change": (_I, [_P, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),

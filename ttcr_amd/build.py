@@ -24,7 +24,7 @@ INC = os.path.join("..", "..", "include", "ttcr_amd.h")
 # source -> (extra flags, files it is compiled from)
 UNITS = {
     "fsm_capi.hip": ([], ["fsm_capi.hip", "fsm_kernels.h", "fsm_fast_api.h", "fsm_march_levels.inc", "fsm_fast.hip", "fsm_tape_api.h",
-                          "fsm_tape.hip", "fsm_adjoint_api.h", "fsm_adjoint.hip", INC]),
+                          "fsm_tape.hip", "fsm_adjoint_api.h", "fsm_adjoint.hip", "fsm_unit_order.h", INC]),
     "fsm_fast.hip": ([], ["fsm_fast.hip", "fsm_fast_api.h", "fsm_kernels.h", "fsm_march_levels.inc"]),
     "fsm_tape.hip": ([], ["fsm_tape.hip", "fsm_tape_api.h"]),
     "fsm_adjoint.hip": ([], ["fsm_adjoint.hip", "fsm_adjoint_api.h", "fsm_kernels.h", "fsm_march_levels.inc"]),

@@ -28,6 +28,7 @@
 #include "fsm_fast_api.h"
 #include "fsm_tape_api.h"
 #include "fsm_adjoint_api.h"
+#include "fsm_unit_order.h"
 
 #ifndef FSM_CHUNK3
 #define FSM_CHUNK3 8
@@ -554,10 +555,7 @@ class GridT : public GridBase {
     // persistent kernel: ticket order = anti-diagonal m = TJ+TK major (a topological order of the
     // patch dependencies), progress counters per (source slot in batch, patch)
     void build_persistent_lists() {
-        std::vector<uint32_t> order;
-        for (int m = 0; m <= geom.npj + geom.npk - 2; ++m)
-            for (int TK = std::max(0, m - geom.npj + 1); TK <= std::min(m, geom.npk - 1); ++TK)
-                order.push_back((uint32_t)(m - TK) | ((uint32_t)TK << 16));
+        const std::vector<uint32_t> order = fsm_diag_order(geom.npj, geom.npk);
         n_patches = (int)order.size();
         d_order.reserve(order.size());
         HIP_CHECK(hipMemcpy(d_order.p, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -575,75 +573,11 @@ class GridT : public GridBase {
             }
     }
 
-    // Ticket order of the whole-iteration launch: every unit (direction d, patch) once, entries TJ | TK << 14 | d << 28.
-    // A unit waits for its two upwind patches of the same sweep and for the patches of sweep d-1 that own a column
-    // within 2H of its own (fsm_sweep_persistent), so any order that puts those first is deadlock free whatever the
-    // number of resident workgroups.  by_time = false: sweep by sweep, anti-diagonals inside a sweep.  by_time = true:
-    // by the start time every unit would have on an unbounded machine (upwind patch + one hand-off; previous sweep's
-    // patches finished), in chunk times.  A sweep has more patches than the chip has workgroup slots; handed out sweep
-    // by sweep, the slots fill up with patches that sit out their turn on the ramp of the patch wavefront while the
-    // next sweep, whose first corner is long free, cannot enter.  In start-time order the resident units are the ones
-    // that can run next, of whichever sweep.
+    // Ticket order of the whole-iteration launch (fsm_unit_order.h, fsm_xs_order) with the tiles and chunks of this grid
     std::vector<uint32_t> xs_order(const std::vector<uint32_t>& diag_order, bool by_time, int H) const {
         const int PJ = dim == 3 ? TileCfg<T, 3>::PJ : TileCfg<T, 2>::PJ, PK = dim == 3 ? TileCfg<T, 3>::PK : 1;
         const int C = dim == 3 ? ChunkCfg<T, 3>::C : ChunkCfg<T, 2>::C;
-        return xs_order_for(diag_order, by_time, H, PJ, PK, C, geom.npj, n_patches);
-    }
-    std::vector<uint32_t> xs_order_for(const std::vector<uint32_t>& diag_order, bool by_time, int H, int PJ, int PK, int C, int npj,
-                                       int n_patches) const {
-        const int ndir = dim == 3 ? 8 : 4;
-        std::vector<uint32_t> out;
-        out.reserve((size_t)n_patches * ndir);
-        if (!by_time) {
-            for (int d = 0; d < ndir; ++d)
-                for (uint32_t e : diag_order) out.push_back((e & 0xffffu) | ((e >> 16) << 14) | ((uint32_t)d << 28));
-            return out;
-        }
-        auto flags = [&](int d, int& rj, int& rk) {
-            if (dim == 3) { rj = (d >> 1) & 1; rk = (d >> 2) & 1; } else { rj = (d == 1) | (d == 2); rk = 0; }
-        };
-        std::vector<double> ts((size_t)n_patches * ndir, 0.0), tf((size_t)n_patches * ndir, 0.0);
-        const double hop_j = (PJ + C - 1.0) / C + 1.0, hop_k = (PK + C - 1.0) / C + 1.0;
-        for (int d = 0; d < ndir; ++d) {
-            int rj, rk, prj = 0, prk = 0;
-            flags(d, rj, rk);
-            if (d > 0) flags(d - 1, prj, prk);
-            for (uint32_t e : diag_order) {
-                const int TJ = e & 0xffffu, TK = e >> 16;
-                const size_t me = (size_t)d * n_patches + (size_t)TK * npj + TJ;
-                double t = 0.0;
-                if (TJ > 0) t = std::max(t, ts[me - 1] + hop_j);
-                if (TK > 0) t = std::max(t, ts[me - npj] + hop_k);
-                const int j0 = TJ * PJ, k0 = TK * PK;
-                const int jm = std::min(j0 + PJ, geom.NJ) - 1, km = std::min(k0 + PK, geom.NK) - 1;
-                if (d > 0) {
-                    const int ja = std::max(j0 - 2 * H, 0), jb = std::min(jm + 2 * H, geom.NJ - 1);
-                    const int ka = std::max(k0 - 2 * H, 0), kb = std::min(km + 2 * H, geom.NK - 1);
-                    const int ja2 = rj != prj ? geom.NJ - 1 - jb : ja, jb2 = rj != prj ? geom.NJ - 1 - ja : jb;
-                    const int ka2 = rk != prk ? geom.NK - 1 - kb : ka, kb2 = rk != prk ? geom.NK - 1 - ka : kb;
-                    for (int tk = ka2 / PK; tk <= kb2 / PK; ++tk)
-                        for (int tj = ja2 / PJ; tj <= jb2 / PJ; ++tj) t = std::max(t, tf[(size_t)(d - 1) * n_patches + (size_t)tk * npj + tj]);
-                }
-                ts[me] = t;
-                tf[me] = t + ((jm - j0) + (km - k0) + geom.NF + C - 1) / C + 1.0;
-            }
-        }
-        std::vector<uint32_t> idx((size_t)n_patches * ndir);
-        // stable sort by start time; ties keep (direction, anti-diagonal) order
-        size_t q = 0;
-        std::vector<uint32_t> ent((size_t)n_patches * ndir);
-        std::vector<double> key((size_t)n_patches * ndir);
-        for (int d = 0; d < ndir; ++d)
-            for (uint32_t e : diag_order) {
-                const int TJ = e & 0xffffu, TK = e >> 16;
-                ent[q] = (uint32_t)TJ | ((uint32_t)TK << 14) | ((uint32_t)d << 28);
-                key[q] = ts[(size_t)d * n_patches + (size_t)TK * npj + TJ];
-                idx[q] = (uint32_t)q;
-                ++q;
-            }
-        std::stable_sort(idx.begin(), idx.end(), [&](uint32_t a2, uint32_t b2) { return key[a2] < key[b2]; });
-        for (uint32_t i2 : idx) out.push_back(ent[i2]);
-        return out;
+        return fsm_xs_order(dim, geom.NF, geom.NJ, geom.NK, PJ, PK, C, H, by_time, diag_order);
     }
 
     // The 3-D WENO stage exists with two chunk lengths: 8 levels (the kernel is latency bound with few
@@ -4338,6 +4272,35 @@ int ttcr_fsm_last_kernel(const ttcr_fsm_grid* g, char* buf, size_t n) {
 #ifndef TTCR_BUILD_ID
 #define TTCR_BUILD_ID "unknown"
 #endif
+int ttcr_fsm_unit_order(int dim, int dtype, int stage, int by_time, uint32_t nnx, uint32_t nny, uint32_t nnz, uint32_t* out,
+                        size_t capacity, size_t* n_units) {
+    return guarded([&] {   // (host arithmetic only: no device is looked for)
+        if (dim != 2 && dim != 3) throw ValueError("dim must be 2 or 3");
+        if (dtype != TTCR_F32 && dtype != TTCR_F64) throw ValueError("dtype must be TTCR_F32 or TTCR_F64");
+        if (stage != 0 && stage != 1) throw ValueError("stage must be 0 (first order) or 1 (WENO)");
+        if (nnx < 2 || nnz < 2 || (dim == 3 && nny < 2)) throw ValueError("grid needs at least two nodes per axis");
+        if (!n_units) throw ValueError("null unit count");
+        // F, J, K axes as in the GridT constructor: 3-D x, y, z; 2-D z, x
+        const uint32_t NF = dim == 3 ? nnx : nnz, NJ = dim == 3 ? nny : nnx, NK = dim == 3 ? nnz : 1;
+        int PJ, PK, C;
+        if (dtype == TTCR_F32) {
+            PJ = dim == 3 ? TileCfg<float, 3>::PJ : TileCfg<float, 2>::PJ; PK = dim == 3 ? TileCfg<float, 3>::PK : 1;
+            C = dim == 3 ? ChunkCfg<float, 3>::C : ChunkCfg<float, 2>::C;
+        } else {
+            PJ = dim == 3 ? TileCfg<double, 3>::PJ : TileCfg<double, 2>::PJ; PK = dim == 3 ? TileCfg<double, 3>::PK : 1;
+            C = dim == 3 ? ChunkCfg<double, 3>::C : ChunkCfg<double, 2>::C;
+        }
+        const uint64_t npj = ((uint64_t)NJ + PJ - 1) / PJ, npk = ((uint64_t)NK + PK - 1) / PK;
+        if (NF >= (1u << 30) || npj >= (1u << 14) || npk >= (1u << 14)) throw ValueError("grid too large for the patch index of the sweep kernel");
+        *n_units = (size_t)(npj * npk) * (dim == 3 ? 8 : 4);
+        if (!out) return;
+        if (capacity < *n_units) throw ValueError("output buffer too small for the units of the launch");
+        const std::vector<uint32_t> xs = fsm_xs_order(dim, (int)NF, (int)NJ, (int)NK, PJ, PK, C, stage == 0 ? 1 : 2, by_time != 0,
+                                                      fsm_diag_order((int)npj, (int)npk));
+        std::copy(xs.begin(), xs.end(), out);
+    });
+}
+
 const char* ttcr_fsm_build_id(void) { return TTCR_BUILD_ID; }
 
 }  // extern "C"
