@@ -1469,6 +1469,17 @@ class GridT : public GridBase {
                 // NF + NJ + NK of them -- in T1 before they go to the fp64 atomics.  Where these bounds put the reference's sum on one
                 // side of eps * N, `change >= epsilon` is decided as the reference decides it without computing the sum (option
                 // "stopping_shortcuts", bit 1); the ordered pass runs for the rest.
+                // What m has to cover, kernel by kernel that adds to d_change -- the T1 additions a thread makes before it converts
+                // its sum to double (each term c - t is one more rounding in T1; the wave reduction and the atomics are fp64):
+                //   fsm_sweep_unit (every persistent kernel)   NF per unit and source: a thread keeps one column (jp, kp) of the patch and
+                //                                              meets one node of it per level, ip = L - jp - kp in [0, NF), whatever the
+                //                                              chunk length (8, 16: the chunks only cut the column up) and NS (dec[l] is per
+                //                                              source); the sum starts from zero in every unit, looped workgroups included
+                //   fsm_sweep_tile (mode 0)                    BL per tile: 16 levels in 3-D, 32 in 2-D
+                //   fsm_sweep45, fsm_sweep45_rows              none: the terms are added in double (in T1 they were 4 ceil(nnx / S) nnz and
+                //                                              4 nnx ceil(nnz / blockDim) -- 8192 x 64 fp32: 32 768 against NF+NJ+NK+64 = 8320)
+                // n such additions of non-negative terms and the rounding of the terms are off by at most n u / (1 - n u) in all, and
+                // n <= NF < NF + NJ + NK + 64 everywhere: m holds with a factor of two to spare (tests/test_change_sum_gpu.py measures it).
                 std::vector<unsigned long long> h_m(nf);
                 HIP_CHECK(hipMemcpyAsync(h_m.data(), d_rs_n.p, nf * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
                 HIP_CHECK(hipStreamSynchronize(stream));

@@ -2130,7 +2130,9 @@ __global__ __launch_bounds__(NT) void fsm_sweep45(const Sweep45Args<T> a) {
     const T TMAX = real_traits<T>::max();
     const int r = threadIdx.x;
     constexpr int S = NT - 2;
-    T dec = 0;
+    // decreases of this thread's nodes, every strip and all four directions: 4 ceil(nnx / S) nnz terms, far more than the host's bound on
+    // the sum allows in T (decide_go_on, fsm_capi.hip) -- each term is rounded once in T, the additions are in double
+    double dec = 0;
     for (int dir = 0; dir < 4; ++dir) {
         const int ri = (dir == 1) | (dir == 2), rj = dir >> 1;
         for (int x0 = 0; x0 < nnx; x0 += S) {
@@ -2207,7 +2209,7 @@ __global__ __launch_bounds__(NT) void fsm_sweep45(const Sweep45Args<T> a) {
                             ring[r * W + (L & (W - 1))] = t;
                             res[e] = t;
                             chg |= 1u << e;
-                            dec += c - t;
+                            dec += (double)(c - t);
                         }
                     }
                     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -2226,7 +2228,7 @@ __global__ __launch_bounds__(NT) void fsm_sweep45(const Sweep45Args<T> a) {
             __syncthreads();
         }
     }
-    double accd = (double)dec;
+    double accd = dec;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) accd += __shfl_down(accd, off, 64);
     if ((threadIdx.x & 63) == 0 && accd != 0.0) atomicAdd(a.change + slot, accd);
@@ -2268,7 +2270,7 @@ __global__ __launch_bounds__(1024) void fsm_sweep45_rows(const Sweep45Args<T> a)
             if (tid == 0) { dst[0] = TMAX; dst[W - 1] = TMAX; }
         }
     };
-    T dec = 0;
+    double dec = 0;   // (4 nnx ceil(nnz / NT) terms per thread: added in double, as in fsm_sweep45)
     for (int dir = 0; dir < 4; ++dir) {
         const int di = (dir == 1 || dir == 2) ? -1 : 1;          // outer loop direction (ttcr/Grid2Drn.h:760-793)
         int i = di > 0 ? 0 : nnx - 1;
@@ -2294,7 +2296,7 @@ __global__ __launch_bounds__(1024) void fsm_sweep45_rows(const Sweep45Args<T> a)
                 if (t < c) {
                     B[j + 1] = t;
                     st_sc1(Tg + (size_t)n * ts, t);
-                    dec += c - t;
+                    dec += (double)(c - t);
                 }
             }
             __syncthreads();
@@ -2304,7 +2306,7 @@ __global__ __launch_bounds__(1024) void fsm_sweep45_rows(const Sweep45Args<T> a)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
-    double accd = (double)dec;
+    double accd = dec;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) accd += __shfl_down(accd, off, 64);
     if ((threadIdx.x & 63) == 0 && accd != 0.0) atomicAdd(a.change + slot, accd);
