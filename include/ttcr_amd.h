@@ -226,6 +226,14 @@ size_t ttcr_fsm_n_cells(const ttcr_fsm_grid* g);
  *                  slot swaps the sets instead of writing n_slots x n_nodes values in front of its first sweep (512^3 x 64: 32 GB,
  *                  6.8 ms).  Calls that restart some slots fill those in place.  1 on, 0 off, -1 (default): on when the fields take
  *                  >= 64 MiB and twice that is at most half the device memory.  env TTCR_FSM_PREFILL.  tests/test_prefill_gpu.py
+ *   "prefill_inline"  who fills the other set ("prefill" on).  1: the work units of the call's first sweep launch, each a slice of it with
+ *                  plain 16-byte stores as it draws its ticket -- no launch and no workgroup slot of its own, and nothing left for a call
+ *                  that comes back at once to wait for.  Only calls that restart every slot, once the other set exists (from the grid's
+ *                  second such call on), with whole-iteration launches ("mode" 2) that are not replayed from a graph ("use_graph" < 2);
+ *                  every other call keeps the side stream.  0: always the side stream.  -1 (default): as 1 for 3-D launches of at least
+ *                  2 048 work units per sweep (the ones bound by throughput, where exact skipping is on) with the reference's arithmetic
+ *                  ("arith" 0), as 0 below and for the tolerance-grade kernels (512^3 x 64: 182.0 -> 179.1 ms per step; with "arith" 1
+ *                  147.5 -> 148.5 ... 149.4, profiles/inline_prefill).  Same results either way.  tests/test_inline_prefill_gpu.py
  *   "pair_sources" 1 (default): where the grid keeps its fields in pairs (n_slots x patches of a sweep > 6 144, env
  *                  TTCR_FSM_PAIR_UNITS; TTCR_FSM_PAIR = 1 / 0 forces / forbids the pair layout at grid creation) the sources
  *                  of a batch are paired by distance before they share a workgroup two by two
@@ -565,6 +573,9 @@ int ttcr_fsm_stopping_stats(const ttcr_fsm_grid* g, long long* reference_sums, l
 /* Calls (solve batches) that found their traveltime fields initialised by the side stream instead of filling them (option "prefill";
  * the fill it replaces: `reinit` of every node, ttcr/Grid3Drnfs.h:92-94).  No reference equivalent: tests and bench.py read it. */
 int ttcr_fsm_prefill_swaps(const ttcr_fsm_grid* g, long long* swaps);
+/* Calls whose first sweep launch re-initialised the other set of fields itself (option "prefill_inline") instead of leaving it to the side
+ * stream.  No reference equivalent: tests read it. */
+int ttcr_fsm_prefill_inline_fills(const ttcr_fsm_grid* g, long long* fills);
 /* The reference's `change` (ttcr/Grid3Drnfs.h:141-152) of two fields given on the host, n_nodes values of the grid's type each, node
  * order: the sum, in node order, in T1, of abs(times[n] - field[n]), into *out (a T1).  parallel != 0: the parallel form the solver
  * uses; 0: one chain of additions.  Both exact; tests compare them. */
@@ -580,6 +591,12 @@ int ttcr_fsm_last_kernel(const ttcr_fsm_grid* g, char* buf, size_t n);
  * of the list; out may be NULL (size query), else capacity (in words) must be >= *n_units.  No reference equivalent. */
 int ttcr_fsm_unit_order(int dim, int dtype, int stage, int by_time, uint32_t nnx, uint32_t nny, uint32_t nnz, uint32_t* out,
                         size_t capacity, size_t* n_units);
+/* Test infrastructure, device free: the slice of the spare traveltime fields that the unit with ticket `ticket` of a launch of n_tickets
+ * units sets to max() (option "prefill_inline"), exactly the arithmetic the kernel does (ttcr_amd/csrc/fsm_prefill_slices.h).  n_el:
+ * elements of the spare set.  *slice_len: elements per ticket, a multiple of the 16-byte vector (4 fp32, 2 fp64 elements); [*begin, *end):
+ * the ticket's elements -- tickets 0 .. n_tickets - 1 tile [0, n_el) in order without gap or overlap, tickets from n_tickets on are
+ * empty.  Any pointer may be NULL.  tests/test_prefill_slices.py.  No reference equivalent. */
+int ttcr_fsm_prefill_slice(int dtype, uint64_t n_el, uint32_t n_tickets, uint32_t ticket, uint64_t* slice_len, uint64_t* begin, uint64_t* end);
 /* Build provenance: the 16-hex-digit hash of the kernel sources and compiler flags this library was compiled from (ttcr_amd/build.py,
  * source_hash(), baked in at compile time).  The Python layer refuses a library whose id is not the hash of the sources beside it, and
  * bench.py / the tests print it: a measured binary is provably the committed code.  "unknown" for a build that did not pass the id. */

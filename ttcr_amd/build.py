@@ -24,10 +24,10 @@ INC = os.path.join("..", "..", "include", "ttcr_amd.h")
 # source -> (extra flags, files it is compiled from)
 UNITS = {
     "fsm_capi.hip": ([], ["fsm_capi.hip", "fsm_kernels.h", "fsm_fast_api.h", "fsm_march_levels.inc", "fsm_fast.hip", "fsm_tape_api.h",
-                          "fsm_tape.hip", "fsm_adjoint_api.h", "fsm_adjoint.hip", "fsm_unit_order.h", INC]),
-    "fsm_fast.hip": ([], ["fsm_fast.hip", "fsm_fast_api.h", "fsm_kernels.h", "fsm_march_levels.inc"]),
+                          "fsm_tape.hip", "fsm_adjoint_api.h", "fsm_adjoint.hip", "fsm_unit_order.h", "fsm_prefill_slices.h", INC]),
+    "fsm_fast.hip": ([], ["fsm_fast.hip", "fsm_fast_api.h", "fsm_kernels.h", "fsm_march_levels.inc", "fsm_prefill_slices.h"]),
     "fsm_tape.hip": ([], ["fsm_tape.hip", "fsm_tape_api.h"]),
-    "fsm_adjoint.hip": ([], ["fsm_adjoint.hip", "fsm_adjoint_api.h", "fsm_kernels.h", "fsm_march_levels.inc"]),
+    "fsm_adjoint.hip": ([], ["fsm_adjoint.hip", "fsm_adjoint_api.h", "fsm_kernels.h", "fsm_march_levels.inc", "fsm_prefill_slices.h"]),
 }
 SOURCES = list(UNITS)
 DEPS = sorted({d for _, ds in UNITS.values() for d in ds})

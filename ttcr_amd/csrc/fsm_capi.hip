@@ -187,6 +187,7 @@ class GridBase {
     virtual void reference_change_host(const void* times, const void* field, bool parallel, void* out) = 0;
     int pair_by_distance = 1;   // option "pair_sources" (0: every source in the slot the block distribution names)
     virtual void set_pair_layout(int) {}
+    virtual long long prefill_inline_count() const { return 0; }   // calls whose first sweep launch filled the spare set (ttcr_fsm_prefill_inline_fills)
     virtual long long prefill_swap_count() const { return 0; }   // calls that took fields initialised on the side stream (ttcr_fsm_prefill_swaps)
     int lone_chunk = 16;   // option "lone_chunk" / TTCR_FSM_LONE_CHUNK: levels per chunk of the fp32 first-order 3-D kernels with one field per workgroup (8 or 16)
     int arith = 0;      // option "arith" / TTCR_FSM_ARITH: 0 (default) the reference's arithmetic, results bit-identical to it; 1 tolerance-grade
@@ -196,6 +197,8 @@ class GridBase {
     int prefill = -1;   // option "prefill" / TTCR_FSM_PREFILL: a second set of traveltime fields, re-initialised on a side stream while a
                         // solve runs, which the next call that restarts EVERY slot swaps in instead of filling (GridT::solve_batch);
                         // 1 on, 0 off, -1 (default): on when the fields take at least 64 MiB and twice that is at most half the device memory
+    int prefill_inline = -1;   // option "prefill_inline": the spare set is filled by the units of the call's first whole-iteration sweep launch
+                               // instead of on the side stream (GridT::inline_fill_now); 1 on, 0 off, -1 (default): see there
     // L1 change of every sweep-iteration of the last solve of a slot (what the stopping rule compared with eps * N), first-
     // order stage then WENO stage
     std::vector<std::vector<double>> change_hist, change_histw;
@@ -251,6 +254,9 @@ class GridBase {
         else if (k == "prefill") {
             if (value != -1 && value != 0 && value != 1) throw ValueError("option 'prefill': -1 (default), 0 or 1");
             prefill = (int)value;
+        } else if (k == "prefill_inline") {
+            if (value != -1 && value != 0 && value != 1) throw ValueError("option 'prefill_inline': -1 (default), 0 or 1");
+            prefill_inline = (int)value;
         } else if (k == "lone_chunk") {
             if (value != 8 && value != 16) throw ValueError("option 'lone_chunk': 8 or 16");
             lone_chunk = (int)value;
@@ -321,6 +327,8 @@ class GridT : public GridBase {
     hipEvent_t ev_fill = nullptr;
     long long prefill_swaps = 0;    // calls that found their fields initialised
     long long prefill_swap_count() const override { return prefill_swaps; }
+    long long prefill_inline_fills = 0;   // calls whose first sweep launch filled the spare set
+    long long prefill_inline_count() const override { return prefill_inline_fills; }
     void set_pair_layout(int v) override { pair_layout = v; }
     DevBuf<int> d_rslot;
     DevBuf<RaySrc> d_rdesc;
@@ -463,7 +471,7 @@ class GridT : public GridBase {
         if (const char* e = std::getenv("TTCR_FSM_PAIR")) { NS = (std::atoi(e) != 0 && n_slots >= 2) ? 2 : 1; ns_window = false; }
         if (const char* e = std::getenv("TTCR_FSM_LAYOUT_LO")) layout_lo = std::atof(e);
         if (const char* e = std::getenv("TTCR_FSM_LAYOUT_HI")) layout_hi = std::atof(e);
-        d_tt.reserve(n_nodes * (size_t)(n_slots + (n_slots & 1)), 64);   // (room for either layout)
+        d_tt.reserve(n_nodes * tt_fields(), 64);   // (room for either layout)
         mask_words = (n_nodes + 31) / 32;
         d_mask.reserve(mask_words * (size_t)n_slots);
         d_bbox.reserve(6 * (size_t)n_slots);
@@ -482,7 +490,7 @@ class GridT : public GridBase {
         *h_abort = 0;
         HIP_CHECK(hipHostMalloc((void**)&h_iter, 2 * sizeof(int)));
         HIP_CHECK(hipHostMalloc((void**)&h_evals, sizeof(unsigned long long) * n_slots));
-        HIP_CHECK(hipMemsetAsync(d_tt.p, 0, n_nodes * (size_t)(n_slots + (n_slots & 1)) * sizeof(T), stream));
+        HIP_CHECK(hipMemsetAsync(d_tt.p, 0, n_nodes * tt_fields() * sizeof(T), stream));
 
         if (dim == 3) {
             using C = TileCfg<T, 3>;
@@ -657,6 +665,9 @@ class GridT : public GridBase {
         pa.sw = std::getenv("TTCR_FSM_NO_SW") ? nullptr : d_sw.p;   // (tuning / bisecting: no whole-sweep shortcut)
         pa.n_sw_groups = n_groups();
         pa.n_sw_sweeps = sw_sweeps;
+        pa.fill_dst = nullptr;
+        pa.fill_slice = 0;
+        pa.fill_n = 0;
 
         // first-order 3-D kernels: workgroups take units until the tickets run out -- no more of them than can be resident
         // (8 per CU is more than any instantiation fits; the surplus finds the ticket counter exhausted).  The others (and
@@ -682,6 +693,14 @@ class GridT : public GridBase {
             const dim3 gridx((unsigned)std::min<size_t>((size_t)n_patches * batch * ndir, wg_cap));
             pa.order = d_order_xs[H == 2 ? 1 : 0][batch < time_order_below ? 1 : 0].p;
             const bool pre = DIM == 2 || batch >= pre_min || dyn_lds > 0;   // counters sampled one chunk ahead (template PRE)
+            if (fill_arm) {
+                // (solve_batch: first launch of a call that restarts every slot) the spare set, one slice per ticket of this launch
+                pa.fill_dst = d_tt_alt.p;
+                pa.fill_n = n_nodes * tt_fields();
+                pa.fill_slice = fsm_fill_slice_len(pa.fill_n, (size_t)n_patches * batch * ndir, 16 / sizeof(T));
+                fill_arm = false;
+                fill_in_flight = true;
+            }
             if constexpr (std::is_same<T, float>::value) {
                 // tolerance-grade arithmetic: the AR = 1 instantiation of the kernel chosen below (fsm_fast.hip); the WENO stage of grids
                 // that keep their fields in pairs (TTCR_FSM_PAIR = 1 on a weno grid: tuning only) has none and keeps the exact kernels
@@ -1048,6 +1067,8 @@ class GridT : public GridBase {
         for (int q = 0; q < n_slots; ++q) phys[q] = q;
     }
     int n_groups() const { return (n_slots + NS - 1) / NS; }
+    // fields of a set (d_tt, d_tt_alt): an odd slot count is padded to whole pairs only where the pair layout is or may come in use
+    size_t tt_fields() const { return (size_t)n_slots + ((ns_window || NS == 2) ? (size_t)(n_slots & 1) : 0); }
     T* tt_ptr(int slot) const { return d_tt.p + (size_t)(slot / NS) * n_nodes * NS + slot % NS; }
     // Tolerance-grade arithmetic (fp32 grids).  arith = 1: the first-order sweeps of grids WITHOUT the WENO stage -- within north_star's
     // 1e-5 s RMS of the reference.  A grid with the WENO stage keeps the reference's arithmetic in BOTH stages under arith = 1: the WENO
@@ -1059,11 +1080,28 @@ class GridT : public GridBase {
     bool fast_now() const { return sizeof(T) == 4 && (arith == 2 || (arith == 1 && !weno)); }
     bool prefill_on() const {
         if (prefill >= 0) return prefill != 0;
-        const size_t bytes = n_nodes * (size_t)(n_slots + (n_slots & 1)) * sizeof(T);
+        const size_t bytes = n_nodes * tt_fields() * sizeof(T);
         if (bytes < ((size_t)64 << 20)) return false;
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
         return d_tt_alt.p || (2 * bytes <= total_b / 2 && bytes + ((size_t)1 << 30) <= free_b);
+    }
+    // The spare set filled by the units of the call's first sweep launch (fsm_sweep_unit: slice `ticket` at ticket draw) instead of by
+    // fsm_fill on the side stream behind the call, which a caller that comes back at once waits for (512^3 x 64: 6-7 ms of a 180 ms
+    // step).  Only for a call that restarts every slot, with a spare set to fill, whose first launch is a whole-iteration launch of
+    // fsm_sweep_persistent issued directly (a captured launch would be replayed with the fill armed).  -1 (default): launches with at
+    // least skip_units_min units per sweep of a 3-D grid -- those are bound by throughput; a lone source or a small batch lives on the
+    // hop of its patch wavefront, and a burst of stores in front of a unit's first drain would sit on that path.
+    bool fill_arm = false;         // the next whole-iteration launch carries the fill (taken by launch_sweeps_persistent_ns)
+    bool fill_in_flight = false;   // ... and it did
+    bool inline_fill_now(int entries) const {
+        if (prefill_inline == 0 || !d_tt_alt.p || d_tt_alt.n < n_nodes * tt_fields()) return false;
+        if (mode != 2 || stage != 0 || use_graph >= 2) return false;
+        if (prefill_inline == 1) return true;
+        // (measured, 512^3 x 64, profiles/inline_prefill: 182.0 -> 179.1 ms per step with the reference's arithmetic; the tolerance-grade
+        // kernels march faster and sit nearer the memory system's limit -- there the stores cost the launch more than the wait they
+        // replace, 147.5 -> 148.5 ... 149.4 ms -- and keep the side stream)
+        return dim == 3 && !fast_now<1>() && (long long)n_patches * entries >= skip_units_min;
     }
 
     int stage = 0;  // 0: first-order sweeps, 1: WENO3 sweeps (persistent kernel only)
@@ -1554,6 +1592,8 @@ class GridT : public GridBase {
         std::vector<char> group_filled(n_groups(), 0);
         // every slot of the grid restarted by this batch: take the fields the side stream has initialised since the last such call
         const bool all_slots = nb == n_slots && prefill_on();
+        fill_arm = fill_in_flight = false;
+        bool inline_filled = false;   // the spare set was filled by this call's first sweep launch, and that launch ended normally
         if (all_slots && alt_filled) {
             HIP_CHECK(hipStreamWaitEvent(stream, ev_fill, 0));
             std::swap(d_tt.p, d_tt_alt.p);
@@ -1672,7 +1712,11 @@ class GridT : public GridBase {
                 h_iter[1] = (int)launch_epoch;   // epoch of this iteration's (first) sweep launch
                 launch_epoch += (persistent_now() && mode == 2) ? 1u : (unsigned)ndir;
                 HIP_CHECK(hipMemcpyAsync(d_iter.p, h_iter, 2 * sizeof(int), hipMemcpyHostToDevice, stream));
+                // first launch of the call: the spare set -- the results of the call before, which nothing enqueued after the swap reads,
+                // the invariant of the side-stream fill below -- is re-initialised by this launch's units; later launches carry no fill
+                fill_arm = it_total == 0 && all_slots && !alt_filled && inline_fill_now(n_entries);
                 run_iteration(n_entries);
+                fill_arm = false;
                 HIP_CHECK(hipMemcpyAsync(h_change, d_change.p, sizeof(double) * n_slots, hipMemcpyDeviceToHost, stream));
                 if (persistent_now()) HIP_CHECK(hipMemcpyAsync(h_abort, d_sync.p + 4, sizeof(int), hipMemcpyDeviceToHost, stream));
                 HIP_CHECK(hipStreamSynchronize(stream));
@@ -1682,6 +1726,7 @@ class GridT : public GridBase {
                     stage = 0;
                     throw DeviceError("persistent sweep kernel: a patch timed out waiting for its upwind neighbour");
                 }
+                if (fill_in_flight) { inline_filled = true; fill_in_flight = false; }   // (synchronised, not aborted: every ticket was drawn)
                 ++it;
                 ++it_total;
                 std::vector<int> next;
@@ -1721,13 +1766,16 @@ class GridT : public GridBase {
         stage = 0;
         sync_clean = true;
         HIP_CHECK(hipEventRecord(ev1, stream));
-        if (all_slots) {
+        if (all_slots && inline_filled) {
+            alt_filled = true;   // (complete since the first launch: ev_fill, long signalled, has nothing to add)
+            ++prefill_inline_fills;
+        } else if (all_slots) {
             // the other set of fields -- fresh, or the results of the call before this one, which nothing enqueued after the swap reads --
             // is initialised for the next call BEHIND this call's sweeps (the event just recorded): beside them the fill took
             // workgroup slots and bandwidth from the sweep kernel and was not done when the next call came (512^3 x 64 back to back:
             // 191.8 ms per step instead of 185.7, profiles/r05/README.md); behind them it runs beside the receiver interpolation and
             // whatever the caller does between two calls, and a call that comes at once waits for what is left of it
-            const size_t n_el = n_nodes * (size_t)(n_slots + (n_slots & 1));   // (room for either layout)
+            const size_t n_el = n_nodes * tt_fields();   // (room for either layout)
             if (!fill_stream) {
                 int lo = 0, hi = 0;
                 HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
@@ -2907,6 +2955,7 @@ class MultiGrid : public GridBase {
     void get_niter(int slot, int* it, int* itw) const override { int l; GridBase& g = of(slot, l); g.get_niter(l, it, itw); }
     std::string kernel_name() const override { return rep[0]->kernel_name(); }
     long long prefill_swap_count() const override { long long a = 0; for (const auto& r : rep) a += r->prefill_swap_count(); return a; }
+    long long prefill_inline_count() const override { long long a = 0; for (const auto& r : rep) a += r->prefill_inline_count(); return a; }
     void stopping_stats(long long* sums, long long* missed, long long* rounds) const override {
         long long a = 0, b = 0, c = 0;
         for (const auto& r : rep) { long long x = 0, y = 0, z = 0; r->stopping_stats(&x, &y, &z); a += x; b += y; c += z; }
@@ -4265,6 +4314,9 @@ int ttcr_fsm_stopping_stats(const ttcr_fsm_grid* g, long long* reference_sums, l
 int ttcr_fsm_prefill_swaps(const ttcr_fsm_grid* g, long long* swaps) {
     return guarded_on(g, [&] { if (swaps) *swaps = g->impl->prefill_swap_count(); });
 }
+int ttcr_fsm_prefill_inline_fills(const ttcr_fsm_grid* g, long long* fills) {
+    return guarded_on(g, [&] { if (fills) *fills = g->impl->prefill_inline_count(); });
+}
 int ttcr_fsm_reference_change(ttcr_fsm_grid* g, const void* times, const void* field, int parallel, void* out) {
     return guarded_on(g, [&] {
         if (!times || !field || !out) throw ValueError("ttcr_fsm_reference_change: null argument");
@@ -4309,6 +4361,19 @@ int ttcr_fsm_unit_order(int dim, int dtype, int stage, int by_time, uint32_t nnx
         const std::vector<uint32_t> xs = fsm_xs_order(dim, (int)NF, (int)NJ, (int)NK, PJ, PK, C, stage == 0 ? 1 : 2, by_time != 0,
                                                       fsm_diag_order((int)npj, (int)npk));
         std::copy(xs.begin(), xs.end(), out);
+    });
+}
+
+int ttcr_fsm_prefill_slice(int dtype, uint64_t n_el, uint32_t n_tickets, uint32_t ticket, uint64_t* slice_len, uint64_t* begin, uint64_t* end) {
+    return guarded([&] {   // (host arithmetic only: no device is looked for)
+        if (dtype != TTCR_F32 && dtype != TTCR_F64) throw ValueError("dtype must be TTCR_F32 or TTCR_F64");
+        if (n_tickets == 0) throw ValueError("a launch has at least one ticket");
+        const size_t slice = fsm_fill_slice_len((size_t)n_el, n_tickets, dtype == TTCR_F32 ? 4 : 2);
+        size_t b = 0, e = 0;
+        fsm_fill_slice_range((size_t)n_el, slice, ticket, &b, &e);
+        if (slice_len) *slice_len = slice;
+        if (begin) *begin = b;
+        if (end) *end = e;
     });
 }
 

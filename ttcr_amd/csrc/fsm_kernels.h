@@ -38,6 +38,8 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "fsm_prefill_slices.h"
+
 namespace ttcr_amd {
 
 // edge of the bricks (natural coordinates) whose last-change sweep number is tracked
@@ -608,6 +610,11 @@ struct PersistArgs {
     // whole-iteration launch (XS): all directions in one grid, sheared copies by family
     const T* ssh;             // [families][ssh_stride]
     size_t ssh_stride;
+    // re-initialisation of the spare set of traveltime fields from inside the launch (fsm_prefill_slices.h): every ticket stores
+    // max() into its slice of fill_dst[0 .. fill_n)
+    T* fill_dst;
+    size_t fill_slice;        // elements per ticket, a multiple of the 16-byte vector; 0: no fill
+    size_t fill_n;
 };
 
 
@@ -1136,6 +1143,26 @@ __device__ __forceinline__ bool fsm_sweep_unit(const PersistArgs<T>& pa) {
     __syncthreads();
     if (LOOPED && s_abort) return false;   // a unit timed out: the solve fails on the host, nobody takes another unit
     const int ticket = __builtin_amdgcn_readfirstlane(s_ticket);
+    // Spare field set of the grid (GridT::solve_batch): slice `ticket` is set to max() here, in front of every return below -- each
+    // ticket of a launch is drawn exactly once whatever the number of workgroups, so the slices cover the set exactly.  Plain
+    // 16-byte stores that nothing in this launch reads or waits for by name; all of it is dead before the unit's own set-up.
+    if (pa.fill_slice) {
+        constexpr int VE = 16 / (int)sizeof(T);
+        typedef T FillV __attribute__((ext_vector_type(VE)));
+        size_t fb, fe;
+        fsm_fill_slice_range(pa.fill_n, pa.fill_slice, (size_t)(unsigned)ticket, &fb, &fe);
+        T* __restrict__ fdst = pa.fill_dst;
+        // (the value is made here, per unit, behind a barrier the compiler does not move: a constant it can see it keeps in registers
+        // across the unit loop of the looped kernels -- four VGPRs the march does not have)
+        T fmax = real_traits<T>::max();
+        asm volatile("" : "+v"(fmax));
+        FillV fv;
+#pragma unroll
+        for (int q = 0; q < VE; ++q) fv[q] = fmax;
+        for (size_t i = fb + (size_t)tid * VE; i + VE <= fe; i += (size_t)NT * VE) *reinterpret_cast<FillV*>(fdst + i) = fv;
+        const size_t rem = (fe - fb) % VE;   // (only the slice that ends at fill_n can have one)
+        if ((size_t)tid < rem) fdst[fe - rem + tid] = fmax;
+    }
     // XS: `order` lists the units (direction, patch) of the whole iteration in ticket order -- any order in which a
     // unit comes after its upwind patches and after the patches of the previous sweep it has to see finished
     const int oidx = ticket / pa.batch, z = ticket - oidx * pa.batch;

@@ -175,6 +175,12 @@ class _GridBase:
         _lib.check(self._lib.ttcr_fsm_prefill_swaps(self._h, C.byref(a)))
         return a.value
 
+    def prefill_inline_fills(self):
+        """Calls whose first sweep launch re-initialised the other set of fields itself (option "prefill_inline")."""
+        a = C.c_longlong(0)
+        _lib.check(self._lib.ttcr_fsm_prefill_inline_fills(self._h, C.byref(a)))
+        return a.value
+
     def reference_change(self, times, field, parallel=True):
         """The reference's `change` of two fields (ttcr/Grid3Drnfs.h:141-152): the sequential sum, in node order and in the grid's
         precision, of abs(times[n] - field[n]).  Flat arrays of get_number_of_nodes() values in node order."""
