@@ -528,6 +528,65 @@ int ttcr_fsm_adjoint_gn_block(const ttcr_fsm_adjoint* t, int n_cols, const void*
 int ttcr_fsm_adjoint_block_release(ttcr_fsm_adjoint* t);
 int ttcr_fsm_adjoint_free(ttcr_fsm_adjoint* t);
 
+/* The normal equations of a field tape: the step of a damped, smoothed least-squares inversion,
+ *     (H + smooth R + damp I) x = rhs,   H = J^T W J of ttcr_fsm_adjoint_gn or the Newton product of ttcr_fsm_adjoint_newton,
+ * solved by conjugate gradients on the tape's stream.  No reference counterpart.  Model vectors hold n_params values (n_params of
+ * ttcr_fsm_adjoint_model) in the tape's order, x fastest: nx x ny x nz nodes, or the (nx - 1) x (ny - 1) x (nz - 1) cells of a cell
+ * tape.  Every value is one fixed expression in the grid dtype T, each operation rounded, no fused multiply-add, no floating-point
+ * atomics; tests/normal_reference.py restates all of it.  An `_on_device` pointer is used in place, a host pointer is staged.
+ * ttcr_fsm_normal_smooth: out = R v = sum_d weights[d] K_d^T (K_d v), d = x, y, z; K_d the order-2 operator of Grid3d.compute_K
+ *   along axis d (second differences of spacing dx, the centred stencil shifted inwards on the two end rows).  Along an axis of length
+ *   n, with c(r) = clip(r, 1, n - 2) and ih2 = T(1 / (dx dx)) (the quotient in double, then rounded):
+ *     y[r] = fl(fl(fl(v[c - 1] + v[c + 1]) - fl(2 v[c])) * ih2)
+ *     z[i] = the sum, over the rows r that touch i in ascending r, from the first term, of fl(coef * y[r]): row 0 if i <= 2 (coef ih2,
+ *            -2 ih2, ih2 for i = 0, 1, 2), rows r in {i - 1, i, i + 1} with 1 <= r <= n - 2 (ih2, -2 ih2, ih2 for r = i + 1, i, i - 1), row
+ *            n - 1 if i >= n - 3 (ih2, -2 ih2, ih2 for i = n - 3, n - 2, n - 1)
+ *     out[m] = fl(fl(fl(a_x z_x) + fl(a_y z_y)) + fl(a_z z_z)),  a_d = T(weights[d])
+ *   One kernel: a tile of v (ttcr_fsm_normal_tile_edge(dtype)^3 parameters, 16 for fp32 and 12 for fp64) with a two-node halo in LDS, y
+ *   recomputed.  v and out are different arrays.  An axis with fewer than 3 parameters: TTCR_ERR_VALUE.
+ * ttcr_fsm_normal_dot: *result = <a, b> in fp64 with a fixed summation order.  e[i] = double(a[i]) * double(b[i]) (exact for fp32,
+ *   rounded for fp64), +0 past the end.  Chunk c = elements [1024 c, 1024 c + 1024), one workgroup of 256 threads: thread t forms
+ *   ((e[t] + e[t + 256]) + e[t + 512]) + e[t + 768], then for stride = 128, 64, ..., 1: s[t] += s[t + stride] for t < stride.  One
+ *   workgroup closes the sum: thread t adds the chunk partials t, t + 256, ... ascending from +0, then the same halving.
+ * ttcr_fsm_normal_solve: A p = fl(fl(H p + fl(T(smooth) * (R p))) + fl(T(damp) * p)), the smooth term not evaluated for smooth == 0, the
+ *   damp term not for damp == 0; H p has the bits of ttcr_fsm_adjoint_gn (newton = 1: ttcr_fsm_adjoint_newton, which needs a held
+ *   cotangent; TTCR_ERR_VALUE with the message of that entry without one).  Vectors in T, scalars in fp64, inner products as above:
+ *     x = x0 (NULL: +0);  r = rhs (x0 given: fl(rhs - A x0));  p = r;  rho = <r, r>;  rho0 = <rhs, rhs>
+ *     for k = 1 .. maxiter:  if rho <= rtol rtol rho0: status 0, stop
+ *        q = A p;  pq = <p, q>;  if not (pq > 0) or not finite: status 2, stop (x is the iterate so far)
+ *        aT = T(rho / pq);  x = fl(x + fl(aT p));  r = fl(r - fl(aT q))
+ *        rho_new = <r, r>;  bT = T(rho_new / rho);  p = fl(r + fl(bT p));  rho = rho_new
+ *     status 1 if the loop ends without meeting the test
+ *   Per iteration: the tape's product, kernel 1 (the smoothing gather of p -- the expression of ttcr_fsm_normal_smooth, read from global
+ *   memory because a workgroup owns a chunk of the flat vector here, not a tile --, q and the chunk partials of <p, q>), the finishing
+ *   reduction (pq, aT, the flag "pq > 0 and finite"), kernel 2 (x, r and the chunk partials of <r, r>), the finishing reduction (rho,
+ *   bT), kernel 3 (p) -- the scalars are formed on the device and read by the update kernels from device memory, which do nothing once
+ *   the flag is down -- and ONE host read of (rho, pq) for the stop test and the history.
+ *   Outputs: x (n_params values); *status; *iterations, the completed updates of x; rho: maxiter + 2 doubles, of which 2 + *iterations
+ *   are written -- rho0, <r, r> of the starting residual, then rho after every completed iteration; pq: maxiter doubles, one per iteration
+ *   that evaluated it (*iterations of them, one more after status 2); passes (may be NULL): 2 (maxiter + 1) ints, the (jvp, vjp)
+ *   relaxation passes of A x0 (0, 0 without x0) and then of every such iteration.  row_weight: n_rows values in tape row order or NULL.
+ *   The first smooth, dot or solve of a tape allocates the work arrays: x, r, p, q and the product output (n_params elem bytes each),
+ *   one double per chunk and 48 bytes of scalars; ttcr_fsm_adjoint_bytes reports them from then on; TTCR_ERR_DEVICE with the byte count
+ *   if an allocation fails.  ttcr_fsm_normal_release frees them (ttcr_fsm_adjoint_bytes falls by the same figure; the next call
+ *   allocates again), ttcr_fsm_adjoint_free too.
+ *   Argument errors -- smooth, damp or rtol negative or not finite, maxiter < 1, newton not 0 or 1, weights that are NULL, negative or
+ *   not finite, an unknown schedule, a NULL rhs, x, status, iterations, rho or pq, a NULL tape, smooth > 0 on a tape with an axis of
+ *   fewer than 3 parameters -- return TTCR_ERR_VALUE with a message that names the argument, in this order, before any device call.
+ * Measured (one MI355X, fp32, 441 receivers per event, 10 iterations, smooth and damp > 0; scripts/normal_solve_time.py,
+ * profiles/normal_solve/; medians of 5): 128^3 x 16 events, ttcr_fsm_normal_solve 403.5 ms, the ten ttcr_fsm_adjoint_gn calls alone
+ * 403.3 / 402.8 ms (before / after); 256^3 x 8 events, 2049.2 ms against 2049.0 / 2048.0 ms.  The differences are below the spread of
+ * the run (1 to 3 ms): the cost the solver adds per iteration is not resolved, it is below 0.3 ms.  The same loop with torch operations
+ * around the Gauss-Newton product: 405.2 and 2056.5 ms. */
+int ttcr_fsm_normal_tile_edge(int dtype);
+int ttcr_fsm_normal_smooth(ttcr_fsm_adjoint* t, const void* v, int v_on_device, const double* weights, void* out, int out_on_device);
+int ttcr_fsm_normal_dot(ttcr_fsm_adjoint* t, const void* a, int a_on_device, const void* b, int b_on_device, double* result);
+int ttcr_fsm_normal_solve(ttcr_fsm_adjoint* t, const void* rhs, int rhs_on_device, const void* row_weight, int rw_on_device, double smooth,
+                          const double* smooth_weights, double damp, const void* x0, int x0_on_device, int maxiter, double rtol,
+                          int newton, int schedule, void* x, int x_on_device, int* status, int* iterations, double* rho, double* pq,
+                          int* passes);
+int ttcr_fsm_normal_release(ttcr_fsm_adjoint* t);
+
 /* Replaces: Grid2D::raytrace(Tx, t0, Rx, traveltimes, l_data, threadNo) (ttcr/Grid2D.h:616-640) and the overload with r_data
  * AND l_data (:583-614) -> Grid2Drn::getRaypath(Tx, t0, Rx, [r_data,] l_data, tt, threadNo) (ttcr/Grid2Drn.h:1852-2190): what
  * `compute_L=True` of the Python layer reaches for 2-D grids with cell slowness (src/ttcrpy/rgrid.pyx:3889-3893, :4060-4143).

@@ -110,6 +110,15 @@ cdef extern from "ttcr_amd.h" nogil:
                                   int* passes_vjp)
     int ttcr_fsm_adjoint_block_release(ttcr_fsm_adjoint* t)
     int ttcr_fsm_adjoint_free(ttcr_fsm_adjoint* t)
+    # normal equations of a field tape: smoothing operator, fixed-order inner product, CG around the Gauss-Newton / Newton product
+    int ttcr_fsm_normal_tile_edge(int dtype)
+    int ttcr_fsm_normal_smooth(ttcr_fsm_adjoint* t, const void* v, int v_on_device, const double* weights, void* out, int out_on_device)
+    int ttcr_fsm_normal_dot(ttcr_fsm_adjoint* t, const void* a, int a_on_device, const void* b, int b_on_device, double* result)
+    int ttcr_fsm_normal_solve(ttcr_fsm_adjoint* t, const void* rhs, int rhs_on_device, const void* row_weight, int rw_on_device,
+                              double smooth, const double* smooth_weights, double damp, const void* x0, int x0_on_device, int maxiter,
+                              double rtol, int newton, int schedule, void* x, int x_on_device, int* status, int* iterations, double* rho,
+                              double* pq, int* passes)
+    int ttcr_fsm_normal_release(ttcr_fsm_adjoint* t)
     int ttcr_fsm_slot_m_size(const ttcr_fsm_grid* g, int slot, size_t* n_rows, size_t* nnz)
     int ttcr_fsm_get_slot_m(const ttcr_fsm_grid* g, int slot, long long* row_off, long long* j, void* v)
     int ttcr_fsm_raytrace_l(ttcr_fsm_grid* g, int slot, int n_tx, const void* tx, const void* t0, int n_rx, const void* rx,

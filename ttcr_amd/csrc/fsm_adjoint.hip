@@ -1149,8 +1149,10 @@ void AdjTapeDev::release() {
     dev_free(src_off); dev_free(src_pt); dev_free(src_key); dev_free(src_node); dev_free(src_c); dev_free(src_io); dev_free(src_rows);
     dev_free(mu4); dev_free(mu4b); dev_free(cell_tmp); dev_free(hold_lam); dev_free(hess_dd);
     dev_free(g4); dev_free(blk_model); dev_free(blk_nodes); dev_free(blk_rows); dev_free(blk_rw);
+    dev_free(nrm_x); dev_free(nrm_r); dev_free(nrm_p); dev_free(nrm_q); dev_free(nrm_hp); dev_free(nrm_partial); dev_free(nrm_ctl);
     blk_owns_mu4 = false;
     blk_bytes = 0;
+    nrm_bytes = 0;
     held = false;
     if (stream) (void)hipStreamDestroy(stream);
     stream = nullptr;

@@ -13,6 +13,9 @@
 //                   -> gradient (events summed in ascending order from +0 inside the thread).
 // Per block product: the same steps for groups of four model vectors, the four values of a node adjacent: K-column seeds,
 //                   K-column relaxations (tiled; what a step needs of the field is read and formed once per node), K-column gradient.
+// Normal equations (fsm_normal.hip): the smoothing operator on the model vector (a tile with a two-node halo in LDS), inner
+//                   products summed in a fixed order (chunks of 1024, one finishing workgroup), and conjugate gradients around the
+//                   Gauss-Newton / Newton product with the scalars of the recurrence formed on the device.
 // No floating-point atomics anywhere: every value is one fixed expression of final values, so the bits do not depend on the schedule.
 // Cell tapes (ttcr_fsm_raytrace_multi_adjoint_cells): the model vector holds one slowness per cell and the node slowness is
 // A times it (fsm_cells_to_nodes3d); a jvp first applies A to ds, a vjp ends with A^T on the node gradient (one thread per cell).
@@ -118,6 +121,15 @@ struct AdjTapeDev {
     void* blk_rw = nullptr;           // 4 n_rows: a group of host row_weight columns
     bool blk_owns_mu4 = false;        // mu4 came with the block arrays (no jvp_source had allocated it) and leaves with them
     size_t blk_bytes = 0;             // what the block arrays added to total_bytes
+    // normal-equation solver: allocated by the first smooth / dot / solve, returned by adj_normal_release
+    void* nrm_x = nullptr;            // n_model() each: the iterate (a host x0 and the host result are staged here), ...
+    void* nrm_r = nullptr;            // ... the residual (a host rhs is staged here; a host operand of dot, a host v of smooth), ...
+    void* nrm_p = nullptr;            // ... the search direction (the second host operand of dot), ...
+    void* nrm_q = nullptr;            // ... A p (a host result of smooth is staged here) ...
+    void* nrm_hp = nullptr;           // ... and the output of the tape's product
+    void* nrm_partial = nullptr;      // one double per chunk of 1024 parameters
+    void* nrm_ctl = nullptr;          // the scalars of the recurrence
+    size_t nrm_bytes = 0;             // what these arrays added to total_bytes
     size_t n_tiles = 0;
     size_t total_bytes = 0;
     hipStream_t stream = nullptr;
@@ -204,5 +216,43 @@ int adj_vjp_block(AdjTapeDev& t, const T* d_w, int n_cols, T* d_grad, int schedu
 template <typename T>
 void adj_gn_block(AdjTapeDev& t, const T* d_v, const T* d_rw, size_t rw_stride, int n_cols, T* d_out, int schedule, int* passes_jvp,
                   int* passes_vjp);
+
+// ---- normal equations (tests/normal_reference.py restates them; kernels in fsm_normal.hip).  Model vectors are n_model()
+// values on the tape's device, parameters x fastest: nnx x nny x nnz nodes, or the (nnx - 1) x (nny - 1) x (nnz - 1) cells of a cell tape.
+int adj_smooth_tile_edge(size_t elem);   // edge of a smoothing tile (interior parameters) for an element size
+// the work arrays: x, r, p, q, the product output (n_model() each), one double per chunk of 1024 parameters and the scalars.
+// adj_normal_prepare is a no-op while they are there (AdjDeviceError naming the byte count if an allocation fails); adj_normal_release
+// frees them and takes them off bytes().
+size_t adj_normal_bytes(const AdjTapeDev& t);
+void adj_normal_prepare(AdjTapeDev& t);
+void adj_normal_release(AdjTapeDev& t);
+// d_out = R d_v = sum_d weights[d] K_d^T (K_d d_v), K_d the second differences of spacing dx along axis d with the centred stencil
+// shifted inwards on the two end rows; d_out and d_v are different arrays.  std::invalid_argument if an axis has fewer than 3 parameters.
+template <typename T>
+void adj_smooth(AdjTapeDev& t, const T* d_v, const double* weights, T* d_out);
+// <d_a, d_b> in fp64 with the fixed summation order of DESIGN.md 6i (chunks of 1024, one finishing workgroup); waits for the stream
+template <typename T>
+double adj_dot(AdjTapeDev& t, const T* d_a, const T* d_b);
+// A = H + smooth R + damp I with H the Gauss-Newton product (newton: the Newton product of the held cotangent); a term whose factor is
+// 0 is not evaluated
+struct NormalOperator {
+    double smooth = 0, damp = 0;
+    double weights[3] = {1, 1, 1};
+    bool newton = false;
+};
+struct NormalResult {
+    int status = 1;                 // 0: the residual test was met; 1: maxiter iterations without meeting it; 2: <p, A p> not positive
+    int iterations = 0;             // completed updates of x
+    std::vector<double> rho;        // <rhs, rhs>, <r, r> of the starting residual, then <r, r> after every completed iteration
+    std::vector<double> pq;         // <p, A p> of every iteration that evaluated it
+    std::vector<int> passes;        // (jvp, vjp) passes of the product of every such iteration
+    int passes0[2] = {0, 0};        // ... and of A x0
+};
+// conjugate gradients on A x = rhs: on entry nrm_r holds rhs and, if with_x0, nrm_x holds x0; on return nrm_x holds the iterate.
+// d_rw (n_rows, may be null) on the tape's device.  Vectors in T, scalars in fp64, inner products as adj_dot; one host read of the
+// scalars per iteration.
+template <typename T>
+void adj_solve_normal(AdjTapeDev& t, const T* d_rw, const NormalOperator& op, bool with_x0, int maxiter, double rtol, int schedule,
+                      NormalResult& res);
 
 }  // namespace ttcr_amd

@@ -4181,6 +4181,100 @@ int ttcr_fsm_adjoint_block_release(ttcr_fsm_adjoint* t) {
     std::lock_guard<std::mutex> lock(t->mu);
     return guarded([&] { ttcr_amd::adj_block_release(t->t); });
 }
+
+// ---- normal equations of the field tape: the smoothing operator, the solver's inner product and the CG solve.  The
+// entries check what needs no tape first and the tape last.  Host staging (the table above stage_in continued): the work arrays of the
+// solver are idle outside a solve, so a host v of smooth, the first operand of dot and a host rhs go through nrm_r, the second operand of
+// dot through nrm_p, a host result of smooth through nrm_q, a host x0 and the host result of a solve through nrm_x (where the solver
+// keeps the iterate anyway); a host row_weight goes through rw_tmp as for gn.  Operands on the device are read in place, rhs and x0
+// are copied into the work arrays, which the solver overwrites.
+static const char* normal_weights_error(const double* w, const char* if_null, const char* if_bad) {
+    if (!w) return if_null;
+    for (int d = 0; d < 3; ++d)
+        if (!(w[d] >= 0.0) || !std::isfinite(w[d])) return if_bad;
+    return nullptr;
+}
+static const char* normal_axes_error(const ttcr_fsm_adjoint* t) {
+    const int c = t->t.cells ? 1 : 0;
+    return std::min({t->t.nnx, t->t.nny, t->t.nnz}) - c < 3 ? "smooth: second-order smoothing needs at least 3 parameters along every axis"
+                                                             : nullptr;
+}
+int ttcr_fsm_normal_tile_edge(int dtype) { return ttcr_amd::adj_smooth_tile_edge(dtype == TTCR_F32 ? 4 : 8); }
+int ttcr_fsm_normal_smooth(ttcr_fsm_adjoint* t, const void* v, int v_on_device, const double* weights, void* out, int out_on_device) {
+    const char* bad = normal_weights_error(weights, "null weights", "weights: three finite values >= 0 (x, y, z)");
+    if (!bad) bad =!v ? "null v" : (!out ? "null out" : (!t ? "null tape" : normal_axes_error(t)));
+    if (bad) return tape_arg_error(bad);
+    return tape_call(t, 0, nullptr, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int&, int&) {
+        using T = decltype(tag);
+        ttcr_amd::adj_normal_prepare(d);
+        const T* dv = stage_in<T>(d, v, v_on_device, d.nrm_r, d.n_model());
+        ttcr_amd::adj_smooth<T>(d, dv, weights, stage_dst<T>(out, out_on_device, d.nrm_q));
+        stage_out<T>(d, out, out_on_device, d.nrm_q, d.n_model());
+    });
+}
+int ttcr_fsm_normal_dot(ttcr_fsm_adjoint* t, const void* a, int a_on_device, const void* b, int b_on_device, double* result) {
+    if (!a || !b || !result || !t) return tape_arg_error(!a ? "null a" : (!b ? "null b" : (!result ? "null result" : "null tape")));
+    return tape_call(t, 0, nullptr, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int&, int&) {
+        using T = decltype(tag);
+        ttcr_amd::adj_normal_prepare(d);
+        const T* da = stage_in<T>(d, a, a_on_device, d.nrm_r, d.n_model());
+        const T* db = b == a && b_on_device == a_on_device ? da : stage_in<T>(d, b, b_on_device, d.nrm_p, d.n_model());
+        *result = ttcr_amd::adj_dot<T>(d, da, db);
+    });
+}
+int ttcr_fsm_normal_solve(ttcr_fsm_adjoint* t, const void* rhs, int rhs_on_device, const void* row_weight, int rw_on_device, double smooth,
+                          const double* smooth_weights, double damp, const void* x0, int x0_on_device, int maxiter, double rtol,
+                          int newton, int schedule, void* x, int x_on_device, int* status, int* iterations, double* rho, double* pq,
+                          int* passes) {
+    const char* bad = nullptr;
+    if (!(smooth >= 0.0) || !std::isfinite(smooth)) bad = "smooth: a finite value >= 0";
+    else if (!(damp >= 0.0) || !std::isfinite(damp)) bad = "damp: a finite value >= 0";
+    else if (maxiter < 1) bad = "maxiter: at least one iteration";
+    else if (!(rtol >= 0.0) || !std::isfinite(rtol)) bad = "rtol: a finite value >= 0";
+    else if (newton != 0 && newton != 1) bad = "hessian: 0 (gauss_newton) or 1 (newton)";
+    else if (const char* w = normal_weights_error(smooth_weights, "null smooth_weights", "smooth_weights: three finite values >= 0 (x, y, z)"))
+        bad = w;
+    else if (const char* s = schedule_error(schedule)) bad = s;
+    else if (!rhs || !x) bad = !rhs ? "null rhs" : "null x";
+    else if (!status || !iterations || !rho || !pq) bad = "null status, iterations, rho or pq";
+    else if (!t) bad = "null tape";
+    else if (smooth != 0.0) bad = normal_axes_error(t);
+    if (bad) return tape_arg_error(bad);
+    return tape_call(t, schedule, nullptr, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int&, int&) {
+        using T = decltype(tag);
+        const size_t n = d.n_model();
+        ttcr_amd::adj_normal_prepare(d);
+        if (row_weight && !rw_on_device) ttcr_amd::adj_jvp_prepare<T>(d);
+        const T* drw = stage_in<T>(d, row_weight, rw_on_device, d.rw_tmp, d.n_rows);
+        const T* drhs = stage_in<T>(d, rhs, rhs_on_device, d.nrm_r, n);
+        const T* dx0 = stage_in<T>(d, x0, x0_on_device, d.nrm_x, n);
+        if (n > 0 && (const void*)drhs != d.nrm_r) HIP_CHECK(hipMemcpyAsync(d.nrm_r, drhs, n * sizeof(T), hipMemcpyDeviceToDevice, d.stream));
+        if (n > 0 && dx0 && (const void*)dx0 != d.nrm_x) HIP_CHECK(hipMemcpyAsync(d.nrm_x, dx0, n * sizeof(T), hipMemcpyDeviceToDevice, d.stream));
+        ttcr_amd::NormalOperator op;
+        op.smooth = smooth;
+        op.damp = damp;
+        std::copy(smooth_weights, smooth_weights + 3, op.weights);
+        op.newton = newton != 0;
+        ttcr_amd::NormalResult res;
+        ttcr_amd::adj_solve_normal<T>(d, drw, op, x0 != nullptr, maxiter, rtol, schedule, res);
+        if (n > 0 && x_on_device) HIP_CHECK(hipMemcpyAsync(x, d.nrm_x, n * sizeof(T), hipMemcpyDeviceToDevice, d.stream));
+        stage_out<T>(d, x, x_on_device, d.nrm_x, n);
+        *status = res.status;
+        *iterations = res.iterations;
+        std::copy(res.rho.begin(), res.rho.end(), rho);
+        std::copy(res.pq.begin(), res.pq.end(), pq);
+        if (passes) {
+            passes[0] = res.passes0[0];
+            passes[1] = res.passes0[1];
+            std::copy(res.passes.begin(), res.passes.end(), passes + 2);
+        }
+    }, newton == 1 ? "newton" : nullptr);
+}
+int ttcr_fsm_normal_release(ttcr_fsm_adjoint* t) {
+    if (!t) return tape_arg_error("null tape");
+    std::lock_guard<std::mutex> lock(t->mu);
+    return guarded([&] { ttcr_amd::adj_normal_release(t->t); });
+}
 int ttcr_fsm_adjoint_free(ttcr_fsm_adjoint* t) {
     if (!t) return TTCR_OK;
     return guarded([&] { delete t; });

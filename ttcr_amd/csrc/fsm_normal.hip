@@ -1,0 +1,435 @@
+// ttcr_amd/csrc/fsm_normal.hip -- translation unit of the field tape's normal-equation solver: the smoothing operator
+// R v = sum_d a_d K_d^T (K_d v) on the tape's model vector, the inner product with a fixed summation order, and conjugate gradients on
+// (H + lam R + mu I) x = b with H the tape's Gauss-Newton (or Newton) product; see fsm_adjoint_api.h.  tests/normal_reference.py restates
+// all of it in numpy.  Compiled with -ffp-contract=off like every other unit: each product, difference, quotient and sum below is
+// rounded on its own, in the order the definition writes them.  No floating-point atomics.
+#include "fsm_adjoint_api.h"
+
+#include <algorithm>
+#include <cmath>
+#include <sstream>
+#include <string>
+#include <type_traits>
+
+#define NRM_CHECK(expr)                                                                                           \
+    do {                                                                                                          \
+        hipError_t _e = (expr);                                                                                   \
+        if (_e != hipSuccess) {                                                                                   \
+            std::ostringstream _m;                                                                                \
+            _m << "HIP error " << hipGetErrorString(_e) << " at " << __FILE__ << ":" << __LINE__ << " (" #expr ")"; \
+            throw AdjDeviceError(_m.str());                                                                       \
+        }                                                                                                         \
+    } while (0)
+
+namespace ttcr_amd {
+
+namespace {
+
+constexpr int NRM_THREADS = 256;
+constexpr int NRM_CHUNK = 1024;   // elements of a chunk partial: one workgroup, four elements per thread
+// interior edge of a smoothing tile: with its two-node halo the tile of v takes (edge + 4)^3 * sizeof(T) bytes of LDS -- 31.25 KiB
+// (fp32, 20^3) and 32 KiB (fp64, 16^3)
+template <typename T> struct NrmTile;
+template <> struct NrmTile<float> { static constexpr int edge = 16; };
+template <> struct NrmTile<double> { static constexpr int edge = 12; };
+
+// what the update kernels read from device memory, and what the host reads once per iteration
+struct NrmCtl {
+    double rho;      // <r, r> of the current residual
+    double pq;       // <p, q> of the running iteration
+    double alpha;    // T(rho / pq), held exactly
+    double beta;     // T(rho_new / rho), held exactly
+    double sum;      // the last plain inner product (rho0; adj_dot)
+    int ok;          // pq > 0 and finite: the update kernels of the iteration run
+};
+
+enum NrmClose { NRM_PLAIN, NRM_RR0, NRM_PQ, NRM_RR };
+
+struct NrmDims {
+    int mx, my, mz;   // parameters along x, y, z (x fastest)
+};
+
+// one axis of K^T K v at the parameter whose value is c[0]: c[o * sd] is the parameter o steps along the axis (|o| <= 2, inside the
+// grid), i its index on the axis and n the length of the axis (>= 3).  Rows in ascending order, the sum starts from its first term.
+template <typename T>
+__device__ __forceinline__ T nrm_axis(const T* c, int sd, int i, int n, T ih2, T m2ih2) {
+    auto y = [&](int r) {
+        const int o = min(max(r, 1), n - 2) - i;
+        return ((c[(o - 1) * sd] + c[(o + 1) * sd]) - T(2) * c[o * sd]) * ih2;
+    };
+    T z = T(0);
+    bool first = true;
+    auto add = [&](T term) {
+        z = first ? term : z + term;
+        first = false;
+    };
+    if (i <= 2) add((i == 1 ? m2ih2 : ih2) * y(0));
+    for (int r = max(i - 1, 1); r <= min(i + 1, n - 2); ++r) add((r == i ? m2ih2 : ih2) * y(r));
+    if (i >= n - 3) add((i == n - 2 ? m2ih2 : ih2) * y(n - 1));
+    return z;
+}
+
+template <typename T>
+struct NrmSmooth {
+    NrmDims g;
+    T ih2, ax, ay, az;   // T(1 / dx^2) and the weights of the axes
+};
+
+// (R v) at the parameter (gx, gy, gz) whose value is c[0]; sx, sy, sz are the strides of the three axes in the array c points into
+template <typename T>
+__device__ __forceinline__ T nrm_smooth_at(const T* c, int sx, int sy, int sz, int gx, int gy, int gz, const NrmSmooth<T>& sm) {
+    const T m2ih2 = T(-2) * sm.ih2;
+    const T zx = nrm_axis<T>(c, sx, gx, sm.g.mx, sm.ih2, m2ih2);
+    const T zy = nrm_axis<T>(c, sy, gy, sm.g.my, sm.ih2, m2ih2);
+    const T zz = nrm_axis<T>(c, sz, gz, sm.g.mz, sm.ih2, m2ih2);
+    return (sm.ax * zx + sm.ay * zy) + sm.az * zz;
+}
+
+// out = R v: one workgroup per tile of TI^3 parameters; the tile of v with a two-node halo (cut at the faces of the grid) sits in LDS,
+// y is recomputed from it.  Thread t owns the interior parameters t + 256 q, x fastest.
+template <typename T, int TI>
+__global__ __launch_bounds__(NRM_THREADS) void nrm_smooth_kernel(const T* __restrict__ v, T* __restrict__ out, NrmSmooth<T> sm, int ntx,
+                                                                 int nty) {
+    const NrmDims g = sm.g;
+    constexpr int P = TI + 4;   // pitch of a row, rows of a plane
+    __shared__ T tile[P * P * P];
+    const int tx = blockIdx.x % ntx, ty = (blockIdx.x / ntx) % nty, tz = blockIdx.x / (ntx * nty);
+    const int x0 = tx * TI, y0 = ty * TI, z0 = tz * TI;
+    for (int l = threadIdx.x; l < P * P * P; l += NRM_THREADS) {
+        const int gx = x0 - 2 + l % P, gy = y0 - 2 + (l / P) % P, gz = z0 - 2 + l / (P * P);
+        const bool in = gx >= 0 && gx < g.mx && gy >= 0 && gy < g.my && gz >= 0 && gz < g.mz;
+        tile[l] = in ? v[((size_t)gz * g.my + gy) * g.mx + gx] : T(0);
+    }
+    __syncthreads();
+    for (int q = threadIdx.x; q < TI * TI * TI; q += NRM_THREADS) {
+        const int lx = q % TI, ly = (q / TI) % TI, lz = q / (TI * TI);
+        const int gx = x0 + lx, gy = y0 + ly, gz = z0 + lz;
+        if (gx >= g.mx || gy >= g.my || gz >= g.mz) continue;
+        const T* c = tile + ((lz + 2) * P + (ly + 2)) * P + (lx + 2);
+        out[((size_t)gz * g.my + gy) * g.mx + gx] = nrm_smooth_at<T>(c, 1, P, P * P, gx, gy, gz, sm);
+    }
+}
+
+// the chunk partial of a workgroup from the four elements e0 .. e3 of thread t (elements t, t + 256, t + 512, t + 768 of the chunk):
+// ((e0 + e1) + e2) + e3, then s[t] += s[t + stride] for stride = 128 .. 1
+__device__ __forceinline__ void nrm_chunk_partial(double e0, double e1, double e2, double e3, double* __restrict__ partial) {
+    __shared__ double s[NRM_THREADS];
+    const int t = threadIdx.x;
+    s[t] = ((e0 + e1) + e2) + e3;
+    __syncthreads();
+    for (int stride = NRM_THREADS / 2; stride >= 1; stride >>= 1) {
+        if (t < stride) s[t] += s[t + stride];
+        __syncthreads();
+    }
+    if (t == 0) partial[blockIdx.x] = s[0];
+}
+
+__device__ __forceinline__ double nrm_prod(float a, float b) { return (double)a * (double)b; }
+__device__ __forceinline__ double nrm_prod(double a, double b) { return a * b; }
+
+// chunk partials of <a, b>
+template <typename T>
+__global__ __launch_bounds__(NRM_THREADS) void nrm_dot_kernel(const T* __restrict__ a, const T* __restrict__ b, size_t n,
+                                                              double* __restrict__ partial) {
+    double e[4];
+    for (int k = 0; k < 4; ++k) {
+        const size_t i = (size_t)blockIdx.x * NRM_CHUNK + threadIdx.x + (size_t)k * NRM_THREADS;
+        e[k] = i < n ? nrm_prod(a[i], b[i]) : 0.0;
+    }
+    nrm_chunk_partial(e[0], e[1], e[2], e[3], partial);
+}
+
+// kernel 1 of an iteration: q = fl(fl(hp + fl(lam * (R p))) + fl(mu * p)) (the smoothing term only if with_smooth, the damping term only
+// if with_damp), and the chunk partials of <p, q>.  A workgroup owns a chunk of the flat vector, as the partials demand, so the smoothing
+// gather reads p around each of its parameters from global memory (the expression is nrm_smooth_kernel's: nrm_smooth_at on other strides)
+template <typename T>
+__global__ __launch_bounds__(NRM_THREADS) void nrm_combine_kernel(const T* __restrict__ hp, const T* __restrict__ p, T* __restrict__ q,
+                                                                  size_t n, NrmSmooth<T> sm, T lam, T mu, int with_smooth, int with_damp,
+                                                                  double* __restrict__ partial) {
+    double e[4];
+    for (int k = 0; k < 4; ++k) {
+        const size_t i = (size_t)blockIdx.x * NRM_CHUNK + threadIdx.x + (size_t)k * NRM_THREADS;
+        e[k] = 0.0;
+        if (i < n) {
+            const T pi = p[i];
+            T a = hp[i];
+            if (with_smooth) {
+                const int gx = (int)(i % sm.g.mx), gy = (int)((i / sm.g.mx) % sm.g.my), gz = (int)(i / ((size_t)sm.g.mx * sm.g.my));
+                a = a + lam * nrm_smooth_at<T>(p + i, 1, sm.g.mx, sm.g.mx * sm.g.my, gx, gy, gz, sm);
+            }
+            if (with_damp) a = a + mu * pi;
+            q[i] = a;
+            e[k] = nrm_prod(pi, a);
+        }
+    }
+    nrm_chunk_partial(e[0], e[1], e[2], e[3], partial);
+}
+
+// the start of a solve: r = rhs (in r on entry), or fl(rhs - q) with q = A x0 if with_x0; p = r; chunk partials of <r, r>
+template <typename T>
+__global__ __launch_bounds__(NRM_THREADS) void nrm_start_kernel(T* __restrict__ r, const T* __restrict__ q, T* __restrict__ p, size_t n,
+                                                                int with_x0, double* __restrict__ partial) {
+    double e[4];
+    for (int k = 0; k < 4; ++k) {
+        const size_t i = (size_t)blockIdx.x * NRM_CHUNK + threadIdx.x + (size_t)k * NRM_THREADS;
+        e[k] = 0.0;
+        if (i < n) {
+            T ri = r[i];
+            if (with_x0) {
+                ri = ri - q[i];
+                r[i] = ri;
+            }
+            p[i] = ri;
+            e[k] = nrm_prod(ri, ri);
+        }
+    }
+    nrm_chunk_partial(e[0], e[1], e[2], e[3], partial);
+}
+
+// kernel 2: x = fl(x + fl(aT * p)), r = fl(r - fl(aT * q)), chunk partials of <r, r>; nothing at all if the iteration broke down
+template <typename T>
+__global__ __launch_bounds__(NRM_THREADS) void nrm_update_kernel(T* __restrict__ x, T* __restrict__ r, const T* __restrict__ p,
+                                                                 const T* __restrict__ q, size_t n, const NrmCtl* __restrict__ ctl,
+                                                                 double* __restrict__ partial) {
+    if (!ctl->ok) return;
+    const T aT = (T)ctl->alpha;
+    double e[4];
+    for (int k = 0; k < 4; ++k) {
+        const size_t i = (size_t)blockIdx.x * NRM_CHUNK + threadIdx.x + (size_t)k * NRM_THREADS;
+        e[k] = 0.0;
+        if (i < n) {
+            x[i] = x[i] + aT * p[i];
+            const T ri = r[i] - aT * q[i];
+            r[i] = ri;
+            e[k] = nrm_prod(ri, ri);
+        }
+    }
+    nrm_chunk_partial(e[0], e[1], e[2], e[3], partial);
+}
+
+// kernel 3: p = fl(r + fl(bT * p))
+template <typename T>
+__global__ __launch_bounds__(NRM_THREADS) void nrm_direction_kernel(const T* __restrict__ r, T* __restrict__ p, size_t n,
+                                                                    const NrmCtl* __restrict__ ctl) {
+    if (!ctl->ok) return;
+    const T bT = (T)ctl->beta;
+    const size_t i = (size_t)blockIdx.x * NRM_THREADS + threadIdx.x;
+    if (i < n) p[i] = r[i] + bT * p[i];
+}
+
+// the finishing reduction, one workgroup: thread t adds the chunk partials t, t + 256, ... ascending from +0, then the halving of the
+// chunk rule.  Thread 0 then closes the inner product: the scalars of the recurrence are formed here, on the device, in fp64, and
+// alpha / beta are rounded to T.  After a breakdown the <r, r> of the iteration is not closed: rho stays what it was.
+template <typename T>
+__global__ __launch_bounds__(NRM_THREADS) void nrm_finish_kernel(const double* __restrict__ partial, size_t n_partials, int what,
+                                                                 NrmCtl* __restrict__ ctl) {
+    if (what == NRM_RR && !ctl->ok) return;
+    __shared__ double s[NRM_THREADS];
+    const int t = threadIdx.x;
+    double acc = 0.0;
+    for (size_t j = t; j < n_partials; j += NRM_THREADS) acc += partial[j];
+    s[t] = acc;
+    __syncthreads();
+    for (int stride = NRM_THREADS / 2; stride >= 1; stride >>= 1) {
+        if (t < stride) s[t] += s[t + stride];
+        __syncthreads();
+    }
+    if (t != 0) return;
+    const double sum = s[0];
+    if (what == NRM_PLAIN) {
+        ctl->sum = sum;
+    } else if (what == NRM_RR0) {
+        ctl->rho = sum;
+    } else if (what == NRM_PQ) {
+        ctl->pq = sum;
+        ctl->ok = (sum > 0.0 && sum <= 1.7976931348623157e308) ? 1 : 0;
+        ctl->alpha = (double)(T)(ctl->rho / sum);
+    } else {
+        ctl->beta = (double)(T)(sum / ctl->rho);
+        ctl->rho = sum;
+    }
+}
+
+template <typename P>
+void nrm_free(P*& p) {
+    if (p) (void)hipFree((void*)p);
+    p = nullptr;
+}
+
+size_t nrm_chunks(const AdjTapeDev& t) { return std::max<size_t>(1, (t.n_model() + NRM_CHUNK - 1) / NRM_CHUNK); }
+
+NrmDims nrm_dims(const AdjTapeDev& t) {
+    const int c = t.cells ? 1 : 0;
+    return NrmDims{t.nnx - c, t.nny - c, t.nnz - c};
+}
+
+template <typename T>
+void nrm_close(AdjTapeDev& t, int what) {
+    nrm_finish_kernel<T><<<1, NRM_THREADS, 0, t.stream>>>((const double*)t.nrm_partial, nrm_chunks(t), what, (NrmCtl*)t.nrm_ctl);
+    NRM_CHECK(hipGetLastError());
+}
+
+template <typename T>
+NrmSmooth<T> nrm_smooth_args(const AdjTapeDev& t, const double* weights) {
+    return NrmSmooth<T>{nrm_dims(t), (T)(1.0 / (t.dx * t.dx)), (T)weights[0], (T)weights[1], (T)weights[2]};
+}
+
+// q = A v (v is p of an iteration or x0) and the chunk partials of <v, q>: the product of the tape into hp, then kernel 1
+template <typename T>
+void nrm_apply(AdjTapeDev& t, const T* v, const T* d_rw, const NormalOperator& op, int schedule, int* pj, int* pv) {
+    T* hp = (T*)t.nrm_hp;
+    if (op.newton) adj_hess<T>(t, v, d_rw, true, hp, schedule, pj, pv);
+    else adj_gn<T>(t, v, d_rw, hp, schedule, pj, pv);
+    nrm_combine_kernel<T><<<(unsigned)nrm_chunks(t), NRM_THREADS, 0, t.stream>>>(hp, v, (T*)t.nrm_q, t.n_model(),
+                                                                                nrm_smooth_args<T>(t, op.weights), (T)op.smooth, (T)op.damp,
+                                                                                op.smooth != 0.0, op.damp != 0.0, (double*)t.nrm_partial);
+    NRM_CHECK(hipGetLastError());
+}
+
+}  // namespace
+
+int adj_smooth_tile_edge(size_t elem) { return elem == 4 ? NrmTile<float>::edge : NrmTile<double>::edge; }
+
+size_t adj_normal_bytes(const AdjTapeDev& t) {
+    return 5 * std::max<size_t>(t.n_model() * t.elem, 1) + nrm_chunks(t) * sizeof(double) + sizeof(NrmCtl);
+}
+
+void adj_normal_prepare(AdjTapeDev& t) {
+    if (t.nrm_x) return;
+    NRM_CHECK(hipSetDevice(t.device));
+    const size_t planned = adj_normal_bytes(t);
+    size_t got = 0;
+    auto alloc = [&](auto*& p, size_t bytes) {
+        const size_t b = std::max<size_t>(bytes, 1);
+        void* raw = nullptr;
+        if (hipMalloc(&raw, b) != hipSuccess) {
+            (void)hipGetLastError();
+            std::ostringstream m;
+            m << "the normal-equation solver of the field tape needs " << planned << " bytes of device memory on device " << t.device
+              << " (an allocation of " << b << " bytes failed)";
+            throw AdjDeviceError(m.str());
+        }
+        p = (std::remove_reference_t<decltype(p)>)raw;
+        got += b;
+    };
+    try {
+        const size_t vec = t.n_model() * t.elem;
+        alloc(t.nrm_x, vec);
+        alloc(t.nrm_r, vec);
+        alloc(t.nrm_p, vec);
+        alloc(t.nrm_q, vec);
+        alloc(t.nrm_hp, vec);
+        alloc(t.nrm_partial, nrm_chunks(t) * sizeof(double));
+        alloc(t.nrm_ctl, sizeof(NrmCtl));
+    } catch (...) {
+        nrm_free(t.nrm_x); nrm_free(t.nrm_r); nrm_free(t.nrm_p); nrm_free(t.nrm_q); nrm_free(t.nrm_hp);
+        nrm_free(t.nrm_partial); nrm_free(t.nrm_ctl);
+        throw;
+    }
+    t.nrm_bytes = got;
+    t.total_bytes += got;
+}
+
+void adj_normal_release(AdjTapeDev& t) {
+    if (!t.nrm_x) return;
+    (void)hipSetDevice(t.device);
+    if (t.stream) (void)hipStreamSynchronize(t.stream);
+    nrm_free(t.nrm_x); nrm_free(t.nrm_r); nrm_free(t.nrm_p); nrm_free(t.nrm_q); nrm_free(t.nrm_hp);
+    nrm_free(t.nrm_partial); nrm_free(t.nrm_ctl);
+    t.total_bytes -= t.nrm_bytes;
+    t.nrm_bytes = 0;
+}
+
+template <typename T>
+void adj_smooth(AdjTapeDev& t, const T* d_v, const double* weights, T* d_out) {
+    const NrmDims g = nrm_dims(t);
+    if (g.mx < 3 || g.my < 3 || g.mz < 3)
+        throw std::invalid_argument("smooth: second-order smoothing needs at least 3 parameters along every axis");
+    constexpr int ed = NrmTile<T>::edge;
+    const int ntx = (g.mx + ed - 1) / ed, nty = (g.my + ed - 1) / ed, ntz = (g.mz + ed - 1) / ed;
+    nrm_smooth_kernel<T, ed><<<(unsigned)((size_t)ntx * nty * ntz), NRM_THREADS, 0, t.stream>>>(d_v, d_out, nrm_smooth_args<T>(t, weights), ntx,
+                                                                                              nty);
+    NRM_CHECK(hipGetLastError());
+}
+
+template <typename T>
+double adj_dot(AdjTapeDev& t, const T* d_a, const T* d_b) {
+    adj_normal_prepare(t);
+    nrm_dot_kernel<T><<<(unsigned)nrm_chunks(t), NRM_THREADS, 0, t.stream>>>(d_a, d_b, t.n_model(), (double*)t.nrm_partial);
+    NRM_CHECK(hipGetLastError());
+    nrm_close<T>(t, NRM_PLAIN);
+    NrmCtl h;
+    NRM_CHECK(hipMemcpyAsync(&h, t.nrm_ctl, sizeof(h), hipMemcpyDeviceToHost, t.stream));
+    NRM_CHECK(hipStreamSynchronize(t.stream));
+    return h.sum;
+}
+
+template <typename T>
+void adj_solve_normal(AdjTapeDev& t, const T* d_rw, const NormalOperator& op, bool with_x0, int maxiter, double rtol, int schedule,
+                      NormalResult& res) {
+    NRM_CHECK(hipSetDevice(t.device));
+    adj_normal_prepare(t);
+    hipStream_t s = t.stream;
+    const size_t n = t.n_model();
+    const unsigned chunks = (unsigned)nrm_chunks(t);
+    T* x = (T*)t.nrm_x;
+    T* r = (T*)t.nrm_r;
+    T* p = (T*)t.nrm_p;
+    T* q = (T*)t.nrm_q;
+    double* partial = (double*)t.nrm_partial;
+    NrmCtl* ctl = (NrmCtl*)t.nrm_ctl;
+    res = NormalResult();
+    // rho0 = <rhs, rhs> (rhs is in r), then the starting residual, p and rho
+    NRM_CHECK(hipMemsetAsync(ctl, 0, sizeof(NrmCtl), s));
+    nrm_dot_kernel<T><<<chunks, NRM_THREADS, 0, s>>>(r, r, n, partial);
+    NRM_CHECK(hipGetLastError());
+    nrm_close<T>(t, NRM_PLAIN);
+    if (with_x0) nrm_apply<T>(t, x, d_rw, op, schedule, &res.passes0[0], &res.passes0[1]);
+    else if (n > 0) NRM_CHECK(hipMemsetAsync(x, 0, n * sizeof(T), s));
+    nrm_start_kernel<T><<<chunks, NRM_THREADS, 0, s>>>(r, q, p, n, with_x0 ? 1 : 0, partial);
+    NRM_CHECK(hipGetLastError());
+    nrm_close<T>(t, NRM_RR0);
+    NrmCtl h;
+    NRM_CHECK(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, s));
+    NRM_CHECK(hipStreamSynchronize(s));
+    const double rho0 = h.sum;
+    double rho = h.rho;
+    res.rho.push_back(rho0);
+    res.rho.push_back(rho);
+    res.status = 1;
+    for (int k = 1; k <= maxiter; ++k) {
+        if (rho <= rtol * rtol * rho0) {
+            res.status = 0;
+            break;
+        }
+        int pj = 0, pv = 0;
+        nrm_apply<T>(t, p, d_rw, op, schedule, &pj, &pv);
+        res.passes.push_back(pj);
+        res.passes.push_back(pv);
+        nrm_close<T>(t, NRM_PQ);
+        nrm_update_kernel<T><<<chunks, NRM_THREADS, 0, s>>>(x, r, p, q, n, ctl, partial);
+        NRM_CHECK(hipGetLastError());
+        nrm_close<T>(t, NRM_RR);
+        nrm_direction_kernel<T><<<(unsigned)std::max<size_t>(1, (n + NRM_THREADS - 1) / NRM_THREADS), NRM_THREADS, 0, s>>>(r, p, n, ctl);
+        NRM_CHECK(hipGetLastError());
+        NRM_CHECK(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, s));   // the one host read of the iteration: (rho, pq)
+        NRM_CHECK(hipStreamSynchronize(s));
+        res.pq.push_back(h.pq);
+        if (!h.ok) {   // (the update kernels saw the same flag and left x, r and p alone)
+            res.status = 2;
+            break;
+        }
+        rho = h.rho;
+        res.rho.push_back(rho);
+        ++res.iterations;
+    }
+}
+
+template void adj_smooth<float>(AdjTapeDev&, const float*, const double*, float*);
+template void adj_smooth<double>(AdjTapeDev&, const double*, const double*, double*);
+template double adj_dot<float>(AdjTapeDev&, const float*, const float*);
+template double adj_dot<double>(AdjTapeDev&, const double*, const double*);
+template void adj_solve_normal<float>(AdjTapeDev&, const float*, const NormalOperator&, bool, int, double, int, NormalResult&);
+template void adj_solve_normal<double>(AdjTapeDev&, const double*, const NormalOperator&, bool, int, double, int, NormalResult&);
+
+}  // namespace ttcr_amd

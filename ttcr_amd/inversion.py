@@ -6,6 +6,9 @@ matrices from the grid geometry alone -- no solver, no device -- and follow the 
   interp_matrix        rgrid.pyx:610-677 (3-D), :3565-3627 (2-D)     one weight 1 per point (cell slowness) or the 2^d multilinear weights
   smoothing_matrices   rgrid.pyx:679-756 (3-D, second differences), :3630-3733 (2-D, order 1 or 2)   one-sided stencils on the faces
   straight_ray_kernel  rgrid.pyx:1381-1720 (3-D), :4259-4470 (2-D, optional elliptical-anisotropy form)   segment lengths per cell
+
+One helper does use a device, through a field tape it is handed: gauss_newton_step, the right-hand side and the solve of a regularised
+Gauss-Newton step (FieldTape.solve_normal); no reference counterpart.
 """
 import numpy as np
 
@@ -85,6 +88,20 @@ def smoothing_matrices(shape, spacings, order=2):
             m = f if m is None else sp.kron(m, f, format='csr')
         out.append(m.tocsr())
     return tuple(out)
+
+
+def gauss_newton_step(tape, residual, model, row_weight=None, smooth=0., damp=0., **solve_args):
+    """The model update of one damped, smoothed Gauss-Newton step on a field tape (rgrid.FieldTape): the right-hand side
+        b = tape.vjp(row_weight * residual) - smooth * tape.smooth(model)            (= J^T W r - smooth R s)
+    and then tape.solve_normal(b, row_weight=row_weight, smooth=smooth, damp=damp, **solve_args), whose result is returned as it is.
+    residual: one value per data row (rcv order); model: the current model vector (n_cols values; not read for smooth == 0).  Host
+    glue only: the products are formed where residual and model live, in their dtype; smooth_weights of solve_args shapes R on both
+    sides."""
+    w = residual if row_weight is None else row_weight * residual
+    b = tape.vjp(w)
+    if smooth != 0:
+        b = b - smooth * tape.smooth(model, solve_args.get('smooth_weights', (1., 1., 1.)))
+    return tape.solve_normal(b, row_weight=row_weight, smooth=smooth, damp=damp, **solve_args)
 
 
 def straight_ray_kernel(Tx, Rx, axes, aniso=False):

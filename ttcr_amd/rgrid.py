@@ -556,7 +556,8 @@ class FieldTape:
     on the grid any more: later calls, set_slowness and deleting the grid leave it as it is.  vjp applies J^T (reverse mode), jvp
     applies J (forward mode) and gauss_newton J^T W J of the same linearisation, all on the device; hold keeps the adjoint of a cotangent
     on the tape, hvp then applies the second-order term sum_r w_r d2 tt_r / ds2 and newton the full Hessian J^T W J + that term (release
-    frees the held adjoint).  The same linearisation with respect
+    frees the held adjoint); solve_normal solves the regularised normal equations of a Gauss-Newton step around those products by
+    conjugate gradients on the device (smooth: its smoothing operator, dot: its inner product).  The same linearisation with respect
     to the source points, parameters (t0, x, y, z) each: jvp_source, source_jacobian and vjp(..., return_source_grad=True); n_points
     points in call order, point_event their events.
     wrt is 'nodes' or 'cells': what the model vector of vjp / jvp / gauss_newton holds, n_cols values -- the node slowness (n_cols =
@@ -968,6 +969,99 @@ class FieldTape:
         """Free the work arrays of the block products (nbytes falls by what the first block call added); the next block call allocates
         them again.  A held cotangent (hold / release) is not touched."""
         _lib.check(self._lib.ttcr_fsm_adjoint_block_release(self._handle()))
+        self._refresh_nbytes()
+
+    # ---- normal equations (DESIGN.md 6i)
+    HESSIANS = {'gauss_newton': 0, 'newton': 1}
+
+    @property
+    def smooth_tile_edge(self):
+        """edge of a tile of the smoothing kernel (parameters) for the tape's dtype"""
+        return self._lib.ttcr_fsm_normal_tile_edge(_lib.TTCR_F32 if self.dtype == np.float32 else _lib.TTCR_F64)
+
+    @staticmethod
+    def _weights(weights, name):
+        w = np.asarray(weights, dtype=np.float64)
+        if w.shape != (3,) or not np.all(np.isfinite(w)) or np.any(w < 0):
+            raise ValueError('%s should be three finite values >= 0 (x, y, z), got %r' % (name, weights))
+        return (C.c_double * 3)(*w)
+
+    def smooth(self, v, weights=(1., 1., 1.)):
+        """R v = sum_d weights[d] K_d^T (K_d v) (n_cols values, grid dtype): K_d the order-2 smoothing operators of Grid3d.compute_K() on
+        the tape's parameters (nodes, or cells on a cell tape; spacing dx), in the tape's own order, x fastest -- compute_K's matrices
+        are z fastest.  One kernel on the device, every value the fixed expression of DESIGN.md 6i (tests/normal_reference.py restates
+        it).  ValueError if an axis has fewer than 3 parameters, like compute_K.  Array handling as in jvp; the first smooth, dot or
+        solve_normal allocates the solver's work arrays (nbytes; release_solve returns them)."""
+        self._handle()
+        w = self._weights(weights, 'weights')
+        va, pv, dv = self._model_arg(v, 'v')
+        po, do, finish = self._model_out(v)
+        self._sync(dv, do)
+        _lib.check(self._lib.ttcr_fsm_normal_smooth(self._h, pv, dv, w, po, do))
+        self._refresh_nbytes()
+        return finish()
+
+    def dot(self, a, b):
+        """<a, b> of two model vectors as the solver forms it: a Python float, the products in fp64 (exact for fp32), summed in the
+        fixed order of DESIGN.md 6i -- chunks of 1024 elements, one finishing workgroup -- so the bits depend on nothing but a and b."""
+        self._handle()
+        aa, pa, da = self._model_arg(a, 'a')
+        ba, pb, db = self._model_arg(b, 'b')
+        self._sync(da, db)
+        out = C.c_double(0.0)
+        _lib.check(self._lib.ttcr_fsm_normal_dot(self._h, pa, da, pb, db, C.byref(out)))
+        self._refresh_nbytes()
+        return out.value
+
+    def solve_normal(self, rhs, row_weight=None, smooth=0.0, smooth_weights=(1., 1., 1.), damp=0.0, x0=None, maxiter=20, rtol=1e-6,
+                     hessian='gauss_newton', schedule='tiled', return_info=False):
+        """The model update x of a damped, smoothed Gauss-Newton step,
+            (J^T W J + smooth * sum_d a_d K_d^T K_d + damp * I) x = rhs,        W = diag(row_weight), a = smooth_weights,
+        by conjugate gradients on the device (at most maxiter iterations, stopped when |r| <= rtol |rhs|): the products are
+        gauss_newton's (hessian='newton': newton's, which needs hold()), the smoothing term is smooth()'s, the inner products are dot()'s,
+        the scalars of the recurrence are formed on the device, and the host reads one (rho, pq) pair per iteration.  Vectors are in
+        the grid dtype, scalars in fp64; the result is defined to the bit (tests/normal_reference.py restates it) and is
+        the same under both schedules.  A term whose factor is 0 is not evaluated.  rhs, x0: n_cols values; row_weight: one value per
+        data row (rcv order) or None.  Returns x where the first torch argument lives (numpy otherwise); with return_info=True
+        (x, info), info a dict: status (0 converged, 1 maxiter reached, 2 <p, A p> not positive: x is the iterate so far), iterations
+        (completed updates), rho (<rhs, rhs>, <r, r> of the starting residual, then after every iteration), pq (<p, A p> of every
+        iteration), passes ((jvp, vjp) per iteration) and passes_x0.  Array handling as in gauss_newton.  The first call allocates five
+        model vectors (nbytes; release_solve returns them)."""
+        self._handle()
+        sch = self._schedule(schedule)
+        for name, val in (('smooth', smooth), ('damp', damp), ('rtol', rtol)):
+            if not (isinstance(val, (int, float, np.floating, np.integer)) and math.isfinite(val) and val >= 0):
+                raise ValueError('%s should be a finite number >= 0, got %r' % (name, val))
+        if not isinstance(maxiter, (int, np.integer)) or maxiter < 1:
+            raise ValueError('maxiter should be a positive integer, got %r' % (maxiter,))
+        if hessian not in self.HESSIANS:
+            raise ValueError("hessian should be 'gauss_newton' or 'newton', got %r" % (hessian,))
+        w = self._weights(smooth_weights, 'smooth_weights')
+        ba, pb, db = self._model_arg(rhs, 'rhs')
+        ra, pr, dr = self._row_arg(row_weight, 'row_weight') if row_weight is not None else (None, None, 0)
+        xa, px0, dx0 = self._model_arg(x0, 'x0') if x0 is not None else (None, None, 0)
+        px, dx, finish = self._model_out(self._first_tensor(rhs, row_weight, x0))
+        self._sync(db, dr, dx0, dx)
+        maxiter = int(maxiter)
+        status, iters = C.c_int(0), C.c_int(0)
+        rho, pq, passes = (C.c_double * (maxiter + 2))(), (C.c_double * maxiter)(), (C.c_int * (2 * maxiter + 2))()
+        _lib.check(self._lib.ttcr_fsm_normal_solve(self._h, pb, db, pr, dr, float(smooth), w, float(damp), px0, dx0, maxiter, float(rtol),
+                                                   self.HESSIANS[hessian], sch, px, dx, C.byref(status), C.byref(iters), rho, pq, passes))
+        self._refresh_nbytes()
+        x = finish()
+        k = iters.value
+        n_pq = k + (1 if status.value == 2 else 0)
+        pairs = [(passes[2 * i], passes[2 * i + 1]) for i in range(n_pq + 1)]
+        self.passes = pairs[-1]    # (of the last product)
+        if not return_info:
+            return x
+        return x, {'status': status.value, 'iterations': k, 'rho': list(rho[:k + 2]), 'pq': list(pq[:n_pq]), 'passes': pairs[1:],
+                   'passes_x0': pairs[0] if x0 is not None else None}
+
+    def release_solve(self):
+        """Free the work arrays of smooth / dot / solve_normal (nbytes falls by what the first such call added); the next call allocates
+        them again.  A held cotangent and the block arrays are not touched."""
+        _lib.check(self._lib.ttcr_fsm_normal_release(self._handle()))
         self._refresh_nbytes()
 
     def _refresh_nbytes(self):
