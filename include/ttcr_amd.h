@@ -587,6 +587,45 @@ int ttcr_fsm_normal_solve(ttcr_fsm_adjoint* t, const void* rhs, int rhs_on_devic
                           int* passes);
 int ttcr_fsm_normal_release(ttcr_fsm_adjoint* t);
 
+/* The joint hypocentre-velocity system of a field tape: the slowness block and the source block of the same
+ * linearisation in one product and one solve.  A joint vector has n_joint = n_params + 4 n_points elements: the model vector, then
+ * (t0, x, y, z) of every source point in call order (ttcr_fsm_adjoint_points); the entries take and return its two blocks as two
+ * arrays.  All arithmetic in the grid dtype T, every operation rounded on its own; tests/joint_reference.py restates all of it.
+ * ttcr_fsm_joint_jvp: dtt (n_rows, tape row order) and / or dfields (n_events x n_nodes) = the tangent of (ds, dsrc) from ONE
+ *   relaxation: a frozen node m holds fl(fl(d_m ds[m]) + sigma[m]), sigma the frozen-node expression of ttcr_fsm_adjoint_jvp_source for
+ *   dsrc of the point that wrote m last, and is never rewritten; every other node obeys ttcr_fsm_adjoint_jvp's expression.  The values
+ *   are those of ttcr_fsm_adjoint_jvp for dsrc == 0 and of ttcr_fsm_adjoint_jvp_source for ds == 0 (the sign of a zero may differ).
+ * ttcr_fsm_joint_gn: (out, out_src) = (g_s, fl(c * g_e')) with (g_s, g_e') the bits of ttcr_fsm_adjoint_vjp_source applied to
+ *   fl(row_weight * dtt), dtt the joint tangent of (v, fl(c * v_src)); c = source_scale, 4 n_points host doubles >= 0 rounded to T, or
+ *   NULL: no scaling and no multiplication.  A scale of 0 fixes that parameter.
+ * ttcr_fsm_joint_solve: conjugate gradients from zero on
+ *       [ Hss + smooth R + damp I    Hse C             ] [x_s]   [ rhs       ]
+ *       [ C Hes                      C Hee C + diag(d) ] [z_e] = [ C rhs_src ],        x_src = fl(c * z_e),
+ *   d = source_damp (4 n_points host doubles >= 0 or NULL), which acts on the scaled unknown z_e; rhs_src is handed over unscaled, as
+ *   ttcr_fsm_adjoint_vjp_source returns it.  A p: the slowness block is ttcr_fsm_normal_solve's expression, the source block
+ *   fl(g_e + fl(T(d) * p_e)); a term whose factor is 0 everywhere is not evaluated.  Inner products, recurrence, scalars, statuses, the
+ *   one host read per iteration and the outputs status, iterations, rho (maxiter + 2), pq (maxiter) are ttcr_fsm_normal_solve's, the
+ *   inner products over the flat joint vector in chunks of 1024 with the block seam wherever it falls; passes (may be NULL): 2 maxiter
+ *   ints.  With source_scale all zeros x_src is zero and x equals ttcr_fsm_normal_solve's element for element.  No x0, no Newton product.
+ *   The first solve allocates work arrays of its own -- five joint vectors, three source blocks, one double per chunk of 1024 joint
+ *   elements, 48 bytes of scalars -- which ttcr_fsm_adjoint_bytes reports; TTCR_ERR_DEVICE with the byte count if that fails;
+ *   ttcr_fsm_joint_release (and ttcr_fsm_adjoint_free) return them.  The arrays of ttcr_fsm_normal_* are not touched.
+ * Argument errors (a NULL array or tape, smooth, damp, rtol, a source_scale or source_damp value negative or not finite, maxiter < 1, an
+ * unknown schedule, smooth > 0 with an axis of fewer than 3 parameters) return TTCR_ERR_VALUE naming the argument before any device call.
+ * Kernels: one seed kernel (a thread per frozen entry), the tangent's tiled and global-Jacobi relaxations compiled with the frozen nodes
+ * left alone, one element-wise scale kernel, kernel 1 of the solver over n_joint elements; everything else is the existing kernels.  No
+ * floating-point atomics.  Measurements: DESIGN.md 6j (scripts/joint_time.py, profiles/joint_solve/). */
+int ttcr_fsm_joint_jvp(const ttcr_fsm_adjoint* t, const void* ds, int ds_on_device, const void* dsrc, int dsrc_on_device, void* dtt,
+                       int dtt_on_device, void* dfields, int df_on_device, int schedule, int* passes);
+int ttcr_fsm_joint_gn(const ttcr_fsm_adjoint* t, const void* v, int v_on_device, const void* v_src, int vs_on_device, const void* row_weight,
+                      int rw_on_device, const double* source_scale, void* out, int out_on_device, void* out_src, int os_on_device,
+                      int schedule, int* passes_jvp, int* passes_vjp);
+int ttcr_fsm_joint_solve(ttcr_fsm_adjoint* t, const void* rhs, int rhs_on_device, const void* rhs_src, int rs_on_device,
+                         const void* row_weight, int rw_on_device, double smooth, const double* smooth_weights, double damp,
+                         const double* source_damp, const double* source_scale, int maxiter, double rtol, int schedule, void* x,
+                         int x_on_device, void* x_src, int xs_on_device, int* status, int* iterations, double* rho, double* pq, int* passes);
+int ttcr_fsm_joint_release(ttcr_fsm_adjoint* t);
+
 /* Replaces: Grid2D::raytrace(Tx, t0, Rx, traveltimes, l_data, threadNo) (ttcr/Grid2D.h:616-640) and the overload with r_data
  * AND l_data (:583-614) -> Grid2Drn::getRaypath(Tx, t0, Rx, [r_data,] l_data, tt, threadNo) (ttcr/Grid2Drn.h:1852-2190): what
  * `compute_L=True` of the Python layer reaches for 2-D grids with cell slowness (src/ttcrpy/rgrid.pyx:3889-3893, :4060-4143).

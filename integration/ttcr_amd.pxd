@@ -119,6 +119,18 @@ cdef extern from "ttcr_amd.h" nogil:
                               double rtol, int newton, int schedule, void* x, int x_on_device, int* status, int* iterations, double* rho,
                               double* pq, int* passes)
     int ttcr_fsm_normal_release(ttcr_fsm_adjoint* t)
+    # joint hypocentre-velocity system of a field tape: one relaxation for both operands, the joint product, CG on the joint system
+    int ttcr_fsm_joint_jvp(const ttcr_fsm_adjoint* t, const void* ds, int ds_on_device, const void* dsrc, int dsrc_on_device, void* dtt,
+                           int dtt_on_device, void* dfields, int df_on_device, int schedule, int* passes)
+    int ttcr_fsm_joint_gn(const ttcr_fsm_adjoint* t, const void* v, int v_on_device, const void* v_src, int vs_on_device,
+                          const void* row_weight, int rw_on_device, const double* source_scale, void* out, int out_on_device,
+                          void* out_src, int os_on_device, int schedule, int* passes_jvp, int* passes_vjp)
+    int ttcr_fsm_joint_solve(ttcr_fsm_adjoint* t, const void* rhs, int rhs_on_device, const void* rhs_src, int rs_on_device,
+                             const void* row_weight, int rw_on_device, double smooth, const double* smooth_weights, double damp,
+                             const double* source_damp, const double* source_scale, int maxiter, double rtol, int schedule, void* x,
+                             int x_on_device, void* x_src, int xs_on_device, int* status, int* iterations, double* rho, double* pq,
+                             int* passes)
+    int ttcr_fsm_joint_release(ttcr_fsm_adjoint* t)
     int ttcr_fsm_slot_m_size(const ttcr_fsm_grid* g, int slot, size_t* n_rows, size_t* nnz)
     int ttcr_fsm_get_slot_m(const ttcr_fsm_grid* g, int slot, long long* row_off, long long* j, void* v)
     int ttcr_fsm_raytrace_l(ttcr_fsm_grid* g, int slot, int n_tx, const void* tx, const void* t0, int n_rx, const void* rx,

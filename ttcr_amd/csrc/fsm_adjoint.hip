@@ -272,7 +272,8 @@ template <> struct TanTile<double> { static constexpr int edge = 8; };
 // Global Jacobi pass of the tangent (the correctness baseline): out = gather(in).  The upwind choice is recomputed from the field:
 //   mu[m] = fl(d_m * ds[m])                                                           m frozen
 //   mu[m] = fl(acc / D_m), acc = fl(fl(dx * fl(s[m] * dx)) * ds[m]), then per active axis x, y, z: acc = fl(acc + fl(mu[u] * fl(T[m] - a)))
-template <typename T>
+// JOINT: a frozen node keeps what joint_seed_kernel wrote (in both buffers), as in src_jacobi_kernel.
+template <typename T, bool JOINT = false>
 __global__ void tan_jacobi_kernel(const T* __restrict__ fields, const T* __restrict__ D, const unsigned char* __restrict__ frozen,
                                   const T* __restrict__ s, const T* __restrict__ ds, const T* __restrict__ mu_in, T* __restrict__ mu_out,
                                   AdjGeom<T> geo, const int* __restrict__ prev, int* __restrict__ cur) {
@@ -280,7 +281,7 @@ __global__ void tan_jacobi_kernel(const T* __restrict__ fields, const T* __restr
     if (prev && prev[e] == 0) return;   // (both buffers of the event hold the fixed point already)
     const size_t m = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     int changed = 0;
-    if (m < geo.nn) {
+    if (m < geo.nn && !(JOINT && frozen[(size_t)e * geo.nn + m])) {
         const size_t idx = (size_t)e * geo.nn + m;
         const T inf = std::numeric_limits<T>::infinity();
         const int pos[3] = {(int)(m % geo.nnx), (int)((m / geo.nnx) % geo.nny), (int)(m / ((size_t)geo.nnx * geo.nny))};
@@ -290,7 +291,7 @@ __global__ void tan_jacobi_kernel(const T* __restrict__ fields, const T* __restr
         const T* L = mu_in + idx;
         const T t = F[0];
         T v;
-        if (frozen[idx]) {
+        if (!JOINT && frozen[idx]) {
             v = D[idx] * ds[m];
         } else {
             T acc = (geo.dx * (s[m] * geo.dx)) * ds[m];
@@ -313,7 +314,9 @@ __global__ void tan_jacobi_kernel(const T* __restrict__ fields, const T* __restr
 // for T outside the grid, so that the upwind choice of 6b falls out of the staged values); every thread keeps, for its interior nodes, the
 // own term, D, the upwind choice (2 bits per axis: active, upper) and the differences T[m] - a in registers, so a Jacobi step reads mu only.
 // Frozen nodes: own term d * ds, no axis, divisor 1 (exact).  Stamps and passes as in adj_tiled_kernel.
-template <typename T, int TI>
+// JOINT: the slowness term and the source seeds in one relaxation -- frozen nodes hold what joint_seed_kernel wrote and are
+// staged like halo nodes, read and never rewritten (src_tiled_kernel's treatment); every other node is the one above.
+template <typename T, int TI, bool JOINT = false>
 __global__ __launch_bounds__(ADJ_THREADS) void tan_tiled_kernel(const T* __restrict__ fields, const T* __restrict__ D,
                                                                  const unsigned char* __restrict__ frozen, const T* __restrict__ s,
                                                                  const T* __restrict__ ds, T* mu, AdjGeom<T> geo, int ntx, int nty, int ntz,
@@ -358,8 +361,9 @@ __global__ __launch_bounds__(ADJ_THREADS) void tan_tiled_kernel(const T* __restr
         if (x >= geo.nnx || y >= geo.nny || z >= geo.nnz) continue;
         const int h = ((lz + 1) * TH + ly + 1) * TH + lx + 1;
         const size_t m = ((size_t)z * geo.nny + y) * geo.nnx + x;
+        if (JOINT && frozen[base + m]) continue;
         hq[q] = h;
-        if (frozen[base + m]) {
+        if (!JOINT && frozen[base + m]) {
             bq[q] = D[base + m] * ds[m];
             continue;
         }
@@ -470,6 +474,33 @@ __global__ void src_seed_kernel(const long long* __restrict__ key, const int* __
         v.v[k] = acc;
     }
     mu[key[i]] = v;
+}
+
+// ---- joint hypocentre-velocity tangent: mu[m] = fl(fl(d_m * ds[m]) + sigma[m]) at the frozen node m, sigma the expression of
+// src_seed_kernel (K = 1) for the point that wrote m last and d_m what D holds there.  One thread per frozen entry; mu2 (may be null) is the
+// second buffer of the Jacobi schedule.  Every other node starts from +0.
+template <typename T>
+__global__ void joint_seed_kernel(const long long* __restrict__ key, const int* __restrict__ node, const int* __restrict__ pt,
+                                  const T* __restrict__ c, size_t n, const T* __restrict__ s, const T* __restrict__ D,
+                                  const T* __restrict__ ds, const T* __restrict__ dsrc, T* __restrict__ mu, T* __restrict__ mu2) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const T sm = s[node[i]];
+    const T* d = dsrc + (size_t)pt[i] * 4;
+    T sigma = d[0];
+    sigma = sigma + (sm * c[3 * i]) * d[1];
+    sigma = sigma + (sm * c[3 * i + 1]) * d[2];
+    sigma = sigma + (sm * c[3 * i + 2]) * d[3];
+    const T v = D[key[i]] * ds[node[i]] + sigma;
+    mu[key[i]] = v;
+    if (mu2) mu2[key[i]] = v;
+}
+
+// out[i] = fl(c[i] * in[i]): the column scaling of the source block (in and out may be the same array)
+template <typename T>
+__global__ void joint_scale_kernel(const T* __restrict__ c, const T* in, T* out, size_t n) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i < n) out[i] = c[i] * in[i];
 }
 
 // Global Jacobi pass of the K-column relaxation (the correctness baseline): for a node that is not frozen
@@ -1150,6 +1181,9 @@ void AdjTapeDev::release() {
     dev_free(mu4); dev_free(mu4b); dev_free(cell_tmp); dev_free(hold_lam); dev_free(hess_dd);
     dev_free(g4); dev_free(blk_model); dev_free(blk_nodes); dev_free(blk_rows); dev_free(blk_rw);
     dev_free(nrm_x); dev_free(nrm_r); dev_free(nrm_p); dev_free(nrm_q); dev_free(nrm_hp); dev_free(nrm_partial); dev_free(nrm_ctl);
+    dev_free(jnt_x); dev_free(jnt_r); dev_free(jnt_p); dev_free(jnt_q); dev_free(jnt_hp); dev_free(jnt_scale); dev_free(jnt_damp);
+    dev_free(jnt_ve); dev_free(jnt_partial); dev_free(jnt_ctl);
+    jnt_bytes = 0;
     blk_owns_mu4 = false;
     blk_bytes = 0;
     nrm_bytes = 0;
@@ -1687,6 +1721,84 @@ int adj_vjp_source(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, T* d_g
     return passes;
 }
 
+// ---- joint hypocentre-velocity products
+template <typename T>
+void adj_src_scale(AdjTapeDev& t, const T* d_c, const T* d_in, T* d_out) {
+    if (t.n_points == 0) return;
+    joint_scale_kernel<T><<<blocks_for(4 * t.n_points), ADJ_THREADS, 0, t.stream>>>(d_c, d_in, d_out, 4 * t.n_points);
+    ADJ_CHECK(hipGetLastError());
+}
+
+template <typename T>
+int adj_jvp_joint(AdjTapeDev& t, const T* d_ds, const T* d_dsrc, T* d_dtt, T* d_dfields, int schedule, const T** mu_out) {
+    ADJ_CHECK(hipSetDevice(t.device));
+    adj_jvp_prepare<T>(t);
+    adj_src_prepare<T>(t);
+    hipStream_t s = t.stream;
+    const size_t E = t.n_events, en = E * t.nn, n_ent = t.h_src_key.size();
+    const AdjGeom<T> geo{t.nnx, t.nny, t.nnz, t.nn, (T)t.dx};
+    if (t.cells) {   // the node perturbation set_slowness would compute from the cell perturbation
+        adj_cells_to_nodes<T>(t, d_ds, (T*)t.grad_tmp);
+        d_ds = (const T*)t.grad_tmp;
+    }
+    T* mu = (T*)t.lam;
+    T* mu2 = schedule != 0 ? (T*)t.lam2 : nullptr;
+    int passes = 0;
+    if (en > 0) {
+        ADJ_CHECK(hipMemsetAsync(mu, 0, en * sizeof(T), s));
+        if (mu2) ADJ_CHECK(hipMemsetAsync(mu2, 0, en * sizeof(T), s));
+        if (n_ent > 0) {
+            joint_seed_kernel<T><<<blocks_for(n_ent), ADJ_THREADS, 0, s>>>(t.src_key, t.src_node, t.src_pt, (const T*)t.src_c, n_ent,
+                                                                          (const T*)t.slowness, (const T*)t.D, d_ds, d_dsrc, mu, mu2);
+            ADJ_CHECK(hipGetLastError());
+        }
+        if (schedule == 0) ADJ_CHECK(hipMemsetAsync(t.tan_stamps, 0xFF, E * t.n_tan_tiles * sizeof(int), s));
+        constexpr int ed = TanTile<T>::edge;
+        const int ntx = (t.nnx + ed - 1) / ed, nty = (t.nny + ed - 1) / ed, ntz = (t.nnz + ed - 1) / ed;
+        const unsigned tiles = (unsigned)t.n_tan_tiles;
+        T* in = mu;
+        T* out = (T*)t.lam2;
+        passes = relax_to_fixed_point(t, "joint tangent", [&](int pass, const int* prev, int* cur) {
+            if (schedule == 0) {
+                tan_tiled_kernel<T, ed, true><<<dim3(tiles, (unsigned)E), ADJ_THREADS, 0, s>>>((const T*)t.fields, (const T*)t.D, t.frozen,
+                                                                                              (const T*)t.slowness, d_ds, mu, geo, ntx, nty,
+                                                                                              ntz, t.tan_stamps, pass, cur);
+            } else {
+                tan_jacobi_kernel<T, true><<<dim3(blocks_for(t.nn), (unsigned)E), ADJ_THREADS, 0, s>>>(
+                    (const T*)t.fields, (const T*)t.D, t.frozen, (const T*)t.slowness, d_ds, in, out, geo, prev, cur);
+                std::swap(in, out);
+            }
+        });
+        if (schedule != 0) mu = in;   // (the buffer the last pass wrote; both hold the fixed point)
+    }
+    if (d_dtt && t.n_rows > 0) {
+        tan_rows_kernel<T><<<blocks_for(t.n_rows), ADJ_THREADS, 0, s>>>(t.rw_off, t.rw_key, (const T*)t.rw_w, t.n_rows, mu, d_dtt);
+        ADJ_CHECK(hipGetLastError());
+    }
+    if (d_dfields && en > 0) ADJ_CHECK(hipMemcpyAsync(d_dfields, mu, en * sizeof(T), hipMemcpyDeviceToDevice, s));
+    if (mu_out) *mu_out = mu;
+    return passes;
+}
+
+template <typename T>
+void adj_gn_joint(AdjTapeDev& t, const T* d_vs, const T* d_ve, const T* d_scale, T* d_ve_scaled, const T* d_rw, T* d_gs, T* d_ge,
+                  int schedule, int* passes_jvp, int* passes_vjp) {
+    ADJ_CHECK(hipSetDevice(t.device));
+    adj_src_prepare<T>(t);
+    if (d_scale) {
+        adj_src_scale<T>(t, d_scale, d_ve, d_ve_scaled);
+        d_ve = d_ve_scaled;
+    }
+    T* w = (T*)t.w_tmp;
+    *passes_jvp = adj_jvp_joint<T>(t, d_vs, d_ve, w, nullptr, schedule, nullptr);
+    if (d_rw && t.n_rows > 0) {
+        tan_scale_rows_kernel<T><<<blocks_for(t.n_rows), ADJ_THREADS, 0, t.stream>>>(d_rw, w, t.n_rows);
+        ADJ_CHECK(hipGetLastError());
+    }
+    *passes_vjp = adj_vjp_source<T>(t, w, nullptr, d_gs, d_ge, schedule);
+    if (d_scale) adj_src_scale<T>(t, d_scale, d_ge, d_ge);
+}
+
 
 // ---- block products
 size_t adj_block_bytes(const AdjTapeDev& t) {
@@ -1860,6 +1972,14 @@ template int adj_jvp_source<float>(AdjTapeDev&, const float*, int, float*, float
 template int adj_jvp_source<double>(AdjTapeDev&, const double*, int, double*, double*, int, const double**, int*);
 template int adj_vjp_source<float>(AdjTapeDev&, const float*, const float*, float*, float*, int);
 template int adj_vjp_source<double>(AdjTapeDev&, const double*, const double*, double*, double*, int);
+
+template void adj_src_scale<float>(AdjTapeDev&, const float*, const float*, float*);
+template void adj_src_scale<double>(AdjTapeDev&, const double*, const double*, double*);
+template int adj_jvp_joint<float>(AdjTapeDev&, const float*, const float*, float*, float*, int, const float**);
+template int adj_jvp_joint<double>(AdjTapeDev&, const double*, const double*, double*, double*, int, const double**);
+template void adj_gn_joint<float>(AdjTapeDev&, const float*, const float*, const float*, float*, const float*, float*, float*, int, int*, int*);
+template void adj_gn_joint<double>(AdjTapeDev&, const double*, const double*, const double*, double*, const double*, double*, double*, int, int*,
+                                   int*);
 
 template void adj_block_prepare<float>(AdjTapeDev&);
 template void adj_block_prepare<double>(AdjTapeDev&);

@@ -130,6 +130,20 @@ struct AdjTapeDev {
     void* nrm_partial = nullptr;      // one double per chunk of 1024 parameters
     void* nrm_ctl = nullptr;          // the scalars of the recurrence
     size_t nrm_bytes = 0;             // what these arrays added to total_bytes
+    // joint hypocentre-velocity solver: allocated by the first joint solve, returned by adj_joint_release.  A joint vector
+    // holds n_joint() values: the model vector, then (t0, x, y, z) of every source point in call order
+    size_t n_joint() const { return n_model() + 4 * n_points; }
+    void* jnt_x = nullptr;            // n_joint() each: the iterate (its source block in the scaled unknown z_e), the residual, ...
+    void* jnt_r = nullptr;
+    void* jnt_p = nullptr;            // ... the search direction, A p ...
+    void* jnt_q = nullptr;
+    void* jnt_hp = nullptr;           // ... and the output of the joint product
+    void* jnt_scale = nullptr;        // 4 n_points each: the column scaling c, the damping delta of the source block, ...
+    void* jnt_damp = nullptr;
+    void* jnt_ve = nullptr;           // ... and fl(c * p_e) of the running product
+    void* jnt_partial = nullptr;      // one double per chunk of 1024 joint elements
+    void* jnt_ctl = nullptr;          // the scalars of the recurrence
+    size_t jnt_bytes = 0;             // what these arrays added to total_bytes
     size_t n_tiles = 0;
     size_t total_bytes = 0;
     hipStream_t stream = nullptr;
@@ -254,5 +268,32 @@ struct NormalResult {
 template <typename T>
 void adj_solve_normal(AdjTapeDev& t, const T* d_rw, const NormalOperator& op, bool with_x0, int maxiter, double rtol, int schedule,
                       NormalResult& res);
+
+// ---- joint hypocentre-velocity products and solve (tests/joint_reference.py restates them).  Source blocks are 4 n_points
+// values, (t0, x, y, z) of every point in call order, on the tape's device.
+// out = fl(c * in) over a source block (in and out may be the same array)
+template <typename T>
+void adj_src_scale(AdjTapeDev& t, const T* d_c, const T* d_in, T* d_out);
+// the joint tangent of (d_ds, d_dsrc) from ONE relaxation: the frozen nodes are seeded with fl(fl(d ds) + sigma), every other node obeys
+// the forward mode's system; outputs as adj_jvp.  *mu_out (may be null) receives the relaxed buffer.  Returns the passes launched.
+template <typename T>
+int adj_jvp_joint(AdjTapeDev& t, const T* d_ds, const T* d_dsrc, T* d_dtt, T* d_dfields, int schedule, const T** mu_out);
+// (d_gs, d_ge) = [J_s J_e C]^T (d_rw * [J_s J_e C] (d_vs, d_ve)), C = diag(d_scale) (null: no scaling, no multiplication); d_ve_scaled (4
+// n_points, unused without a scale) receives fl(c * d_ve).  d_gs has the bits of adj_vjp_source's gradient, d_ge = fl(c * its gsrc).
+template <typename T>
+void adj_gn_joint(AdjTapeDev& t, const T* d_vs, const T* d_ve, const T* d_scale, T* d_ve_scaled, const T* d_rw, T* d_gs, T* d_ge,
+                  int schedule, int* passes_jvp, int* passes_vjp);
+// the work arrays of the joint solver: five joint vectors, three source blocks, one double per chunk of 1024 joint elements and the
+// scalars.  adj_joint_prepare is a no-op while they are there (AdjDeviceError naming the byte count if an allocation fails);
+// adj_joint_release frees them and takes them off bytes().
+size_t adj_joint_bytes(const AdjTapeDev& t);
+void adj_joint_prepare(AdjTapeDev& t);
+void adj_joint_release(AdjTapeDev& t);
+// conjugate gradients from zero on the regularised joint normal equations (the recurrence, scalars, statuses and host reads of
+// adj_solve_normal; inner products over the flat joint vector).  On entry jnt_r holds (b_s, b_e unscaled), jnt_scale / jnt_damp hold c and
+// delta if with_scale / with_damp; on return jnt_x holds (x_s, x_e = fl(c * z_e)).  op.newton is not offered.
+template <typename T>
+void adj_solve_joint(AdjTapeDev& t, const T* d_rw, const NormalOperator& op, bool with_scale, bool with_damp, int maxiter, double rtol,
+                     int schedule, NormalResult& res);
 
 }  // namespace ttcr_amd

@@ -4275,6 +4275,128 @@ int ttcr_fsm_normal_release(ttcr_fsm_adjoint* t) {
     std::lock_guard<std::mutex> lock(t->mu);
     return guarded([&] { ttcr_amd::adj_normal_release(t->t); });
 }
+
+// ---- joint hypocentre-velocity products and solve of the field tape.  A source block is 4 n_points values, (t0, x, y, z)
+// of every point in call order.  Host staging (the table above stage_in continued): joint_jvp stages like jvp and jvp_source do (ds in
+// model_tmp(), dsrc in src_io, dtt in w_tmp).  joint_gn parts src_io, 16 n_points values, into four source blocks: a host v_src, the scale
+// c, fl(c * v_src) and a host out_src; v and out go through model_tmp() and row_weight through rw_tmp as for gn.  joint_solve copies its
+// right-hand sides into the residual of its own work arrays and reads the result from the iterate.  source_scale and source_damp are
+// settings, not data: 4 n_points host doubles each (or NULL), checked here and rounded to the tape's dtype.
+static const char* joint_block_error(const double* v, size_t n, const char* if_bad) {
+    for (size_t i = 0; v && i < n; ++i)
+        if (!(v[i] >= 0.0) || !std::isfinite(v[i])) return if_bad;
+    return nullptr;
+}
+static bool joint_any(const double* v, size_t n) {
+    for (size_t i = 0; v && i < n; ++i)
+        if (v[i] != 0.0) return true;
+    return false;
+}
+extern "C++" {
+// the doubles of a setting rounded to T and uploaded to dst (the stream is waited for: the host vector leaves scope)
+template <typename T>
+static void joint_upload(ttcr_amd::AdjTapeDev& d, const double* v, size_t n, void* dst) {
+    if (n == 0) return;
+    const std::vector<T> h(v, v + n);
+    HIP_CHECK(hipMemcpyAsync(dst, h.data(), n * sizeof(T), hipMemcpyHostToDevice, d.stream));
+    HIP_CHECK(hipStreamSynchronize(d.stream));
+}
+}  // extern "C++"
+
+int ttcr_fsm_joint_jvp(const ttcr_fsm_adjoint* t, const void* ds, int ds_on_device, const void* dsrc, int dsrc_on_device, void* dtt,
+                       int dtt_on_device, void* dfields, int df_on_device, int schedule, int* passes) {
+    if (!ds || !dsrc || (!dtt && !dfields) || !t)
+        return tape_arg_error(!ds ? "null ds" : (!dsrc ? "null dsrc" : (!t ? "null tape" : "dtt and dfields are both null: nothing to compute")));
+    return tape_call(t, schedule, passes, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int& np, int&) {
+        using T = decltype(tag);
+        ttcr_amd::adj_src_prepare<T>(d);
+        const T* dds = stage_in<T>(d, ds, ds_on_device, d.model_tmp(), d.n_model());
+        const T* dd = stage_in<T>(d, dsrc, dsrc_on_device, d.src_io, 4 * d.n_points);
+        const T* mu = nullptr;
+        np = ttcr_amd::adj_jvp_joint<T>(d, dds, dd, stage_dst<T>(dtt, dtt_on_device, d.w_tmp), df_on_device ? (T*)dfields : nullptr, schedule,
+                                        &mu);
+        stage_out<T>(d, dtt, dtt_on_device, d.w_tmp, d.n_rows);
+        stage_out<T>(d, dfields, df_on_device, mu, d.n_events * d.nn);
+    });
+}
+int ttcr_fsm_joint_gn(const ttcr_fsm_adjoint* t, const void* v, int v_on_device, const void* v_src, int vs_on_device, const void* row_weight,
+                      int rw_on_device, const double* source_scale, void* out, int out_on_device, void* out_src, int os_on_device,
+                      int schedule, int* passes_jvp, int* passes_vjp) {
+    const char* bad = !v ? "null v" : (!v_src ? "null v_src" : (!out ? "null out" : (!out_src ? "null out_src" : (!t ? "null tape" : nullptr))));
+    if (!bad) bad = joint_block_error(source_scale, 4 * t->t.n_points, "source_scale: finite values >= 0");
+    if (bad) return tape_arg_error(bad);
+    return tape_call(t, schedule, passes_jvp, passes_vjp, [&](ttcr_amd::AdjTapeDev& d, auto tag, int& pj, int& pv) {
+        using T = decltype(tag);
+        const size_t blk = 4 * d.n_points;
+        ttcr_amd::adj_src_prepare<T>(d);
+        T* io = (T*)d.src_io;
+        const T* dv = stage_in<T>(d, v, v_on_device, d.model_tmp(), d.n_model());
+        const T* dve = stage_in<T>(d, v_src, vs_on_device, io, blk);
+        if (row_weight && !rw_on_device) ttcr_amd::adj_jvp_prepare<T>(d);
+        const T* drw = stage_in<T>(d, row_weight, rw_on_device, d.rw_tmp, d.n_rows);
+        if (source_scale) joint_upload<T>(d, source_scale, blk, io + blk);
+        T* dout = stage_dst<T>(out, out_on_device, d.model_tmp());
+        T* dos = stage_dst<T>(out_src, os_on_device, io + 3 * blk);
+        ttcr_amd::adj_gn_joint<T>(d, dv, dve, source_scale ? io + blk : nullptr, io + 2 * blk, drw, dout, dos, schedule, &pj, &pv);
+        stage_out<T>(d, out, out_on_device, d.model_tmp(), d.n_model());
+        stage_out<T>(d, out_src, os_on_device, io + 3 * blk, blk);
+    });
+}
+int ttcr_fsm_joint_solve(ttcr_fsm_adjoint* t, const void* rhs, int rhs_on_device, const void* rhs_src, int rs_on_device,
+                         const void* row_weight, int rw_on_device, double smooth, const double* smooth_weights, double damp,
+                         const double* source_damp, const double* source_scale, int maxiter, double rtol, int schedule, void* x,
+                         int x_on_device, void* x_src, int xs_on_device, int* status, int* iterations, double* rho, double* pq, int* passes) {
+    const char* bad = nullptr;
+    if (!(smooth >= 0.0) || !std::isfinite(smooth)) bad = "smooth: a finite value >= 0";
+    else if (!(damp >= 0.0) || !std::isfinite(damp)) bad = "damp: a finite value >= 0";
+    else if (maxiter < 1) bad = "maxiter: at least one iteration";
+    else if (!(rtol >= 0.0) || !std::isfinite(rtol)) bad = "rtol: a finite value >= 0";
+    else if (const char* w = normal_weights_error(smooth_weights, "null smooth_weights", "smooth_weights: three finite values >= 0 (x, y, z)"))
+        bad = w;
+    else if (const char* s = schedule_error(schedule)) bad = s;
+    else if (!rhs || !rhs_src) bad = !rhs ? "null rhs" : "null rhs_src";
+    else if (!x || !x_src) bad = !x ? "null x" : "null x_src";
+    else if (!status || !iterations || !rho || !pq) bad = "null status, iterations, rho or pq";
+    else if (!t) bad = "null tape";
+    else if (const char* c = joint_block_error(source_scale, 4 * t->t.n_points, "source_scale: finite values >= 0")) bad = c;
+    else if (const char* c = joint_block_error(source_damp, 4 * t->t.n_points, "source_damp: finite values >= 0")) bad = c;
+    else if (smooth != 0.0) bad = normal_axes_error(t);
+    if (bad) return tape_arg_error(bad);
+    return tape_call(t, schedule, nullptr, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int&, int&) {
+        using T = decltype(tag);
+        const size_t nm = d.n_model(), blk = 4 * d.n_points;
+        ttcr_amd::adj_joint_prepare(d);
+        if (row_weight && !rw_on_device) ttcr_amd::adj_jvp_prepare<T>(d);
+        const T* drw = stage_in<T>(d, row_weight, rw_on_device, d.rw_tmp, d.n_rows);
+        T* r = (T*)d.jnt_r;
+        if (nm > 0) HIP_CHECK(hipMemcpyAsync(r, rhs, nm * sizeof(T), rhs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d.stream));
+        if (blk > 0)
+            HIP_CHECK(hipMemcpyAsync(r + nm, rhs_src, blk * sizeof(T), rs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d.stream));
+        const bool with_damp = joint_any(source_damp, blk);   // (a term whose factor is 0 everywhere is not evaluated)
+        if (source_scale) joint_upload<T>(d, source_scale, blk, d.jnt_scale);
+        if (with_damp) joint_upload<T>(d, source_damp, blk, d.jnt_damp);
+        ttcr_amd::NormalOperator op;
+        op.smooth = smooth;
+        op.damp = damp;
+        std::copy(smooth_weights, smooth_weights + 3, op.weights);
+        ttcr_amd::NormalResult res;
+        ttcr_amd::adj_solve_joint<T>(d, drw, op, source_scale != nullptr, with_damp, maxiter, rtol, schedule, res);
+        const T* xd = (const T*)d.jnt_x;
+        if (nm > 0) HIP_CHECK(hipMemcpyAsync(x, xd, nm * sizeof(T), x_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, d.stream));
+        if (blk > 0)
+            HIP_CHECK(hipMemcpyAsync(x_src, xd + nm, blk * sizeof(T), xs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, d.stream));
+        *status = res.status;
+        *iterations = res.iterations;
+        std::copy(res.rho.begin(), res.rho.end(), rho);
+        std::copy(res.pq.begin(), res.pq.end(), pq);
+        if (passes) std::copy(res.passes.begin(), res.passes.end(), passes);
+    });
+}
+int ttcr_fsm_joint_release(ttcr_fsm_adjoint* t) {
+    if (!t) return tape_arg_error("null tape");
+    std::lock_guard<std::mutex> lock(t->mu);
+    return guarded([&] { ttcr_amd::adj_joint_release(t->t); });
+}
 int ttcr_fsm_adjoint_free(ttcr_fsm_adjoint* t) {
     if (!t) return TTCR_OK;
     return guarded([&] { delete t; });

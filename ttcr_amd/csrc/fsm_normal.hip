@@ -143,6 +143,18 @@ __global__ __launch_bounds__(NRM_THREADS) void nrm_dot_kernel(const T* __restric
 // if with_damp), and the chunk partials of <p, q>.  A workgroup owns a chunk of the flat vector, as the partials demand, so the smoothing
 // gather reads p around each of its parameters from global memory (the expression is nrm_smooth_kernel's: nrm_smooth_at on other strides)
 template <typename T>
+__device__ __forceinline__ T nrm_combine_at(const T* __restrict__ hp, const T* __restrict__ p, size_t i, T pi, const NrmSmooth<T>& sm, T lam,
+                                            T mu, int with_smooth, int with_damp) {
+    T a = hp[i];
+    if (with_smooth) {
+        const int gx = (int)(i % sm.g.mx), gy = (int)((i / sm.g.mx) % sm.g.my), gz = (int)(i / ((size_t)sm.g.mx * sm.g.my));
+        a = a + lam * nrm_smooth_at<T>(p + i, 1, sm.g.mx, sm.g.mx * sm.g.my, gx, gy, gz, sm);
+    }
+    if (with_damp) a = a + mu * pi;
+    return a;
+}
+
+template <typename T>
 __global__ __launch_bounds__(NRM_THREADS) void nrm_combine_kernel(const T* __restrict__ hp, const T* __restrict__ p, T* __restrict__ q,
                                                                   size_t n, NrmSmooth<T> sm, T lam, T mu, int with_smooth, int with_damp,
                                                                   double* __restrict__ partial) {
@@ -152,12 +164,35 @@ __global__ __launch_bounds__(NRM_THREADS) void nrm_combine_kernel(const T* __res
         e[k] = 0.0;
         if (i < n) {
             const T pi = p[i];
-            T a = hp[i];
-            if (with_smooth) {
-                const int gx = (int)(i % sm.g.mx), gy = (int)((i / sm.g.mx) % sm.g.my), gz = (int)(i / ((size_t)sm.g.mx * sm.g.my));
-                a = a + lam * nrm_smooth_at<T>(p + i, 1, sm.g.mx, sm.g.mx * sm.g.my, gx, gy, gz, sm);
+            const T a = nrm_combine_at<T>(hp, p, i, pi, sm, lam, mu, with_smooth, with_damp);
+            q[i] = a;
+            e[k] = nrm_prod(pi, a);
+        }
+    }
+    nrm_chunk_partial(e[0], e[1], e[2], e[3], partial);
+}
+
+// kernel 1 of a joint iteration over the n_joint elements of the flat joint vector: below n_model the expression of
+// nrm_combine_kernel, above it q = fl(hp + fl(delta * p)) (delta null: q = hp); the chunk partials of <p, q> with the block seam wherever it
+// falls in a chunk
+template <typename T>
+__global__ __launch_bounds__(NRM_THREADS) void jnt_combine_kernel(const T* __restrict__ hp, const T* __restrict__ p, T* __restrict__ q,
+                                                                  size_t n_model, size_t n_joint, NrmSmooth<T> sm, T lam, T mu,
+                                                                  int with_smooth, int with_damp, const T* __restrict__ delta,
+                                                                  double* __restrict__ partial) {
+    double e[4];
+    for (int k = 0; k < 4; ++k) {
+        const size_t i = (size_t)blockIdx.x * NRM_CHUNK + threadIdx.x + (size_t)k * NRM_THREADS;
+        e[k] = 0.0;
+        if (i < n_joint) {
+            const T pi = p[i];
+            T a;
+            if (i < n_model) {
+                a = nrm_combine_at<T>(hp, p, i, pi, sm, lam, mu, with_smooth, with_damp);
+            } else {
+                a = hp[i];
+                if (delta) a = a + delta[i - n_model] * pi;
             }
-            if (with_damp) a = a + mu * pi;
             q[i] = a;
             e[k] = nrm_prod(pi, a);
         }
@@ -425,11 +460,147 @@ void adj_solve_normal(AdjTapeDev& t, const T* d_rw, const NormalOperator& op, bo
     }
 }
 
+// ---- the joint hypocentre-velocity system
+namespace {
+size_t jnt_chunks(const AdjTapeDev& t) { return std::max<size_t>(1, (t.n_joint() + NRM_CHUNK - 1) / NRM_CHUNK); }
+
+template <typename T>
+void jnt_close(AdjTapeDev& t, int what) {
+    nrm_finish_kernel<T><<<1, NRM_THREADS, 0, t.stream>>>((const double*)t.jnt_partial, jnt_chunks(t), what, (NrmCtl*)t.jnt_ctl);
+    NRM_CHECK(hipGetLastError());
+}
+
+void jnt_free_all(AdjTapeDev& t) {
+    nrm_free(t.jnt_x); nrm_free(t.jnt_r); nrm_free(t.jnt_p); nrm_free(t.jnt_q); nrm_free(t.jnt_hp); nrm_free(t.jnt_scale);
+    nrm_free(t.jnt_damp); nrm_free(t.jnt_ve); nrm_free(t.jnt_partial); nrm_free(t.jnt_ctl);
+}
+}  // namespace
+
+size_t adj_joint_bytes(const AdjTapeDev& t) {
+    return 5 * std::max<size_t>(t.n_joint() * t.elem, 1) + 3 * std::max<size_t>(4 * t.n_points * t.elem, 1) + jnt_chunks(t) * sizeof(double) +
+           sizeof(NrmCtl);
+}
+
+void adj_joint_prepare(AdjTapeDev& t) {
+    if (t.jnt_x) return;
+    NRM_CHECK(hipSetDevice(t.device));
+    const size_t planned = adj_joint_bytes(t);
+    size_t got = 0;
+    auto alloc = [&](void*& p, size_t bytes) {
+        const size_t b = std::max<size_t>(bytes, 1);
+        if (hipMalloc(&p, b) != hipSuccess) {
+            (void)hipGetLastError();
+            p = nullptr;
+            std::ostringstream m;
+            m << "the joint solver of the field tape needs " << planned << " bytes of device memory on device " << t.device
+              << " (an allocation of " << b << " bytes failed)";
+            throw AdjDeviceError(m.str());
+        }
+        got += b;
+    };
+    try {
+        const size_t vec = t.n_joint() * t.elem, blk = 4 * t.n_points * t.elem;
+        alloc(t.jnt_x, vec);
+        alloc(t.jnt_r, vec);
+        alloc(t.jnt_p, vec);
+        alloc(t.jnt_q, vec);
+        alloc(t.jnt_hp, vec);
+        alloc(t.jnt_scale, blk);
+        alloc(t.jnt_damp, blk);
+        alloc(t.jnt_ve, blk);
+        alloc(t.jnt_partial, jnt_chunks(t) * sizeof(double));
+        alloc(t.jnt_ctl, sizeof(NrmCtl));
+    } catch (...) {
+        jnt_free_all(t);
+        throw;
+    }
+    t.jnt_bytes = got;
+    t.total_bytes += got;
+}
+
+void adj_joint_release(AdjTapeDev& t) {
+    if (!t.jnt_x) return;
+    (void)hipSetDevice(t.device);
+    if (t.stream) (void)hipStreamSynchronize(t.stream);
+    jnt_free_all(t);
+    t.total_bytes -= t.jnt_bytes;
+    t.jnt_bytes = 0;
+}
+
+template <typename T>
+void adj_solve_joint(AdjTapeDev& t, const T* d_rw, const NormalOperator& op, bool with_scale, bool with_damp, int maxiter, double rtol,
+                     int schedule, NormalResult& res) {
+    NRM_CHECK(hipSetDevice(t.device));
+    adj_joint_prepare(t);
+    hipStream_t s = t.stream;
+    const size_t nm = t.n_model(), n = t.n_joint();
+    const unsigned chunks = (unsigned)jnt_chunks(t);
+    T* x = (T*)t.jnt_x;
+    T* r = (T*)t.jnt_r;
+    T* p = (T*)t.jnt_p;
+    T* q = (T*)t.jnt_q;
+    T* hp = (T*)t.jnt_hp;
+    const T* c = with_scale ? (const T*)t.jnt_scale : nullptr;
+    const T* delta = with_damp ? (const T*)t.jnt_damp : nullptr;
+    double* partial = (double*)t.jnt_partial;
+    NrmCtl* ctl = (NrmCtl*)t.jnt_ctl;
+    res = NormalResult();
+    NRM_CHECK(hipMemsetAsync(ctl, 0, sizeof(NrmCtl), s));
+    if (c) adj_src_scale<T>(t, c, r + nm, r + nm);   // the right-hand side of the scaled system: (b_s, fl(c * b_e))
+    nrm_dot_kernel<T><<<chunks, NRM_THREADS, 0, s>>>(r, r, n, partial);
+    NRM_CHECK(hipGetLastError());
+    jnt_close<T>(t, NRM_PLAIN);
+    if (n > 0) NRM_CHECK(hipMemsetAsync(x, 0, n * sizeof(T), s));
+    nrm_start_kernel<T><<<chunks, NRM_THREADS, 0, s>>>(r, q, p, n, 0, partial);
+    NRM_CHECK(hipGetLastError());
+    jnt_close<T>(t, NRM_RR0);
+    NrmCtl h;
+    NRM_CHECK(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, s));
+    NRM_CHECK(hipStreamSynchronize(s));
+    const double rho0 = h.sum;
+    double rho = h.rho;
+    res.rho.push_back(rho0);
+    res.rho.push_back(rho);
+    res.status = 1;
+    for (int k = 1; k <= maxiter; ++k) {
+        if (rho <= rtol * rtol * rho0) {
+            res.status = 0;
+            break;
+        }
+        int pj = 0, pv = 0;
+        adj_gn_joint<T>(t, p, p + nm, c, (T*)t.jnt_ve, d_rw, hp, hp + nm, schedule, &pj, &pv);
+        jnt_combine_kernel<T><<<chunks, NRM_THREADS, 0, s>>>(hp, p, q, nm, n, nrm_smooth_args<T>(t, op.weights), (T)op.smooth, (T)op.damp,
+                                                            op.smooth != 0.0, op.damp != 0.0, delta, partial);
+        NRM_CHECK(hipGetLastError());
+        res.passes.push_back(pj);
+        res.passes.push_back(pv);
+        jnt_close<T>(t, NRM_PQ);
+        nrm_update_kernel<T><<<chunks, NRM_THREADS, 0, s>>>(x, r, p, q, n, ctl, partial);
+        NRM_CHECK(hipGetLastError());
+        jnt_close<T>(t, NRM_RR);
+        nrm_direction_kernel<T><<<(unsigned)std::max<size_t>(1, (n + NRM_THREADS - 1) / NRM_THREADS), NRM_THREADS, 0, s>>>(r, p, n, ctl);
+        NRM_CHECK(hipGetLastError());
+        NRM_CHECK(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, s));   // the one host read of the iteration: (rho, pq)
+        NRM_CHECK(hipStreamSynchronize(s));
+        res.pq.push_back(h.pq);
+        if (!h.ok) {
+            res.status = 2;
+            break;
+        }
+        rho = h.rho;
+        res.rho.push_back(rho);
+        ++res.iterations;
+    }
+    if (c) adj_src_scale<T>(t, c, x + nm, x + nm);   // x_e = fl(c * z_e)
+}
+
 template void adj_smooth<float>(AdjTapeDev&, const float*, const double*, float*);
 template void adj_smooth<double>(AdjTapeDev&, const double*, const double*, double*);
 template double adj_dot<float>(AdjTapeDev&, const float*, const float*);
 template double adj_dot<double>(AdjTapeDev&, const double*, const double*);
 template void adj_solve_normal<float>(AdjTapeDev&, const float*, const NormalOperator&, bool, int, double, int, NormalResult&);
 template void adj_solve_normal<double>(AdjTapeDev&, const double*, const NormalOperator&, bool, int, double, int, NormalResult&);
+template void adj_solve_joint<float>(AdjTapeDev&, const float*, const NormalOperator&, bool, bool, int, double, int, NormalResult&);
+template void adj_solve_joint<double>(AdjTapeDev&, const double*, const NormalOperator&, bool, bool, int, double, int, NormalResult&);
 
 }  // namespace ttcr_amd

@@ -104,6 +104,21 @@ def gauss_newton_step(tape, residual, model, row_weight=None, smooth=0., damp=0.
     return tape.solve_normal(b, row_weight=row_weight, smooth=smooth, damp=damp, **solve_args)
 
 
+def joint_gauss_newton_step(tape, residual, model, row_weight=None, smooth=0., damp=0., source_damp=0., source_scale=None, **solve_args):
+    """The update (x, x_src) of slowness and source points of one regularised joint hypocentre-velocity Gauss-Newton step on a field
+    tape: the right-hand sides
+        b, b_src = tape.vjp(row_weight * residual, return_source_grad=True);   b -= smooth * tape.smooth(model)
+    and then tape.solve_joint(b, b_src, row_weight=row_weight, smooth=smooth, damp=damp, source_damp=source_damp,
+    source_scale=source_scale, **solve_args), whose result is returned as it is (b_src goes in unscaled: the solver scales it).
+    Arguments as gauss_newton_step.  Host glue only."""
+    w = residual if row_weight is None else row_weight * residual
+    b, b_src = tape.vjp(w, return_source_grad=True)
+    if smooth != 0:
+        b = b - smooth * tape.smooth(model, solve_args.get('smooth_weights', (1., 1., 1.)))
+    return tape.solve_joint(b, b_src, row_weight=row_weight, smooth=smooth, damp=damp, source_damp=source_damp, source_scale=source_scale,
+                            **solve_args)
+
+
 def straight_ray_kernel(Tx, Rx, axes, aniso=False):
     """L (nrays x ncells) with L @ slowness = traveltimes along the straight segments Tx[n] -> Rx[n] through the cells of the grid `axes`
     (node coordinates per dimension, any spacing).  Cells in C order ((ix * ncy + iy) * ncz + iz).  aniso (2-D only): L is nrays x 2 ncells,

@@ -559,7 +559,8 @@ class FieldTape:
     frees the held adjoint); solve_normal solves the regularised normal equations of a Gauss-Newton step around those products by
     conjugate gradients on the device (smooth: its smoothing operator, dot: its inner product).  The same linearisation with respect
     to the source points, parameters (t0, x, y, z) each: jvp_source, source_jacobian and vjp(..., return_source_grad=True); n_points
-    points in call order, point_event their events.
+    points in call order, point_event their events.  Both halves together, for joint hypocentre-velocity inversion: jvp_joint (one
+    relaxation for a slowness step and a source step), gauss_newton_joint and solve_joint (the regularised joint normal equations).
     wrt is 'nodes' or 'cells': what the model vector of vjp / jvp / gauss_newton holds, n_cols values -- the node slowness (n_cols =
     n_nodes) or, for the tape of raytrace_adjoint(..., wrt='cells'), the cell slowness in set_slowness's flat order (n_cols = cells).
     Fields, field cotangents and field tangents hold n_nodes values per event on either tape."""
@@ -1062,6 +1063,135 @@ class FieldTape:
         """Free the work arrays of smooth / dot / solve_normal (nbytes falls by what the first such call added); the next call allocates
         them again.  A held cotangent and the block arrays are not touched."""
         _lib.check(self._lib.ttcr_fsm_normal_release(self._handle()))
+        self._refresh_nbytes()
+
+    # ---- joint hypocentre-velocity system (DESIGN.md 6j)
+    def _source_arg(self, a, name):
+        """a source block, (n_points, 4) values (t0, x, y, z) per point in call order: (array, pointer, on_device)"""
+        a = self._seen(a)
+        if tuple(a.shape) != (self.n_points, 4):
+            raise ValueError('%s should be (%d, 4), one row (t0, x, y, z) per source point, got shape %s'
+                             % (name, self.n_points, tuple(a.shape)))
+        return self._arg(a)
+
+    def _source_setting(self, v, name, allow_none):
+        """source_scale / source_damp, (4,) or (n_points, 4) values (source_damp: or a scalar), broadcast to (n_points, 4) doubles for
+        the C entry; None stays None"""
+        if v is None and allow_none:
+            return None
+        try:
+            a = np.asarray(v.detach().cpu().numpy() if hasattr(v, 'detach') else v, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError('%s should be numbers, got %r' % (name, v))
+        if a.shape not in ((4,), (self.n_points, 4)) + (() if allow_none else ((),)):
+            raise ValueError('%s should be %s(4,) or (%d, 4) values, got shape %s'
+                             % (name, '' if allow_none else 'a scalar, ', self.n_points, a.shape))
+        if not np.all(np.isfinite(a)) or np.any(a < 0):
+            raise ValueError('%s should be finite and >= 0, got %r' % (name, v))
+        a = np.ascontiguousarray(np.broadcast_to(a, (self.n_points, 4)))
+        return (C.c_double * max(a.size, 1))(*a.ravel())
+
+    def jvp_joint(self, ds, dsrc, return_fields=False, schedule='tiled'):
+        """J_s ds + J_src dsrc from ONE relaxation: the change of the receiver traveltimes for the slowness perturbation ds (as in jvp)
+        and the source perturbation dsrc, (n_points, 4) values (dt0, dx, dy, dz) per point (as in jvp_source) -- the tangent system is
+        linear, so both operands ride the same pass.  Returns dtt in rcv order; with return_fields=True (dtt, dfields), dfields
+        (n_events, n_nodes).  The values are jvp(ds)'s for dsrc == 0 and jvp_source(dsrc)'s for ds == 0 (the sign of a zero may
+        differ).  Array handling and schedule as in jvp; the result lives where the first torch tensor of (ds, dsrc) does."""
+        self._handle()
+        sch = self._schedule(schedule)
+        a, pa, da = self._model_arg(ds, 'ds')
+        b, pb, db = self._source_arg(dsrc, 'dsrc')
+        like = self._first_tensor(ds, dsrc)
+        pr, dr, fin_r = self._out(like, 1, self.n_rows, rows=True)
+        pf, df, fin_f = self._out(like, self.n_events, self.n_nodes) if return_fields else (None, 0, None)
+        self._sync(da, db, dr, df)
+        np_ = C.c_int(0)
+        want_r, want_f = self.n_rows > 0, return_fields and self.n_events * self.n_nodes > 0
+        if want_r or want_f:
+            _lib.check(self._lib.ttcr_fsm_joint_jvp(self._h, pa, da, pb, db, pr if want_r else None, dr, pf if want_f else None, df, sch,
+                                                    C.byref(np_)))
+        self.passes = np_.value
+        self._refresh_nbytes()
+        dtt = fin_r()[0]
+        return (dtt, fin_f()) if return_fields else dtt
+
+    def gauss_newton_joint(self, v, v_src, row_weight=None, source_scale=None, schedule='tiled'):
+        """The joint Gauss-Newton product (g, g_src) = [J_s  J_src C]^T (row_weight * ([J_s  J_src C] (v, v_src))), C = diag(source_scale):
+        one tangent relaxation for both blocks (jvp_joint), one adjoint relaxation for both gradients (vjp(...,
+        return_source_grad=True)), all on the tape's stream.  v: n_cols values; v_src: (n_points, 4); source_scale: (4,) or (n_points,
+        4) values >= 0 that scale the columns of the source block (0 fixes a parameter) or None: no scaling, no multiplication.  g has the
+        bits of the vjp's gradient, g_src = source_scale * its source gradient.  Array handling and schedule as in gauss_newton; passes
+        becomes (passes of the jvp, passes of the vjp)."""
+        self._handle()
+        sch = self._schedule(schedule)
+        va, pv, dv = self._model_arg(v, 'v')
+        ea, pe, de = self._source_arg(v_src, 'v_src')
+        ra, pr, dr = self._row_arg(row_weight, 'row_weight') if row_weight is not None else (None, None, 0)
+        sc = self._source_setting(source_scale, 'source_scale', True)
+        like = self._first_tensor(v, v_src, row_weight)
+        pg, dg, fin_g = self._model_out(like)
+        ps, dsrc, fin_s = self._out(like, self.n_points, 4)
+        self._sync(dv, de, dr, dg, dsrc)
+        pj, pa = C.c_int(0), C.c_int(0)
+        _lib.check(self._lib.ttcr_fsm_joint_gn(self._h, pv, dv, pe, de, pr, dr, sc, pg, dg, ps, dsrc, sch, C.byref(pj), C.byref(pa)))
+        self.passes = (pj.value, pa.value)
+        self._refresh_nbytes()
+        return fin_g(), fin_s()
+
+    def solve_joint(self, rhs, rhs_src, row_weight=None, smooth=0.0, smooth_weights=(1., 1., 1.), damp=0.0, source_damp=0.0,
+                    source_scale=None, maxiter=20, rtol=1e-6, schedule='tiled', return_info=False, hessian='gauss_newton'):
+        """The update (x, x_src) of slowness and source points of one regularised joint Gauss-Newton step, by conjugate gradients from
+        zero on the device:
+            [ Hss + smooth R + damp I    Hse C                       ] [x  ]   [ rhs       ]
+            [ C Hes                      C Hee C + diag(source_damp) ] [z_e] = [ C rhs_src ],        x_src = source_scale * z_e,
+        H the blocks of gauss_newton_joint's product, C = diag(source_scale), R and damp as in solve_normal.  Slowness, origin time and
+        coordinates differ by orders of magnitude: source_scale, (4,) or (n_points, 4) values >= 0, is the column scaling that makes
+        the joint system solvable in a few iterations (0 fixes a parameter; None: none).  rhs_src is handed over UNSCALED, as
+        vjp(..., return_source_grad=True) returns it -- the solver forms C rhs_src --, and source_damp (a scalar, (4,) or (n_points, 4),
+        >= 0) acts on the SCALED unknown z_e.  Inner products over the flat joint vector (rhs, then the source block), everything
+        else -- recurrence, scalars, statuses, the info dict, the bits being the same under both schedules -- as in solve_normal
+        (tests/joint_reference.py restates it).  No x0; hessian other than 'gauss_newton' raises.  Returns (x, x_src), with
+        return_info=True (x, x_src, info).  The first call allocates work arrays of its own (nbytes; release_joint returns them)."""
+        self._handle()
+        sch = self._schedule(schedule)
+        for name, val in (('smooth', smooth), ('damp', damp), ('rtol', rtol)):
+            if not (isinstance(val, (int, float, np.floating, np.integer)) and math.isfinite(val) and val >= 0):
+                raise ValueError('%s should be a finite number >= 0, got %r' % (name, val))
+        if not isinstance(maxiter, (int, np.integer)) or maxiter < 1:
+            raise ValueError('maxiter should be a positive integer, got %r' % (maxiter,))
+        if hessian != 'gauss_newton':
+            raise ValueError("hessian: the joint system offers 'gauss_newton' only, got %r" % (hessian,))
+        w = self._weights(smooth_weights, 'smooth_weights')
+        ba, pb, db = self._model_arg(rhs, 'rhs')
+        ea, pe, de = self._source_arg(rhs_src, 'rhs_src')
+        ra, pr, dr = self._row_arg(row_weight, 'row_weight') if row_weight is not None else (None, None, 0)
+        sd = self._source_setting(source_damp, 'source_damp', False)
+        sc = self._source_setting(source_scale, 'source_scale', True)
+        like = self._first_tensor(rhs, rhs_src, row_weight)
+        px, dx, fin_x = self._model_out(like)
+        ps, dxs, fin_s = self._out(like, self.n_points, 4)
+        self._sync(db, de, dr, dx, dxs)
+        maxiter = int(maxiter)
+        status, iters = C.c_int(0), C.c_int(0)
+        rho, pq, passes = (C.c_double * (maxiter + 2))(), (C.c_double * maxiter)(), (C.c_int * (2 * maxiter))()
+        _lib.check(self._lib.ttcr_fsm_joint_solve(self._h, pb, db, pe, de, pr, dr, float(smooth), w, float(damp), sd, sc, maxiter,
+                                                  float(rtol), sch, px, dx, ps, dxs, C.byref(status), C.byref(iters), rho, pq, passes))
+        self._refresh_nbytes()
+        x, xs = fin_x(), fin_s()
+        k = iters.value
+        n_pq = k + (1 if status.value == 2 else 0)
+        pairs = [(passes[2 * i], passes[2 * i + 1]) for i in range(n_pq)]
+        if pairs:
+            self.passes = pairs[-1]    # (of the last product)
+        if not return_info:
+            return x, xs
+        return x, xs, {'status': status.value, 'iterations': k, 'rho': list(rho[:k + 2]), 'pq': list(pq[:n_pq]), 'passes': pairs,
+                       'passes_x0': None}
+
+    def release_joint(self):
+        """Free the work arrays of solve_joint (nbytes falls by what the first call added); the next call allocates them again.  The
+        arrays of solve_normal, a held cotangent and the block arrays are not touched."""
+        _lib.check(self._lib.ttcr_fsm_joint_release(self._handle()))
         self._refresh_nbytes()
 
     def _refresh_nbytes(self):
