@@ -626,6 +626,58 @@ int ttcr_fsm_joint_solve(ttcr_fsm_adjoint* t, const void* rhs, int rhs_on_device
                          int x_on_device, void* x_src, int xs_on_device, int* status, int* iterations, double* rho, double* pq, int* passes);
 int ttcr_fsm_joint_release(ttcr_fsm_adjoint* t);
 
+/* Derivatives of the returned traveltimes with respect to the RECEIVER points of a field tape, and the joint system with the receiver
+ * block in the place of the source block -- what a reciprocal layout needs: solve from the stations, read the traveltimes
+ * at the hypocentres, which are then the receivers of the call.  For a tape row r the receiver p is taken as the solver sees it (after the
+ * origin shift of a translated grid); G[r][a] = d tt[r] / d p_a (a = x, y, z) is the derivative of the trilinear interpolation exactly as
+ * the solver evaluates it, with the cell and the on-plane flags held fixed: +0 on an axis the point lies on (within 1e-8), otherwise
+ * fl(I_a / dx), I_a the solver's nested interpolation over the remaining axes (z, then y, then x) of the differences
+ * fl(T[upper node] - T[lower node]) along a; a clamped upper node gives +0.  All arithmetic in the grid dtype, every operation rounded
+ * on its own; tests/receiver_reference.py restates all of it.
+ * Receiver points: the tape has n_rcv_points points with parameters (t0, x, y, z) each and a map from rows to points; one point per row
+ * by default.  ttcr_fsm_rcv_points: with set_point_of_row != NULL replaces the map (n_rows ints in tape row order, values in
+ * 0 .. set_n_points - 1; rows that share a point must have bit-equal receiver coordinates, else TTCR_ERR_VALUE naming the first offending
+ * pair of tape rows, which differing_rows (2 ints, may be NULL) receives; at most 2^29 points; a point may have no rows) and frees what
+ * the receiver calls hold on the device; then, either way, returns the
+ * number of points in *n_points and the map in point_of_row (each may be NULL).
+ * ttcr_fsm_rcv_eval: for n_pts queries, pts (3 n_pts values of the grid dtype, user coordinates) read in the field of event
+ *   event_of_pt[i] (host ints): tt (n_pts, may be NULL) with the bits of ttcr_fsm_interp on that field, grad (3 n_pts, may be NULL) = G.
+ *   No solve, no relaxation.  Node indices are clamped, so a point outside the grid reads the nearest cell.  Events, host points and
+ *   host results are staged in one buffer of the tape (7 n_pts values and n_pts ints) that grows to the largest call, is reported by
+ *   ttcr_fsm_adjoint_bytes and returned by ttcr_fsm_rcv_release: a loop of calls allocates once.  pts == NULL: the tape's own
+ *   rows (n_pts and event_of_pt ignored; n_rows values, tape row order), evaluated once and kept on the tape.
+ * ttcr_fsm_rcv_jvp: dtt[r] = acc, acc = drcv[q][0], then for a = x, y, z acc = fl(acc + fl(G[r][a] * drcv[q][1 + a])), q the point
+ *   of row r.  ttcr_fsm_rcv_vjp: grcv[q][0] = the sum of w[r], grcv[q][1 + a] the sum of fl(w[r] * G[r][a]) over the rows of q in
+ *   ascending tape row order from +0 (one thread per value; a point without rows gets +0).
+ * ttcr_fsm_rjoint_jvp: dtt[r] = fl(jvp(ds)[r] + jvp_rcv(drcv)[r]); dfields is ttcr_fsm_adjoint_jvp's.
+ * ttcr_fsm_rjoint_gn and ttcr_fsm_rjoint_solve: ttcr_fsm_joint_gn and ttcr_fsm_joint_solve with the receiver block (4 n_rcv_points values)
+ *   in the place of the source block: out has the bits of ttcr_fsm_adjoint_vjp, out_rcv = fl(c * grcv); the system, its scaling (rcv_scale),
+ *   the damping of the scaled unknown (rcv_damp), inner products, recurrence, statuses and outputs are those of ttcr_fsm_joint_solve with
+ *   n_joint = n_params + 4 n_rcv_points.  With rcv_scale all zeros x_rcv is zero and x equals ttcr_fsm_normal_solve's element for element.
+ * The first receiver call uploads the receivers and the map, evaluates G of the rows and allocates its staging arrays (3 n_rows + 3
+ * n_rows + n_rows + 16 n_rcv_points values, 3 n_rows + n_rcv_points + 1 ints); the first rjoint_solve allocates work arrays of its own,
+ * as ttcr_fsm_joint_solve does for n_joint; ttcr_fsm_adjoint_bytes reports both, TTCR_ERR_DEVICE with the byte count if an allocation
+ * fails, ttcr_fsm_rcv_release (and ttcr_fsm_adjoint_free) return both.  No other entry's memory changes.
+ * Argument errors return TTCR_ERR_VALUE naming the argument before any device call.  Kernels: one evaluation kernel (a thread per
+ * query), one row kernel (a thread per row), one gradient kernel (a thread per point and parameter); everything else is the existing
+ * kernels.  No floating-point atomics.  Not covered: 2-D, WENO, tt_from_rp = 1, second derivatives. */
+int ttcr_fsm_rcv_eval(const ttcr_fsm_adjoint* t, size_t n_pts, const void* pts, int pts_on_device, const int* event_of_pt, void* tt,
+                              int tt_on_device, void* grad, int grad_on_device);
+int ttcr_fsm_rcv_points(ttcr_fsm_adjoint* t, const int* set_point_of_row, size_t set_n_points, size_t* n_points, int* point_of_row,
+                        int* differing_rows);
+int ttcr_fsm_rcv_jvp(const ttcr_fsm_adjoint* t, const void* drcv, int drcv_on_device, void* dtt, int dtt_on_device);
+int ttcr_fsm_rcv_vjp(const ttcr_fsm_adjoint* t, const void* w, int w_on_device, void* grcv, int grcv_on_device);
+int ttcr_fsm_rjoint_jvp(const ttcr_fsm_adjoint* t, const void* ds, int ds_on_device, const void* drcv, int drcv_on_device, void* dtt,
+                        int dtt_on_device, void* dfields, int df_on_device, int schedule, int* passes);
+int ttcr_fsm_rjoint_gn(const ttcr_fsm_adjoint* t, const void* v, int v_on_device, const void* v_rcv, int vr_on_device, const void* row_weight,
+                       int rw_on_device, const double* rcv_scale, void* out, int out_on_device, void* out_rcv, int or_on_device,
+                       int schedule, int* passes_jvp, int* passes_vjp);
+int ttcr_fsm_rjoint_solve(ttcr_fsm_adjoint* t, const void* rhs, int rhs_on_device, const void* rhs_rcv, int rr_on_device,
+                          const void* row_weight, int rw_on_device, double smooth, const double* smooth_weights, double damp,
+                          const double* rcv_damp, const double* rcv_scale, int maxiter, double rtol, int schedule, void* x,
+                          int x_on_device, void* x_rcv, int xr_on_device, int* status, int* iterations, double* rho, double* pq, int* passes);
+int ttcr_fsm_rcv_release(ttcr_fsm_adjoint* t);
+
 /* Replaces: Grid2D::raytrace(Tx, t0, Rx, traveltimes, l_data, threadNo) (ttcr/Grid2D.h:616-640) and the overload with r_data
  * AND l_data (:583-614) -> Grid2Drn::getRaypath(Tx, t0, Rx, [r_data,] l_data, tt, threadNo) (ttcr/Grid2Drn.h:1852-2190): what
  * `compute_L=True` of the Python layer reaches for 2-D grids with cell slowness (src/ttcrpy/rgrid.pyx:3889-3893, :4060-4143).

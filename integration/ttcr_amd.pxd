@@ -131,6 +131,24 @@ cdef extern from "ttcr_amd.h" nogil:
                              int x_on_device, void* x_src, int xs_on_device, int* status, int* iterations, double* rho, double* pq,
                              int* passes)
     int ttcr_fsm_joint_release(ttcr_fsm_adjoint* t)
+    # receiver-point derivatives of a field tape and the joint system with the receiver block (the reciprocal layout)
+    int ttcr_fsm_rcv_eval(const ttcr_fsm_adjoint* t, size_t n_pts, const void* pts, int pts_on_device, const int* event_of_pt,
+                                  void* tt, int tt_on_device, void* grad, int grad_on_device)
+    int ttcr_fsm_rcv_points(ttcr_fsm_adjoint* t, const int* set_point_of_row, size_t set_n_points, size_t* n_points,
+                            int* point_of_row, int* differing_rows)
+    int ttcr_fsm_rcv_jvp(const ttcr_fsm_adjoint* t, const void* drcv, int drcv_on_device, void* dtt, int dtt_on_device)
+    int ttcr_fsm_rcv_vjp(const ttcr_fsm_adjoint* t, const void* w, int w_on_device, void* grcv, int grcv_on_device)
+    int ttcr_fsm_rjoint_jvp(const ttcr_fsm_adjoint* t, const void* ds, int ds_on_device, const void* drcv, int drcv_on_device, void* dtt,
+                            int dtt_on_device, void* dfields, int df_on_device, int schedule, int* passes)
+    int ttcr_fsm_rjoint_gn(const ttcr_fsm_adjoint* t, const void* v, int v_on_device, const void* v_rcv, int vr_on_device,
+                           const void* row_weight, int rw_on_device, const double* rcv_scale, void* out, int out_on_device,
+                           void* out_rcv, int or_on_device, int schedule, int* passes_jvp, int* passes_vjp)
+    int ttcr_fsm_rjoint_solve(ttcr_fsm_adjoint* t, const void* rhs, int rhs_on_device, const void* rhs_rcv, int rr_on_device,
+                              const void* row_weight, int rw_on_device, double smooth, const double* smooth_weights, double damp,
+                              const double* rcv_damp, const double* rcv_scale, int maxiter, double rtol, int schedule, void* x,
+                              int x_on_device, void* x_rcv, int xr_on_device, int* status, int* iterations, double* rho, double* pq,
+                              int* passes)
+    int ttcr_fsm_rcv_release(ttcr_fsm_adjoint* t)
     int ttcr_fsm_slot_m_size(const ttcr_fsm_grid* g, int slot, size_t* n_rows, size_t* nnz)
     int ttcr_fsm_get_slot_m(const ttcr_fsm_grid* g, int slot, long long* row_off, long long* j, void* v)
     int ttcr_fsm_raytrace_l(ttcr_fsm_grid* g, int slot, int n_tx, const void* tx, const void* t0, int n_rx, const void* rx,

@@ -112,6 +112,15 @@ SYMBOLS = {
     "ttcr_fsm_joint_solve": (_I, [_P, _P, _I, _P, _I, _P, _I, _D, C.POINTER(_D), _D, C.POINTER(_D), C.POINTER(_D), _I, _D, _I, _P, _I, _P, _I,
                                   C.POINTER(_I), C.POINTER(_I), C.POINTER(_D), C.POINTER(_D), C.POINTER(_I)]),
     "ttcr_fsm_joint_release": (_I, [_P]),
+    "ttcr_fsm_rcv_eval": (_I, [_P, C.c_size_t, _P, _I, C.POINTER(_I), _P, _I, _P, _I]),
+    "ttcr_fsm_rcv_points": (_I, [_P, C.POINTER(_I), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(_I), C.POINTER(_I)]),
+    "ttcr_fsm_rcv_jvp": (_I, [_P, _P, _I, _P, _I]),
+    "ttcr_fsm_rcv_vjp": (_I, [_P, _P, _I, _P, _I]),
+    "ttcr_fsm_rjoint_jvp": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _I, _I, C.POINTER(_I)]),
+    "ttcr_fsm_rjoint_gn": (_I, [_P, _P, _I, _P, _I, _P, _I, C.POINTER(_D), _P, _I, _P, _I, _I, C.POINTER(_I), C.POINTER(_I)]),
+    "ttcr_fsm_rjoint_solve": (_I, [_P, _P, _I, _P, _I, _P, _I, _D, C.POINTER(_D), _D, C.POINTER(_D), C.POINTER(_D), _I, _D, _I, _P, _I, _P, _I,
+                                   C.POINTER(_I), C.POINTER(_I), C.POINTER(_D), C.POINTER(_D), C.POINTER(_I)]),
+    "ttcr_fsm_rcv_release": (_I, [_P]),
     "ttcr_fsm_raytrace_multi_l": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I]),
     "ttcr_fsm_multi_l_size": (_I, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "ttcr_fsm_get_multi_l": (_I, [_P, _P, _P, _P]),

@@ -33,6 +33,10 @@ mode adds FieldTape.jvp and FieldTape.jvp_source.  The derivative with respect t
 face or comes within 1e-4 of a node: the formula of the side the point is on is returned.  Second derivatives through raytrace_events
 (with respect to the source points, and mixed ones) are not implemented: a double backward raises instead of returning a part.
 
+raytrace_adjoint and raytrace_events are differentiable in `rcv` too when it is a torch tensor that requires grad (or carries a forward
+tangent): the backward is g[r] * G[r], G = FieldTape.receiver_jacobian() -- the derivative of the receiver interpolation as the solver
+evaluates it --, forward mode adds FieldTape.jvp_receiver's rows.  A second derivative through rcv raises.
+
 Both take wrt='nodes' (default) or wrt='cells'.  With wrt='cells' `grid` is a 3-D cell grid (Grid3d(..., cell_slowness=1, weno=0)),
 `velocity` holds one value per cell, shape (ncx, ncy, ncz) or flat in C order, and the derivative is the one with respect to the cell
 velocities (FieldTape of raytrace_adjoint(..., wrt='cells'): the node tape composed with the cell-to-node averaging of set_slowness);
@@ -202,9 +206,10 @@ def _adjoint_function():
 
     class RaytraceAdjointFn(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, velocity, grid, source, rcv, aggregate_src, return_fields, wrt):
+        def forward(ctx, velocity, grid, source, rcv, aggregate_src, return_fields, wrt, holder):
             grid.set_velocity(velocity.detach().cpu().numpy())
             tt, tape = grid.raytrace_adjoint(source, rcv, aggregate_src=aggregate_src, wrt=wrt)
+            holder.append(tape)   # (for the receiver term: _with_receiver_term)
             nx, ny, nz = grid.x.size, grid.y.size, grid.z.size
             ctx.tape = tape
             ctx.layout = (tuple(velocity.shape), (nx, ny, nz), _model_dims(grid, wrt))
@@ -220,7 +225,7 @@ def _adjoint_function():
         @staticmethod
         def backward(ctx, g, gf=None):
             (velocity,) = ctx.saved_tensors
-            return _AdjBackwardFn.apply(g, gf, velocity, ctx.tape, ctx.layout), None, None, None, None, None, None
+            return _AdjBackwardFn.apply(g, gf, velocity, ctx.tape, ctx.layout), None, None, None, None, None, None, None
 
         @staticmethod
         def jvp(ctx, tv, *_):
@@ -235,6 +240,66 @@ def _adjoint_function():
 
     _AdjFn = RaytraceAdjointFn
     return _AdjFn
+
+
+_RcvFn = None
+
+
+def _receiver_function():
+    global _RcvFn
+    if _RcvFn is not None:
+        return _RcvFn
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class ReceiverTermFn(torch.autograd.Function):
+        """zeros(n_data) whose derivative with respect to rcv is that of the traveltimes of the tape's rows: added to tt, it makes the
+        operator differentiable in the receiver positions without touching the operator itself"""
+
+        @staticmethod
+        def forward(ctx, rcv, tape):
+            ctx.tape, ctx.like = tape, (rcv.dtype, rcv.device)
+            G = torch.from_numpy(tape.receiver_jacobian()).to(rcv.device)
+            ctx.save_for_backward(G)
+            return torch.zeros(tape.n_data, dtype=G.dtype, device=rcv.device)
+
+        @staticmethod
+        @once_differentiable   # (second-order terms in the receiver coordinates are not implemented: raise, not a part)
+        def backward(ctx, g):
+            (G,) = ctx.saved_tensors
+            return (g.to(G.dtype)[:, None] * G).to(dtype=ctx.like[0], device=ctx.like[1]), None
+
+        @staticmethod
+        def jvp(ctx, t_rcv, _):
+            tape = ctx.tape
+            d = t_rcv.detach().cpu().numpy()
+            drcv = np.zeros((tape.n_rcv_points, 4), dtype=tape.dtype)   # (a fresh tape: one receiver point per tape row)
+            drcv[:, 1:] = d[tape._rows, :3]
+            return torch.from_numpy(tape.jvp_receiver(drcv)).to(t_rcv.device)
+
+    _RcvFn = ReceiverTermFn
+    return _RcvFn
+
+
+def _split_rcv(rcv):
+    """(rcv as a numpy array, rcv itself if it is a torch tensor the result has to be differentiated by, else None)"""
+    if not type(rcv).__module__.startswith('torch'):
+        return np.asarray(rcv), None
+    import torch.autograd.forward_ad as fwad
+
+    wanted = rcv.requires_grad or fwad.unpack_dual(rcv).tangent is not None
+    return rcv.detach().cpu().numpy(), (rcv if wanted else None)
+
+
+def _with_receiver_term(out, rcv_t, holder, return_fields):
+    """tt + the receiver term where rcv is to be differentiated by (fl(a + b) in forward mode; the values of tt are not changed)"""
+    if rcv_t is None:
+        return out
+    if rcv_t.dim() != 2 or rcv_t.shape[1] != 3:
+        raise ValueError('rcv should be (n, 3) to be differentiated by, got shape %s' % (tuple(rcv_t.shape),))
+    tt = out[0] if return_fields else out
+    term = _receiver_function().apply(rcv_t, holder[0]).to(tt.device)
+    return (tt + term, out[1]) if return_fields else tt + term
 
 
 def _check_wrt(grid, wrt):
@@ -263,8 +328,10 @@ def raytrace_adjoint(grid, velocity, source, rcv, aggregate_src=False, return_fi
     (n_events, nx, ny, nz) traveltime fields, differentiable as well."""
     _check_wrt(grid, wrt)
     source = np.asarray(source)
-    rcv = np.asarray(rcv)
-    return _adjoint_function().apply(velocity, grid, source, rcv, bool(aggregate_src), bool(return_fields), wrt)
+    rcv, rcv_t = _split_rcv(rcv)
+    holder = []
+    out = _adjoint_function().apply(velocity, grid, source, rcv, bool(aggregate_src), bool(return_fields), wrt, holder)
+    return _with_receiver_term(out, rcv_t, holder, return_fields)
 
 
 def _events_function():
@@ -276,12 +343,13 @@ def _events_function():
 
     class RaytraceEventsFn(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, velocity, events, grid, event_of_row, rcv, return_fields, wrt):
+        def forward(ctx, velocity, events, grid, event_of_row, rcv, return_fields, wrt, holder):
             grid.set_velocity(velocity.detach().cpu().numpy())
             ev = events.detach().cpu().numpy().astype(np.float64)
             # the 5-column source form of _split_sources: (event number, t0, x, y, z) per rcv row; events are taken in ascending number
             source = np.column_stack([event_of_row.astype(np.float64), ev[event_of_row]])
             tt, tape = grid.raytrace_adjoint(source, rcv, wrt=wrt)
+            holder.append(tape)   # (for the receiver term: _with_receiver_term)
             nx, ny, nz = grid.x.size, grid.y.size, grid.z.size
             ctx.tape = tape
             ctx.layout = (tuple(velocity.shape), (nx, ny, nz), _model_dims(grid, wrt))
@@ -304,7 +372,7 @@ def _events_function():
                 fc = gf.permute(0, 3, 2, 1).contiguous().reshape(gf.shape[0], -1)
             gn, gs = ctx.tape.vjp(g.contiguous(), fc, return_source_grad=True)
             gs_v = gn.reshape(mz, my, mx).permute(2, 1, 0).contiguous().reshape(shape).to(velocity.dtype)
-            return -gs_v / (velocity * velocity), gs.to(device=events.device, dtype=events.dtype), None, None, None, None, None
+            return -gs_v / (velocity * velocity), gs.to(device=events.device, dtype=events.dtype), None, None, None, None, None, None
 
         @staticmethod
         def jvp(ctx, tv, te, *_):
@@ -331,7 +399,7 @@ def raytrace_events(grid, velocity, events, event_of_row, rcv, return_fields=Fal
     and position, exact, FieldTape.vjp(..., return_source_grad=True)).  return_fields=True: (tt, fields) with the (n_events, nx, ny, nz)
     traveltime fields, differentiable as well.  wrt='cells': a cell grid, velocity in the cell layout."""
     _check_wrt(grid, wrt)
-    rcv = np.asarray(rcv)
+    rcv, rcv_t = _split_rcv(rcv)
     event_of_row = np.asarray(event_of_row)
     if events.dim() != 2 or events.shape[1] != 4:
         raise ValueError('events should be (n_events, 4): t0, x, y, z; got shape %s' % (tuple(events.shape),))
@@ -339,4 +407,6 @@ def raytrace_events(grid, velocity, events, event_of_row, rcv, return_fields=Fal
         raise ValueError('event_of_row should hold one integer per rcv row')
     if not np.array_equal(np.unique(event_of_row), np.arange(events.shape[0])):
         raise ValueError('event_of_row should name events 0 .. %d, every one of them at least once' % (events.shape[0] - 1))
-    return _events_function().apply(velocity, events, grid, event_of_row.astype(np.int64), rcv, bool(return_fields), wrt)
+    holder = []
+    out = _events_function().apply(velocity, events, grid, event_of_row.astype(np.int64), rcv, bool(return_fields), wrt, holder)
+    return _with_receiver_term(out, rcv_t, holder, return_fields)

@@ -11,9 +11,10 @@ Five translation units, compiled to objects under ttcr_amd/csrc/_obj and linked:
   fsm_adjoint.hip the field tape: discrete adjoint of the first-order 3-D update (coupling, seeds, relaxation, gradient)
                   and its forward mode (tangent relaxation, receiver rows); the source derivative (K-column relaxation, source gradient);
                   cell tapes (the transpose of the cell-to-node averaging); block products (four model vectors per relaxation);
-                  the joint hypocentre-velocity tangent (seeds and the tangent relaxations with the frozen nodes left alone)
+                  the joint hypocentre-velocity tangent (seeds and the tangent relaxations with the frozen nodes left alone);
+                  the receiver-point derivative (evaluation of traveltime and gradient at points, forward rows, gradient by point)
   fsm_normal.hip  the field tape's normal equations: smoothing operator, fixed-order inner product, CG around the Gauss-Newton product;
-                  CG on the joint hypocentre-velocity system
+                  CG on the joint hypocentre-velocity system and on the receiver joint system (one solver over the extra block)
 """
 import os
 import shutil

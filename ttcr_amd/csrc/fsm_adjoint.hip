@@ -503,6 +503,110 @@ __global__ void joint_scale_kernel(const T* __restrict__ c, const T* in, T* out,
     if (i < n) out[i] = c[i] * in[i];
 }
 
+// ---- derivatives with respect to the receiver points
+template <typename T>
+struct RcvGeom {
+    int nn[3];
+    size_t nodes;
+    T dx, cmin[3], shift[3];
+};
+
+// G[a] = d interp3d_pt / d p_a with the cell and the on flags held fixed: +0 on an axis the point lies on; otherwise fl(I_a / dx), I_a the
+// nested interpolation of interp3d_pt over the remaining axes that are not on (z, then y, then x; the same w1, w2;
+// fl(fl(t1 * w1) + fl(t2 * w2))) applied to the differences fl(T[hi_a] - T[lo_a]).  lo, on, w1, w2 as interp3d_stencil computes them, node
+// indices clamped as TT clamps them: a clamped upper node reads the lower one again and the difference is +0.
+template <typename T>
+__device__ __forceinline__ void rcv_grad_pt(const T* __restrict__ Tn, const T* p, const RcvGeom<T>& g, T* G) {
+    const double small2 = 1.e-4 * 1.e-4;
+    uint32_t c0[3], c1[3];
+    bool on[3];
+    T w1[3], w2[3];
+    for (int a = 0; a < 3; ++a) {
+        const uint32_t lo = idx_u32(small2 + (double)((p[a] - g.cmin[a]) / g.dx));
+        const T off = p[a] - (g.cmin[a] + (T)lo * g.dx);
+        on[a] = (double)(off < 0 ? -off : off) < small2;
+        w1[a] = (g.cmin[a] + (T)(lo + 1) * g.dx - p[a]) / g.dx;
+        w2[a] = (p[a] - (g.cmin[a] + (T)lo * g.dx)) / g.dx;
+        const uint32_t last = (uint32_t)g.nn[a] - 1u;
+        c0[a] = lo < last ? lo : last;
+        c1[a] = lo + 1u < (uint32_t)g.nn[a] ? lo + 1u : last;
+    }
+    const size_t stride[3] = {1, (size_t)g.nn[0], (size_t)g.nn[0] * g.nn[1]};
+    for (int a = 0; a < 3; ++a) {
+        if (on[a]) {
+            G[a] = 0;
+            continue;
+        }
+        const int b = a == 0 ? 1 : 0, c = a == 2 ? 1 : 2;   // the other two axes, b < c: c is interpolated first
+        const int nb = on[b] ? 1 : 2, nc = on[c] ? 1 : 2;
+        T e[2];
+        for (int ib = 0; ib < nb; ++ib) {
+            T d[2];
+            for (int ic = 0; ic < nc; ++ic) {
+                const size_t rest = (ib ? c1[b] : c0[b]) * stride[b] + (ic ? c1[c] : c0[c]) * stride[c];
+                d[ic] = Tn[rest + c1[a] * stride[a]] - Tn[rest + c0[a] * stride[a]];
+            }
+            e[ib] = on[c] ? d[0] : d[0] * w1[c] + d[1] * w2[c];
+        }
+        const T i_a = on[b] ? e[0] : e[0] * w1[b] + e[1] * w2[b];
+        G[a] = i_a / g.dx;
+    }
+}
+
+// one thread per query (point, event): tt = interp3d_pt of the event's field, the three G values behind it.  pts and event are never
+// null (the tape's own rows are evaluated by passing rcv_p and rcv_event with shift = 0: they are held as the solver sees them);
+// shift: the origin of a translated grid is subtracted first, as the solver's entries do
+template <typename T>
+__global__ void rcv_eval_kernel(const T* __restrict__ fields, const T* __restrict__ pts, const int* __restrict__ event, size_t n,
+                                RcvGeom<T> g, int shift, T* __restrict__ tt, T* __restrict__ grad) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    T p[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
+    if (shift)
+        for (int a = 0; a < 3; ++a) p[a] = p[a] - g.shift[a];
+    const T* Tn = fields + (size_t)event[i] * g.nodes;
+    if (tt) tt[i] = interp3d_pt<T>(Tn, 1, p[0], p[1], p[2], g.nn[0], g.nn[1], g.nn[2], g.dx, g.cmin[0], g.cmin[1], g.cmin[2]);
+    if (grad) {
+        T G[3];
+        rcv_grad_pt<T>(Tn, p, g, G);
+        grad[3 * i] = G[0];
+        grad[3 * i + 1] = G[1];
+        grad[3 * i + 2] = G[2];
+    }
+}
+
+// the forward chain, one thread per row: acc = drcv[q][0], then per axis x, y, z acc = fl(acc + fl(G[r][a] * drcv[q][1 + a])), q the point
+// of the row; dtt[r] = acc, or fl(base[r] + acc) in the joint tangent (base may be dtt)
+template <typename T>
+__global__ void rcv_rows_kernel(const int* __restrict__ pt, const T* __restrict__ G, const T* __restrict__ drcv, size_t n_rows,
+                                const T* base, T* dtt) {
+    const size_t r = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (r >= n_rows) return;
+    const T* d = drcv + (size_t)pt[r] * 4;
+    T acc = d[0];
+    acc = acc + G[3 * r] * d[1];
+    acc = acc + G[3 * r + 1] * d[2];
+    acc = acc + G[3 * r + 2] * d[3];
+    dtt[r] = base ? base[r] + acc : acc;
+}
+
+// the reverse chains, one thread per (receiver point, parameter): over the rows of the point in ascending row order, from +0,
+// acc = fl(acc + w[r]) for t0 and acc = fl(acc + fl(w[r] * G[r][a])) for x, y, z
+template <typename T>
+__global__ void rcv_grad_kernel(const int* __restrict__ off, const int* __restrict__ rows, const T* __restrict__ G,
+                                const T* __restrict__ w, size_t n_points, T* __restrict__ grcv) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= 4 * n_points) return;
+    const size_t q = i / 4;
+    const int k = (int)(i % 4);
+    T acc = 0;
+    for (int j = off[q]; j < off[q + 1]; ++j) {
+        const int r = rows[j];
+        acc = k == 0 ? acc + w[r] : acc + w[r] * G[3 * (size_t)r + k - 1];
+    }
+    grcv[i] = acc;
+}
+
 // Global Jacobi pass of the K-column relaxation (the correctness baseline): for a node that is not frozen
 //   mu[m][k] = fl(acc / D_m), acc = +0, then per active axis x, y, z: acc = fl(acc + fl(mu[u][k] * fl(T[m] - a)))
 // with the upwind choice recomputed from the field once for the K columns.  Frozen nodes keep what src_seed_kernel wrote (in both buffers).
@@ -1184,6 +1288,13 @@ void AdjTapeDev::release() {
     dev_free(jnt_x); dev_free(jnt_r); dev_free(jnt_p); dev_free(jnt_q); dev_free(jnt_hp); dev_free(jnt_scale); dev_free(jnt_damp);
     dev_free(jnt_ve); dev_free(jnt_partial); dev_free(jnt_ctl);
     jnt_bytes = 0;
+    dev_free(rcv_p); dev_free(rcv_event); dev_free(rcv_pt); dev_free(rcv_rows); dev_free(rcv_off); dev_free(rcv_G); dev_free(rcv_tt);
+    dev_free(rcv_io); dev_free(rcv_stage);
+    rcv_stage_bytes = 0;
+    dev_free(rj_x); dev_free(rj_r); dev_free(rj_p); dev_free(rj_q); dev_free(rj_hp); dev_free(rj_scale); dev_free(rj_damp);
+    dev_free(rj_ve); dev_free(rj_partial); dev_free(rj_ctl);
+    rcv_bytes = 0;
+    rj_bytes = 0;
     blk_owns_mu4 = false;
     blk_bytes = 0;
     nrm_bytes = 0;
@@ -1265,6 +1376,18 @@ void adj_finish(AdjTapeDev& t, const AdjSink& sink) {
             t.h_src_c.insert(t.h_src_c.end(), en_.c, en_.c + 3);
         }
         for (size_t q = 0; q < t.n_points; ++q) t.h_src_off[q + 1] += t.h_src_off[q];
+    }
+    // the receivers of the rows, for the receiver derivative: kept on the host until the first call that needs them; one
+    // receiver point per row until adj_rcv_set_points says otherwise
+    {
+        t.h_rcv_p = sink.st_p;
+        t.h_rcv_p.resize(3 * t.n_rows, 0.0);
+        t.h_rcv_event.assign(sink.st_event.begin(), sink.st_event.end());
+        std::copy(sink.rcv_min, sink.rcv_min + 3, t.rcv_min);
+        std::copy(sink.rcv_shift, sink.rcv_shift + 3, t.rcv_shift);
+        std::vector<int> one(t.n_rows);
+        std::iota(one.begin(), one.end(), 0);
+        adj_rcv_set_points(t, one.data(), t.n_rows);
     }
 
     Alloc alloc{t, planned_bytes(t)};
@@ -1799,6 +1922,168 @@ void adj_gn_joint(AdjTapeDev& t, const T* d_vs, const T* d_ve, const T* d_scale,
     if (d_scale) adj_src_scale<T>(t, d_scale, d_ge, d_ge);
 }
 
+// ---- derivatives with respect to the receiver points
+void adj_rcv_set_points(AdjTapeDev& t, const int* point_of_row, size_t n_points) {
+    adj_rcv_release(t);   // (what is on the device belongs to the old map)
+    t.h_rcv_pt.assign(point_of_row, point_of_row + t.n_rows);
+    t.n_rcv_points = n_points;
+    t.h_rcv_off.assign(n_points + 1, 0);
+    for (size_t r = 0; r < t.n_rows; ++r) t.h_rcv_off[t.h_rcv_pt[r] + 1] += 1;
+    for (size_t q = 0; q < n_points; ++q) t.h_rcv_off[q + 1] += t.h_rcv_off[q];
+    t.h_rcv_rows.assign(t.n_rows, 0);
+    std::vector<int> fill(t.h_rcv_off.begin(), t.h_rcv_off.end() - 1);
+    for (size_t r = 0; r < t.n_rows; ++r) t.h_rcv_rows[fill[t.h_rcv_pt[r]]++] = (int)r;   // (rows ascending within a point)
+}
+
+size_t adj_rcv_extra_bytes(const AdjTapeDev& t) {
+    auto at_least_1 = [](size_t b) { return std::max<size_t>(b, 1); };
+    return at_least_1(3 * t.n_rows * t.elem) + 3 * at_least_1(t.n_rows * sizeof(int)) + at_least_1((t.n_rcv_points + 1) * sizeof(int)) +
+           at_least_1(3 * t.n_rows * t.elem) + at_least_1(t.n_rows * t.elem) + at_least_1(16 * t.n_rcv_points * t.elem);
+}
+
+template <typename T>
+static RcvGeom<T> rcv_geom(const AdjTapeDev& t) {
+    RcvGeom<T> g;
+    g.nn[0] = t.nnx; g.nn[1] = t.nny; g.nn[2] = t.nnz;
+    g.nodes = t.nn;
+    g.dx = (T)t.dx;
+    for (int a = 0; a < 3; ++a) { g.cmin[a] = (T)t.rcv_min[a]; g.shift[a] = (T)t.rcv_shift[a]; }
+    return g;
+}
+
+template <typename T>
+void adj_rcv_prepare(AdjTapeDev& t) {
+    if (t.rcv_p) return;
+    ADJ_CHECK(hipSetDevice(t.device));
+    Alloc alloc{t, adj_rcv_extra_bytes(t)};
+    const size_t before = t.total_bytes;
+    try {
+        alloc(t.rcv_p, 3 * t.n_rows * sizeof(T));
+        alloc(t.rcv_event, t.n_rows * sizeof(int));
+        alloc(t.rcv_pt, t.n_rows * sizeof(int));
+        alloc(t.rcv_rows, t.n_rows * sizeof(int));
+        alloc(t.rcv_off, (t.n_rcv_points + 1) * sizeof(int));
+        alloc(t.rcv_G, 3 * t.n_rows * sizeof(T));
+        alloc(t.rcv_tt, t.n_rows * sizeof(T));
+        alloc(t.rcv_io, 16 * t.n_rcv_points * sizeof(T));
+        const std::vector<T> p(t.h_rcv_p.begin(), t.h_rcv_p.end());
+        ADJ_CHECK(hipMemcpyAsync(t.rcv_off, t.h_rcv_off.data(), (t.n_rcv_points + 1) * sizeof(int), hipMemcpyHostToDevice, t.stream));
+        if (t.n_rows > 0) {
+            ADJ_CHECK(hipMemcpyAsync(t.rcv_p, p.data(), 3 * t.n_rows * sizeof(T), hipMemcpyHostToDevice, t.stream));
+            ADJ_CHECK(hipMemcpyAsync(t.rcv_event, t.h_rcv_event.data(), t.n_rows * sizeof(int), hipMemcpyHostToDevice, t.stream));
+            ADJ_CHECK(hipMemcpyAsync(t.rcv_pt, t.h_rcv_pt.data(), t.n_rows * sizeof(int), hipMemcpyHostToDevice, t.stream));
+            ADJ_CHECK(hipMemcpyAsync(t.rcv_rows, t.h_rcv_rows.data(), t.n_rows * sizeof(int), hipMemcpyHostToDevice, t.stream));
+            // G (and tt) of the tape's rows: computed once, kept with the receiver arrays
+            rcv_eval_kernel<T><<<blocks_for(t.n_rows), ADJ_THREADS, 0, t.stream>>>((const T*)t.fields, (const T*)t.rcv_p, t.rcv_event, t.n_rows,
+                                                                                  rcv_geom<T>(t), 0, (T*)t.rcv_tt, (T*)t.rcv_G);
+            ADJ_CHECK(hipGetLastError());
+        }
+        ADJ_CHECK(hipStreamSynchronize(t.stream));   // (p leaves scope)
+    } catch (...) {
+        dev_free(t.rcv_p); dev_free(t.rcv_event); dev_free(t.rcv_pt); dev_free(t.rcv_rows); dev_free(t.rcv_off); dev_free(t.rcv_G);
+        dev_free(t.rcv_tt); dev_free(t.rcv_io);
+        t.total_bytes = before;
+        throw;
+    }
+    t.rcv_bytes = t.total_bytes - before;
+}
+
+void* adj_rcv_stage(AdjTapeDev& t, size_t bytes) {
+    if (bytes <= t.rcv_stage_bytes && t.rcv_stage) return t.rcv_stage;
+    ADJ_CHECK(hipSetDevice(t.device));
+    dev_free(t.rcv_stage);
+    t.total_bytes -= t.rcv_stage_bytes;
+    t.rcv_stage_bytes = 0;
+    Alloc alloc{t, bytes};
+    alloc(t.rcv_stage, bytes);
+    t.rcv_stage_bytes = std::max<size_t>(bytes, 1);
+    return t.rcv_stage;
+}
+
+void adj_rcv_release(AdjTapeDev& t) {
+    adj_rjoint_release(t);
+    if (!t.rcv_p && !t.rcv_stage) return;
+    (void)hipSetDevice(t.device);
+    if (t.stream) (void)hipStreamSynchronize(t.stream);
+    dev_free(t.rcv_stage);
+    t.total_bytes -= t.rcv_stage_bytes;
+    t.rcv_stage_bytes = 0;
+    if (!t.rcv_p) return;
+    dev_free(t.rcv_p); dev_free(t.rcv_event); dev_free(t.rcv_pt); dev_free(t.rcv_rows); dev_free(t.rcv_off); dev_free(t.rcv_G);
+    dev_free(t.rcv_tt); dev_free(t.rcv_io);
+    t.total_bytes -= t.rcv_bytes;
+    t.rcv_bytes = 0;
+}
+
+template <typename T>
+void adj_rcv_eval(AdjTapeDev& t, size_t n, const T* d_pts, const int* d_event, bool shift, T* d_tt, T* d_grad) {
+    ADJ_CHECK(hipSetDevice(t.device));
+    if (!d_pts) {   // the tape's own rows: evaluated by adj_rcv_prepare
+        adj_rcv_prepare<T>(t);
+        if (d_tt && t.n_rows > 0) ADJ_CHECK(hipMemcpyAsync(d_tt, t.rcv_tt, t.n_rows * sizeof(T), hipMemcpyDeviceToDevice, t.stream));
+        if (d_grad && t.n_rows > 0) ADJ_CHECK(hipMemcpyAsync(d_grad, t.rcv_G, 3 * t.n_rows * sizeof(T), hipMemcpyDeviceToDevice, t.stream));
+        return;
+    }
+    if (n == 0) return;
+    rcv_eval_kernel<T><<<blocks_for(n), ADJ_THREADS, 0, t.stream>>>((const T*)t.fields, d_pts, d_event, n, rcv_geom<T>(t), shift ? 1 : 0, d_tt,
+                                                                   d_grad);
+    ADJ_CHECK(hipGetLastError());
+}
+
+template <typename T>
+void adj_jvp_rcv(AdjTapeDev& t, const T* d_drcv, const T* d_base, T* d_dtt) {
+    ADJ_CHECK(hipSetDevice(t.device));
+    adj_rcv_prepare<T>(t);
+    if (t.n_rows == 0) return;
+    rcv_rows_kernel<T><<<blocks_for(t.n_rows), ADJ_THREADS, 0, t.stream>>>(t.rcv_pt, (const T*)t.rcv_G, d_drcv, t.n_rows, d_base, d_dtt);
+    ADJ_CHECK(hipGetLastError());
+}
+
+template <typename T>
+void adj_vjp_rcv(AdjTapeDev& t, const T* d_w, T* d_grcv) {
+    ADJ_CHECK(hipSetDevice(t.device));
+    adj_rcv_prepare<T>(t);
+    if (t.n_rcv_points == 0) return;
+    rcv_grad_kernel<T><<<blocks_for(4 * t.n_rcv_points), ADJ_THREADS, 0, t.stream>>>(t.rcv_off, t.rcv_rows, (const T*)t.rcv_G, d_w,
+                                                                                    t.n_rcv_points, d_grcv);
+    ADJ_CHECK(hipGetLastError());
+}
+
+template <typename T>
+void adj_scale(AdjTapeDev& t, const T* d_c, const T* d_in, T* d_out, size_t n) {
+    if (n == 0) return;
+    joint_scale_kernel<T><<<blocks_for(n), ADJ_THREADS, 0, t.stream>>>(d_c, d_in, d_out, n);
+    ADJ_CHECK(hipGetLastError());
+}
+
+template <typename T>
+int adj_jvp_rjoint(AdjTapeDev& t, const T* d_ds, const T* d_drcv, T* d_dtt, T* d_dfields, int schedule) {
+    const int passes = adj_jvp<T>(t, d_ds, d_dtt, d_dfields, schedule);
+    if (d_dtt) adj_jvp_rcv<T>(t, d_drcv, d_dtt, d_dtt);
+    return passes;
+}
+
+template <typename T>
+void adj_gn_rjoint(AdjTapeDev& t, const T* d_vs, const T* d_ve, const T* d_scale, T* d_ve_scaled, const T* d_rw, T* d_gs, T* d_ge,
+                   int schedule, int* passes_jvp, int* passes_vjp) {
+    ADJ_CHECK(hipSetDevice(t.device));
+    adj_rcv_prepare<T>(t);
+    const size_t blk = 4 * t.n_rcv_points;
+    if (d_scale) {
+        adj_scale<T>(t, d_scale, d_ve, d_ve_scaled, blk);
+        d_ve = d_ve_scaled;
+    }
+    T* w = (T*)t.w_tmp;
+    *passes_jvp = adj_jvp_rjoint<T>(t, d_vs, d_ve, w, nullptr, schedule);
+    if (d_rw && t.n_rows > 0) {
+        tan_scale_rows_kernel<T><<<blocks_for(t.n_rows), ADJ_THREADS, 0, t.stream>>>(d_rw, w, t.n_rows);
+        ADJ_CHECK(hipGetLastError());
+    }
+    adj_vjp_rcv<T>(t, w, d_ge);
+    *passes_vjp = adj_vjp<T>(t, w, nullptr, d_gs, schedule);
+    if (d_scale) adj_scale<T>(t, d_scale, d_ge, d_ge, blk);
+}
+
 
 // ---- block products
 size_t adj_block_bytes(const AdjTapeDev& t) {
@@ -1980,6 +2265,22 @@ template int adj_jvp_joint<double>(AdjTapeDev&, const double*, const double*, do
 template void adj_gn_joint<float>(AdjTapeDev&, const float*, const float*, const float*, float*, const float*, float*, float*, int, int*, int*);
 template void adj_gn_joint<double>(AdjTapeDev&, const double*, const double*, const double*, double*, const double*, double*, double*, int, int*,
                                    int*);
+
+template void adj_rcv_prepare<float>(AdjTapeDev&);
+template void adj_rcv_prepare<double>(AdjTapeDev&);
+template void adj_rcv_eval<float>(AdjTapeDev&, size_t, const float*, const int*, bool, float*, float*);
+template void adj_rcv_eval<double>(AdjTapeDev&, size_t, const double*, const int*, bool, double*, double*);
+template void adj_jvp_rcv<float>(AdjTapeDev&, const float*, const float*, float*);
+template void adj_jvp_rcv<double>(AdjTapeDev&, const double*, const double*, double*);
+template void adj_vjp_rcv<float>(AdjTapeDev&, const float*, float*);
+template void adj_vjp_rcv<double>(AdjTapeDev&, const double*, double*);
+template void adj_scale<float>(AdjTapeDev&, const float*, const float*, float*, size_t);
+template void adj_scale<double>(AdjTapeDev&, const double*, const double*, double*, size_t);
+template int adj_jvp_rjoint<float>(AdjTapeDev&, const float*, const float*, float*, float*, int);
+template int adj_jvp_rjoint<double>(AdjTapeDev&, const double*, const double*, double*, double*, int);
+template void adj_gn_rjoint<float>(AdjTapeDev&, const float*, const float*, const float*, float*, const float*, float*, float*, int, int*, int*);
+template void adj_gn_rjoint<double>(AdjTapeDev&, const double*, const double*, const double*, double*, const double*, double*, double*, int, int*,
+                                    int*);
 
 template void adj_block_prepare<float>(AdjTapeDev&);
 template void adj_block_prepare<double>(AdjTapeDev&);

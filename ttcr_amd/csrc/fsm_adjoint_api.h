@@ -53,6 +53,10 @@ struct AdjSink {
     std::vector<int> st_cnt, st_event;
     std::vector<long long> st_node;
     std::vector<double> st_w;
+    // ... and, for the receiver derivative: the receiver of every row as the solver sees it (after the origin shift of a
+    // translated grid; T values held exactly, 3 per row), the origin the solver interpolates with and the shift of a translated grid
+    std::vector<double> st_p;
+    double rcv_min[3] = {0, 0, 0}, rcv_shift[3] = {0, 0, 0};
 };
 
 struct AdjTapeDev {
@@ -144,6 +148,42 @@ struct AdjTapeDev {
     void* jnt_partial = nullptr;      // one double per chunk of 1024 joint elements
     void* jnt_ctl = nullptr;          // the scalars of the recurrence
     size_t jnt_bytes = 0;             // what these arrays added to total_bytes
+    // receiver points.  Host lists, kept from adj_finish on: the receiver of every row as the solver sees it, the point of
+    // every row (default: one point per row) and the rows of every point (CSR, rows ascending within a point).  The first receiver call
+    // uploads them, evaluates G of the tape's rows and allocates the staging arrays; adj_rcv_release returns all of it
+    std::vector<double> h_rcv_p;      // 3 n_rows
+    std::vector<int> h_rcv_event;     // n_rows
+    std::vector<int> h_rcv_pt;        // n_rows: receiver point of every row
+    std::vector<int> h_rcv_off;       // n_rcv_points + 1: rows of point q at h_rcv_rows[h_rcv_off[q] .. h_rcv_off[q + 1])
+    std::vector<int> h_rcv_rows;      // n_rows
+    size_t n_rcv_points = 0;
+    double rcv_min[3] = {0, 0, 0};    // the origin the solver interpolates with
+    double rcv_shift[3] = {0, 0, 0};  // what a translated grid subtracts from a point first (zeros otherwise)
+    void* rcv_p = nullptr;            // 3 n_rows
+    int* rcv_event = nullptr;         // n_rows
+    int* rcv_pt = nullptr;            // n_rows
+    int* rcv_off = nullptr;           // n_rcv_points + 1
+    int* rcv_rows = nullptr;          // n_rows
+    void* rcv_G = nullptr;            // 3 n_rows: d tt[row] / d (x, y, z) of its receiver
+    void* rcv_tt = nullptr;           // n_rows: interp3d_pt of the tape's rows (a host dtt of jvp_rcv is staged here too)
+    void* rcv_io = nullptr;           // 16 n_rcv_points values: a host drcv / grcv is staged here (four blocks, as src_io)
+    size_t rcv_bytes = 0;             // what these arrays added to total_bytes
+    void* rcv_stage = nullptr;        // staging of rcv_eval at arbitrary points: grow-only, returned by adj_rcv_release
+    size_t rcv_stage_bytes = 0;
+    // receiver joint solver: the arrays of the joint solver above for joint vectors of n_rjoint() values, the model vector,
+    // then (t0, x, y, z) of every receiver point; allocated by the first receiver joint solve, returned by adj_rcv_release
+    size_t n_rjoint() const { return n_model() + 4 * n_rcv_points; }
+    void* rj_x = nullptr;
+    void* rj_r = nullptr;
+    void* rj_p = nullptr;
+    void* rj_q = nullptr;
+    void* rj_hp = nullptr;
+    void* rj_scale = nullptr;
+    void* rj_damp = nullptr;
+    void* rj_ve = nullptr;
+    void* rj_partial = nullptr;
+    void* rj_ctl = nullptr;
+    size_t rj_bytes = 0;
     size_t n_tiles = 0;
     size_t total_bytes = 0;
     hipStream_t stream = nullptr;
@@ -292,8 +332,48 @@ void adj_joint_release(AdjTapeDev& t);
 // conjugate gradients from zero on the regularised joint normal equations (the recurrence, scalars, statuses and host reads of
 // adj_solve_normal; inner products over the flat joint vector).  On entry jnt_r holds (b_s, b_e unscaled), jnt_scale / jnt_damp hold c and
 // delta if with_scale / with_damp; on return jnt_x holds (x_s, x_e = fl(c * z_e)).  op.newton is not offered.
+// receiver: the extra block is the receiver block of DESIGN.md 6k (arrays rj_*, n_rjoint(), adj_gn_rjoint) instead of the source block.
 template <typename T>
 void adj_solve_joint(AdjTapeDev& t, const T* d_rw, const NormalOperator& op, bool with_scale, bool with_damp, int maxiter, double rtol,
-                     int schedule, NormalResult& res);
+                     int schedule, NormalResult& res, bool receiver = false);
+
+// ---- derivatives with respect to the receiver points (tests/receiver_reference.py restates them).  Receiver blocks are 4
+// n_rcv_points values, (t0, x, y, z) of every receiver point, on the tape's device.
+// replaces the map row -> receiver point (tape row order; n_points >= every value + 1) and rebuilds the CSR by point; frees what the
+// receiver calls hold on the device (the next call uploads the new map).  Host only apart from that.
+void adj_rcv_set_points(AdjTapeDev& t, const int* point_of_row, size_t n_points);
+// what the first receiver call adds to the tape; adj_rcv_prepare is a no-op while it is there (AdjDeviceError naming the byte count if
+// an allocation fails); adj_rcv_release frees it and the receiver joint solver's arrays and takes them off bytes()
+size_t adj_rcv_extra_bytes(const AdjTapeDev& t);
+template <typename T>
+void adj_rcv_prepare(AdjTapeDev& t);
+void adj_rcv_release(AdjTapeDev& t);
+// the staging buffer of rcv_eval at arbitrary points, at least `bytes` long: grown (never shrunk) when a call needs more, counted in
+// bytes(), freed by adj_rcv_release.  The stream has to be idle (every entry waits for it before it returns).
+void* adj_rcv_stage(AdjTapeDev& t, size_t bytes);
+// n queries (point, event): d_tt (n, may be null) = interp3d_pt of the event's field at the point, d_grad (3 n, may be null) = G.  d_pts
+// (3 n) on the tape's device; shift: subtract the origin of a translated grid first.  d_pts null: the tape's own rows (n ignored)
+template <typename T>
+void adj_rcv_eval(AdjTapeDev& t, size_t n, const T* d_pts, const int* d_event, bool shift, T* d_tt, T* d_grad);
+// d_dtt[r] = the forward chain of d_drcv (4 n_rcv_points) over row r; d_base (n_rows, may be null, may be d_dtt): fl(d_base[r] + that)
+template <typename T>
+void adj_jvp_rcv(AdjTapeDev& t, const T* d_drcv, const T* d_base, T* d_dtt);
+// d_grcv (4 n_rcv_points) = the reverse chains of d_w (n_rows) over the rows of every point
+template <typename T>
+void adj_vjp_rcv(AdjTapeDev& t, const T* d_w, T* d_grcv);
+// out = fl(c * in) over n values (the kernel of adj_src_scale)
+template <typename T>
+void adj_scale(AdjTapeDev& t, const T* d_c, const T* d_in, T* d_out, size_t n);
+// the receiver joint tangent: adj_jvp of d_ds, then the receiver rows added; outputs as adj_jvp
+template <typename T>
+int adj_jvp_rjoint(AdjTapeDev& t, const T* d_ds, const T* d_drcv, T* d_dtt, T* d_dfields, int schedule);
+// adj_gn_joint with the receiver block in the place of the source block: one tangent relaxation, one adjoint relaxation, the row kernels
+template <typename T>
+void adj_gn_rjoint(AdjTapeDev& t, const T* d_vs, const T* d_ve, const T* d_scale, T* d_ve_scaled, const T* d_rw, T* d_gs, T* d_ge,
+                   int schedule, int* passes_jvp, int* passes_vjp);
+// the work arrays of the receiver joint solver (as adj_joint_bytes, for n_rjoint())
+size_t adj_rjoint_bytes(const AdjTapeDev& t);
+void adj_rjoint_prepare(AdjTapeDev& t);
+void adj_rjoint_release(AdjTapeDev& t);
 
 }  // namespace ttcr_amd

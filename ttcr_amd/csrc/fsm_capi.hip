@@ -2465,6 +2465,11 @@ class GridT : public GridBase {
                 sk.st_cnt[row] = cnt;
                 sk.st_event[row] = (int)e;
                 for (int c = 0; c < cnt; ++c) { sk.st_node[8 * row + c] = nd[c]; sk.st_w[8 * row + c] = (double)wt[c]; }
+                for (int c = 0; c < 3; ++c) sk.st_p[3 * row + c] = (double)rx[3 * (size_t)r + c];   // (the point as the solver sees it: 6k)
+            }
+            if (e == 0) {   // (written once, like the slowness: the replicas of a multi-device grid share the geometry)
+                sk.rcv_min[0] = (double)xmin; sk.rcv_min[1] = (double)ymin; sk.rcv_min[2] = (double)zmin;
+                sk.rcv_shift[0] = (double)ox; sk.rcv_shift[1] = (double)oy; sk.rcv_shift[2] = (double)oz;
             }
         }
         HIP_CHECK(hipStreamSynchronize(stream));
@@ -3838,6 +3843,7 @@ static int raytrace_multi_adjoint_entry(ttcr_fsm_grid* g, int n_src, const int* 
             sink.pt_off.assign(tx_off ? tx_off : &n_src, tx_off ? tx_off + n_src + 1 : &n_src + 1);   // (n_src = 0: the one offset 0)
             sink.st_cnt.assign(t.n_rows, 0); sink.st_event.assign(t.n_rows, 0);
             sink.st_node.assign(8 * t.n_rows, 0); sink.st_w.assign(8 * t.n_rows, 0.0);
+            sink.st_p.assign(3 * t.n_rows, 0.0);
             G.raytrace_multi_adjoint(n_src, tx_off, tx, t0, rx_off, rx, tt_out, sink);
             HIP_CHECK(hipSetDevice(t.device));
             HIP_CHECK(hipDeviceSynchronize());   // (the replicas of a multi-device grid wrote from their own streams)
@@ -4396,6 +4402,194 @@ int ttcr_fsm_joint_release(ttcr_fsm_adjoint* t) {
     if (!t) return tape_arg_error("null tape");
     std::lock_guard<std::mutex> lock(t->mu);
     return guarded([&] { ttcr_amd::adj_joint_release(t->t); });
+}
+
+// ---- derivatives with respect to the receiver points and the receiver joint system of the field tape.  A receiver block is
+// 4 n_rcv_points values, (t0, x, y, z) of every receiver point.  Host staging (the table above stage_in continued): rcv_eval stages the
+// events, host points and host results in rcv_stage (7 n_pts values and n_pts ints: points, gradients, traveltimes, events), a buffer of
+// the tape that grows to the largest call and is returned by rcv_release -- its sizes are the caller's, not the tape's --; jvp_rcv a
+// host drcv in rcv_io and a host dtt in w_tmp; vjp_rcv a host w in w_tmp and a host grcv in rcv_io; rjoint_jvp as joint_jvp with rcv_io in the
+// place of src_io; rjoint_gn parts rcv_io into four receiver blocks as joint_gn parts src_io; rjoint_solve copies its right-hand sides
+// into the residual of its own work arrays and reads the result from the iterate.
+int ttcr_fsm_rcv_eval(const ttcr_fsm_adjoint* t, size_t n_pts, const void* pts, int pts_on_device, const int* event_of_pt, void* tt,
+                              int tt_on_device, void* grad, int grad_on_device) {
+    const char* bad = (!tt && !grad) ? "tt and grad are both null: nothing to compute"
+                                     : (pts && !event_of_pt ? "null event_of_pt" : (!t ? "null tape" : nullptr));
+    if (bad) return tape_arg_error(bad);
+    if (pts)
+        for (size_t i = 0; i < n_pts; ++i)
+            if (event_of_pt[i] < 0 || (size_t)event_of_pt[i] >= t->t.n_events) return tape_arg_error("event_of_pt: an event index out of range");
+    return tape_call(t, 0, nullptr, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int&, int&) {
+        using T = decltype(tag);
+        if (!pts) {   // the tape's own rows
+            ttcr_amd::adj_rcv_prepare<T>(d);
+            ttcr_amd::adj_rcv_eval<T>(d, d.n_rows, nullptr, nullptr, false, tt_on_device ? (T*)tt : nullptr, grad_on_device ? (T*)grad : nullptr);
+            stage_out<T>(d, tt, tt_on_device, d.rcv_tt, d.n_rows);
+            stage_out<T>(d, grad, grad_on_device, d.rcv_G, 3 * d.n_rows);
+            return;
+        }
+        if (n_pts == 0) return;
+        T* sp = (T*)ttcr_amd::adj_rcv_stage(d, 7 * n_pts * sizeof(T) + n_pts * sizeof(int));   // points, gradients, traveltimes, events
+        T* sg = sp + 3 * n_pts;
+        T* st = sg + 3 * n_pts;
+        int* ev = (int*)(st + n_pts);
+        HIP_CHECK(hipMemcpyAsync(ev, event_of_pt, n_pts * sizeof(int), hipMemcpyHostToDevice, d.stream));
+        const T* dp = stage_in<T>(d, pts, pts_on_device, sp, 3 * n_pts);
+        ttcr_amd::adj_rcv_eval<T>(d, n_pts, dp, ev, true, stage_dst<T>(tt, tt_on_device, st), stage_dst<T>(grad, grad_on_device, sg));
+        stage_out<T>(d, tt, tt_on_device, st, n_pts);
+        stage_out<T>(d, grad, grad_on_device, sg, 3 * n_pts);
+    });
+}
+int ttcr_fsm_rcv_points(ttcr_fsm_adjoint* t, const int* set_point_of_row, size_t set_n_points, size_t* n_points, int* point_of_row,
+                        int* differing_rows) {
+    if (!t) return tape_arg_error("null tape");
+    std::lock_guard<std::mutex> lock(t->mu);
+    ttcr_amd::AdjTapeDev& d = t->t;
+    if (set_point_of_row) {
+        if (set_n_points > ((size_t)1 << 29)) return tape_arg_error("n_points: at most 2^29 receiver points");
+        for (size_t r = 0; r < d.n_rows; ++r)
+            if (set_point_of_row[r] < 0 || (size_t)set_point_of_row[r] >= set_n_points)
+                return tape_arg_error("point_of_row: a receiver point index outside 0 .. n_points - 1");
+        int pair[2] = {-1, -1};
+        const int st = guarded([&] {
+            std::vector<int> first(set_n_points, -1);
+            for (size_t r = 0; r < d.n_rows; ++r) {   // rows that share a point: bit-equal coordinates (-0 and +0 differ: compared as bytes)
+                int& f = first[set_point_of_row[r]];
+                if (f < 0) { f = (int)r; continue; }
+                if (std::memcmp(&d.h_rcv_p[3 * (size_t)f], &d.h_rcv_p[3 * r], 3 * sizeof(double)) != 0) {
+                    pair[0] = f; pair[1] = (int)r;
+                    return;
+                }
+            }
+            ttcr_amd::adj_rcv_set_points(d, set_point_of_row, set_n_points);
+        });
+        if (st != TTCR_OK) return st;
+        if (pair[0] >= 0) {
+            if (differing_rows) { differing_rows[0] = pair[0]; differing_rows[1] = pair[1]; }
+            g_last_error = "point_of_row: tape rows " + std::to_string(pair[0]) + " and " + std::to_string(pair[1]) +
+                           " share a receiver point but their receiver coordinates differ";
+            return TTCR_ERR_VALUE;
+        }
+    }
+    if (n_points) *n_points = d.n_rcv_points;
+    if (point_of_row) std::copy(d.h_rcv_pt.begin(), d.h_rcv_pt.end(), point_of_row);
+    return TTCR_OK;
+}
+int ttcr_fsm_rcv_jvp(const ttcr_fsm_adjoint* t, const void* drcv, int drcv_on_device, void* dtt, int dtt_on_device) {
+    if (!drcv || !dtt || !t) return tape_arg_error(!drcv ? "null drcv" : (!dtt ? "null dtt" : "null tape"));
+    return tape_call(t, 0, nullptr, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int&, int&) {
+        using T = decltype(tag);
+        ttcr_amd::adj_rcv_prepare<T>(d);
+        const T* dd = stage_in<T>(d, drcv, drcv_on_device, d.rcv_io, 4 * d.n_rcv_points);
+        ttcr_amd::adj_jvp_rcv<T>(d, dd, nullptr, stage_dst<T>(dtt, dtt_on_device, d.w_tmp));
+        stage_out<T>(d, dtt, dtt_on_device, d.w_tmp, d.n_rows);
+    });
+}
+int ttcr_fsm_rcv_vjp(const ttcr_fsm_adjoint* t, const void* w, int w_on_device, void* grcv, int grcv_on_device) {
+    if (!w || !grcv || !t) return tape_arg_error(!w ? "null w" : (!grcv ? "null grcv" : "null tape"));
+    return tape_call(t, 0, nullptr, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int&, int&) {
+        using T = decltype(tag);
+        ttcr_amd::adj_rcv_prepare<T>(d);
+        const T* dw = stage_in<T>(d, w, w_on_device, d.w_tmp, d.n_rows);
+        ttcr_amd::adj_vjp_rcv<T>(d, dw, stage_dst<T>(grcv, grcv_on_device, d.rcv_io));
+        stage_out<T>(d, grcv, grcv_on_device, d.rcv_io, 4 * d.n_rcv_points);
+    });
+}
+int ttcr_fsm_rjoint_jvp(const ttcr_fsm_adjoint* t, const void* ds, int ds_on_device, const void* drcv, int drcv_on_device, void* dtt,
+                        int dtt_on_device, void* dfields, int df_on_device, int schedule, int* passes) {
+    if (!ds || !drcv || (!dtt && !dfields) || !t)
+        return tape_arg_error(!ds ? "null ds" : (!drcv ? "null drcv" : (!t ? "null tape" : "dtt and dfields are both null: nothing to compute")));
+    return tape_call(t, schedule, passes, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int& np, int&) {
+        using T = decltype(tag);
+        ttcr_amd::adj_rcv_prepare<T>(d);
+        ttcr_amd::adj_jvp_prepare<T>(d);
+        const T* dds = stage_in<T>(d, ds, ds_on_device, d.model_tmp(), d.n_model());
+        const T* dd = stage_in<T>(d, drcv, drcv_on_device, d.rcv_io, 4 * d.n_rcv_points);
+        // (the fields' tangent does not depend on drcv: it is adj_jvp's, staged as ttcr_fsm_adjoint_jvp stages it)
+        np = ttcr_amd::adj_jvp_rjoint<T>(d, dds, dd, stage_dst<T>(dtt, dtt_on_device, d.w_tmp), df_on_device ? (T*)dfields : nullptr, schedule);
+        stage_out<T>(d, dtt, dtt_on_device, d.w_tmp, d.n_rows);
+        stage_out<T>(d, dfields, df_on_device, (schedule != 0 && np % 2 == 1) ? d.lam2 : d.lam, d.n_events * d.nn);
+    });
+}
+int ttcr_fsm_rjoint_gn(const ttcr_fsm_adjoint* t, const void* v, int v_on_device, const void* v_rcv, int vr_on_device, const void* row_weight,
+                       int rw_on_device, const double* rcv_scale, void* out, int out_on_device, void* out_rcv, int or_on_device,
+                       int schedule, int* passes_jvp, int* passes_vjp) {
+    const char* bad = !v ? "null v" : (!v_rcv ? "null v_rcv" : (!out ? "null out" : (!out_rcv ? "null out_rcv" : (!t ? "null tape" : nullptr))));
+    if (!bad) bad = schedule_error(schedule);
+    if (!bad) bad = joint_block_error(rcv_scale, 4 * t->t.n_rcv_points, "rcv_scale: finite values >= 0");
+    if (bad) return tape_arg_error(bad);
+    return tape_call(t, schedule, passes_jvp, passes_vjp, [&](ttcr_amd::AdjTapeDev& d, auto tag, int& pj, int& pv) {
+        using T = decltype(tag);
+        const size_t blk = 4 * d.n_rcv_points;
+        ttcr_amd::adj_rcv_prepare<T>(d);
+        T* io = (T*)d.rcv_io;
+        const T* dv = stage_in<T>(d, v, v_on_device, d.model_tmp(), d.n_model());
+        const T* dve = stage_in<T>(d, v_rcv, vr_on_device, io, blk);
+        if (row_weight && !rw_on_device) ttcr_amd::adj_jvp_prepare<T>(d);
+        const T* drw = stage_in<T>(d, row_weight, rw_on_device, d.rw_tmp, d.n_rows);
+        if (rcv_scale) joint_upload<T>(d, rcv_scale, blk, io + blk);
+        T* dout = stage_dst<T>(out, out_on_device, d.model_tmp());
+        T* dor = stage_dst<T>(out_rcv, or_on_device, io + 3 * blk);
+        ttcr_amd::adj_gn_rjoint<T>(d, dv, dve, rcv_scale ? io + blk : nullptr, io + 2 * blk, drw, dout, dor, schedule, &pj, &pv);
+        stage_out<T>(d, out, out_on_device, d.model_tmp(), d.n_model());
+        stage_out<T>(d, out_rcv, or_on_device, io + 3 * blk, blk);
+    });
+}
+int ttcr_fsm_rjoint_solve(ttcr_fsm_adjoint* t, const void* rhs, int rhs_on_device, const void* rhs_rcv, int rr_on_device,
+                          const void* row_weight, int rw_on_device, double smooth, const double* smooth_weights, double damp,
+                          const double* rcv_damp, const double* rcv_scale, int maxiter, double rtol, int schedule, void* x,
+                          int x_on_device, void* x_rcv, int xr_on_device, int* status, int* iterations, double* rho, double* pq, int* passes) {
+    const char* bad = nullptr;
+    if (!(smooth >= 0.0) || !std::isfinite(smooth)) bad = "smooth: a finite value >= 0";
+    else if (!(damp >= 0.0) || !std::isfinite(damp)) bad = "damp: a finite value >= 0";
+    else if (maxiter < 1) bad = "maxiter: at least one iteration";
+    else if (!(rtol >= 0.0) || !std::isfinite(rtol)) bad = "rtol: a finite value >= 0";
+    else if (const char* w = normal_weights_error(smooth_weights, "null smooth_weights", "smooth_weights: three finite values >= 0 (x, y, z)"))
+        bad = w;
+    else if (const char* s = schedule_error(schedule)) bad = s;
+    else if (!rhs || !rhs_rcv) bad = !rhs ? "null rhs" : "null rhs_rcv";
+    else if (!x || !x_rcv) bad = !x ? "null x" : "null x_rcv";
+    else if (!status || !iterations || !rho || !pq) bad = "null status, iterations, rho or pq";
+    else if (!t) bad = "null tape";
+    else if (const char* c = joint_block_error(rcv_scale, 4 * t->t.n_rcv_points, "rcv_scale: finite values >= 0")) bad = c;
+    else if (const char* c = joint_block_error(rcv_damp, 4 * t->t.n_rcv_points, "rcv_damp: finite values >= 0")) bad = c;
+    else if (smooth != 0.0) bad = normal_axes_error(t);
+    if (bad) return tape_arg_error(bad);
+    return tape_call(t, schedule, nullptr, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int&, int&) {
+        using T = decltype(tag);
+        const size_t nm = d.n_model(), blk = 4 * d.n_rcv_points;
+        ttcr_amd::adj_rcv_prepare<T>(d);
+        ttcr_amd::adj_rjoint_prepare(d);
+        if (row_weight && !rw_on_device) ttcr_amd::adj_jvp_prepare<T>(d);
+        const T* drw = stage_in<T>(d, row_weight, rw_on_device, d.rw_tmp, d.n_rows);
+        T* r = (T*)d.rj_r;
+        if (nm > 0) HIP_CHECK(hipMemcpyAsync(r, rhs, nm * sizeof(T), rhs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d.stream));
+        if (blk > 0)
+            HIP_CHECK(hipMemcpyAsync(r + nm, rhs_rcv, blk * sizeof(T), rr_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d.stream));
+        const bool with_damp = joint_any(rcv_damp, blk);   // (a term whose factor is 0 everywhere is not evaluated)
+        if (rcv_scale) joint_upload<T>(d, rcv_scale, blk, d.rj_scale);
+        if (with_damp) joint_upload<T>(d, rcv_damp, blk, d.rj_damp);
+        ttcr_amd::NormalOperator op;
+        op.smooth = smooth;
+        op.damp = damp;
+        std::copy(smooth_weights, smooth_weights + 3, op.weights);
+        ttcr_amd::NormalResult res;
+        ttcr_amd::adj_solve_joint<T>(d, drw, op, rcv_scale != nullptr, with_damp, maxiter, rtol, schedule, res, true);
+        const T* xd = (const T*)d.rj_x;
+        if (nm > 0) HIP_CHECK(hipMemcpyAsync(x, xd, nm * sizeof(T), x_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, d.stream));
+        if (blk > 0)
+            HIP_CHECK(hipMemcpyAsync(x_rcv, xd + nm, blk * sizeof(T), xr_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, d.stream));
+        *status = res.status;
+        *iterations = res.iterations;
+        std::copy(res.rho.begin(), res.rho.end(), rho);
+        std::copy(res.pq.begin(), res.pq.end(), pq);
+        if (passes) std::copy(res.passes.begin(), res.passes.end(), passes);
+    });
+}
+int ttcr_fsm_rcv_release(ttcr_fsm_adjoint* t) {
+    if (!t) return tape_arg_error("null tape");
+    std::lock_guard<std::mutex> lock(t->mu);
+    return guarded([&] { ttcr_amd::adj_rcv_release(t->t); });
 }
 int ttcr_fsm_adjoint_free(ttcr_fsm_adjoint* t) {
     if (!t) return TTCR_OK;

@@ -460,31 +460,46 @@ void adj_solve_normal(AdjTapeDev& t, const T* d_rw, const NormalOperator& op, bo
     }
 }
 
-// ---- the joint hypocentre-velocity system
+// ---- the joint hypocentre-velocity system and the receiver joint system: one solver over which extra block
+// the joint vector carries behind the model vector -- (t0, x, y, z) of the source points or of the receiver points.  Each has work arrays
+// of its own.
 namespace {
-size_t jnt_chunks(const AdjTapeDev& t) { return std::max<size_t>(1, (t.n_joint() + NRM_CHUNK - 1) / NRM_CHUNK); }
+// the work arrays of one of the two systems, by reference into the tape
+struct JntWork {
+    void*& x; void*& r; void*& p; void*& q; void*& hp; void*& scale; void*& damp; void*& ve; void*& partial; void*& ctl;
+    size_t& bytes;
+    size_t n_joint, n_block;   // elements of a joint vector and of its extra block
+    const char* what;
+};
+JntWork jnt_work(AdjTapeDev& t, bool receiver) {
+    if (receiver)
+        return {t.rj_x, t.rj_r, t.rj_p, t.rj_q, t.rj_hp, t.rj_scale, t.rj_damp, t.rj_ve, t.rj_partial, t.rj_ctl, t.rj_bytes, t.n_rjoint(),
+                4 * t.n_rcv_points, "the receiver joint solver"};
+    return {t.jnt_x, t.jnt_r, t.jnt_p, t.jnt_q, t.jnt_hp, t.jnt_scale, t.jnt_damp, t.jnt_ve, t.jnt_partial, t.jnt_ctl, t.jnt_bytes, t.n_joint(),
+            4 * t.n_points, "the joint solver"};
+}
+size_t jnt_chunks(size_t n_joint) { return std::max<size_t>(1, (n_joint + NRM_CHUNK - 1) / NRM_CHUNK); }
 
 template <typename T>
-void jnt_close(AdjTapeDev& t, int what) {
-    nrm_finish_kernel<T><<<1, NRM_THREADS, 0, t.stream>>>((const double*)t.jnt_partial, jnt_chunks(t), what, (NrmCtl*)t.jnt_ctl);
+void jnt_close(AdjTapeDev& t, const JntWork& w, int what) {
+    nrm_finish_kernel<T><<<1, NRM_THREADS, 0, t.stream>>>((const double*)w.partial, jnt_chunks(w.n_joint), what, (NrmCtl*)w.ctl);
     NRM_CHECK(hipGetLastError());
 }
 
-void jnt_free_all(AdjTapeDev& t) {
-    nrm_free(t.jnt_x); nrm_free(t.jnt_r); nrm_free(t.jnt_p); nrm_free(t.jnt_q); nrm_free(t.jnt_hp); nrm_free(t.jnt_scale);
-    nrm_free(t.jnt_damp); nrm_free(t.jnt_ve); nrm_free(t.jnt_partial); nrm_free(t.jnt_ctl);
+void jnt_free_all(const JntWork& w) {
+    nrm_free(w.x); nrm_free(w.r); nrm_free(w.p); nrm_free(w.q); nrm_free(w.hp); nrm_free(w.scale);
+    nrm_free(w.damp); nrm_free(w.ve); nrm_free(w.partial); nrm_free(w.ctl);
 }
-}  // namespace
 
-size_t adj_joint_bytes(const AdjTapeDev& t) {
-    return 5 * std::max<size_t>(t.n_joint() * t.elem, 1) + 3 * std::max<size_t>(4 * t.n_points * t.elem, 1) + jnt_chunks(t) * sizeof(double) +
+size_t jnt_bytes_of(const AdjTapeDev& t, size_t n_joint, size_t n_block) {
+    return 5 * std::max<size_t>(n_joint * t.elem, 1) + 3 * std::max<size_t>(n_block * t.elem, 1) + jnt_chunks(n_joint) * sizeof(double) +
            sizeof(NrmCtl);
 }
 
-void adj_joint_prepare(AdjTapeDev& t) {
-    if (t.jnt_x) return;
+void jnt_prepare(AdjTapeDev& t, const JntWork& w) {
+    if (w.x) return;
     NRM_CHECK(hipSetDevice(t.device));
-    const size_t planned = adj_joint_bytes(t);
+    const size_t planned = jnt_bytes_of(t, w.n_joint, w.n_block);
     size_t got = 0;
     auto alloc = [&](void*& p, size_t bytes) {
         const size_t b = std::max<size_t>(bytes, 1);
@@ -492,68 +507,77 @@ void adj_joint_prepare(AdjTapeDev& t) {
             (void)hipGetLastError();
             p = nullptr;
             std::ostringstream m;
-            m << "the joint solver of the field tape needs " << planned << " bytes of device memory on device " << t.device
+            m << w.what << " of the field tape needs " << planned << " bytes of device memory on device " << t.device
               << " (an allocation of " << b << " bytes failed)";
             throw AdjDeviceError(m.str());
         }
         got += b;
     };
     try {
-        const size_t vec = t.n_joint() * t.elem, blk = 4 * t.n_points * t.elem;
-        alloc(t.jnt_x, vec);
-        alloc(t.jnt_r, vec);
-        alloc(t.jnt_p, vec);
-        alloc(t.jnt_q, vec);
-        alloc(t.jnt_hp, vec);
-        alloc(t.jnt_scale, blk);
-        alloc(t.jnt_damp, blk);
-        alloc(t.jnt_ve, blk);
-        alloc(t.jnt_partial, jnt_chunks(t) * sizeof(double));
-        alloc(t.jnt_ctl, sizeof(NrmCtl));
+        const size_t vec = w.n_joint * t.elem, blk = w.n_block * t.elem;
+        alloc(w.x, vec);
+        alloc(w.r, vec);
+        alloc(w.p, vec);
+        alloc(w.q, vec);
+        alloc(w.hp, vec);
+        alloc(w.scale, blk);
+        alloc(w.damp, blk);
+        alloc(w.ve, blk);
+        alloc(w.partial, jnt_chunks(w.n_joint) * sizeof(double));
+        alloc(w.ctl, sizeof(NrmCtl));
     } catch (...) {
-        jnt_free_all(t);
+        jnt_free_all(w);
         throw;
     }
-    t.jnt_bytes = got;
+    w.bytes = got;
     t.total_bytes += got;
 }
 
-void adj_joint_release(AdjTapeDev& t) {
-    if (!t.jnt_x) return;
+void jnt_release(AdjTapeDev& t, const JntWork& w) {
+    if (!w.x) return;
     (void)hipSetDevice(t.device);
     if (t.stream) (void)hipStreamSynchronize(t.stream);
-    jnt_free_all(t);
-    t.total_bytes -= t.jnt_bytes;
-    t.jnt_bytes = 0;
+    jnt_free_all(w);
+    t.total_bytes -= w.bytes;
+    w.bytes = 0;
 }
+}  // namespace
+
+size_t adj_joint_bytes(const AdjTapeDev& t) { return jnt_bytes_of(t, t.n_joint(), 4 * t.n_points); }
+void adj_joint_prepare(AdjTapeDev& t) { jnt_prepare(t, jnt_work(t, false)); }
+void adj_joint_release(AdjTapeDev& t) { jnt_release(t, jnt_work(t, false)); }
+size_t adj_rjoint_bytes(const AdjTapeDev& t) { return jnt_bytes_of(t, t.n_rjoint(), 4 * t.n_rcv_points); }
+void adj_rjoint_prepare(AdjTapeDev& t) { jnt_prepare(t, jnt_work(t, true)); }
+void adj_rjoint_release(AdjTapeDev& t) { jnt_release(t, jnt_work(t, true)); }
 
 template <typename T>
 void adj_solve_joint(AdjTapeDev& t, const T* d_rw, const NormalOperator& op, bool with_scale, bool with_damp, int maxiter, double rtol,
-                     int schedule, NormalResult& res) {
+                     int schedule, NormalResult& res, bool receiver) {
     NRM_CHECK(hipSetDevice(t.device));
-    adj_joint_prepare(t);
+    const JntWork wk = jnt_work(t, receiver);
+    jnt_prepare(t, wk);
     hipStream_t s = t.stream;
-    const size_t nm = t.n_model(), n = t.n_joint();
-    const unsigned chunks = (unsigned)jnt_chunks(t);
-    T* x = (T*)t.jnt_x;
-    T* r = (T*)t.jnt_r;
-    T* p = (T*)t.jnt_p;
-    T* q = (T*)t.jnt_q;
-    T* hp = (T*)t.jnt_hp;
-    const T* c = with_scale ? (const T*)t.jnt_scale : nullptr;
-    const T* delta = with_damp ? (const T*)t.jnt_damp : nullptr;
-    double* partial = (double*)t.jnt_partial;
-    NrmCtl* ctl = (NrmCtl*)t.jnt_ctl;
+    const size_t nm = t.n_model(), n = wk.n_joint;
+    const unsigned chunks = (unsigned)jnt_chunks(n);
+    T* x = (T*)wk.x;
+    T* r = (T*)wk.r;
+    T* p = (T*)wk.p;
+    T* q = (T*)wk.q;
+    T* hp = (T*)wk.hp;
+    const T* c = with_scale ? (const T*)wk.scale : nullptr;
+    const T* delta = with_damp ? (const T*)wk.damp : nullptr;
+    double* partial = (double*)wk.partial;
+    NrmCtl* ctl = (NrmCtl*)wk.ctl;
     res = NormalResult();
     NRM_CHECK(hipMemsetAsync(ctl, 0, sizeof(NrmCtl), s));
-    if (c) adj_src_scale<T>(t, c, r + nm, r + nm);   // the right-hand side of the scaled system: (b_s, fl(c * b_e))
+    if (c) adj_scale<T>(t, c, r + nm, r + nm, wk.n_block);   // the right-hand side of the scaled system: (b_s, fl(c * b_e))
     nrm_dot_kernel<T><<<chunks, NRM_THREADS, 0, s>>>(r, r, n, partial);
     NRM_CHECK(hipGetLastError());
-    jnt_close<T>(t, NRM_PLAIN);
+    jnt_close<T>(t, wk, NRM_PLAIN);
     if (n > 0) NRM_CHECK(hipMemsetAsync(x, 0, n * sizeof(T), s));
     nrm_start_kernel<T><<<chunks, NRM_THREADS, 0, s>>>(r, q, p, n, 0, partial);
     NRM_CHECK(hipGetLastError());
-    jnt_close<T>(t, NRM_RR0);
+    jnt_close<T>(t, wk, NRM_RR0);
     NrmCtl h;
     NRM_CHECK(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, s));
     NRM_CHECK(hipStreamSynchronize(s));
@@ -568,16 +592,17 @@ void adj_solve_joint(AdjTapeDev& t, const T* d_rw, const NormalOperator& op, boo
             break;
         }
         int pj = 0, pv = 0;
-        adj_gn_joint<T>(t, p, p + nm, c, (T*)t.jnt_ve, d_rw, hp, hp + nm, schedule, &pj, &pv);
+        if (receiver) adj_gn_rjoint<T>(t, p, p + nm, c, (T*)wk.ve, d_rw, hp, hp + nm, schedule, &pj, &pv);
+        else adj_gn_joint<T>(t, p, p + nm, c, (T*)wk.ve, d_rw, hp, hp + nm, schedule, &pj, &pv);
         jnt_combine_kernel<T><<<chunks, NRM_THREADS, 0, s>>>(hp, p, q, nm, n, nrm_smooth_args<T>(t, op.weights), (T)op.smooth, (T)op.damp,
                                                             op.smooth != 0.0, op.damp != 0.0, delta, partial);
         NRM_CHECK(hipGetLastError());
         res.passes.push_back(pj);
         res.passes.push_back(pv);
-        jnt_close<T>(t, NRM_PQ);
+        jnt_close<T>(t, wk, NRM_PQ);
         nrm_update_kernel<T><<<chunks, NRM_THREADS, 0, s>>>(x, r, p, q, n, ctl, partial);
         NRM_CHECK(hipGetLastError());
-        jnt_close<T>(t, NRM_RR);
+        jnt_close<T>(t, wk, NRM_RR);
         nrm_direction_kernel<T><<<(unsigned)std::max<size_t>(1, (n + NRM_THREADS - 1) / NRM_THREADS), NRM_THREADS, 0, s>>>(r, p, n, ctl);
         NRM_CHECK(hipGetLastError());
         NRM_CHECK(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, s));   // the one host read of the iteration: (rho, pq)
@@ -591,7 +616,7 @@ void adj_solve_joint(AdjTapeDev& t, const T* d_rw, const NormalOperator& op, boo
         res.rho.push_back(rho);
         ++res.iterations;
     }
-    if (c) adj_src_scale<T>(t, c, x + nm, x + nm);   // x_e = fl(c * z_e)
+    if (c) adj_scale<T>(t, c, x + nm, x + nm, wk.n_block);   // x_e = fl(c * z_e)
 }
 
 template void adj_smooth<float>(AdjTapeDev&, const float*, const double*, float*);
@@ -600,7 +625,7 @@ template double adj_dot<float>(AdjTapeDev&, const float*, const float*);
 template double adj_dot<double>(AdjTapeDev&, const double*, const double*);
 template void adj_solve_normal<float>(AdjTapeDev&, const float*, const NormalOperator&, bool, int, double, int, NormalResult&);
 template void adj_solve_normal<double>(AdjTapeDev&, const double*, const NormalOperator&, bool, int, double, int, NormalResult&);
-template void adj_solve_joint<float>(AdjTapeDev&, const float*, const NormalOperator&, bool, bool, int, double, int, NormalResult&);
-template void adj_solve_joint<double>(AdjTapeDev&, const double*, const NormalOperator&, bool, bool, int, double, int, NormalResult&);
+template void adj_solve_joint<float>(AdjTapeDev&, const float*, const NormalOperator&, bool, bool, int, double, int, NormalResult&, bool);
+template void adj_solve_joint<double>(AdjTapeDev&, const double*, const NormalOperator&, bool, bool, int, double, int, NormalResult&, bool);
 
 }  // namespace ttcr_amd

@@ -119,6 +119,22 @@ def joint_gauss_newton_step(tape, residual, model, row_weight=None, smooth=0., d
                             **solve_args)
 
 
+def reciprocal_gauss_newton_step(tape, residual, model, row_weight=None, smooth=0., damp=0., rcv_damp=0., rcv_scale=None, **solve_args):
+    """The update (x, x_rcv) of slowness and receiver points of one regularised joint Gauss-Newton step on a field tape in the
+    reciprocal layout -- solved from the stations, the hypocentres being the receiver points of the call
+    (tape.set_receiver_points) --: the right-hand sides
+        b, b_rcv = tape.vjp(row_weight * residual, return_receiver_grad=True);   b -= smooth * tape.smooth(model)
+    and then tape.solve_receiver_joint(b, b_rcv, row_weight=row_weight, smooth=smooth, damp=damp, rcv_damp=rcv_damp,
+    rcv_scale=rcv_scale, **solve_args), whose result is returned as it is (b_rcv goes in unscaled: the solver scales it).
+    Arguments as joint_gauss_newton_step.  Host glue only."""
+    w = residual if row_weight is None else row_weight * residual
+    b, b_rcv = tape.vjp(w, return_receiver_grad=True)
+    if smooth != 0:
+        b = b - smooth * tape.smooth(model, solve_args.get('smooth_weights', (1., 1., 1.)))
+    return tape.solve_receiver_joint(b, b_rcv, row_weight=row_weight, smooth=smooth, damp=damp, rcv_damp=rcv_damp, rcv_scale=rcv_scale,
+                                     **solve_args)
+
+
 def straight_ray_kernel(Tx, Rx, axes, aniso=False):
     """L (nrays x ncells) with L @ slowness = traveltimes along the straight segments Tx[n] -> Rx[n] through the cells of the grid `axes`
     (node coordinates per dimension, any spacing).  Cells in C order ((ix * ncy + iy) * ncz + iz).  aniso (2-D only): L is nrays x 2 ncells,

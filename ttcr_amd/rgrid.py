@@ -561,6 +561,12 @@ class FieldTape:
     to the source points, parameters (t0, x, y, z) each: jvp_source, source_jacobian and vjp(..., return_source_grad=True); n_points
     points in call order, point_event their events.  Both halves together, for joint hypocentre-velocity inversion: jvp_joint (one
     relaxation for a slowness step and a source step), gauss_newton_joint and solve_joint (the regularised joint normal equations).
+    And with respect to the RECEIVER points, for the reciprocal layout (solved from the stations, the hypocentres being the receivers of
+    the call): receiver_eval (traveltime and gradient at arbitrary points of the tape's fields, no solve), receiver_jacobian,
+    jvp_receiver and vjp(..., return_receiver_grad=True); n_rcv_points receiver points with parameters (t0, x, y, z) each,
+    rcv_point_of_row their rows (set_receiver_points groups the rows of one hypocentre; the default is one point per row);
+    jvp_joint_receiver, gauss_newton_receiver_joint and solve_receiver_joint are the joint calls with the receiver block in the place
+    of the source block, release_receiver frees what these calls hold on the device.
     wrt is 'nodes' or 'cells': what the model vector of vjp / jvp / gauss_newton holds, n_cols values -- the node slowness (n_cols =
     n_nodes) or, for the tape of raytrace_adjoint(..., wrt='cells'), the cell slowness in set_slowness's flat order (n_cols = cells).
     Fields, field cotangents and field tangents hold n_nodes values per event on either tape."""
@@ -593,6 +599,7 @@ class FieldTape:
         ev = (C.c_int * max(self.n_points, 1))()
         _lib.check(lib.ttcr_fsm_adjoint_points(handle, C.byref(npt), ev))
         self.point_event = np.array(ev[:self.n_points], dtype=np.int64)   # event of every point
+        self._refresh_receiver_points()
 
     def _handle(self):
         if not self._h:
@@ -757,11 +764,13 @@ class FieldTape:
         fa, pf, df = self._fields_arg(field_cotangent) if field_cotangent is not None else (None, None, 0)
         return (wa, fa), pw, dw, pf, df
 
-    def vjp(self, w=None, field_cotangent=None, schedule='tiled', return_source_grad=False):
+    def vjp(self, w=None, field_cotangent=None, schedule='tiled', return_source_grad=False, return_receiver_grad=False):
         """d loss / d slowness (n_cols values -- nodes, or cells on a cell tape --, x fastest, grid dtype) for  loss = w . tt +
         field_cotangent . fields.
         return_source_grad=True: (grad, gsrc) with gsrc (n_points, 4) = d loss / d (t0, x, y, z) of every source point, from the same
         relaxation (a point whose frozen nodes a later point of its event all overwrote gets zeros).
+        return_receiver_grad=True: the receiver gradient grcv (n_rcv_points, 4) = d loss / d (t0, x, y, z) of every receiver point is
+        appended to what is returned otherwise ((grad, grcv), or (grad, gsrc, grcv)); it depends on w only (zeros for w=None).
         w: one value per data row of the raytrace_adjoint call (rcv order); field_cotangent: (n_events, n_nodes) values, node order x
         fastest; either may be None, not both.  schedule: 'tiled' (default) or 'jacobi', the bit-equal baseline.  Torch tensors in give
         a torch tensor out, where the first of them lives; tensors on the tape's device are used in place (torch's current stream is
@@ -783,7 +792,15 @@ class FieldTape:
             _lib.check(self._lib.ttcr_fsm_adjoint_vjp(self._h, pw, dw, pf, df, pg, dg, sch, C.byref(np_)))
         self.passes = np_.value
         self._refresh_nbytes()
-        return (fin_g(), fin_s()) if return_source_grad else fin_g()
+        out = (fin_g(), fin_s()) if return_source_grad else fin_g()
+        if not return_receiver_grad:
+            return out
+        if w is not None:
+            grcv = self._vjp_receiver(w, like)
+        else:
+            grcv = self._out(like, self.n_rcv_points, 4)[2]()
+            grcv[...] = 0
+        return out + (grcv,) if return_source_grad else (out, grcv)
 
     def jvp(self, ds, return_fields=False, schedule='tiled'):
         """J ds: the change of the receiver traveltimes for the slowness perturbation ds (n_cols values -- nodes, or cells on a cell
@@ -1066,29 +1083,32 @@ class FieldTape:
         self._refresh_nbytes()
 
     # ---- joint hypocentre-velocity system
-    def _source_arg(self, a, name):
-        """a source block, (n_points, 4) values (t0, x, y, z) per point in call order: (array, pointer, on_device)"""
+    def _source_arg(self, a, name, n_points=None, what='source'):
+        """a source block, (n_points, 4) values (t0, x, y, z) per point in call order: (array, pointer, on_device).  n_points, what: the
+        receiver block of the receiver joint system instead"""
+        n = self.n_points if n_points is None else n_points
         a = self._seen(a)
-        if tuple(a.shape) != (self.n_points, 4):
-            raise ValueError('%s should be (%d, 4), one row (t0, x, y, z) per source point, got shape %s'
-                             % (name, self.n_points, tuple(a.shape)))
+        if tuple(a.shape) != (n, 4):
+            raise ValueError('%s should be (%d, 4), one row (t0, x, y, z) per %s point, got shape %s'
+                             % (name, n, what, tuple(a.shape)))
         return self._arg(a)
 
-    def _source_setting(self, v, name, allow_none):
+    def _source_setting(self, v, name, allow_none, n_points=None):
         """source_scale / source_damp, (4,) or (n_points, 4) values (source_damp: or a scalar), broadcast to (n_points, 4) doubles for
-        the C entry; None stays None"""
+        the C entry; None stays None.  n_points: the receiver points' rcv_scale / rcv_damp instead"""
+        n = self.n_points if n_points is None else n_points
         if v is None and allow_none:
             return None
         try:
             a = np.asarray(v.detach().cpu().numpy() if hasattr(v, 'detach') else v, dtype=np.float64)
         except (TypeError, ValueError):
             raise ValueError('%s should be numbers, got %r' % (name, v))
-        if a.shape not in ((4,), (self.n_points, 4)) + (() if allow_none else ((),)):
+        if a.shape not in ((4,), (n, 4)) + (() if allow_none else ((),)):
             raise ValueError('%s should be %s(4,) or (%d, 4) values, got shape %s'
-                             % (name, '' if allow_none else 'a scalar, ', self.n_points, a.shape))
+                             % (name, '' if allow_none else 'a scalar, ', n, a.shape))
         if not np.all(np.isfinite(a)) or np.any(a < 0):
             raise ValueError('%s should be finite and >= 0, got %r' % (name, v))
-        a = np.ascontiguousarray(np.broadcast_to(a, (self.n_points, 4)))
+        a = np.ascontiguousarray(np.broadcast_to(a, (n, 4)))
         return (C.c_double * max(a.size, 1))(*a.ravel())
 
     def jvp_joint(self, ds, dsrc, return_fields=False, schedule='tiled'):
@@ -1192,6 +1212,205 @@ class FieldTape:
         """Free the work arrays of solve_joint (nbytes falls by what the first call added); the next call allocates them again.  The
         arrays of solve_normal, a held cotangent and the block arrays are not touched."""
         _lib.check(self._lib.ttcr_fsm_joint_release(self._handle()))
+        self._refresh_nbytes()
+
+    # ---- receiver points and the receiver joint system (DESIGN.md 6k)
+    def _refresh_receiver_points(self):
+        n = C.c_size_t(0)
+        m = (C.c_int * max(self.n_rows, 1))()
+        _lib.check(self._lib.ttcr_fsm_rcv_points(self._h, None, 0, C.byref(n), m, None))
+        self.n_rcv_points = n.value            # receiver points, parameters (t0, x, y, z) each
+        por = np.full(self.n_data, -1, dtype=np.int64)
+        por[self._rows] = np.array(m[:self.n_rows], dtype=np.int64)
+        self.rcv_point_of_row = por            # receiver point of every data row (rcv order; -1: the row is not on the tape)
+
+    def set_receiver_points(self, point_of_row, n_points=None):
+        """Group the data rows into receiver points: point_of_row holds, per data row in the order of rcv (like w), the index of the
+        receiver point the row belongs to; n_points (default: the largest index + 1) may name more points than have rows -- such a
+        point gets zero gradients.  Rows that share a point must have bit-equal receiver coordinates (ValueError naming the first
+        offending pair of data rows otherwise): in a reciprocal layout, the rows of one hypocentre seen from every station.  The
+        default of a new tape is one point per row.  Frees what earlier receiver calls hold on the device (as release_receiver)."""
+        self._handle()
+        try:
+            a = np.asarray(point_of_row.detach().cpu().numpy() if hasattr(point_of_row, 'detach') else point_of_row)
+        except (TypeError, ValueError):
+            raise ValueError('point_of_row should be integers, got %r' % (point_of_row,))
+        if a.shape != (self.n_data,) or a.dtype.kind not in 'iu':
+            raise ValueError('point_of_row should hold %d integers (one per data row), got shape %s and dtype %s'
+                             % (self.n_data, a.shape, a.dtype))
+        on_tape = a[self._rows].astype(np.int64)
+        top = int(on_tape.max()) + 1 if on_tape.size else 0
+        if n_points is None:
+            n_points = top
+        if not isinstance(n_points, (int, np.integer)) or n_points < top or n_points >= 2 ** 29:
+            raise ValueError('n_points should be an integer >= %d (the largest point index + 1), got %r' % (top, n_points))
+        if on_tape.size and on_tape.min() < 0:
+            raise ValueError('point_of_row should be >= 0, got %d' % on_tape.min())
+        m = (C.c_int * max(self.n_rows, 1))(*on_tape.tolist())
+        pair = (C.c_int * 2)(-1, -1)
+        st = self._lib.ttcr_fsm_rcv_points(self._h, m, int(n_points), None, None, pair)
+        if st != 0 and pair[0] >= 0:   # (the C entry counts tape rows; say it in data rows)
+            raise ValueError('point_of_row: data rows %d and %d share a receiver point but their receiver coordinates differ'
+                             % (self._rows[pair[0]], self._rows[pair[1]]))
+        _lib.check(st)
+        self._refresh_receiver_points()
+        self._refresh_nbytes()
+
+    def receiver_eval(self, pts, event_of_pt, return_grad=True):
+        """The traveltime of event event_of_pt[i] at the point pts[i] and its derivative with respect to the point, for n arbitrary points
+        inside the grid (pts (n, 3), user coordinates; event_of_pt n integers) -- read from the tape's fields, no solve and no
+        relaxation: what a relocation loop on a fixed model calls between solves.  tt has the bits the grid's own interpolation gives on
+        that field; grad (n, 3) is the derivative of that interpolation as it is evaluated, with the cell and the on-plane flags held
+        fixed (zero along an axis on whose grid plane the point lies).  Returns (tt, grad), or tt with return_grad=False.  Array
+        handling as in jvp."""
+        self._handle()
+        pa = self._seen(pts)
+        if len(pa.shape) != 2 or pa.shape[1] != 3:
+            raise ValueError('pts should be (n, 3), got shape %s' % (tuple(pa.shape),))
+        n = int(pa.shape[0])
+        try:
+            ev = np.asarray(event_of_pt.detach().cpu().numpy() if hasattr(event_of_pt, 'detach') else event_of_pt)
+        except (TypeError, ValueError):
+            raise ValueError('event_of_pt should be integers, got %r' % (event_of_pt,))
+        if ev.shape != (n,) or (n > 0 and ev.dtype.kind not in 'iu'):
+            raise ValueError('event_of_pt should hold %d integers (one per point), got shape %s and dtype %s' % (n, ev.shape, ev.dtype))
+        if n > 0 and (ev.min() < 0 or ev.max() >= self.n_events):
+            raise ValueError('event_of_pt should be in 0 .. %d, got %d .. %d' % (self.n_events - 1, ev.min(), ev.max()))
+        ev = np.ascontiguousarray(ev, dtype=np.int32)
+        a, pp, dp = self._arg(pa)
+        pt, dt, fin_t = self._out(pts, 1, n)
+        pg, dg, fin_g = self._out(pts, n, 3) if return_grad else (None, 0, None)
+        self._sync(dp, dt, dg)
+        if n > 0:
+            _lib.check(self._lib.ttcr_fsm_rcv_eval(self._h, n, pp, dp, ev.ctypes.data_as(C.POINTER(C.c_int)), pt, dt, pg, dg))
+        self._refresh_nbytes()
+        return (fin_t()[0], fin_g()) if return_grad else fin_t()[0]
+
+    def receiver_jacobian(self):
+        """(n_data, 3): d tt[row] / d (x, y, z) of the row's receiver, rows in rcv order (zeros for a row that is not on the tape), a
+        numpy array: receiver_eval's gradient at the tape's own receivers, computed once and kept on the tape."""
+        self._handle()
+        pg, dg, fin = self._out(None, self.n_rows, 3)
+        if self.n_rows > 0:
+            _lib.check(self._lib.ttcr_fsm_rcv_eval(self._h, 0, None, 0, None, None, 0, pg, dg))
+        self._refresh_nbytes()
+        G = np.zeros((self.n_data, 3), dtype=self.dtype)
+        G[self._rows] = fin()
+        return G
+
+    def jvp_receiver(self, drcv):
+        """J_rcv drcv: the change of the receiver traveltimes for a perturbation of the receiver points, drcv (n_rcv_points, 4) holding
+        (dt0, dx, dy, dz) of every point: dtt[row] = dt0 + G[row] . (dx, dy, dz) of the row's point, G = receiver_jacobian().  Returns dtt
+        in rcv order.  No relaxation.  Array handling as in jvp."""
+        self._handle()
+        a, pa, da = self._source_arg(drcv, 'drcv', self.n_rcv_points, 'receiver')
+        pr, dr, fin_r = self._out(drcv, 1, self.n_rows, rows=True)
+        self._sync(da, dr)
+        if self.n_rows > 0:
+            _lib.check(self._lib.ttcr_fsm_rcv_jvp(self._h, pa, da, pr, dr))
+        self._refresh_nbytes()
+        return fin_r()[0]
+
+    def _vjp_receiver(self, w, like):
+        wa, pw, dw = self._row_arg(w, 'w')
+        pg, dg, fin = self._out(like, self.n_rcv_points, 4)
+        self._sync(dw, dg)
+        _lib.check(self._lib.ttcr_fsm_rcv_vjp(self._h, pw, dw, pg, dg))
+        self._refresh_nbytes()
+        return fin()
+
+    def jvp_joint_receiver(self, ds, drcv, return_fields=False, schedule='tiled'):
+        """J_s ds + J_rcv drcv: jvp(ds) with the rows of jvp_receiver(drcv) added, dtt[row] = fl(jvp + jvp_receiver); one tangent
+        relaxation.  Returns dtt in rcv order; with return_fields=True (dtt, dfields), dfields being jvp's (a receiver step moves no
+        field).  Array handling and schedule as in jvp; the result lives where the first torch tensor of (ds, drcv) does."""
+        self._handle()
+        sch = self._schedule(schedule)
+        a, pa, da = self._model_arg(ds, 'ds')
+        b, pb, db = self._source_arg(drcv, 'drcv', self.n_rcv_points, 'receiver')
+        like = self._first_tensor(ds, drcv)
+        pr, dr, fin_r = self._out(like, 1, self.n_rows, rows=True)
+        pf, df, fin_f = self._out(like, self.n_events, self.n_nodes) if return_fields else (None, 0, None)
+        self._sync(da, db, dr, df)
+        np_ = C.c_int(0)
+        want_r, want_f = self.n_rows > 0, return_fields and self.n_events * self.n_nodes > 0
+        if want_r or want_f:
+            _lib.check(self._lib.ttcr_fsm_rjoint_jvp(self._h, pa, da, pb, db, pr if want_r else None, dr, pf if want_f else None, df, sch,
+                                                     C.byref(np_)))
+        self.passes = np_.value
+        self._refresh_nbytes()
+        dtt = fin_r()[0]
+        return (dtt, fin_f()) if return_fields else dtt
+
+    def gauss_newton_receiver_joint(self, v, v_rcv, row_weight=None, rcv_scale=None, schedule='tiled'):
+        """The receiver joint Gauss-Newton product (g, g_rcv) = [J_s  J_rcv C]^T (row_weight * ([J_s  J_rcv C] (v, v_rcv))), C =
+        diag(rcv_scale): one tangent relaxation, one adjoint relaxation and the row kernels.  v: n_cols values; v_rcv: (n_rcv_points, 4);
+        rcv_scale as gauss_newton_joint's source_scale, over the receiver points.  g has the bits of vjp's gradient, g_rcv = rcv_scale *
+        the receiver gradient.  passes becomes (passes of the jvp, passes of the vjp)."""
+        self._handle()
+        sch = self._schedule(schedule)
+        va, pv, dv = self._model_arg(v, 'v')
+        ea, pe, de = self._source_arg(v_rcv, 'v_rcv', self.n_rcv_points, 'receiver')
+        ra, pr, dr = self._row_arg(row_weight, 'row_weight') if row_weight is not None else (None, None, 0)
+        sc = self._source_setting(rcv_scale, 'rcv_scale', True, self.n_rcv_points)
+        like = self._first_tensor(v, v_rcv, row_weight)
+        pg, dg, fin_g = self._model_out(like)
+        ps, dsr, fin_s = self._out(like, self.n_rcv_points, 4)
+        self._sync(dv, de, dr, dg, dsr)
+        pj, pa = C.c_int(0), C.c_int(0)
+        _lib.check(self._lib.ttcr_fsm_rjoint_gn(self._h, pv, dv, pe, de, pr, dr, sc, pg, dg, ps, dsr, sch, C.byref(pj), C.byref(pa)))
+        self.passes = (pj.value, pa.value)
+        self._refresh_nbytes()
+        return fin_g(), fin_s()
+
+    def solve_receiver_joint(self, rhs, rhs_rcv, row_weight=None, smooth=0.0, smooth_weights=(1., 1., 1.), damp=0.0, rcv_damp=0.0,
+                             rcv_scale=None, maxiter=20, rtol=1e-6, schedule='tiled', return_info=False, hessian='gauss_newton'):
+        """The update (x, x_rcv) of slowness and receiver points of one regularised joint Gauss-Newton step -- solve_joint's system,
+        solver and info dict with the receiver block (n_rcv_points, 4) in the place of the source block: rcv_scale scales its columns,
+        rcv_damp acts on the scaled unknown, rhs_rcv goes in unscaled as vjp(..., return_receiver_grad=True) returns it.  With the
+        hypocentres as receivers of solves from the stations (reciprocity) this is the joint hypocentre-velocity step whose solves and
+        fields grow with the stations, not the events.  With rcv_scale all zeros x_rcv is zero and x is solve_normal's.  No x0; hessian
+        other than 'gauss_newton' raises.  The first call allocates work arrays of its own (nbytes; release_receiver returns them)."""
+        self._handle()
+        sch = self._schedule(schedule)
+        for name, val in (('smooth', smooth), ('damp', damp), ('rtol', rtol)):
+            if not (isinstance(val, (int, float, np.floating, np.integer)) and math.isfinite(val) and val >= 0):
+                raise ValueError('%s should be a finite number >= 0, got %r' % (name, val))
+        if not isinstance(maxiter, (int, np.integer)) or maxiter < 1:
+            raise ValueError('maxiter should be a positive integer, got %r' % (maxiter,))
+        if hessian != 'gauss_newton':
+            raise ValueError("hessian: the receiver joint system offers 'gauss_newton' only, got %r" % (hessian,))
+        w = self._weights(smooth_weights, 'smooth_weights')
+        ba, pb, db = self._model_arg(rhs, 'rhs')
+        ea, pe, de = self._source_arg(rhs_rcv, 'rhs_rcv', self.n_rcv_points, 'receiver')
+        ra, pr, dr = self._row_arg(row_weight, 'row_weight') if row_weight is not None else (None, None, 0)
+        sd = self._source_setting(rcv_damp, 'rcv_damp', False, self.n_rcv_points)
+        sc = self._source_setting(rcv_scale, 'rcv_scale', True, self.n_rcv_points)
+        like = self._first_tensor(rhs, rhs_rcv, row_weight)
+        px, dx, fin_x = self._model_out(like)
+        ps, dxs, fin_s = self._out(like, self.n_rcv_points, 4)
+        self._sync(db, de, dr, dx, dxs)
+        maxiter = int(maxiter)
+        status, iters = C.c_int(0), C.c_int(0)
+        rho, pq, passes = (C.c_double * (maxiter + 2))(), (C.c_double * maxiter)(), (C.c_int * (2 * maxiter))()
+        _lib.check(self._lib.ttcr_fsm_rjoint_solve(self._h, pb, db, pe, de, pr, dr, float(smooth), w, float(damp), sd, sc, maxiter,
+                                                   float(rtol), sch, px, dx, ps, dxs, C.byref(status), C.byref(iters), rho, pq, passes))
+        self._refresh_nbytes()
+        x, xs = fin_x(), fin_s()
+        k = iters.value
+        n_pq = k + (1 if status.value == 2 else 0)
+        pairs = [(passes[2 * i], passes[2 * i + 1]) for i in range(n_pq)]
+        if pairs:
+            self.passes = pairs[-1]    # (of the last product)
+        if not return_info:
+            return x, xs
+        return x, xs, {'status': status.value, 'iterations': k, 'rho': list(rho[:k + 2]), 'pq': list(pq[:n_pq]), 'passes': pairs,
+                       'passes_x0': None}
+
+    def release_receiver(self):
+        """Free what the receiver calls hold on the device -- the receivers, the point map, G of the rows, the staging arrays and the work
+        arrays of solve_receiver_joint (nbytes falls by what they added); the next receiver call uploads them again.  The receiver
+        points stay as set.  Nothing of the other calls is touched."""
+        _lib.check(self._lib.ttcr_fsm_rcv_release(self._handle()))
         self._refresh_nbytes()
 
     def _refresh_nbytes(self):
