@@ -1284,20 +1284,13 @@ void AdjTapeDev::release() {
     dev_free(src_off); dev_free(src_pt); dev_free(src_key); dev_free(src_node); dev_free(src_c); dev_free(src_io); dev_free(src_rows);
     dev_free(mu4); dev_free(mu4b); dev_free(cell_tmp); dev_free(hold_lam); dev_free(hess_dd);
     dev_free(g4); dev_free(blk_model); dev_free(blk_nodes); dev_free(blk_rows); dev_free(blk_rw);
-    dev_free(nrm_x); dev_free(nrm_r); dev_free(nrm_p); dev_free(nrm_q); dev_free(nrm_hp); dev_free(nrm_partial); dev_free(nrm_ctl);
-    dev_free(jnt_x); dev_free(jnt_r); dev_free(jnt_p); dev_free(jnt_q); dev_free(jnt_hp); dev_free(jnt_scale); dev_free(jnt_damp);
-    dev_free(jnt_ve); dev_free(jnt_partial); dev_free(jnt_ctl);
-    jnt_bytes = 0;
+    for (CgSystem sys : {CG_MODEL, CG_SOURCE, CG_RECEIVER}) adj_cg_release(*this, sys);
     dev_free(rcv_p); dev_free(rcv_event); dev_free(rcv_pt); dev_free(rcv_rows); dev_free(rcv_off); dev_free(rcv_G); dev_free(rcv_tt);
     dev_free(rcv_io); dev_free(rcv_stage);
     rcv_stage_bytes = 0;
-    dev_free(rj_x); dev_free(rj_r); dev_free(rj_p); dev_free(rj_q); dev_free(rj_hp); dev_free(rj_scale); dev_free(rj_damp);
-    dev_free(rj_ve); dev_free(rj_partial); dev_free(rj_ctl);
     rcv_bytes = 0;
-    rj_bytes = 0;
     blk_owns_mu4 = false;
     blk_bytes = 0;
-    nrm_bytes = 0;
     held = false;
     if (stream) (void)hipStreamDestroy(stream);
     stream = nullptr;
@@ -1846,13 +1839,6 @@ int adj_vjp_source(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, T* d_g
 
 // ---- joint hypocentre-velocity products
 template <typename T>
-void adj_src_scale(AdjTapeDev& t, const T* d_c, const T* d_in, T* d_out) {
-    if (t.n_points == 0) return;
-    joint_scale_kernel<T><<<blocks_for(4 * t.n_points), ADJ_THREADS, 0, t.stream>>>(d_c, d_in, d_out, 4 * t.n_points);
-    ADJ_CHECK(hipGetLastError());
-}
-
-template <typename T>
 int adj_jvp_joint(AdjTapeDev& t, const T* d_ds, const T* d_dsrc, T* d_dtt, T* d_dfields, int schedule, const T** mu_out) {
     ADJ_CHECK(hipSetDevice(t.device));
     adj_jvp_prepare<T>(t);
@@ -1909,7 +1895,7 @@ void adj_gn_joint(AdjTapeDev& t, const T* d_vs, const T* d_ve, const T* d_scale,
     ADJ_CHECK(hipSetDevice(t.device));
     adj_src_prepare<T>(t);
     if (d_scale) {
-        adj_src_scale<T>(t, d_scale, d_ve, d_ve_scaled);
+        adj_scale<T>(t, d_scale, d_ve, d_ve_scaled, 4 * t.n_points);
         d_ve = d_ve_scaled;
     }
     T* w = (T*)t.w_tmp;
@@ -1919,7 +1905,7 @@ void adj_gn_joint(AdjTapeDev& t, const T* d_vs, const T* d_ve, const T* d_scale,
         ADJ_CHECK(hipGetLastError());
     }
     *passes_vjp = adj_vjp_source<T>(t, w, nullptr, d_gs, d_ge, schedule);
-    if (d_scale) adj_src_scale<T>(t, d_scale, d_ge, d_ge);
+    if (d_scale) adj_scale<T>(t, d_scale, d_ge, d_ge, 4 * t.n_points);
 }
 
 // ---- derivatives with respect to the receiver points
@@ -2001,7 +1987,7 @@ void* adj_rcv_stage(AdjTapeDev& t, size_t bytes) {
 }
 
 void adj_rcv_release(AdjTapeDev& t) {
-    adj_rjoint_release(t);
+    adj_cg_release(t, CG_RECEIVER);
     if (!t.rcv_p && !t.rcv_stage) return;
     (void)hipSetDevice(t.device);
     if (t.stream) (void)hipStreamSynchronize(t.stream);
@@ -2258,8 +2244,6 @@ template int adj_jvp_source<double>(AdjTapeDev&, const double*, int, double*, do
 template int adj_vjp_source<float>(AdjTapeDev&, const float*, const float*, float*, float*, int);
 template int adj_vjp_source<double>(AdjTapeDev&, const double*, const double*, double*, double*, int);
 
-template void adj_src_scale<float>(AdjTapeDev&, const float*, const float*, float*);
-template void adj_src_scale<double>(AdjTapeDev&, const double*, const double*, double*);
 template int adj_jvp_joint<float>(AdjTapeDev&, const float*, const float*, float*, float*, int, const float**);
 template int adj_jvp_joint<double>(AdjTapeDev&, const double*, const double*, double*, double*, int, const double**);
 template void adj_gn_joint<float>(AdjTapeDev&, const float*, const float*, const float*, float*, const float*, float*, float*, int, int*, int*);

@@ -15,7 +15,8 @@
 //                   K-column relaxations (tiled; what a step needs of the field is read and formed once per node), K-column gradient.
 // Normal equations (fsm_normal.hip): the smoothing operator on the model vector (a tile with a two-node halo in LDS), inner
 //                   products summed in a fixed order (chunks of 1024, one finishing workgroup), and conjugate gradients around the
-//                   Gauss-Newton / Newton product with the scalars of the recurrence formed on the device.
+//                   Gauss-Newton / Newton product with the scalars of the recurrence formed on the device.  One solver (adj_solve) over
+//                   three systems (CgSystem): the model vector alone, or with the source block (6j) or the receiver block (6k) behind it.
 // No floating-point atomics anywhere: every value is one fixed expression of final values, so the bits do not depend on the schedule.
 // Cell tapes (ttcr_fsm_raytrace_multi_adjoint_cells): the model vector holds one slowness per cell and the node slowness is
 // A times it (fsm_cells_to_nodes3d); a jvp first applies A to ds, a vjp ends with A^T on the node gradient (one thread per cell).
@@ -57,6 +58,24 @@ struct AdjSink {
     // translated grid; T values held exactly, 3 per row), the origin the solver interpolates with and the shift of a translated grid
     std::vector<double> st_p;
     double rcv_min[3] = {0, 0, 0}, rcv_shift[3] = {0, 0, 0};
+};
+
+// The systems the conjugate-gradient solver of fsm_normal.hip runs on: the model vector alone, the model vector followed by
+// the source block (the joint hypocentre-velocity system, 6j), or followed by the receiver block (the receiver joint system, 6k).
+enum CgSystem { CG_MODEL = 0, CG_SOURCE = 1, CG_RECEIVER = 2 };
+// the work arrays of the solver for one system, all on the tape's device; n = cg_len(system), b = cg_block(system)
+struct CgWork {
+    void* x = nullptr;        // n each: the iterate (a host x0 and the host result are staged here; its block in the scaled unknown z_e), ...
+    void* r = nullptr;        // ... the residual (the rhs goes here; model system: a host operand of dot, a host v of smooth), ...
+    void* p = nullptr;        // ... the search direction (model system: the second host operand of dot), ...
+    void* q = nullptr;        // ... A p (model system: a host result of smooth is staged here) ...
+    void* hp = nullptr;       // ... and the output of the tape's product
+    void* scale = nullptr;    // b each, only for a system with a block: the column scaling c, the damping delta of the block, ...
+    void* damp = nullptr;
+    void* ve = nullptr;       // ... and fl(c * p_e) of the running product
+    void* partial = nullptr;  // one double per chunk of 1024 elements
+    void* ctl = nullptr;      // the scalars of the recurrence
+    size_t bytes = 0;         // what these arrays added to total_bytes
 };
 
 struct AdjTapeDev {
@@ -125,29 +144,13 @@ struct AdjTapeDev {
     void* blk_rw = nullptr;           // 4 n_rows: a group of host row_weight columns
     bool blk_owns_mu4 = false;        // mu4 came with the block arrays (no jvp_source had allocated it) and leaves with them
     size_t blk_bytes = 0;             // what the block arrays added to total_bytes
-    // normal-equation solver: allocated by the first smooth / dot / solve, returned by adj_normal_release
-    void* nrm_x = nullptr;            // n_model() each: the iterate (a host x0 and the host result are staged here), ...
-    void* nrm_r = nullptr;            // ... the residual (a host rhs is staged here; a host operand of dot, a host v of smooth), ...
-    void* nrm_p = nullptr;            // ... the search direction (the second host operand of dot), ...
-    void* nrm_q = nullptr;            // ... A p (a host result of smooth is staged here) ...
-    void* nrm_hp = nullptr;           // ... and the output of the tape's product
-    void* nrm_partial = nullptr;      // one double per chunk of 1024 parameters
-    void* nrm_ctl = nullptr;          // the scalars of the recurrence
-    size_t nrm_bytes = 0;             // what these arrays added to total_bytes
-    // joint hypocentre-velocity solver: allocated by the first joint solve, returned by adj_joint_release.  A joint vector
-    // holds n_joint() values: the model vector, then (t0, x, y, z) of every source point in call order
-    size_t n_joint() const { return n_model() + 4 * n_points; }
-    void* jnt_x = nullptr;            // n_joint() each: the iterate (its source block in the scaled unknown z_e), the residual, ...
-    void* jnt_r = nullptr;
-    void* jnt_p = nullptr;            // ... the search direction, A p ...
-    void* jnt_q = nullptr;
-    void* jnt_hp = nullptr;           // ... and the output of the joint product
-    void* jnt_scale = nullptr;        // 4 n_points each: the column scaling c, the damping delta of the source block, ...
-    void* jnt_damp = nullptr;
-    void* jnt_ve = nullptr;           // ... and fl(c * p_e) of the running product
-    void* jnt_partial = nullptr;      // one double per chunk of 1024 joint elements
-    void* jnt_ctl = nullptr;          // the scalars of the recurrence
-    size_t jnt_bytes = 0;             // what these arrays added to total_bytes
+    // the conjugate-gradient solver: one set of work arrays per system, allocated by the first call that needs it
+    // (smooth, dot or solve for the model system; the first solve for the other two) and returned by adj_cg_release
+    CgWork cg[3];                     // by CgSystem
+    // elements of a system's extra block, (t0, x, y, z) of every source point in call order or of every receiver point, and of its vector:
+    // the model vector, then the block
+    size_t cg_block(CgSystem s) const { return s == CG_MODEL ? 0 : 4 * (s == CG_SOURCE ? n_points : n_rcv_points); }
+    size_t cg_len(CgSystem s) const { return n_model() + cg_block(s); }
     // receiver points.  Host lists, kept from adj_finish on: the receiver of every row as the solver sees it, the point of
     // every row (default: one point per row) and the rows of every point (CSR, rows ascending within a point).  The first receiver call
     // uploads them, evaluates G of the tape's rows and allocates the staging arrays; adj_rcv_release returns all of it
@@ -170,20 +173,6 @@ struct AdjTapeDev {
     size_t rcv_bytes = 0;             // what these arrays added to total_bytes
     void* rcv_stage = nullptr;        // staging of rcv_eval at arbitrary points: grow-only, returned by adj_rcv_release
     size_t rcv_stage_bytes = 0;
-    // receiver joint solver: the arrays of the joint solver above for joint vectors of n_rjoint() values, the model vector,
-    // then (t0, x, y, z) of every receiver point; allocated by the first receiver joint solve, returned by adj_rcv_release
-    size_t n_rjoint() const { return n_model() + 4 * n_rcv_points; }
-    void* rj_x = nullptr;
-    void* rj_r = nullptr;
-    void* rj_p = nullptr;
-    void* rj_q = nullptr;
-    void* rj_hp = nullptr;
-    void* rj_scale = nullptr;
-    void* rj_damp = nullptr;
-    void* rj_ve = nullptr;
-    void* rj_partial = nullptr;
-    void* rj_ctl = nullptr;
-    size_t rj_bytes = 0;
     size_t n_tiles = 0;
     size_t total_bytes = 0;
     hipStream_t stream = nullptr;
@@ -274,12 +263,13 @@ void adj_gn_block(AdjTapeDev& t, const T* d_v, const T* d_rw, size_t rw_stride, 
 // ---- normal equations (tests/normal_reference.py restates them; kernels in fsm_normal.hip).  Model vectors are n_model()
 // values on the tape's device, parameters x fastest: nnx x nny x nnz nodes, or the (nnx - 1) x (nny - 1) x (nnz - 1) cells of a cell tape.
 int adj_smooth_tile_edge(size_t elem);   // edge of a smoothing tile (interior parameters) for an element size
-// the work arrays: x, r, p, q, the product output (n_model() each), one double per chunk of 1024 parameters and the scalars.
-// adj_normal_prepare is a no-op while they are there (AdjDeviceError naming the byte count if an allocation fails); adj_normal_release
-// frees them and takes them off bytes().
-size_t adj_normal_bytes(const AdjTapeDev& t);
-void adj_normal_prepare(AdjTapeDev& t);
-void adj_normal_release(AdjTapeDev& t);
+// the work arrays of the solver for one system (CgWork): five vectors of cg_len(sys) values, one double per chunk of 1024 elements and the
+// scalars; for a system with a block three arrays of cg_block(sys) values more.  adj_cg_prepare is a no-op while they are there
+// (AdjDeviceError naming the byte count if an allocation fails); adj_cg_release frees them and takes them off bytes().  adj_smooth's host
+// staging and adj_dot use the model system's.
+size_t adj_cg_bytes(const AdjTapeDev& t, CgSystem sys);
+void adj_cg_prepare(AdjTapeDev& t, CgSystem sys);
+void adj_cg_release(AdjTapeDev& t, CgSystem sys);
 // d_out = R d_v = sum_d weights[d] K_d^T (K_d d_v), K_d the second differences of spacing dx along axis d with the centred stencil
 // shifted inwards on the two end rows; d_out and d_v are different arrays.  std::invalid_argument if an axis has fewer than 3 parameters.
 template <typename T>
@@ -302,18 +292,19 @@ struct NormalResult {
     std::vector<int> passes;        // (jvp, vjp) passes of the product of every such iteration
     int passes0[2] = {0, 0};        // ... and of A x0
 };
-// conjugate gradients on A x = rhs: on entry nrm_r holds rhs and, if with_x0, nrm_x holds x0; on return nrm_x holds the iterate.
-// d_rw (n_rows, may be null) on the tape's device.  Vectors in T, scalars in fp64, inner products as adj_dot; one host read of the
-// scalars per iteration.
+// Conjugate gradients on A x = rhs for one of the three systems, w = t.cg[sys]: on entry w.r holds rhs (its block unscaled) and, if
+// with_x0, w.x holds x0; on return w.x holds the iterate.  d_rw (n_rows, may be null) on the tape's device.  Vectors in T, scalars in
+// fp64, inner products as adj_dot over the flat vector of the system; one host read of the scalars per iteration.  What differs between
+// the systems: the product (adj_gn, or adj_hess if op.newton, for CG_MODEL; adj_gn_joint for CG_SOURCE; adj_gn_rjoint for CG_RECEIVER) and
+// the block -- w.scale / w.damp hold c and delta if with_scale / with_damp, the block of rhs is scaled by c before the loop and the block
+// of x after it (x_e = fl(c * z_e)), and the block of A p is fl(hp + fl(delta * p)).  x0 and op.newton are offered for CG_MODEL only
+// (std::invalid_argument otherwise), a scale and a block damping only for the other two.
 template <typename T>
-void adj_solve_normal(AdjTapeDev& t, const T* d_rw, const NormalOperator& op, bool with_x0, int maxiter, double rtol, int schedule,
-                      NormalResult& res);
+void adj_solve(AdjTapeDev& t, CgSystem sys, const T* d_rw, const NormalOperator& op, bool with_x0, bool with_scale, bool with_damp,
+               int maxiter, double rtol, int schedule, NormalResult& res);
 
-// ---- joint hypocentre-velocity products and solve (tests/joint_reference.py restates them).  Source blocks are 4 n_points
+// ---- joint hypocentre-velocity products (tests/joint_reference.py restates them and the solve).  Source blocks are 4 n_points
 // values, (t0, x, y, z) of every point in call order, on the tape's device.
-// out = fl(c * in) over a source block (in and out may be the same array)
-template <typename T>
-void adj_src_scale(AdjTapeDev& t, const T* d_c, const T* d_in, T* d_out);
 // the joint tangent of (d_ds, d_dsrc) from ONE relaxation: the frozen nodes are seeded with fl(fl(d ds) + sigma), every other node obeys
 // the forward mode's system; outputs as adj_jvp.  *mu_out (may be null) receives the relaxed buffer.  Returns the passes launched.
 template <typename T>
@@ -323,19 +314,6 @@ int adj_jvp_joint(AdjTapeDev& t, const T* d_ds, const T* d_dsrc, T* d_dtt, T* d_
 template <typename T>
 void adj_gn_joint(AdjTapeDev& t, const T* d_vs, const T* d_ve, const T* d_scale, T* d_ve_scaled, const T* d_rw, T* d_gs, T* d_ge,
                   int schedule, int* passes_jvp, int* passes_vjp);
-// the work arrays of the joint solver: five joint vectors, three source blocks, one double per chunk of 1024 joint elements and the
-// scalars.  adj_joint_prepare is a no-op while they are there (AdjDeviceError naming the byte count if an allocation fails);
-// adj_joint_release frees them and takes them off bytes().
-size_t adj_joint_bytes(const AdjTapeDev& t);
-void adj_joint_prepare(AdjTapeDev& t);
-void adj_joint_release(AdjTapeDev& t);
-// conjugate gradients from zero on the regularised joint normal equations (the recurrence, scalars, statuses and host reads of
-// adj_solve_normal; inner products over the flat joint vector).  On entry jnt_r holds (b_s, b_e unscaled), jnt_scale / jnt_damp hold c and
-// delta if with_scale / with_damp; on return jnt_x holds (x_s, x_e = fl(c * z_e)).  op.newton is not offered.
-// receiver: the extra block is the receiver block of DESIGN.md 6k (arrays rj_*, n_rjoint(), adj_gn_rjoint) instead of the source block.
-template <typename T>
-void adj_solve_joint(AdjTapeDev& t, const T* d_rw, const NormalOperator& op, bool with_scale, bool with_damp, int maxiter, double rtol,
-                     int schedule, NormalResult& res, bool receiver = false);
 
 // ---- derivatives with respect to the receiver points (tests/receiver_reference.py restates them).  Receiver blocks are 4
 // n_rcv_points values, (t0, x, y, z) of every receiver point, on the tape's device.
@@ -343,7 +321,7 @@ void adj_solve_joint(AdjTapeDev& t, const T* d_rw, const NormalOperator& op, boo
 // receiver calls hold on the device (the next call uploads the new map).  Host only apart from that.
 void adj_rcv_set_points(AdjTapeDev& t, const int* point_of_row, size_t n_points);
 // what the first receiver call adds to the tape; adj_rcv_prepare is a no-op while it is there (AdjDeviceError naming the byte count if
-// an allocation fails); adj_rcv_release frees it and the receiver joint solver's arrays and takes them off bytes()
+// an allocation fails); adj_rcv_release frees it and the solver's arrays of the receiver system and takes them off bytes()
 size_t adj_rcv_extra_bytes(const AdjTapeDev& t);
 template <typename T>
 void adj_rcv_prepare(AdjTapeDev& t);
@@ -361,7 +339,7 @@ void adj_jvp_rcv(AdjTapeDev& t, const T* d_drcv, const T* d_base, T* d_dtt);
 // d_grcv (4 n_rcv_points) = the reverse chains of d_w (n_rows) over the rows of every point
 template <typename T>
 void adj_vjp_rcv(AdjTapeDev& t, const T* d_w, T* d_grcv);
-// out = fl(c * in) over n values (the kernel of adj_src_scale)
+// out = fl(c * in) over n values (in and out may be the same array)
 template <typename T>
 void adj_scale(AdjTapeDev& t, const T* d_c, const T* d_in, T* d_out, size_t n);
 // the receiver joint tangent: adj_jvp of d_ds, then the receiver rows added; outputs as adj_jvp
@@ -371,9 +349,5 @@ int adj_jvp_rjoint(AdjTapeDev& t, const T* d_ds, const T* d_drcv, T* d_dtt, T* d
 template <typename T>
 void adj_gn_rjoint(AdjTapeDev& t, const T* d_vs, const T* d_ve, const T* d_scale, T* d_ve_scaled, const T* d_rw, T* d_gs, T* d_ge,
                    int schedule, int* passes_jvp, int* passes_vjp);
-// the work arrays of the receiver joint solver (as adj_joint_bytes, for n_rjoint())
-size_t adj_rjoint_bytes(const AdjTapeDev& t);
-void adj_rjoint_prepare(AdjTapeDev& t);
-void adj_rjoint_release(AdjTapeDev& t);
 
 }  // namespace ttcr_amd

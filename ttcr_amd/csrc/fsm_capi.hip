@@ -3895,6 +3895,10 @@ int ttcr_fsm_raytrace_multi_adjoint_cells(ttcr_fsm_grid* g, int n_src, const int
 //   gn_block (per group)         v and out          blk_model     both, as for gn
 //                                row_weight         blk_rw        one set shared by the columns: uploaded once, before the loop; a set per
 //                                                                 column: the group's columns, uploaded in the loop
+//   normal_smooth, normal_dot    v / a, b, out      r, p, q of    the work arrays of the solver's model system (cg[CG_MODEL]): idle outside
+//                                                   cg[CG_MODEL]  a solve
+//   the three solves             rhs, x0, x         r, x of       not staged but copied, from the host or the device: the solver overwrites
+//                                                   cg[system]    r and keeps the iterate in x anyway
 //
 // The groups of a block product run one after the other on the stream, so a group's staging is free again when the next group's copy is
 // enqueued behind it.  Nothing is copied for an empty array, and an argument that is null stays null.
@@ -3952,6 +3956,13 @@ static int tape_call(const ttcr_fsm_adjoint* t, int schedule, int* passes1, int*
             if (passes2) *passes2 = p2;
         });
     });
+}
+// the frame of the release entries: free(d) returns a group of the tape's arrays
+template <typename Free>
+static int tape_release(ttcr_fsm_adjoint* t, Free&& free) {
+    if (!t) return tape_arg_error("null tape");
+    std::lock_guard<std::mutex> lock(t->mu);
+    return guarded([&] { free(t->t); });
 }
 }  // extern "C++"
 
@@ -4035,11 +4046,7 @@ int ttcr_fsm_adjoint_hold(ttcr_fsm_adjoint* t, const void* w, int w_on_device, c
     if (!t || (!w && !field_cot)) return tape_arg_error(!t ? "null tape" : "w and field_cot are both null: no cotangent to hold");
     return tape_back(t, TAPE_HOLD, w, w_on_device, field_cot, fc_on_device, grad, grad_on_device, nullptr, 0, schedule, passes);
 }
-int ttcr_fsm_adjoint_release(ttcr_fsm_adjoint* t) {
-    if (!t) return tape_arg_error("null tape");
-    std::lock_guard<std::mutex> lock(t->mu);
-    return guarded([&] { ttcr_amd::adj_release_hold(t->t); });
-}
+int ttcr_fsm_adjoint_release(ttcr_fsm_adjoint* t) { return tape_release(t, ttcr_amd::adj_release_hold); }
 
 int ttcr_fsm_adjoint_jvp(const ttcr_fsm_adjoint* t, const void* ds, int ds_on_device, void* dtt, int dtt_on_device, void* dfields,
                          int df_on_device, int schedule, int* passes) {
@@ -4182,18 +4189,18 @@ int ttcr_fsm_adjoint_gn_block(const ttcr_fsm_adjoint* t, int n_cols, const void*
         }
     });
 }
-int ttcr_fsm_adjoint_block_release(ttcr_fsm_adjoint* t) {
-    if (!t) return tape_arg_error("null tape");
-    std::lock_guard<std::mutex> lock(t->mu);
-    return guarded([&] { ttcr_amd::adj_block_release(t->t); });
-}
+int ttcr_fsm_adjoint_block_release(ttcr_fsm_adjoint* t) { return tape_release(t, ttcr_amd::adj_block_release); }
 
-// ---- normal equations of the field tape: the smoothing operator, the solver's inner product and the CG solve.  The
-// entries check what needs no tape first and the tape last.  Host staging (the table above stage_in continued): the work arrays of the
-// solver are idle outside a solve, so a host v of smooth, the first operand of dot and a host rhs go through nrm_r, the second operand of
-// dot through nrm_p, a host result of smooth through nrm_q, a host x0 and the host result of a solve through nrm_x (where the solver
-// keeps the iterate anyway); a host row_weight goes through rw_tmp as for gn.  Operands on the device are read in place, rhs and x0
-// are copied into the work arrays, which the solver overwrites.
+// ---- the solver of the field tape: the smoothing operator, the solver's inner product and the CG solve of the three
+// systems (ttcr_amd::CgSystem) -- the model vector alone (normal_*), with the source block behind it (joint_*: 4 n_points values, (t0, x, y,
+// z) of every point in call order) or with the receiver block (rjoint_*: 4 n_rcv_points values).  The entries check what needs no tape
+// first and the tape last.  Host staging (the table above stage_in continued): the work arrays cg[CG_MODEL] are idle outside a solve, so a
+// host v of smooth and the first operand of dot go through its r, the second operand of dot through its p, a host result of smooth
+// through its q.  A solve copies its right-hand sides (and x0) into r (and x) of its system's work arrays, which the solver overwrites, and
+// reads the result from x; a host row_weight goes through rw_tmp as for gn.  The joint tangents stage like jvp and jvp_source do (ds in
+// model_tmp(), the block in src_io or rcv_io, dtt in w_tmp).  The joint Gauss-Newton products part src_io or rcv_io, 16 points' values,
+// into four blocks: a host v block, the scale c, fl(c * v block) and a host out block; v and out go through model_tmp().  The scale and
+// the damping of a block are settings, not data: host doubles (or NULL), checked here and rounded to the tape's dtype.
 static const char* normal_weights_error(const double* w, const char* if_null, const char* if_bad) {
     if (!w) return if_null;
     for (int d = 0; d < 3; ++d)
@@ -4205,89 +4212,6 @@ static const char* normal_axes_error(const ttcr_fsm_adjoint* t) {
     return std::min({t->t.nnx, t->t.nny, t->t.nnz}) - c < 3 ? "smooth: second-order smoothing needs at least 3 parameters along every axis"
                                                              : nullptr;
 }
-int ttcr_fsm_normal_tile_edge(int dtype) { return ttcr_amd::adj_smooth_tile_edge(dtype == TTCR_F32 ? 4 : 8); }
-int ttcr_fsm_normal_smooth(ttcr_fsm_adjoint* t, const void* v, int v_on_device, const double* weights, void* out, int out_on_device) {
-    const char* bad = normal_weights_error(weights, "null weights", "weights: three finite values >= 0 (x, y, z)");
-    if (!bad) bad =!v ? "null v" : (!out ? "null out" : (!t ? "null tape" : normal_axes_error(t)));
-    if (bad) return tape_arg_error(bad);
-    return tape_call(t, 0, nullptr, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int&, int&) {
-        using T = decltype(tag);
-        ttcr_amd::adj_normal_prepare(d);
-        const T* dv = stage_in<T>(d, v, v_on_device, d.nrm_r, d.n_model());
-        ttcr_amd::adj_smooth<T>(d, dv, weights, stage_dst<T>(out, out_on_device, d.nrm_q));
-        stage_out<T>(d, out, out_on_device, d.nrm_q, d.n_model());
-    });
-}
-int ttcr_fsm_normal_dot(ttcr_fsm_adjoint* t, const void* a, int a_on_device, const void* b, int b_on_device, double* result) {
-    if (!a || !b || !result || !t) return tape_arg_error(!a ? "null a" : (!b ? "null b" : (!result ? "null result" : "null tape")));
-    return tape_call(t, 0, nullptr, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int&, int&) {
-        using T = decltype(tag);
-        ttcr_amd::adj_normal_prepare(d);
-        const T* da = stage_in<T>(d, a, a_on_device, d.nrm_r, d.n_model());
-        const T* db = b == a && b_on_device == a_on_device ? da : stage_in<T>(d, b, b_on_device, d.nrm_p, d.n_model());
-        *result = ttcr_amd::adj_dot<T>(d, da, db);
-    });
-}
-int ttcr_fsm_normal_solve(ttcr_fsm_adjoint* t, const void* rhs, int rhs_on_device, const void* row_weight, int rw_on_device, double smooth,
-                          const double* smooth_weights, double damp, const void* x0, int x0_on_device, int maxiter, double rtol,
-                          int newton, int schedule, void* x, int x_on_device, int* status, int* iterations, double* rho, double* pq,
-                          int* passes) {
-    const char* bad = nullptr;
-    if (!(smooth >= 0.0) || !std::isfinite(smooth)) bad = "smooth: a finite value >= 0";
-    else if (!(damp >= 0.0) || !std::isfinite(damp)) bad = "damp: a finite value >= 0";
-    else if (maxiter < 1) bad = "maxiter: at least one iteration";
-    else if (!(rtol >= 0.0) || !std::isfinite(rtol)) bad = "rtol: a finite value >= 0";
-    else if (newton != 0 && newton != 1) bad = "hessian: 0 (gauss_newton) or 1 (newton)";
-    else if (const char* w = normal_weights_error(smooth_weights, "null smooth_weights", "smooth_weights: three finite values >= 0 (x, y, z)"))
-        bad = w;
-    else if (const char* s = schedule_error(schedule)) bad = s;
-    else if (!rhs || !x) bad = !rhs ? "null rhs" : "null x";
-    else if (!status || !iterations || !rho || !pq) bad = "null status, iterations, rho or pq";
-    else if (!t) bad = "null tape";
-    else if (smooth != 0.0) bad = normal_axes_error(t);
-    if (bad) return tape_arg_error(bad);
-    return tape_call(t, schedule, nullptr, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int&, int&) {
-        using T = decltype(tag);
-        const size_t n = d.n_model();
-        ttcr_amd::adj_normal_prepare(d);
-        if (row_weight && !rw_on_device) ttcr_amd::adj_jvp_prepare<T>(d);
-        const T* drw = stage_in<T>(d, row_weight, rw_on_device, d.rw_tmp, d.n_rows);
-        const T* drhs = stage_in<T>(d, rhs, rhs_on_device, d.nrm_r, n);
-        const T* dx0 = stage_in<T>(d, x0, x0_on_device, d.nrm_x, n);
-        if (n > 0 && (const void*)drhs != d.nrm_r) HIP_CHECK(hipMemcpyAsync(d.nrm_r, drhs, n * sizeof(T), hipMemcpyDeviceToDevice, d.stream));
-        if (n > 0 && dx0 && (const void*)dx0 != d.nrm_x) HIP_CHECK(hipMemcpyAsync(d.nrm_x, dx0, n * sizeof(T), hipMemcpyDeviceToDevice, d.stream));
-        ttcr_amd::NormalOperator op;
-        op.smooth = smooth;
-        op.damp = damp;
-        std::copy(smooth_weights, smooth_weights + 3, op.weights);
-        op.newton = newton != 0;
-        ttcr_amd::NormalResult res;
-        ttcr_amd::adj_solve_normal<T>(d, drw, op, x0 != nullptr, maxiter, rtol, schedule, res);
-        if (n > 0 && x_on_device) HIP_CHECK(hipMemcpyAsync(x, d.nrm_x, n * sizeof(T), hipMemcpyDeviceToDevice, d.stream));
-        stage_out<T>(d, x, x_on_device, d.nrm_x, n);
-        *status = res.status;
-        *iterations = res.iterations;
-        std::copy(res.rho.begin(), res.rho.end(), rho);
-        std::copy(res.pq.begin(), res.pq.end(), pq);
-        if (passes) {
-            passes[0] = res.passes0[0];
-            passes[1] = res.passes0[1];
-            std::copy(res.passes.begin(), res.passes.end(), passes + 2);
-        }
-    }, newton == 1 ? "newton" : nullptr);
-}
-int ttcr_fsm_normal_release(ttcr_fsm_adjoint* t) {
-    if (!t) return tape_arg_error("null tape");
-    std::lock_guard<std::mutex> lock(t->mu);
-    return guarded([&] { ttcr_amd::adj_normal_release(t->t); });
-}
-
-// ---- joint hypocentre-velocity products and solve of the field tape.  A source block is 4 n_points values, (t0, x, y, z)
-// of every point in call order.  Host staging (the table above stage_in continued): joint_jvp stages like jvp and jvp_source do (ds in
-// model_tmp(), dsrc in src_io, dtt in w_tmp).  joint_gn parts src_io, 16 n_points values, into four source blocks: a host v_src, the scale
-// c, fl(c * v_src) and a host out_src; v and out go through model_tmp() and row_weight through rw_tmp as for gn.  joint_solve copies its
-// right-hand sides into the residual of its own work arrays and reads the result from the iterate.  source_scale and source_damp are
-// settings, not data: 4 n_points host doubles each (or NULL), checked here and rounded to the tape's dtype.
 static const char* joint_block_error(const double* v, size_t n, const char* if_bad) {
     for (size_t i = 0; v && i < n; ++i)
         if (!(v[i] >= 0.0) || !std::isfinite(v[i])) return if_bad;
@@ -4309,108 +4233,228 @@ static void joint_upload(ttcr_amd::AdjTapeDev& d, const double* v, size_t n, voi
 }
 }  // extern "C++"
 
-int ttcr_fsm_joint_jvp(const ttcr_fsm_adjoint* t, const void* ds, int ds_on_device, const void* dsrc, int dsrc_on_device, void* dtt,
-                       int dtt_on_device, void* dfields, int df_on_device, int schedule, int* passes) {
-    if (!ds || !dsrc || (!dtt && !dfields) || !t)
-        return tape_arg_error(!ds ? "null ds" : (!dsrc ? "null dsrc" : (!t ? "null tape" : "dtt and dfields are both null: nothing to compute")));
-    return tape_call(t, schedule, passes, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int& np, int&) {
-        using T = decltype(tag);
-        ttcr_amd::adj_src_prepare<T>(d);
-        const T* dds = stage_in<T>(d, ds, ds_on_device, d.model_tmp(), d.n_model());
-        const T* dd = stage_in<T>(d, dsrc, dsrc_on_device, d.src_io, 4 * d.n_points);
-        const T* mu = nullptr;
-        np = ttcr_amd::adj_jvp_joint<T>(d, dds, dd, stage_dst<T>(dtt, dtt_on_device, d.w_tmp), df_on_device ? (T*)dfields : nullptr, schedule,
-                                        &mu);
-        stage_out<T>(d, dtt, dtt_on_device, d.w_tmp, d.n_rows);
-        stage_out<T>(d, dfields, df_on_device, mu, d.n_events * d.nn);
-    });
+
+// the extra block of a joint system as its entries name it
+struct TapeBlock {
+    ttcr_amd::CgSystem sys;
+    const char *null_d, *null_v, *null_out, *null_rhs, *null_x, *bad_scale, *bad_damp;
+};
+static const TapeBlock SOURCE_BLOCK = {ttcr_amd::CG_SOURCE, "null dsrc", "null v_src", "null out_src", "null rhs_src", "null x_src",
+                                       "source_scale: finite values >= 0", "source_damp: finite values >= 0"};
+static const TapeBlock RCV_BLOCK = {ttcr_amd::CG_RECEIVER, "null drcv", "null v_rcv", "null out_rcv", "null rhs_rcv", "null x_rcv",
+                                    "rcv_scale: finite values >= 0", "rcv_damp: finite values >= 0"};
+extern "C++" {
+// what the products of a block need on the tape, and the 16 points' values a host block is staged in (allocated by that)
+template <typename T>
+static T* block_prepare(ttcr_amd::AdjTapeDev& d, ttcr_amd::CgSystem sys) {
+    if (sys == ttcr_amd::CG_SOURCE) ttcr_amd::adj_src_prepare<T>(d);
+    else ttcr_amd::adj_rcv_prepare<T>(d);
+    return (T*)(sys == ttcr_amd::CG_SOURCE ? d.src_io : d.rcv_io);
 }
-int ttcr_fsm_joint_gn(const ttcr_fsm_adjoint* t, const void* v, int v_on_device, const void* v_src, int vs_on_device, const void* row_weight,
-                      int rw_on_device, const double* source_scale, void* out, int out_on_device, void* out_src, int os_on_device,
-                      int schedule, int* passes_jvp, int* passes_vjp) {
-    const char* bad = !v ? "null v" : (!v_src ? "null v_src" : (!out ? "null out" : (!out_src ? "null out_src" : (!t ? "null tape" : nullptr))));
-    if (!bad) bad = joint_block_error(source_scale, 4 * t->t.n_points, "source_scale: finite values >= 0");
+}  // extern "C++"
+
+int ttcr_fsm_normal_tile_edge(int dtype) { return ttcr_amd::adj_smooth_tile_edge(dtype == TTCR_F32 ? 4 : 8); }
+int ttcr_fsm_normal_smooth(ttcr_fsm_adjoint* t, const void* v, int v_on_device, const double* weights, void* out, int out_on_device) {
+    const char* bad = normal_weights_error(weights, "null weights", "weights: three finite values >= 0 (x, y, z)");
+    if (!bad) bad =!v ? "null v" : (!out ? "null out" : (!t ? "null tape" : normal_axes_error(t)));
     if (bad) return tape_arg_error(bad);
-    return tape_call(t, schedule, passes_jvp, passes_vjp, [&](ttcr_amd::AdjTapeDev& d, auto tag, int& pj, int& pv) {
+    return tape_call(t, 0, nullptr, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int&, int&) {
         using T = decltype(tag);
-        const size_t blk = 4 * d.n_points;
-        ttcr_amd::adj_src_prepare<T>(d);
-        T* io = (T*)d.src_io;
-        const T* dv = stage_in<T>(d, v, v_on_device, d.model_tmp(), d.n_model());
-        const T* dve = stage_in<T>(d, v_src, vs_on_device, io, blk);
-        if (row_weight && !rw_on_device) ttcr_amd::adj_jvp_prepare<T>(d);
-        const T* drw = stage_in<T>(d, row_weight, rw_on_device, d.rw_tmp, d.n_rows);
-        if (source_scale) joint_upload<T>(d, source_scale, blk, io + blk);
-        T* dout = stage_dst<T>(out, out_on_device, d.model_tmp());
-        T* dos = stage_dst<T>(out_src, os_on_device, io + 3 * blk);
-        ttcr_amd::adj_gn_joint<T>(d, dv, dve, source_scale ? io + blk : nullptr, io + 2 * blk, drw, dout, dos, schedule, &pj, &pv);
-        stage_out<T>(d, out, out_on_device, d.model_tmp(), d.n_model());
-        stage_out<T>(d, out_src, os_on_device, io + 3 * blk, blk);
+        ttcr_amd::adj_cg_prepare(d, ttcr_amd::CG_MODEL);
+        const ttcr_amd::CgWork& w = d.cg[ttcr_amd::CG_MODEL];
+        const T* dv = stage_in<T>(d, v, v_on_device, w.r, d.n_model());
+        ttcr_amd::adj_smooth<T>(d, dv, weights, stage_dst<T>(out, out_on_device, w.q));
+        stage_out<T>(d, out, out_on_device, w.q, d.n_model());
     });
 }
-int ttcr_fsm_joint_solve(ttcr_fsm_adjoint* t, const void* rhs, int rhs_on_device, const void* rhs_src, int rs_on_device,
-                         const void* row_weight, int rw_on_device, double smooth, const double* smooth_weights, double damp,
-                         const double* source_damp, const double* source_scale, int maxiter, double rtol, int schedule, void* x,
-                         int x_on_device, void* x_src, int xs_on_device, int* status, int* iterations, double* rho, double* pq, int* passes) {
+int ttcr_fsm_normal_dot(ttcr_fsm_adjoint* t, const void* a, int a_on_device, const void* b, int b_on_device, double* result) {
+    if (!a || !b || !result || !t) return tape_arg_error(!a ? "null a" : (!b ? "null b" : (!result ? "null result" : "null tape")));
+    return tape_call(t, 0, nullptr, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int&, int&) {
+        using T = decltype(tag);
+        ttcr_amd::adj_cg_prepare(d, ttcr_amd::CG_MODEL);
+        const ttcr_amd::CgWork& w = d.cg[ttcr_amd::CG_MODEL];
+        const T* da = stage_in<T>(d, a, a_on_device, w.r, d.n_model());
+        const T* db = b == a && b_on_device == a_on_device ? da : stage_in<T>(d, b, b_on_device, w.p, d.n_model());
+        *result = ttcr_amd::adj_dot<T>(d, da, db);
+    });
+}
+
+// The three solves: one check of the arguments, one body.  blk is the extra block of a joint system (null: the model system, the only one
+// with x0 and newton); rhs_b, x_b, b_damp and b_scale are the block's arguments.  passes: (jvp, vjp) of every iteration, behind the pair of
+// A x0 for the model system.
+static int tape_solve(ttcr_fsm_adjoint* t, const TapeBlock* blk, const void* rhs, int rhs_on_device, const void* rhs_b, int rb_on_device,
+                      const void* row_weight, int rw_on_device, double smooth, const double* smooth_weights, double damp,
+                      const double* b_damp, const double* b_scale, const void* x0, int x0_on_device, int maxiter, double rtol, int newton,
+                      int schedule, void* x, int x_on_device, void* x_b, int xb_on_device, int* status, int* iterations, double* rho,
+                      double* pq, int* passes) {
+    const ttcr_amd::CgSystem sys = blk ? blk->sys : ttcr_amd::CG_MODEL;
     const char* bad = nullptr;
     if (!(smooth >= 0.0) || !std::isfinite(smooth)) bad = "smooth: a finite value >= 0";
     else if (!(damp >= 0.0) || !std::isfinite(damp)) bad = "damp: a finite value >= 0";
     else if (maxiter < 1) bad = "maxiter: at least one iteration";
     else if (!(rtol >= 0.0) || !std::isfinite(rtol)) bad = "rtol: a finite value >= 0";
+    else if (newton != 0 && newton != 1) bad = "hessian: 0 (gauss_newton) or 1 (newton)";
     else if (const char* w = normal_weights_error(smooth_weights, "null smooth_weights", "smooth_weights: three finite values >= 0 (x, y, z)"))
         bad = w;
     else if (const char* s = schedule_error(schedule)) bad = s;
-    else if (!rhs || !rhs_src) bad = !rhs ? "null rhs" : "null rhs_src";
-    else if (!x || !x_src) bad = !x ? "null x" : "null x_src";
+    else if (!rhs) bad = "null rhs";
+    else if (blk && !rhs_b) bad = blk->null_rhs;
+    else if (!x) bad = "null x";
+    else if (blk && !x_b) bad = blk->null_x;
     else if (!status || !iterations || !rho || !pq) bad = "null status, iterations, rho or pq";
     else if (!t) bad = "null tape";
-    else if (const char* c = joint_block_error(source_scale, 4 * t->t.n_points, "source_scale: finite values >= 0")) bad = c;
-    else if (const char* c = joint_block_error(source_damp, 4 * t->t.n_points, "source_damp: finite values >= 0")) bad = c;
+    else if (const char* c = joint_block_error(b_scale, t->t.cg_block(sys), blk ? blk->bad_scale : nullptr)) bad = c;
+    else if (const char* c = joint_block_error(b_damp, t->t.cg_block(sys), blk ? blk->bad_damp : nullptr)) bad = c;
     else if (smooth != 0.0) bad = normal_axes_error(t);
     if (bad) return tape_arg_error(bad);
     return tape_call(t, schedule, nullptr, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int&, int&) {
         using T = decltype(tag);
-        const size_t nm = d.n_model(), blk = 4 * d.n_points;
-        ttcr_amd::adj_joint_prepare(d);
+        const size_t nm = d.n_model(), nb = d.cg_block(sys);
+        if (sys == ttcr_amd::CG_RECEIVER) ttcr_amd::adj_rcv_prepare<T>(d);
+        ttcr_amd::adj_cg_prepare(d, sys);
+        const ttcr_amd::CgWork& w = d.cg[sys];
         if (row_weight && !rw_on_device) ttcr_amd::adj_jvp_prepare<T>(d);
         const T* drw = stage_in<T>(d, row_weight, rw_on_device, d.rw_tmp, d.n_rows);
-        T* r = (T*)d.jnt_r;
-        if (nm > 0) HIP_CHECK(hipMemcpyAsync(r, rhs, nm * sizeof(T), rhs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d.stream));
-        if (blk > 0)
-            HIP_CHECK(hipMemcpyAsync(r + nm, rhs_src, blk * sizeof(T), rs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d.stream));
-        const bool with_damp = joint_any(source_damp, blk);   // (a term whose factor is 0 everywhere is not evaluated)
-        if (source_scale) joint_upload<T>(d, source_scale, blk, d.jnt_scale);
-        if (with_damp) joint_upload<T>(d, source_damp, blk, d.jnt_damp);
+        auto copy = [&](void* dst, const void* src, size_t n, hipMemcpyKind kind) {
+            if (n > 0) HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(T), kind, d.stream));
+        };
+        copy(w.r, rhs, nm, rhs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
+        copy((T*)w.r + nm, rhs_b, nb, rb_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
+        if (x0) copy(w.x, x0, nm, x0_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
+        const bool with_damp = joint_any(b_damp, nb);   // (a term whose factor is 0 everywhere is not evaluated)
+        if (b_scale) joint_upload<T>(d, b_scale, nb, w.scale);
+        if (with_damp) joint_upload<T>(d, b_damp, nb, w.damp);
         ttcr_amd::NormalOperator op;
         op.smooth = smooth;
         op.damp = damp;
         std::copy(smooth_weights, smooth_weights + 3, op.weights);
+        op.newton = newton != 0;
         ttcr_amd::NormalResult res;
-        ttcr_amd::adj_solve_joint<T>(d, drw, op, source_scale != nullptr, with_damp, maxiter, rtol, schedule, res);
-        const T* xd = (const T*)d.jnt_x;
-        if (nm > 0) HIP_CHECK(hipMemcpyAsync(x, xd, nm * sizeof(T), x_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, d.stream));
-        if (blk > 0)
-            HIP_CHECK(hipMemcpyAsync(x_src, xd + nm, blk * sizeof(T), xs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, d.stream));
+        ttcr_amd::adj_solve<T>(d, sys, drw, op, x0 != nullptr, b_scale != nullptr, with_damp, maxiter, rtol, schedule, res);
+        copy(x, w.x, nm, x_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost);
+        copy(x_b, (const T*)w.x + nm, nb, xb_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost);
         *status = res.status;
         *iterations = res.iterations;
         std::copy(res.rho.begin(), res.rho.end(), rho);
         std::copy(res.pq.begin(), res.pq.end(), pq);
+        if (passes && !blk) {
+            passes[0] = res.passes0[0];
+            passes[1] = res.passes0[1];
+            passes += 2;
+        }
         if (passes) std::copy(res.passes.begin(), res.passes.end(), passes);
-    });
+    }, newton == 1 ? "newton" : nullptr);
+}
+int ttcr_fsm_normal_solve(ttcr_fsm_adjoint* t, const void* rhs, int rhs_on_device, const void* row_weight, int rw_on_device, double smooth,
+                          const double* smooth_weights, double damp, const void* x0, int x0_on_device, int maxiter, double rtol,
+                          int newton, int schedule, void* x, int x_on_device, int* status, int* iterations, double* rho, double* pq,
+                          int* passes) {
+    return tape_solve(t, nullptr, rhs, rhs_on_device, nullptr, 0, row_weight, rw_on_device, smooth, smooth_weights, damp, nullptr, nullptr, x0,
+                      x0_on_device, maxiter, rtol, newton, schedule, x, x_on_device, nullptr, 0, status, iterations, rho, pq, passes);
+}
+int ttcr_fsm_joint_solve(ttcr_fsm_adjoint* t, const void* rhs, int rhs_on_device, const void* rhs_src, int rs_on_device,
+                         const void* row_weight, int rw_on_device, double smooth, const double* smooth_weights, double damp,
+                         const double* source_damp, const double* source_scale, int maxiter, double rtol, int schedule, void* x,
+                         int x_on_device, void* x_src, int xs_on_device, int* status, int* iterations, double* rho, double* pq, int* passes) {
+    return tape_solve(t, &SOURCE_BLOCK, rhs, rhs_on_device, rhs_src, rs_on_device, row_weight, rw_on_device, smooth, smooth_weights, damp,
+                      source_damp, source_scale, nullptr, 0, maxiter, rtol, 0, schedule, x, x_on_device, x_src, xs_on_device, status,
+                      iterations, rho, pq, passes);
+}
+int ttcr_fsm_rjoint_solve(ttcr_fsm_adjoint* t, const void* rhs, int rhs_on_device, const void* rhs_rcv, int rr_on_device,
+                          const void* row_weight, int rw_on_device, double smooth, const double* smooth_weights, double damp,
+                          const double* rcv_damp, const double* rcv_scale, int maxiter, double rtol, int schedule, void* x,
+                          int x_on_device, void* x_rcv, int xr_on_device, int* status, int* iterations, double* rho, double* pq, int* passes) {
+    return tape_solve(t, &RCV_BLOCK, rhs, rhs_on_device, rhs_rcv, rr_on_device, row_weight, rw_on_device, smooth, smooth_weights, damp, rcv_damp,
+                      rcv_scale, nullptr, 0, maxiter, rtol, 0, schedule, x, x_on_device, x_rcv, xr_on_device, status, iterations, rho, pq,
+                      passes);
+}
+int ttcr_fsm_normal_release(ttcr_fsm_adjoint* t) {
+    return tape_release(t, [](ttcr_amd::AdjTapeDev& d) { ttcr_amd::adj_cg_release(d, ttcr_amd::CG_MODEL); });
 }
 int ttcr_fsm_joint_release(ttcr_fsm_adjoint* t) {
-    if (!t) return tape_arg_error("null tape");
-    std::lock_guard<std::mutex> lock(t->mu);
-    return guarded([&] { ttcr_amd::adj_joint_release(t->t); });
+    return tape_release(t, [](ttcr_amd::AdjTapeDev& d) { ttcr_amd::adj_cg_release(d, ttcr_amd::CG_SOURCE); });
 }
 
-// ---- derivatives with respect to the receiver points and the receiver joint system of the field tape.  A receiver block is
-// 4 n_rcv_points values, (t0, x, y, z) of every receiver point.  Host staging (the table above stage_in continued): rcv_eval stages the
-// events, host points and host results in rcv_stage (7 n_pts values and n_pts ints: points, gradients, traveltimes, events), a buffer of
-// the tape that grows to the largest call and is returned by rcv_release -- its sizes are the caller's, not the tape's --; jvp_rcv a
-// host drcv in rcv_io and a host dtt in w_tmp; vjp_rcv a host w in w_tmp and a host grcv in rcv_io; rjoint_jvp as joint_jvp with rcv_io in the
-// place of src_io; rjoint_gn parts rcv_io into four receiver blocks as joint_gn parts src_io; rjoint_solve copies its right-hand sides
-// into the residual of its own work arrays and reads the result from the iterate.
+// The joint tangents: one body.  The source tangent comes from a relaxation of its own, which names the buffer it relaxed in; the
+// receiver tangent's fields are adj_jvp's (they do not depend on drcv), in the buffer ttcr_fsm_adjoint_jvp reads them from: lam, or lam2
+// after an odd number of passes of the Jacobi schedule.
+static int tape_joint_jvp(const ttcr_fsm_adjoint* t, const TapeBlock& blk, const void* ds, int ds_on_device, const void* db, int db_on_device,
+                          void* dtt, int dtt_on_device, void* dfields, int df_on_device, int schedule, int* passes) {
+    if (!ds || !db || (!dtt && !dfields) || !t)
+        return tape_arg_error(!ds ? "null ds" : (!db ? blk.null_d : (!t ? "null tape" : "dtt and dfields are both null: nothing to compute")));
+    return tape_call(t, schedule, passes, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int& np, int&) {
+        using T = decltype(tag);
+        const bool source = blk.sys == ttcr_amd::CG_SOURCE;
+        T* io = block_prepare<T>(d, blk.sys);
+        if (!source) ttcr_amd::adj_jvp_prepare<T>(d);
+        const T* dds = stage_in<T>(d, ds, ds_on_device, d.model_tmp(), d.n_model());
+        const T* dd = stage_in<T>(d, db, db_on_device, io, d.cg_block(blk.sys));
+        T* ddtt = stage_dst<T>(dtt, dtt_on_device, d.w_tmp);
+        T* ddf = df_on_device ? (T*)dfields : nullptr;
+        const T* mu = nullptr;
+        if (source) {
+            np = ttcr_amd::adj_jvp_joint<T>(d, dds, dd, ddtt, ddf, schedule, &mu);
+        } else {
+            np = ttcr_amd::adj_jvp_rjoint<T>(d, dds, dd, ddtt, ddf, schedule);
+            mu = (const T*)((schedule != 0 && np % 2 == 1) ? d.lam2 : d.lam);
+        }
+        stage_out<T>(d, dtt, dtt_on_device, d.w_tmp, d.n_rows);
+        stage_out<T>(d, dfields, df_on_device, mu, d.n_events * d.nn);
+    });
+}
+int ttcr_fsm_joint_jvp(const ttcr_fsm_adjoint* t, const void* ds, int ds_on_device, const void* dsrc, int dsrc_on_device, void* dtt,
+                       int dtt_on_device, void* dfields, int df_on_device, int schedule, int* passes) {
+    return tape_joint_jvp(t, SOURCE_BLOCK, ds, ds_on_device, dsrc, dsrc_on_device, dtt, dtt_on_device, dfields, df_on_device, schedule, passes);
+}
+int ttcr_fsm_rjoint_jvp(const ttcr_fsm_adjoint* t, const void* ds, int ds_on_device, const void* drcv, int drcv_on_device, void* dtt,
+                        int dtt_on_device, void* dfields, int df_on_device, int schedule, int* passes) {
+    return tape_joint_jvp(t, RCV_BLOCK, ds, ds_on_device, drcv, drcv_on_device, dtt, dtt_on_device, dfields, df_on_device, schedule, passes);
+}
+
+// The joint Gauss-Newton products: one body.  The order of the two checks behind the tape differs between the entries and is kept:
+// rjoint_gn checks the schedule before rcv_scale, joint_gn leaves the schedule to tape_call and so checks it after source_scale.
+static int tape_joint_gn(const ttcr_fsm_adjoint* t, const TapeBlock& blk, const void* v, int v_on_device, const void* v_b, int vb_on_device,
+                         const void* row_weight, int rw_on_device, const double* b_scale, void* out, int out_on_device, void* out_b,
+                         int ob_on_device, int schedule, int* passes_jvp, int* passes_vjp) {
+    const char* bad = !v ? "null v" : (!v_b ? blk.null_v : (!out ? "null out" : (!out_b ? blk.null_out : (!t ? "null tape" : nullptr))));
+    if (!bad && blk.sys == ttcr_amd::CG_RECEIVER) bad = schedule_error(schedule);
+    if (!bad) bad = joint_block_error(b_scale, t->t.cg_block(blk.sys), blk.bad_scale);
+    if (bad) return tape_arg_error(bad);
+    return tape_call(t, schedule, passes_jvp, passes_vjp, [&](ttcr_amd::AdjTapeDev& d, auto tag, int& pj, int& pv) {
+        using T = decltype(tag);
+        const size_t nb = d.cg_block(blk.sys);
+        T* io = block_prepare<T>(d, blk.sys);
+        const T* dv = stage_in<T>(d, v, v_on_device, d.model_tmp(), d.n_model());
+        const T* dve = stage_in<T>(d, v_b, vb_on_device, io, nb);
+        if (row_weight && !rw_on_device) ttcr_amd::adj_jvp_prepare<T>(d);
+        const T* drw = stage_in<T>(d, row_weight, rw_on_device, d.rw_tmp, d.n_rows);
+        if (b_scale) joint_upload<T>(d, b_scale, nb, io + nb);
+        T* dout = stage_dst<T>(out, out_on_device, d.model_tmp());
+        T* dob = stage_dst<T>(out_b, ob_on_device, io + 3 * nb);
+        const T* dc = b_scale ? io + nb : nullptr;
+        if (blk.sys == ttcr_amd::CG_SOURCE) ttcr_amd::adj_gn_joint<T>(d, dv, dve, dc, io + 2 * nb, drw, dout, dob, schedule, &pj, &pv);
+        else ttcr_amd::adj_gn_rjoint<T>(d, dv, dve, dc, io + 2 * nb, drw, dout, dob, schedule, &pj, &pv);
+        stage_out<T>(d, out, out_on_device, d.model_tmp(), d.n_model());
+        stage_out<T>(d, out_b, ob_on_device, io + 3 * nb, nb);
+    });
+}
+int ttcr_fsm_joint_gn(const ttcr_fsm_adjoint* t, const void* v, int v_on_device, const void* v_src, int vs_on_device, const void* row_weight,
+                      int rw_on_device, const double* source_scale, void* out, int out_on_device, void* out_src, int os_on_device,
+                      int schedule, int* passes_jvp, int* passes_vjp) {
+    return tape_joint_gn(t, SOURCE_BLOCK, v, v_on_device, v_src, vs_on_device, row_weight, rw_on_device, source_scale, out, out_on_device,
+                         out_src, os_on_device, schedule, passes_jvp, passes_vjp);
+}
+int ttcr_fsm_rjoint_gn(const ttcr_fsm_adjoint* t, const void* v, int v_on_device, const void* v_rcv, int vr_on_device, const void* row_weight,
+                       int rw_on_device, const double* rcv_scale, void* out, int out_on_device, void* out_rcv, int or_on_device,
+                       int schedule, int* passes_jvp, int* passes_vjp) {
+    return tape_joint_gn(t, RCV_BLOCK, v, v_on_device, v_rcv, vr_on_device, row_weight, rw_on_device, rcv_scale, out, out_on_device, out_rcv,
+                         or_on_device, schedule, passes_jvp, passes_vjp);
+}
+
+// ---- derivatives with respect to the receiver points of the field tape.  Host staging (the table above stage_in
+// continued): rcv_eval stages the events, host points and host results in rcv_stage (7 n_pts values and n_pts ints: points, gradients,
+// traveltimes, events), a buffer of the tape that grows to the largest call and is returned by rcv_release -- its sizes are the caller's,
+// not the tape's --; jvp_rcv a host drcv in rcv_io and a host dtt in w_tmp; vjp_rcv a host w in w_tmp and a host grcv in rcv_io.
 int ttcr_fsm_rcv_eval(const ttcr_fsm_adjoint* t, size_t n_pts, const void* pts, int pts_on_device, const int* event_of_pt, void* tt,
                               int tt_on_device, void* grad, int grad_on_device) {
     const char* bad = (!tt && !grad) ? "tt and grad are both null: nothing to compute"
@@ -4495,102 +4539,7 @@ int ttcr_fsm_rcv_vjp(const ttcr_fsm_adjoint* t, const void* w, int w_on_device, 
         stage_out<T>(d, grcv, grcv_on_device, d.rcv_io, 4 * d.n_rcv_points);
     });
 }
-int ttcr_fsm_rjoint_jvp(const ttcr_fsm_adjoint* t, const void* ds, int ds_on_device, const void* drcv, int drcv_on_device, void* dtt,
-                        int dtt_on_device, void* dfields, int df_on_device, int schedule, int* passes) {
-    if (!ds || !drcv || (!dtt && !dfields) || !t)
-        return tape_arg_error(!ds ? "null ds" : (!drcv ? "null drcv" : (!t ? "null tape" : "dtt and dfields are both null: nothing to compute")));
-    return tape_call(t, schedule, passes, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int& np, int&) {
-        using T = decltype(tag);
-        ttcr_amd::adj_rcv_prepare<T>(d);
-        ttcr_amd::adj_jvp_prepare<T>(d);
-        const T* dds = stage_in<T>(d, ds, ds_on_device, d.model_tmp(), d.n_model());
-        const T* dd = stage_in<T>(d, drcv, drcv_on_device, d.rcv_io, 4 * d.n_rcv_points);
-        // (the fields' tangent does not depend on drcv: it is adj_jvp's, staged as ttcr_fsm_adjoint_jvp stages it)
-        np = ttcr_amd::adj_jvp_rjoint<T>(d, dds, dd, stage_dst<T>(dtt, dtt_on_device, d.w_tmp), df_on_device ? (T*)dfields : nullptr, schedule);
-        stage_out<T>(d, dtt, dtt_on_device, d.w_tmp, d.n_rows);
-        stage_out<T>(d, dfields, df_on_device, (schedule != 0 && np % 2 == 1) ? d.lam2 : d.lam, d.n_events * d.nn);
-    });
-}
-int ttcr_fsm_rjoint_gn(const ttcr_fsm_adjoint* t, const void* v, int v_on_device, const void* v_rcv, int vr_on_device, const void* row_weight,
-                       int rw_on_device, const double* rcv_scale, void* out, int out_on_device, void* out_rcv, int or_on_device,
-                       int schedule, int* passes_jvp, int* passes_vjp) {
-    const char* bad = !v ? "null v" : (!v_rcv ? "null v_rcv" : (!out ? "null out" : (!out_rcv ? "null out_rcv" : (!t ? "null tape" : nullptr))));
-    if (!bad) bad = schedule_error(schedule);
-    if (!bad) bad = joint_block_error(rcv_scale, 4 * t->t.n_rcv_points, "rcv_scale: finite values >= 0");
-    if (bad) return tape_arg_error(bad);
-    return tape_call(t, schedule, passes_jvp, passes_vjp, [&](ttcr_amd::AdjTapeDev& d, auto tag, int& pj, int& pv) {
-        using T = decltype(tag);
-        const size_t blk = 4 * d.n_rcv_points;
-        ttcr_amd::adj_rcv_prepare<T>(d);
-        T* io = (T*)d.rcv_io;
-        const T* dv = stage_in<T>(d, v, v_on_device, d.model_tmp(), d.n_model());
-        const T* dve = stage_in<T>(d, v_rcv, vr_on_device, io, blk);
-        if (row_weight && !rw_on_device) ttcr_amd::adj_jvp_prepare<T>(d);
-        const T* drw = stage_in<T>(d, row_weight, rw_on_device, d.rw_tmp, d.n_rows);
-        if (rcv_scale) joint_upload<T>(d, rcv_scale, blk, io + blk);
-        T* dout = stage_dst<T>(out, out_on_device, d.model_tmp());
-        T* dor = stage_dst<T>(out_rcv, or_on_device, io + 3 * blk);
-        ttcr_amd::adj_gn_rjoint<T>(d, dv, dve, rcv_scale ? io + blk : nullptr, io + 2 * blk, drw, dout, dor, schedule, &pj, &pv);
-        stage_out<T>(d, out, out_on_device, d.model_tmp(), d.n_model());
-        stage_out<T>(d, out_rcv, or_on_device, io + 3 * blk, blk);
-    });
-}
-int ttcr_fsm_rjoint_solve(ttcr_fsm_adjoint* t, const void* rhs, int rhs_on_device, const void* rhs_rcv, int rr_on_device,
-                          const void* row_weight, int rw_on_device, double smooth, const double* smooth_weights, double damp,
-                          const double* rcv_damp, const double* rcv_scale, int maxiter, double rtol, int schedule, void* x,
-                          int x_on_device, void* x_rcv, int xr_on_device, int* status, int* iterations, double* rho, double* pq, int* passes) {
-    const char* bad = nullptr;
-    if (!(smooth >= 0.0) || !std::isfinite(smooth)) bad = "smooth: a finite value >= 0";
-    else if (!(damp >= 0.0) || !std::isfinite(damp)) bad = "damp: a finite value >= 0";
-    else if (maxiter < 1) bad = "maxiter: at least one iteration";
-    else if (!(rtol >= 0.0) || !std::isfinite(rtol)) bad = "rtol: a finite value >= 0";
-    else if (const char* w = normal_weights_error(smooth_weights, "null smooth_weights", "smooth_weights: three finite values >= 0 (x, y, z)"))
-        bad = w;
-    else if (const char* s = schedule_error(schedule)) bad = s;
-    else if (!rhs || !rhs_rcv) bad = !rhs ? "null rhs" : "null rhs_rcv";
-    else if (!x || !x_rcv) bad = !x ? "null x" : "null x_rcv";
-    else if (!status || !iterations || !rho || !pq) bad = "null status, iterations, rho or pq";
-    else if (!t) bad = "null tape";
-    else if (const char* c = joint_block_error(rcv_scale, 4 * t->t.n_rcv_points, "rcv_scale: finite values >= 0")) bad = c;
-    else if (const char* c = joint_block_error(rcv_damp, 4 * t->t.n_rcv_points, "rcv_damp: finite values >= 0")) bad = c;
-    else if (smooth != 0.0) bad = normal_axes_error(t);
-    if (bad) return tape_arg_error(bad);
-    return tape_call(t, schedule, nullptr, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int&, int&) {
-        using T = decltype(tag);
-        const size_t nm = d.n_model(), blk = 4 * d.n_rcv_points;
-        ttcr_amd::adj_rcv_prepare<T>(d);
-        ttcr_amd::adj_rjoint_prepare(d);
-        if (row_weight && !rw_on_device) ttcr_amd::adj_jvp_prepare<T>(d);
-        const T* drw = stage_in<T>(d, row_weight, rw_on_device, d.rw_tmp, d.n_rows);
-        T* r = (T*)d.rj_r;
-        if (nm > 0) HIP_CHECK(hipMemcpyAsync(r, rhs, nm * sizeof(T), rhs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d.stream));
-        if (blk > 0)
-            HIP_CHECK(hipMemcpyAsync(r + nm, rhs_rcv, blk * sizeof(T), rr_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d.stream));
-        const bool with_damp = joint_any(rcv_damp, blk);   // (a term whose factor is 0 everywhere is not evaluated)
-        if (rcv_scale) joint_upload<T>(d, rcv_scale, blk, d.rj_scale);
-        if (with_damp) joint_upload<T>(d, rcv_damp, blk, d.rj_damp);
-        ttcr_amd::NormalOperator op;
-        op.smooth = smooth;
-        op.damp = damp;
-        std::copy(smooth_weights, smooth_weights + 3, op.weights);
-        ttcr_amd::NormalResult res;
-        ttcr_amd::adj_solve_joint<T>(d, drw, op, rcv_scale != nullptr, with_damp, maxiter, rtol, schedule, res, true);
-        const T* xd = (const T*)d.rj_x;
-        if (nm > 0) HIP_CHECK(hipMemcpyAsync(x, xd, nm * sizeof(T), x_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, d.stream));
-        if (blk > 0)
-            HIP_CHECK(hipMemcpyAsync(x_rcv, xd + nm, blk * sizeof(T), xr_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, d.stream));
-        *status = res.status;
-        *iterations = res.iterations;
-        std::copy(res.rho.begin(), res.rho.end(), rho);
-        std::copy(res.pq.begin(), res.pq.end(), pq);
-        if (passes) std::copy(res.passes.begin(), res.passes.end(), passes);
-    });
-}
-int ttcr_fsm_rcv_release(ttcr_fsm_adjoint* t) {
-    if (!t) return tape_arg_error("null tape");
-    std::lock_guard<std::mutex> lock(t->mu);
-    return guarded([&] { ttcr_amd::adj_rcv_release(t->t); });
-}
+int ttcr_fsm_rcv_release(ttcr_fsm_adjoint* t) { return tape_release(t, ttcr_amd::adj_rcv_release); }
 int ttcr_fsm_adjoint_free(ttcr_fsm_adjoint* t) {
     if (!t) return TTCR_OK;
     return guarded([&] { delete t; });

@@ -1,7 +1,8 @@
 // ttcr_amd/csrc/fsm_normal.hip -- translation unit of the field tape's normal-equation solver: the smoothing operator
 // R v = sum_d a_d K_d^T (K_d v) on the tape's model vector, the inner product with a fixed summation order, and conjugate gradients on
 // (H + lam R + mu I) x = b with H the tape's Gauss-Newton (or Newton) product; see fsm_adjoint_api.h.  tests/normal_reference.py restates
-// all of it in numpy.  Compiled with -ffp-contract=off like every other unit: each product, difference, quotient and sum below is
+// all of it in numpy.  The same solver runs the joint hypocentre-velocity system (6j) and the receiver joint system (6k), whose vectors
+// carry an extra block behind the model vector (tests/joint_reference.py, tests/receiver_reference.py).  Compiled with -ffp-contract=off like every other unit: each product, difference, quotient and sum below is
 // rounded on its own, in the order the definition writes them.  No floating-point atomics.
 #include "fsm_adjoint_api.h"
 
@@ -139,8 +140,8 @@ __global__ __launch_bounds__(NRM_THREADS) void nrm_dot_kernel(const T* __restric
     nrm_chunk_partial(e[0], e[1], e[2], e[3], partial);
 }
 
-// kernel 1 of an iteration: q = fl(fl(hp + fl(lam * (R p))) + fl(mu * p)) (the smoothing term only if with_smooth, the damping term only
-// if with_damp), and the chunk partials of <p, q>.  A workgroup owns a chunk of the flat vector, as the partials demand, so the smoothing
+// kernel 1 of an iteration at a parameter of the model vector: q = fl(fl(hp + fl(lam * (R p))) + fl(mu * p)) (the smoothing term only if
+// with_smooth, the damping term only if with_damp).  A workgroup owns a chunk of the flat vector, as the partials demand, so the smoothing
 // gather reads p around each of its parameters from global memory (the expression is nrm_smooth_kernel's: nrm_smooth_at on other strides)
 template <typename T>
 __device__ __forceinline__ T nrm_combine_at(const T* __restrict__ hp, const T* __restrict__ p, size_t i, T pi, const NrmSmooth<T>& sm, T lam,
@@ -154,27 +155,9 @@ __device__ __forceinline__ T nrm_combine_at(const T* __restrict__ hp, const T* _
     return a;
 }
 
-template <typename T>
-__global__ __launch_bounds__(NRM_THREADS) void nrm_combine_kernel(const T* __restrict__ hp, const T* __restrict__ p, T* __restrict__ q,
-                                                                  size_t n, NrmSmooth<T> sm, T lam, T mu, int with_smooth, int with_damp,
-                                                                  double* __restrict__ partial) {
-    double e[4];
-    for (int k = 0; k < 4; ++k) {
-        const size_t i = (size_t)blockIdx.x * NRM_CHUNK + threadIdx.x + (size_t)k * NRM_THREADS;
-        e[k] = 0.0;
-        if (i < n) {
-            const T pi = p[i];
-            const T a = nrm_combine_at<T>(hp, p, i, pi, sm, lam, mu, with_smooth, with_damp);
-            q[i] = a;
-            e[k] = nrm_prod(pi, a);
-        }
-    }
-    nrm_chunk_partial(e[0], e[1], e[2], e[3], partial);
-}
-
-// kernel 1 of a joint iteration over the n_joint elements of the flat joint vector: below n_model the expression of
-// nrm_combine_kernel, above it q = fl(hp + fl(delta * p)) (delta null: q = hp); the chunk partials of <p, q> with the block seam wherever it
-// falls in a chunk
+// kernel 1 over the n_joint elements of the flat vector of a system: below n_model the expression above, in the block behind it (DESIGN.md
+// 6j) q = fl(hp + fl(delta * p)) (delta null: q = hp); the chunk partials of <p, q> with the block seam wherever it falls in a chunk.  The
+// model system has no block: n_joint == n_model and a null delta.
 template <typename T>
 __global__ __launch_bounds__(NRM_THREADS) void jnt_combine_kernel(const T* __restrict__ hp, const T* __restrict__ p, T* __restrict__ q,
                                                                   size_t n_model, size_t n_joint, NrmSmooth<T> sm, T lam, T mu,
@@ -285,22 +268,28 @@ __global__ __launch_bounds__(NRM_THREADS) void nrm_finish_kernel(const double* _
     }
 }
 
-template <typename P>
-void nrm_free(P*& p) {
-    if (p) (void)hipFree((void*)p);
+void nrm_free(void*& p) {
+    if (p) (void)hipFree(p);
     p = nullptr;
 }
 
-size_t nrm_chunks(const AdjTapeDev& t) { return std::max<size_t>(1, (t.n_model() + NRM_CHUNK - 1) / NRM_CHUNK); }
+void cg_free_all(CgWork& w) {
+    nrm_free(w.x); nrm_free(w.r); nrm_free(w.p); nrm_free(w.q); nrm_free(w.hp); nrm_free(w.scale);
+    nrm_free(w.damp); nrm_free(w.ve); nrm_free(w.partial); nrm_free(w.ctl);
+}
+
+size_t nrm_chunks(size_t n) { return std::max<size_t>(1, (n + NRM_CHUNK - 1) / NRM_CHUNK); }
 
 NrmDims nrm_dims(const AdjTapeDev& t) {
     const int c = t.cells ? 1 : 0;
     return NrmDims{t.nnx - c, t.nny - c, t.nnz - c};
 }
 
+// closes the inner product whose chunk partials a kernel of the system has just written
 template <typename T>
-void nrm_close(AdjTapeDev& t, int what) {
-    nrm_finish_kernel<T><<<1, NRM_THREADS, 0, t.stream>>>((const double*)t.nrm_partial, nrm_chunks(t), what, (NrmCtl*)t.nrm_ctl);
+void nrm_close(AdjTapeDev& t, CgSystem sys, int what) {
+    const CgWork& w = t.cg[sys];
+    nrm_finish_kernel<T><<<1, NRM_THREADS, 0, t.stream>>>((const double*)w.partial, nrm_chunks(t.cg_len(sys)), what, (NrmCtl*)w.ctl);
     NRM_CHECK(hipGetLastError());
 }
 
@@ -309,70 +298,65 @@ NrmSmooth<T> nrm_smooth_args(const AdjTapeDev& t, const double* weights) {
     return NrmSmooth<T>{nrm_dims(t), (T)(1.0 / (t.dx * t.dx)), (T)weights[0], (T)weights[1], (T)weights[2]};
 }
 
-// q = A v (v is p of an iteration or x0) and the chunk partials of <v, q>: the product of the tape into hp, then kernel 1
-template <typename T>
-void nrm_apply(AdjTapeDev& t, const T* v, const T* d_rw, const NormalOperator& op, int schedule, int* pj, int* pv) {
-    T* hp = (T*)t.nrm_hp;
-    if (op.newton) adj_hess<T>(t, v, d_rw, true, hp, schedule, pj, pv);
-    else adj_gn<T>(t, v, d_rw, hp, schedule, pj, pv);
-    nrm_combine_kernel<T><<<(unsigned)nrm_chunks(t), NRM_THREADS, 0, t.stream>>>(hp, v, (T*)t.nrm_q, t.n_model(),
-                                                                                nrm_smooth_args<T>(t, op.weights), (T)op.smooth, (T)op.damp,
-                                                                                op.smooth != 0.0, op.damp != 0.0, (double*)t.nrm_partial);
-    NRM_CHECK(hipGetLastError());
-}
-
 }  // namespace
 
 int adj_smooth_tile_edge(size_t elem) { return elem == 4 ? NrmTile<float>::edge : NrmTile<double>::edge; }
 
-size_t adj_normal_bytes(const AdjTapeDev& t) {
-    return 5 * std::max<size_t>(t.n_model() * t.elem, 1) + nrm_chunks(t) * sizeof(double) + sizeof(NrmCtl);
+size_t adj_cg_bytes(const AdjTapeDev& t, CgSystem sys) {
+    const size_t n = t.cg_len(sys);
+    return 5 * std::max<size_t>(n * t.elem, 1) + (sys == CG_MODEL ? 0 : 3 * std::max<size_t>(t.cg_block(sys) * t.elem, 1)) +
+           nrm_chunks(n) * sizeof(double) + sizeof(NrmCtl);
 }
 
-void adj_normal_prepare(AdjTapeDev& t) {
-    if (t.nrm_x) return;
+void adj_cg_prepare(AdjTapeDev& t, CgSystem sys) {
+    CgWork& w = t.cg[sys];
+    if (w.x) return;
     NRM_CHECK(hipSetDevice(t.device));
-    const size_t planned = adj_normal_bytes(t);
+    static const char* const what[3] = {"the normal-equation solver", "the joint solver", "the receiver joint solver"};
+    const size_t planned = adj_cg_bytes(t, sys);
     size_t got = 0;
-    auto alloc = [&](auto*& p, size_t bytes) {
+    auto alloc = [&](void*& p, size_t bytes) {
         const size_t b = std::max<size_t>(bytes, 1);
-        void* raw = nullptr;
-        if (hipMalloc(&raw, b) != hipSuccess) {
+        if (hipMalloc(&p, b) != hipSuccess) {
             (void)hipGetLastError();
+            p = nullptr;
             std::ostringstream m;
-            m << "the normal-equation solver of the field tape needs " << planned << " bytes of device memory on device " << t.device
+            m << what[sys] << " of the field tape needs " << planned << " bytes of device memory on device " << t.device
               << " (an allocation of " << b << " bytes failed)";
             throw AdjDeviceError(m.str());
         }
-        p = (std::remove_reference_t<decltype(p)>)raw;
         got += b;
     };
     try {
-        const size_t vec = t.n_model() * t.elem;
-        alloc(t.nrm_x, vec);
-        alloc(t.nrm_r, vec);
-        alloc(t.nrm_p, vec);
-        alloc(t.nrm_q, vec);
-        alloc(t.nrm_hp, vec);
-        alloc(t.nrm_partial, nrm_chunks(t) * sizeof(double));
-        alloc(t.nrm_ctl, sizeof(NrmCtl));
+        const size_t vec = t.cg_len(sys) * t.elem, blk = t.cg_block(sys) * t.elem;
+        alloc(w.x, vec);
+        alloc(w.r, vec);
+        alloc(w.p, vec);
+        alloc(w.q, vec);
+        alloc(w.hp, vec);
+        if (sys != CG_MODEL) {
+            alloc(w.scale, blk);
+            alloc(w.damp, blk);
+            alloc(w.ve, blk);
+        }
+        alloc(w.partial, nrm_chunks(t.cg_len(sys)) * sizeof(double));
+        alloc(w.ctl, sizeof(NrmCtl));
     } catch (...) {
-        nrm_free(t.nrm_x); nrm_free(t.nrm_r); nrm_free(t.nrm_p); nrm_free(t.nrm_q); nrm_free(t.nrm_hp);
-        nrm_free(t.nrm_partial); nrm_free(t.nrm_ctl);
+        cg_free_all(w);
         throw;
     }
-    t.nrm_bytes = got;
+    w.bytes = got;
     t.total_bytes += got;
 }
 
-void adj_normal_release(AdjTapeDev& t) {
-    if (!t.nrm_x) return;
+void adj_cg_release(AdjTapeDev& t, CgSystem sys) {
+    CgWork& w = t.cg[sys];
+    if (!w.x) return;
     (void)hipSetDevice(t.device);
     if (t.stream) (void)hipStreamSynchronize(t.stream);
-    nrm_free(t.nrm_x); nrm_free(t.nrm_r); nrm_free(t.nrm_p); nrm_free(t.nrm_q); nrm_free(t.nrm_hp);
-    nrm_free(t.nrm_partial); nrm_free(t.nrm_ctl);
-    t.total_bytes -= t.nrm_bytes;
-    t.nrm_bytes = 0;
+    cg_free_all(w);
+    t.total_bytes -= w.bytes;
+    w.bytes = 0;
 }
 
 template <typename T>
@@ -389,41 +373,59 @@ void adj_smooth(AdjTapeDev& t, const T* d_v, const double* weights, T* d_out) {
 
 template <typename T>
 double adj_dot(AdjTapeDev& t, const T* d_a, const T* d_b) {
-    adj_normal_prepare(t);
-    nrm_dot_kernel<T><<<(unsigned)nrm_chunks(t), NRM_THREADS, 0, t.stream>>>(d_a, d_b, t.n_model(), (double*)t.nrm_partial);
+    adj_cg_prepare(t, CG_MODEL);
+    const CgWork& w = t.cg[CG_MODEL];
+    nrm_dot_kernel<T><<<(unsigned)nrm_chunks(t.n_model()), NRM_THREADS, 0, t.stream>>>(d_a, d_b, t.n_model(), (double*)w.partial);
     NRM_CHECK(hipGetLastError());
-    nrm_close<T>(t, NRM_PLAIN);
+    nrm_close<T>(t, CG_MODEL, NRM_PLAIN);
     NrmCtl h;
-    NRM_CHECK(hipMemcpyAsync(&h, t.nrm_ctl, sizeof(h), hipMemcpyDeviceToHost, t.stream));
+    NRM_CHECK(hipMemcpyAsync(&h, w.ctl, sizeof(h), hipMemcpyDeviceToHost, t.stream));
     NRM_CHECK(hipStreamSynchronize(t.stream));
     return h.sum;
 }
 
 template <typename T>
-void adj_solve_normal(AdjTapeDev& t, const T* d_rw, const NormalOperator& op, bool with_x0, int maxiter, double rtol, int schedule,
-                      NormalResult& res) {
+void adj_solve(AdjTapeDev& t, CgSystem sys, const T* d_rw, const NormalOperator& op, bool with_x0, bool with_scale, bool with_damp,
+               int maxiter, double rtol, int schedule, NormalResult& res) {
+    if (sys != CG_MODEL && (with_x0 || op.newton))
+        throw std::invalid_argument("solve: x0 and the Newton product are offered for the model system only");
     NRM_CHECK(hipSetDevice(t.device));
-    adj_normal_prepare(t);
+    adj_cg_prepare(t, sys);
+    const CgWork& wk = t.cg[sys];
     hipStream_t s = t.stream;
-    const size_t n = t.n_model();
-    const unsigned chunks = (unsigned)nrm_chunks(t);
-    T* x = (T*)t.nrm_x;
-    T* r = (T*)t.nrm_r;
-    T* p = (T*)t.nrm_p;
-    T* q = (T*)t.nrm_q;
-    double* partial = (double*)t.nrm_partial;
-    NrmCtl* ctl = (NrmCtl*)t.nrm_ctl;
+    const size_t nm = t.n_model(), n = t.cg_len(sys), blk = t.cg_block(sys);
+    const unsigned chunks = (unsigned)nrm_chunks(n);
+    T* x = (T*)wk.x;
+    T* r = (T*)wk.r;
+    T* p = (T*)wk.p;
+    T* q = (T*)wk.q;
+    T* hp = (T*)wk.hp;
+    const T* c = with_scale ? (const T*)wk.scale : nullptr;
+    const T* delta = with_damp ? (const T*)wk.damp : nullptr;
+    double* partial = (double*)wk.partial;
+    NrmCtl* ctl = (NrmCtl*)wk.ctl;
+    // q = A v (v is p of an iteration or x0) and the chunk partials of <v, q>: the product of the system into hp, then kernel 1
+    auto apply = [&](const T* v, int* pj, int* pv) {
+        if (sys == CG_SOURCE) adj_gn_joint<T>(t, v, v + nm, c, (T*)wk.ve, d_rw, hp, hp + nm, schedule, pj, pv);
+        else if (sys == CG_RECEIVER) adj_gn_rjoint<T>(t, v, v + nm, c, (T*)wk.ve, d_rw, hp, hp + nm, schedule, pj, pv);
+        else if (op.newton) adj_hess<T>(t, v, d_rw, true, hp, schedule, pj, pv);
+        else adj_gn<T>(t, v, d_rw, hp, schedule, pj, pv);
+        jnt_combine_kernel<T><<<chunks, NRM_THREADS, 0, s>>>(hp, v, q, nm, n, nrm_smooth_args<T>(t, op.weights), (T)op.smooth, (T)op.damp,
+                                                            op.smooth != 0.0, op.damp != 0.0, delta, partial);
+        NRM_CHECK(hipGetLastError());
+    };
     res = NormalResult();
-    // rho0 = <rhs, rhs> (rhs is in r), then the starting residual, p and rho
+    // rho0 = <rhs, rhs> (rhs is in r; its block scaled first: (b_s, fl(c * b_e))), then the starting residual, p and rho
     NRM_CHECK(hipMemsetAsync(ctl, 0, sizeof(NrmCtl), s));
+    if (c) adj_scale<T>(t, c, r + nm, r + nm, blk);
     nrm_dot_kernel<T><<<chunks, NRM_THREADS, 0, s>>>(r, r, n, partial);
     NRM_CHECK(hipGetLastError());
-    nrm_close<T>(t, NRM_PLAIN);
-    if (with_x0) nrm_apply<T>(t, x, d_rw, op, schedule, &res.passes0[0], &res.passes0[1]);
+    nrm_close<T>(t, sys, NRM_PLAIN);
+    if (with_x0) apply(x, &res.passes0[0], &res.passes0[1]);
     else if (n > 0) NRM_CHECK(hipMemsetAsync(x, 0, n * sizeof(T), s));
     nrm_start_kernel<T><<<chunks, NRM_THREADS, 0, s>>>(r, q, p, n, with_x0 ? 1 : 0, partial);
     NRM_CHECK(hipGetLastError());
-    nrm_close<T>(t, NRM_RR0);
+    nrm_close<T>(t, sys, NRM_RR0);
     NrmCtl h;
     NRM_CHECK(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, s));
     NRM_CHECK(hipStreamSynchronize(s));
@@ -438,13 +440,13 @@ void adj_solve_normal(AdjTapeDev& t, const T* d_rw, const NormalOperator& op, bo
             break;
         }
         int pj = 0, pv = 0;
-        nrm_apply<T>(t, p, d_rw, op, schedule, &pj, &pv);
+        apply(p, &pj, &pv);
         res.passes.push_back(pj);
         res.passes.push_back(pv);
-        nrm_close<T>(t, NRM_PQ);
+        nrm_close<T>(t, sys, NRM_PQ);
         nrm_update_kernel<T><<<chunks, NRM_THREADS, 0, s>>>(x, r, p, q, n, ctl, partial);
         NRM_CHECK(hipGetLastError());
-        nrm_close<T>(t, NRM_RR);
+        nrm_close<T>(t, sys, NRM_RR);
         nrm_direction_kernel<T><<<(unsigned)std::max<size_t>(1, (n + NRM_THREADS - 1) / NRM_THREADS), NRM_THREADS, 0, s>>>(r, p, n, ctl);
         NRM_CHECK(hipGetLastError());
         NRM_CHECK(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, s));   // the one host read of the iteration: (rho, pq)
@@ -458,174 +460,14 @@ void adj_solve_normal(AdjTapeDev& t, const T* d_rw, const NormalOperator& op, bo
         res.rho.push_back(rho);
         ++res.iterations;
     }
-}
-
-// ---- the joint hypocentre-velocity system and the receiver joint system: one solver over which extra block
-// the joint vector carries behind the model vector -- (t0, x, y, z) of the source points or of the receiver points.  Each has work arrays
-// of its own.
-namespace {
-// the work arrays of one of the two systems, by reference into the tape
-struct JntWork {
-    void*& x; void*& r; void*& p; void*& q; void*& hp; void*& scale; void*& damp; void*& ve; void*& partial; void*& ctl;
-    size_t& bytes;
-    size_t n_joint, n_block;   // elements of a joint vector and of its extra block
-    const char* what;
-};
-JntWork jnt_work(AdjTapeDev& t, bool receiver) {
-    if (receiver)
-        return {t.rj_x, t.rj_r, t.rj_p, t.rj_q, t.rj_hp, t.rj_scale, t.rj_damp, t.rj_ve, t.rj_partial, t.rj_ctl, t.rj_bytes, t.n_rjoint(),
-                4 * t.n_rcv_points, "the receiver joint solver"};
-    return {t.jnt_x, t.jnt_r, t.jnt_p, t.jnt_q, t.jnt_hp, t.jnt_scale, t.jnt_damp, t.jnt_ve, t.jnt_partial, t.jnt_ctl, t.jnt_bytes, t.n_joint(),
-            4 * t.n_points, "the joint solver"};
-}
-size_t jnt_chunks(size_t n_joint) { return std::max<size_t>(1, (n_joint + NRM_CHUNK - 1) / NRM_CHUNK); }
-
-template <typename T>
-void jnt_close(AdjTapeDev& t, const JntWork& w, int what) {
-    nrm_finish_kernel<T><<<1, NRM_THREADS, 0, t.stream>>>((const double*)w.partial, jnt_chunks(w.n_joint), what, (NrmCtl*)w.ctl);
-    NRM_CHECK(hipGetLastError());
-}
-
-void jnt_free_all(const JntWork& w) {
-    nrm_free(w.x); nrm_free(w.r); nrm_free(w.p); nrm_free(w.q); nrm_free(w.hp); nrm_free(w.scale);
-    nrm_free(w.damp); nrm_free(w.ve); nrm_free(w.partial); nrm_free(w.ctl);
-}
-
-size_t jnt_bytes_of(const AdjTapeDev& t, size_t n_joint, size_t n_block) {
-    return 5 * std::max<size_t>(n_joint * t.elem, 1) + 3 * std::max<size_t>(n_block * t.elem, 1) + jnt_chunks(n_joint) * sizeof(double) +
-           sizeof(NrmCtl);
-}
-
-void jnt_prepare(AdjTapeDev& t, const JntWork& w) {
-    if (w.x) return;
-    NRM_CHECK(hipSetDevice(t.device));
-    const size_t planned = jnt_bytes_of(t, w.n_joint, w.n_block);
-    size_t got = 0;
-    auto alloc = [&](void*& p, size_t bytes) {
-        const size_t b = std::max<size_t>(bytes, 1);
-        if (hipMalloc(&p, b) != hipSuccess) {
-            (void)hipGetLastError();
-            p = nullptr;
-            std::ostringstream m;
-            m << w.what << " of the field tape needs " << planned << " bytes of device memory on device " << t.device
-              << " (an allocation of " << b << " bytes failed)";
-            throw AdjDeviceError(m.str());
-        }
-        got += b;
-    };
-    try {
-        const size_t vec = w.n_joint * t.elem, blk = w.n_block * t.elem;
-        alloc(w.x, vec);
-        alloc(w.r, vec);
-        alloc(w.p, vec);
-        alloc(w.q, vec);
-        alloc(w.hp, vec);
-        alloc(w.scale, blk);
-        alloc(w.damp, blk);
-        alloc(w.ve, blk);
-        alloc(w.partial, jnt_chunks(w.n_joint) * sizeof(double));
-        alloc(w.ctl, sizeof(NrmCtl));
-    } catch (...) {
-        jnt_free_all(w);
-        throw;
-    }
-    w.bytes = got;
-    t.total_bytes += got;
-}
-
-void jnt_release(AdjTapeDev& t, const JntWork& w) {
-    if (!w.x) return;
-    (void)hipSetDevice(t.device);
-    if (t.stream) (void)hipStreamSynchronize(t.stream);
-    jnt_free_all(w);
-    t.total_bytes -= w.bytes;
-    w.bytes = 0;
-}
-}  // namespace
-
-size_t adj_joint_bytes(const AdjTapeDev& t) { return jnt_bytes_of(t, t.n_joint(), 4 * t.n_points); }
-void adj_joint_prepare(AdjTapeDev& t) { jnt_prepare(t, jnt_work(t, false)); }
-void adj_joint_release(AdjTapeDev& t) { jnt_release(t, jnt_work(t, false)); }
-size_t adj_rjoint_bytes(const AdjTapeDev& t) { return jnt_bytes_of(t, t.n_rjoint(), 4 * t.n_rcv_points); }
-void adj_rjoint_prepare(AdjTapeDev& t) { jnt_prepare(t, jnt_work(t, true)); }
-void adj_rjoint_release(AdjTapeDev& t) { jnt_release(t, jnt_work(t, true)); }
-
-template <typename T>
-void adj_solve_joint(AdjTapeDev& t, const T* d_rw, const NormalOperator& op, bool with_scale, bool with_damp, int maxiter, double rtol,
-                     int schedule, NormalResult& res, bool receiver) {
-    NRM_CHECK(hipSetDevice(t.device));
-    const JntWork wk = jnt_work(t, receiver);
-    jnt_prepare(t, wk);
-    hipStream_t s = t.stream;
-    const size_t nm = t.n_model(), n = wk.n_joint;
-    const unsigned chunks = (unsigned)jnt_chunks(n);
-    T* x = (T*)wk.x;
-    T* r = (T*)wk.r;
-    T* p = (T*)wk.p;
-    T* q = (T*)wk.q;
-    T* hp = (T*)wk.hp;
-    const T* c = with_scale ? (const T*)wk.scale : nullptr;
-    const T* delta = with_damp ? (const T*)wk.damp : nullptr;
-    double* partial = (double*)wk.partial;
-    NrmCtl* ctl = (NrmCtl*)wk.ctl;
-    res = NormalResult();
-    NRM_CHECK(hipMemsetAsync(ctl, 0, sizeof(NrmCtl), s));
-    if (c) adj_scale<T>(t, c, r + nm, r + nm, wk.n_block);   // the right-hand side of the scaled system: (b_s, fl(c * b_e))
-    nrm_dot_kernel<T><<<chunks, NRM_THREADS, 0, s>>>(r, r, n, partial);
-    NRM_CHECK(hipGetLastError());
-    jnt_close<T>(t, wk, NRM_PLAIN);
-    if (n > 0) NRM_CHECK(hipMemsetAsync(x, 0, n * sizeof(T), s));
-    nrm_start_kernel<T><<<chunks, NRM_THREADS, 0, s>>>(r, q, p, n, 0, partial);
-    NRM_CHECK(hipGetLastError());
-    jnt_close<T>(t, wk, NRM_RR0);
-    NrmCtl h;
-    NRM_CHECK(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, s));
-    NRM_CHECK(hipStreamSynchronize(s));
-    const double rho0 = h.sum;
-    double rho = h.rho;
-    res.rho.push_back(rho0);
-    res.rho.push_back(rho);
-    res.status = 1;
-    for (int k = 1; k <= maxiter; ++k) {
-        if (rho <= rtol * rtol * rho0) {
-            res.status = 0;
-            break;
-        }
-        int pj = 0, pv = 0;
-        if (receiver) adj_gn_rjoint<T>(t, p, p + nm, c, (T*)wk.ve, d_rw, hp, hp + nm, schedule, &pj, &pv);
-        else adj_gn_joint<T>(t, p, p + nm, c, (T*)wk.ve, d_rw, hp, hp + nm, schedule, &pj, &pv);
-        jnt_combine_kernel<T><<<chunks, NRM_THREADS, 0, s>>>(hp, p, q, nm, n, nrm_smooth_args<T>(t, op.weights), (T)op.smooth, (T)op.damp,
-                                                            op.smooth != 0.0, op.damp != 0.0, delta, partial);
-        NRM_CHECK(hipGetLastError());
-        res.passes.push_back(pj);
-        res.passes.push_back(pv);
-        jnt_close<T>(t, wk, NRM_PQ);
-        nrm_update_kernel<T><<<chunks, NRM_THREADS, 0, s>>>(x, r, p, q, n, ctl, partial);
-        NRM_CHECK(hipGetLastError());
-        jnt_close<T>(t, wk, NRM_RR);
-        nrm_direction_kernel<T><<<(unsigned)std::max<size_t>(1, (n + NRM_THREADS - 1) / NRM_THREADS), NRM_THREADS, 0, s>>>(r, p, n, ctl);
-        NRM_CHECK(hipGetLastError());
-        NRM_CHECK(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, s));   // the one host read of the iteration: (rho, pq)
-        NRM_CHECK(hipStreamSynchronize(s));
-        res.pq.push_back(h.pq);
-        if (!h.ok) {
-            res.status = 2;
-            break;
-        }
-        rho = h.rho;
-        res.rho.push_back(rho);
-        ++res.iterations;
-    }
-    if (c) adj_scale<T>(t, c, x + nm, x + nm, wk.n_block);   // x_e = fl(c * z_e)
+    if (c) adj_scale<T>(t, c, x + nm, x + nm, blk);   // x_e = fl(c * z_e)
 }
 
 template void adj_smooth<float>(AdjTapeDev&, const float*, const double*, float*);
 template void adj_smooth<double>(AdjTapeDev&, const double*, const double*, double*);
 template double adj_dot<float>(AdjTapeDev&, const float*, const float*);
 template double adj_dot<double>(AdjTapeDev&, const double*, const double*);
-template void adj_solve_normal<float>(AdjTapeDev&, const float*, const NormalOperator&, bool, int, double, int, NormalResult&);
-template void adj_solve_normal<double>(AdjTapeDev&, const double*, const NormalOperator&, bool, int, double, int, NormalResult&);
-template void adj_solve_joint<float>(AdjTapeDev&, const float*, const NormalOperator&, bool, bool, int, double, int, NormalResult&, bool);
-template void adj_solve_joint<double>(AdjTapeDev&, const double*, const NormalOperator&, bool, bool, int, double, int, NormalResult&, bool);
+template void adj_solve<float>(AdjTapeDev&, CgSystem, const float*, const NormalOperator&, bool, bool, bool, int, double, int, NormalResult&);
+template void adj_solve<double>(AdjTapeDev&, CgSystem, const double*, const NormalOperator&, bool, bool, bool, int, double, int, NormalResult&);
 
 }  // namespace ttcr_amd

@@ -15,6 +15,7 @@ supported, and so is tt_from_rp=True in 3-D (the 3-D default: traveltimes integr
 ray traced back through the field).  What is not on the FSM hot path raises NotImplementedError
 (SPM/DSPM, compute_L).  There is no CPU fallback.
 """
+import collections
 import ctypes as C
 import math
 
@@ -1046,35 +1047,51 @@ class FieldTape:
         iteration), passes ((jvp, vjp) per iteration) and passes_x0.  Array handling as in gauss_newton.  The first call allocates five
         model vectors (nbytes; release_solve returns them)."""
         self._handle()
+        sch, w, maxiter = self._solve_settings(schedule, smooth, damp, rtol, maxiter, hessian, smooth_weights, None)
+        ba, pb, db = self._model_arg(rhs, 'rhs')
+        ra, pr, dr = self._row_arg(row_weight, 'row_weight') if row_weight is not None else (None, None, 0)
+        xa, px0, dx0 = self._model_arg(x0, 'x0') if x0 is not None else (None, None, 0)
+        px, dx, finish = self._model_out(self._first_tensor(rhs, row_weight, x0))
+        self._sync(db, dr, dx0, dx)
+        res = self._solve_results(maxiter, 1)
+        _lib.check(self._lib.ttcr_fsm_normal_solve(self._h, pb, db, pr, dr, float(smooth), w, float(damp), px0, dx0, maxiter, float(rtol),
+                                                   self.HESSIANS[hessian], sch, px, dx, *res))
+        self._refresh_nbytes()
+        x = finish()
+        info = self._solve_info(res, 1, x0 is not None)
+        return (x, info) if return_info else x
+
+    def _solve_settings(self, schedule, smooth, damp, rtol, maxiter, hessian, smooth_weights, system):
+        """the settings every solve checks, in the order it checks them: (schedule code, the weights for the C entry, int(maxiter)).
+        system: None for solve_normal, else the name of a system that offers 'gauss_newton' only"""
         sch = self._schedule(schedule)
         for name, val in (('smooth', smooth), ('damp', damp), ('rtol', rtol)):
             if not (isinstance(val, (int, float, np.floating, np.integer)) and math.isfinite(val) and val >= 0):
                 raise ValueError('%s should be a finite number >= 0, got %r' % (name, val))
         if not isinstance(maxiter, (int, np.integer)) or maxiter < 1:
             raise ValueError('maxiter should be a positive integer, got %r' % (maxiter,))
-        if hessian not in self.HESSIANS:
+        if system is None and hessian not in self.HESSIANS:
             raise ValueError("hessian should be 'gauss_newton' or 'newton', got %r" % (hessian,))
-        w = self._weights(smooth_weights, 'smooth_weights')
-        ba, pb, db = self._model_arg(rhs, 'rhs')
-        ra, pr, dr = self._row_arg(row_weight, 'row_weight') if row_weight is not None else (None, None, 0)
-        xa, px0, dx0 = self._model_arg(x0, 'x0') if x0 is not None else (None, None, 0)
-        px, dx, finish = self._model_out(self._first_tensor(rhs, row_weight, x0))
-        self._sync(db, dr, dx0, dx)
-        maxiter = int(maxiter)
-        status, iters = C.c_int(0), C.c_int(0)
-        rho, pq, passes = (C.c_double * (maxiter + 2))(), (C.c_double * maxiter)(), (C.c_int * (2 * maxiter + 2))()
-        _lib.check(self._lib.ttcr_fsm_normal_solve(self._h, pb, db, pr, dr, float(smooth), w, float(damp), px0, dx0, maxiter, float(rtol),
-                                                   self.HESSIANS[hessian], sch, px, dx, C.byref(status), C.byref(iters), rho, pq, passes))
-        self._refresh_nbytes()
-        x = finish()
+        if system is not None and hessian != 'gauss_newton':
+            raise ValueError("hessian: the %s system offers 'gauss_newton' only, got %r" % (system, hessian))
+        return sch, self._weights(smooth_weights, 'smooth_weights'), int(maxiter)
+
+    @staticmethod
+    def _solve_results(maxiter, lead):
+        """what a solve entry writes, in the order of its arguments: status, iterations, rho, pq, passes -- `lead` pairs of passes (the
+        product A x0 of solve_normal) before those of the iterations"""
+        return (C.c_int(0), C.c_int(0), (C.c_double * (maxiter + 2))(), (C.c_double * maxiter)(), (C.c_int * (2 * (maxiter + lead)))())
+
+    def _solve_info(self, res, lead, with_x0):
+        """the info dict of a solve from _solve_results' buffers; passes becomes the pair of the last product"""
+        status, iters, rho, pq, passes = res
         k = iters.value
         n_pq = k + (1 if status.value == 2 else 0)
-        pairs = [(passes[2 * i], passes[2 * i + 1]) for i in range(n_pq + 1)]
-        self.passes = pairs[-1]    # (of the last product)
-        if not return_info:
-            return x
-        return x, {'status': status.value, 'iterations': k, 'rho': list(rho[:k + 2]), 'pq': list(pq[:n_pq]), 'passes': pairs[1:],
-                   'passes_x0': pairs[0] if x0 is not None else None}
+        pairs = [(passes[2 * i], passes[2 * i + 1]) for i in range(n_pq + lead)]
+        if pairs:
+            self.passes = pairs[-1]    # (of the last product)
+        return {'status': status.value, 'iterations': k, 'rho': list(rho[:k + 2]), 'pq': list(pq[:n_pq]), 'passes': pairs[lead:],
+                'passes_x0': pairs[0] if with_x0 else None}
 
     def release_solve(self):
         """Free the work arrays of smooth / dot / solve_normal (nbytes falls by what the first such call added); the next call allocates
@@ -1083,20 +1100,27 @@ class FieldTape:
         self._refresh_nbytes()
 
     # ---- joint hypocentre-velocity system
-    def _source_arg(self, a, name, n_points=None, what='source'):
-        """a source block, (n_points, 4) values (t0, x, y, z) per point in call order: (array, pointer, on_device).  n_points, what: the
-        receiver block of the receiver joint system instead"""
-        n = self.n_points if n_points is None else n_points
+    # The extra block of a joint system: `count` names the attribute with its number of points, `what` is the word of the messages, `arg`
+    # and `setting` the endings and beginnings of its argument names (dsrc, v_src, rhs_src; source_scale, source_damp), `entry` the stem
+    # of its three C entries (_jvp, _gn, _solve) and `system` its name in solve's hessian message.  The receiver block is that of the
+    # receiver joint system.
+    _JointBlock = collections.namedtuple('_JointBlock', 'count what arg setting entry system')
+    _SOURCE = _JointBlock('n_points', 'source', 'src', 'source', 'ttcr_fsm_joint', 'joint')
+    _RECEIVER = _JointBlock('n_rcv_points', 'receiver', 'rcv', 'rcv', 'ttcr_fsm_rjoint', 'receiver joint')
+
+    def _joint_arg(self, a, name, blk):
+        """a block, (n, 4) values (t0, x, y, z) per point of blk in call order: (array, pointer, on_device)"""
+        n = getattr(self, blk.count)
         a = self._seen(a)
         if tuple(a.shape) != (n, 4):
             raise ValueError('%s should be (%d, 4), one row (t0, x, y, z) per %s point, got shape %s'
-                             % (name, n, what, tuple(a.shape)))
+                             % (name, n, blk.what, tuple(a.shape)))
         return self._arg(a)
 
-    def _source_setting(self, v, name, allow_none, n_points=None):
-        """source_scale / source_damp, (4,) or (n_points, 4) values (source_damp: or a scalar), broadcast to (n_points, 4) doubles for
-        the C entry; None stays None.  n_points: the receiver points' rcv_scale / rcv_damp instead"""
-        n = self.n_points if n_points is None else n_points
+    def _joint_setting(self, v, name, allow_none, blk):
+        """the scale / damping of a block, (4,) or (n, 4) values (the damping: or a scalar), broadcast to (n, 4) doubles for the C entry;
+        None stays None"""
+        n = getattr(self, blk.count)
         if v is None and allow_none:
             return None
         try:
@@ -1111,29 +1135,70 @@ class FieldTape:
         a = np.ascontiguousarray(np.broadcast_to(a, (n, 4)))
         return (C.c_double * max(a.size, 1))(*a.ravel())
 
-    def jvp_joint(self, ds, dsrc, return_fields=False, schedule='tiled'):
-        """J_s ds + J_src dsrc from ONE relaxation: the change of the receiver traveltimes for the slowness perturbation ds (as in jvp)
-        and the source perturbation dsrc, (n_points, 4) values (dt0, dx, dy, dz) per point (as in jvp_source) -- the tangent system is
-        linear, so both operands ride the same pass.  Returns dtt in rcv order; with return_fields=True (dtt, dfields), dfields
-        (n_events, n_nodes).  The values are jvp(ds)'s for dsrc == 0 and jvp_source(dsrc)'s for ds == 0 (the sign of a zero may
-        differ).  Array handling and schedule as in jvp; the result lives where the first torch tensor of (ds, dsrc) does."""
+    def _jvp_joint(self, blk, ds, d_blk, return_fields, schedule):
         self._handle()
         sch = self._schedule(schedule)
         a, pa, da = self._model_arg(ds, 'ds')
-        b, pb, db = self._source_arg(dsrc, 'dsrc')
-        like = self._first_tensor(ds, dsrc)
+        b, pb, db = self._joint_arg(d_blk, 'd' + blk.arg, blk)
+        like = self._first_tensor(ds, d_blk)
         pr, dr, fin_r = self._out(like, 1, self.n_rows, rows=True)
         pf, df, fin_f = self._out(like, self.n_events, self.n_nodes) if return_fields else (None, 0, None)
         self._sync(da, db, dr, df)
         np_ = C.c_int(0)
         want_r, want_f = self.n_rows > 0, return_fields and self.n_events * self.n_nodes > 0
         if want_r or want_f:
-            _lib.check(self._lib.ttcr_fsm_joint_jvp(self._h, pa, da, pb, db, pr if want_r else None, dr, pf if want_f else None, df, sch,
-                                                    C.byref(np_)))
+            _lib.check(getattr(self._lib, blk.entry + '_jvp')(self._h, pa, da, pb, db, pr if want_r else None, dr, pf if want_f else None,
+                                                              df, sch, C.byref(np_)))
         self.passes = np_.value
         self._refresh_nbytes()
         dtt = fin_r()[0]
         return (dtt, fin_f()) if return_fields else dtt
+
+    def _gauss_newton_joint(self, blk, v, v_blk, row_weight, scale, schedule):
+        self._handle()
+        sch = self._schedule(schedule)
+        va, pv, dv = self._model_arg(v, 'v')
+        ea, pe, de = self._joint_arg(v_blk, 'v_' + blk.arg, blk)
+        ra, pr, dr = self._row_arg(row_weight, 'row_weight') if row_weight is not None else (None, None, 0)
+        sc = self._joint_setting(scale, blk.setting + '_scale', True, blk)
+        like = self._first_tensor(v, v_blk, row_weight)
+        pg, dg, fin_g = self._model_out(like)
+        ps, dsb, fin_s = self._out(like, getattr(self, blk.count), 4)
+        self._sync(dv, de, dr, dg, dsb)
+        pj, pa = C.c_int(0), C.c_int(0)
+        _lib.check(getattr(self._lib, blk.entry + '_gn')(self._h, pv, dv, pe, de, pr, dr, sc, pg, dg, ps, dsb, sch, C.byref(pj), C.byref(pa)))
+        self.passes = (pj.value, pa.value)
+        self._refresh_nbytes()
+        return fin_g(), fin_s()
+
+    def _solve_joint(self, blk, rhs, rhs_blk, row_weight, smooth, smooth_weights, damp, blk_damp, blk_scale, maxiter, rtol, schedule,
+                     return_info, hessian):
+        self._handle()
+        sch, w, maxiter = self._solve_settings(schedule, smooth, damp, rtol, maxiter, hessian, smooth_weights, blk.system)
+        ba, pb, db = self._model_arg(rhs, 'rhs')
+        ea, pe, de = self._joint_arg(rhs_blk, 'rhs_' + blk.arg, blk)
+        ra, pr, dr = self._row_arg(row_weight, 'row_weight') if row_weight is not None else (None, None, 0)
+        sd = self._joint_setting(blk_damp, blk.setting + '_damp', False, blk)
+        sc = self._joint_setting(blk_scale, blk.setting + '_scale', True, blk)
+        like = self._first_tensor(rhs, rhs_blk, row_weight)
+        px, dx, fin_x = self._model_out(like)
+        ps, dxs, fin_s = self._out(like, getattr(self, blk.count), 4)
+        self._sync(db, de, dr, dx, dxs)
+        res = self._solve_results(maxiter, 0)
+        _lib.check(getattr(self._lib, blk.entry + '_solve')(self._h, pb, db, pe, de, pr, dr, float(smooth), w, float(damp), sd, sc, maxiter,
+                                                            float(rtol), sch, px, dx, ps, dxs, *res))
+        self._refresh_nbytes()
+        x, xs = fin_x(), fin_s()
+        info = self._solve_info(res, 0, False)
+        return (x, xs, info) if return_info else (x, xs)
+
+    def jvp_joint(self, ds, dsrc, return_fields=False, schedule='tiled'):
+        """J_s ds + J_src dsrc from ONE relaxation: the change of the receiver traveltimes for the slowness perturbation ds (as in jvp)
+        and the source perturbation dsrc, (n_points, 4) values (dt0, dx, dy, dz) per point (as in jvp_source) -- the tangent system is
+        linear, so both operands ride the same pass.  Returns dtt in rcv order; with return_fields=True (dtt, dfields), dfields
+        (n_events, n_nodes).  The values are jvp(ds)'s for dsrc == 0 and jvp_source(dsrc)'s for ds == 0 (the sign of a zero may
+        differ).  Array handling and schedule as in jvp; the result lives where the first torch tensor of (ds, dsrc) does."""
+        return self._jvp_joint(self._SOURCE, ds, dsrc, return_fields, schedule)
 
     def gauss_newton_joint(self, v, v_src, row_weight=None, source_scale=None, schedule='tiled'):
         """The joint Gauss-Newton product (g, g_src) = [J_s  J_src C]^T (row_weight * ([J_s  J_src C] (v, v_src))), C = diag(source_scale):
@@ -1142,21 +1207,7 @@ class FieldTape:
         4) values >= 0 that scale the columns of the source block (0 fixes a parameter) or None: no scaling, no multiplication.  g has the
         bits of the vjp's gradient, g_src = source_scale * its source gradient.  Array handling and schedule as in gauss_newton; passes
         becomes (passes of the jvp, passes of the vjp)."""
-        self._handle()
-        sch = self._schedule(schedule)
-        va, pv, dv = self._model_arg(v, 'v')
-        ea, pe, de = self._source_arg(v_src, 'v_src')
-        ra, pr, dr = self._row_arg(row_weight, 'row_weight') if row_weight is not None else (None, None, 0)
-        sc = self._source_setting(source_scale, 'source_scale', True)
-        like = self._first_tensor(v, v_src, row_weight)
-        pg, dg, fin_g = self._model_out(like)
-        ps, dsrc, fin_s = self._out(like, self.n_points, 4)
-        self._sync(dv, de, dr, dg, dsrc)
-        pj, pa = C.c_int(0), C.c_int(0)
-        _lib.check(self._lib.ttcr_fsm_joint_gn(self._h, pv, dv, pe, de, pr, dr, sc, pg, dg, ps, dsrc, sch, C.byref(pj), C.byref(pa)))
-        self.passes = (pj.value, pa.value)
-        self._refresh_nbytes()
-        return fin_g(), fin_s()
+        return self._gauss_newton_joint(self._SOURCE, v, v_src, row_weight, source_scale, schedule)
 
     def solve_joint(self, rhs, rhs_src, row_weight=None, smooth=0.0, smooth_weights=(1., 1., 1.), damp=0.0, source_damp=0.0,
                     source_scale=None, maxiter=20, rtol=1e-6, schedule='tiled', return_info=False, hessian='gauss_newton'):
@@ -1172,41 +1223,8 @@ class FieldTape:
         else -- recurrence, scalars, statuses, the info dict, the bits being the same under both schedules -- as in solve_normal
         (tests/joint_reference.py restates it).  No x0; hessian other than 'gauss_newton' raises.  Returns (x, x_src), with
         return_info=True (x, x_src, info).  The first call allocates work arrays of its own (nbytes; release_joint returns them)."""
-        self._handle()
-        sch = self._schedule(schedule)
-        for name, val in (('smooth', smooth), ('damp', damp), ('rtol', rtol)):
-            if not (isinstance(val, (int, float, np.floating, np.integer)) and math.isfinite(val) and val >= 0):
-                raise ValueError('%s should be a finite number >= 0, got %r' % (name, val))
-        if not isinstance(maxiter, (int, np.integer)) or maxiter < 1:
-            raise ValueError('maxiter should be a positive integer, got %r' % (maxiter,))
-        if hessian != 'gauss_newton':
-            raise ValueError("hessian: the joint system offers 'gauss_newton' only, got %r" % (hessian,))
-        w = self._weights(smooth_weights, 'smooth_weights')
-        ba, pb, db = self._model_arg(rhs, 'rhs')
-        ea, pe, de = self._source_arg(rhs_src, 'rhs_src')
-        ra, pr, dr = self._row_arg(row_weight, 'row_weight') if row_weight is not None else (None, None, 0)
-        sd = self._source_setting(source_damp, 'source_damp', False)
-        sc = self._source_setting(source_scale, 'source_scale', True)
-        like = self._first_tensor(rhs, rhs_src, row_weight)
-        px, dx, fin_x = self._model_out(like)
-        ps, dxs, fin_s = self._out(like, self.n_points, 4)
-        self._sync(db, de, dr, dx, dxs)
-        maxiter = int(maxiter)
-        status, iters = C.c_int(0), C.c_int(0)
-        rho, pq, passes = (C.c_double * (maxiter + 2))(), (C.c_double * maxiter)(), (C.c_int * (2 * maxiter))()
-        _lib.check(self._lib.ttcr_fsm_joint_solve(self._h, pb, db, pe, de, pr, dr, float(smooth), w, float(damp), sd, sc, maxiter,
-                                                  float(rtol), sch, px, dx, ps, dxs, C.byref(status), C.byref(iters), rho, pq, passes))
-        self._refresh_nbytes()
-        x, xs = fin_x(), fin_s()
-        k = iters.value
-        n_pq = k + (1 if status.value == 2 else 0)
-        pairs = [(passes[2 * i], passes[2 * i + 1]) for i in range(n_pq)]
-        if pairs:
-            self.passes = pairs[-1]    # (of the last product)
-        if not return_info:
-            return x, xs
-        return x, xs, {'status': status.value, 'iterations': k, 'rho': list(rho[:k + 2]), 'pq': list(pq[:n_pq]), 'passes': pairs,
-                       'passes_x0': None}
+        return self._solve_joint(self._SOURCE, rhs, rhs_src, row_weight, smooth, smooth_weights, damp, source_damp, source_scale, maxiter, rtol,
+                                 schedule, return_info, hessian)
 
     def release_joint(self):
         """Free the work arrays of solve_joint (nbytes falls by what the first call added); the next call allocates them again.  The
@@ -1303,7 +1321,7 @@ class FieldTape:
         (dt0, dx, dy, dz) of every point: dtt[row] = dt0 + G[row] . (dx, dy, dz) of the row's point, G = receiver_jacobian().  Returns dtt
         in rcv order.  No relaxation.  Array handling as in jvp."""
         self._handle()
-        a, pa, da = self._source_arg(drcv, 'drcv', self.n_rcv_points, 'receiver')
+        a, pa, da = self._joint_arg(drcv, 'drcv', self._RECEIVER)
         pr, dr, fin_r = self._out(drcv, 1, self.n_rows, rows=True)
         self._sync(da, dr)
         if self.n_rows > 0:
@@ -1323,44 +1341,14 @@ class FieldTape:
         """J_s ds + J_rcv drcv: jvp(ds) with the rows of jvp_receiver(drcv) added, dtt[row] = fl(jvp + jvp_receiver); one tangent
         relaxation.  Returns dtt in rcv order; with return_fields=True (dtt, dfields), dfields being jvp's (a receiver step moves no
         field).  Array handling and schedule as in jvp; the result lives where the first torch tensor of (ds, drcv) does."""
-        self._handle()
-        sch = self._schedule(schedule)
-        a, pa, da = self._model_arg(ds, 'ds')
-        b, pb, db = self._source_arg(drcv, 'drcv', self.n_rcv_points, 'receiver')
-        like = self._first_tensor(ds, drcv)
-        pr, dr, fin_r = self._out(like, 1, self.n_rows, rows=True)
-        pf, df, fin_f = self._out(like, self.n_events, self.n_nodes) if return_fields else (None, 0, None)
-        self._sync(da, db, dr, df)
-        np_ = C.c_int(0)
-        want_r, want_f = self.n_rows > 0, return_fields and self.n_events * self.n_nodes > 0
-        if want_r or want_f:
-            _lib.check(self._lib.ttcr_fsm_rjoint_jvp(self._h, pa, da, pb, db, pr if want_r else None, dr, pf if want_f else None, df, sch,
-                                                     C.byref(np_)))
-        self.passes = np_.value
-        self._refresh_nbytes()
-        dtt = fin_r()[0]
-        return (dtt, fin_f()) if return_fields else dtt
+        return self._jvp_joint(self._RECEIVER, ds, drcv, return_fields, schedule)
 
     def gauss_newton_receiver_joint(self, v, v_rcv, row_weight=None, rcv_scale=None, schedule='tiled'):
         """The receiver joint Gauss-Newton product (g, g_rcv) = [J_s  J_rcv C]^T (row_weight * ([J_s  J_rcv C] (v, v_rcv))), C =
         diag(rcv_scale): one tangent relaxation, one adjoint relaxation and the row kernels.  v: n_cols values; v_rcv: (n_rcv_points, 4);
         rcv_scale as gauss_newton_joint's source_scale, over the receiver points.  g has the bits of vjp's gradient, g_rcv = rcv_scale *
         the receiver gradient.  passes becomes (passes of the jvp, passes of the vjp)."""
-        self._handle()
-        sch = self._schedule(schedule)
-        va, pv, dv = self._model_arg(v, 'v')
-        ea, pe, de = self._source_arg(v_rcv, 'v_rcv', self.n_rcv_points, 'receiver')
-        ra, pr, dr = self._row_arg(row_weight, 'row_weight') if row_weight is not None else (None, None, 0)
-        sc = self._source_setting(rcv_scale, 'rcv_scale', True, self.n_rcv_points)
-        like = self._first_tensor(v, v_rcv, row_weight)
-        pg, dg, fin_g = self._model_out(like)
-        ps, dsr, fin_s = self._out(like, self.n_rcv_points, 4)
-        self._sync(dv, de, dr, dg, dsr)
-        pj, pa = C.c_int(0), C.c_int(0)
-        _lib.check(self._lib.ttcr_fsm_rjoint_gn(self._h, pv, dv, pe, de, pr, dr, sc, pg, dg, ps, dsr, sch, C.byref(pj), C.byref(pa)))
-        self.passes = (pj.value, pa.value)
-        self._refresh_nbytes()
-        return fin_g(), fin_s()
+        return self._gauss_newton_joint(self._RECEIVER, v, v_rcv, row_weight, rcv_scale, schedule)
 
     def solve_receiver_joint(self, rhs, rhs_rcv, row_weight=None, smooth=0.0, smooth_weights=(1., 1., 1.), damp=0.0, rcv_damp=0.0,
                              rcv_scale=None, maxiter=20, rtol=1e-6, schedule='tiled', return_info=False, hessian='gauss_newton'):
@@ -1370,41 +1358,8 @@ class FieldTape:
         hypocentres as receivers of solves from the stations (reciprocity) this is the joint hypocentre-velocity step whose solves and
         fields grow with the stations, not the events.  With rcv_scale all zeros x_rcv is zero and x is solve_normal's.  No x0; hessian
         other than 'gauss_newton' raises.  The first call allocates work arrays of its own (nbytes; release_receiver returns them)."""
-        self._handle()
-        sch = self._schedule(schedule)
-        for name, val in (('smooth', smooth), ('damp', damp), ('rtol', rtol)):
-            if not (isinstance(val, (int, float, np.floating, np.integer)) and math.isfinite(val) and val >= 0):
-                raise ValueError('%s should be a finite number >= 0, got %r' % (name, val))
-        if not isinstance(maxiter, (int, np.integer)) or maxiter < 1:
-            raise ValueError('maxiter should be a positive integer, got %r' % (maxiter,))
-        if hessian != 'gauss_newton':
-            raise ValueError("hessian: the receiver joint system offers 'gauss_newton' only, got %r" % (hessian,))
-        w = self._weights(smooth_weights, 'smooth_weights')
-        ba, pb, db = self._model_arg(rhs, 'rhs')
-        ea, pe, de = self._source_arg(rhs_rcv, 'rhs_rcv', self.n_rcv_points, 'receiver')
-        ra, pr, dr = self._row_arg(row_weight, 'row_weight') if row_weight is not None else (None, None, 0)
-        sd = self._source_setting(rcv_damp, 'rcv_damp', False, self.n_rcv_points)
-        sc = self._source_setting(rcv_scale, 'rcv_scale', True, self.n_rcv_points)
-        like = self._first_tensor(rhs, rhs_rcv, row_weight)
-        px, dx, fin_x = self._model_out(like)
-        ps, dxs, fin_s = self._out(like, self.n_rcv_points, 4)
-        self._sync(db, de, dr, dx, dxs)
-        maxiter = int(maxiter)
-        status, iters = C.c_int(0), C.c_int(0)
-        rho, pq, passes = (C.c_double * (maxiter + 2))(), (C.c_double * maxiter)(), (C.c_int * (2 * maxiter))()
-        _lib.check(self._lib.ttcr_fsm_rjoint_solve(self._h, pb, db, pe, de, pr, dr, float(smooth), w, float(damp), sd, sc, maxiter,
-                                                   float(rtol), sch, px, dx, ps, dxs, C.byref(status), C.byref(iters), rho, pq, passes))
-        self._refresh_nbytes()
-        x, xs = fin_x(), fin_s()
-        k = iters.value
-        n_pq = k + (1 if status.value == 2 else 0)
-        pairs = [(passes[2 * i], passes[2 * i + 1]) for i in range(n_pq)]
-        if pairs:
-            self.passes = pairs[-1]    # (of the last product)
-        if not return_info:
-            return x, xs
-        return x, xs, {'status': status.value, 'iterations': k, 'rho': list(rho[:k + 2]), 'pq': list(pq[:n_pq]), 'passes': pairs,
-                       'passes_x0': None}
+        return self._solve_joint(self._RECEIVER, rhs, rhs_rcv, row_weight, smooth, smooth_weights, damp, rcv_damp, rcv_scale, maxiter, rtol,
+                                 schedule, return_info, hessian)
 
     def release_receiver(self):
         """Free what the receiver calls hold on the device -- the receivers, the point map, G of the rows, the staging arrays and the work
