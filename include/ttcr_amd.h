@@ -99,7 +99,11 @@ void ttcr_fsm_destroy(ttcr_fsm_grid* g);
  * Grid2Drcfs::setSlowness (ttcr/Grid2Drcfs.h:98-138).  n must equal the node count
  * (node grids) or the cell count (cell grids), else TTCR_ERR_RUNTIME with the
  * reference's message.  `s` is a host pointer; the _device variant takes a pointer
- * that is already resident in HBM on the grid's device (no PCIe copy). */
+ * that is already resident in HBM on the grid's device (no PCIe copy).
+ * PRECONDITION: every value is finite and >= 0 (0: what set_velocity makes of an infinite velocity).  The values are not
+ * checked; what the sweep kernels do with a NaN, an infinity or a negative slowness is undefined.  Inside the precondition the
+ * sweeps are tested bit for bit against the reference from subnormal s dx to s dx whose fp32 candidates overflow (nodes then
+ * keep the reference's unreached value max()): DESIGN.md section 4, tests/test_range_gpu.py. */
 int ttcr_fsm_set_slowness(ttcr_fsm_grid* g, const void* s, size_t n);
 int ttcr_fsm_set_slowness_device(ttcr_fsm_grid* g, const void* d_s, size_t n);
 /* The same for a 3-D model that lies in host memory as an (nx, ny, nz) array in C order (z fastest) -- what

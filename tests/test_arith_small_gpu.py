@@ -258,20 +258,38 @@ def test_rotated_template_per_node(oracle, capsys):
 
 @pytest.mark.parametrize("name,arith", [("rand-33x31x35", 1), ("rand2d-150x70", 1), ("rand-33x31x35", 0)],
                          ids=["3d-arith1", "2d-arith1", "3d-default"])
-def test_results_scale_exactly_with_the_units(name, arith):
+def test_results_scale_exactly_with_the_units(oracle, name, arith):
     """slowness and eps times 2^k: every operation of update3_fast / update2_fast (and of the reference's chain) scales exactly by a power of
-    two, and so does the source initialisation s d -- the field times 2^k bit for bit, with the same iteration count"""
+    two, and so does the source initialisation s d -- the field times 2^k bit for bit, with the same iteration count.  3-D: also k = -70
+    and + 60, where fh^2 underflows / comes within 2^8 of overflowing fp32 (update3_fast never forms it).  2-D stays inside +- 40:
+    update2_fast forms fh^2 in fp32.
+    The reference's chain (arith = 0) squares a1 - a2 in fp32 (ttcr/Grid3Drn.h:2943): from s dx 2^-60 down that square is subnormal and the
+    compiled reference itself stops scaling (this model: 591 nodes off at k = -60, 35 777 of 35 805 at k = -70, one iteration fewer).  At
+    k = -70 the default mode is therefore held to what it promises, the oracle's field at k = -70 bit for bit, not to 2^-70 times its own
+    field at k = 0."""
     c = ac.BY_NAME[name]
     s = ac.slowness(c)
     src, rcv = ac.source_array(c), ac.receivers(c)
     out = {}
-    for k in (0, -10, 10):
+    ks = (-10, 10, -40, 40) + ((-70, 60) if c["dim"] == 3 else ())
+    for k in (0,) + ks:
         g = _grid(c, eps=ar.EPS_FIXED * 2.0 ** k)
         g.set_option("arith", arith)
-        tt = g.raytrace(src, rcv, slowness=(s * np.float32(2.0 ** k)).astype(np.float32), aggregate_src=True)
+        sk = (s * np.float32(2.0 ** k)).astype(np.float32)
+        tt = g.raytrace(src, rcv, slowness=sk, aggregate_src=True)
         assert g.last_kernel().endswith(",1>") == (arith == 1)
         out[k] = (_field(g).copy(), g.get_niter(0), tt)
-    for k in (-10, 10):
+        if arith == 0 and k == -70:
+            assert not np.any(c["t0"])
+            o = oracle.solve3d(np.float32, tuple(m - 1 for m in c["n"]), g.dx, (0, 0, 0), ac.flat(c, sk), c["src"], c["t0"], rcv=rcv,
+                               eps=ar.EPS_FIXED * 2.0 ** k, maxit=ar.MAXIT_FIXED)
+            np.testing.assert_array_equal(out[k][0], o["tt"], err_msg=f"{name} k = {k} against the oracle")
+            assert out[k][1] == o["niter"]
+            np.testing.assert_array_equal(tt, o["tt_rcv"])
+            assert np.any(o["tt"] != out[0][0] * np.float32(2.0 ** k))   # (the reference does not scale here)
+    for k in ks:
+        if arith == 0 and k == -70:
+            continue
         np.testing.assert_array_equal(out[k][0], out[0][0] * np.float32(2.0 ** k), err_msg=f"{name} k = {k}")
         assert out[k][1] == out[0][1]
         np.testing.assert_array_equal(out[k][2], out[0][2] * np.float32(2.0 ** k), err_msg=f"{name} k = {k} (receivers)")

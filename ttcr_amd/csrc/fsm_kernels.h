@@ -144,9 +144,16 @@ __device__ __forceinline__ float update3(float ax, float ay, float az, float s, 
         //     fh^2 - u^2 - v^2  >  4e-6 fh (|a1|+|a3|+fh)        ("clearly 3-D")
         // implies t1 > a2 and t2 > a3 with a > 2x margin (derivation: DESIGN.md section 4).  When
         // every live lane is either 1-D or clearly 3-D the wave skips t2 and its fp64 sqrt.
+        // Those error bounds are RELATIVE: they need fh^2, u^2, v^2 in the normal fp32 range.  Below it (fh < 2^-63) the squares
+        // keep a few bits or none, the right-hand side underflows to 0, and a slack that is wrong in sign passed the test (s dx
+        // 2^-74 ... 2^-72: 61 nodes of 13 965 off the reference, tests/test_range_gpu.py).  So the right-hand side is formed from
+        // fh^2 itself, with a floor of 2^-120: no square below that counts as clear (their absolute errors are < 2^-147), an fh^2
+        // that overflowed makes the right-hand side infinite, and from fh^2 = 2^-76 on the floor is below half an ulp of the rest.  Same
+        // operation count as the product form (two fused multiply-adds for two multiplications and an addition).
         const float u = a3 - a1, v = a3 - a2;
-        const float slack = fh * fh - (u * u + v * v);
-        const float thr = 4e-6f * fh * (__builtin_fabsf(a1) + __builtin_fabsf(a3) + fh);
+        const float fh2 = fh * fh;
+        const float slack = fh2 - (u * u + v * v);
+        const float thr = __builtin_fmaf(4e-6f * fh, __builtin_fabsf(a1) + __builtin_fabsf(a3), __builtin_fmaf(4e-6f, fh2, 0x1p-120f));
         if ((beyond1d & ~lanes_gt(slack, thr)) != 0ull) {
             // 2.*fh*fh - (a1-a2)*(a1-a2): fh*fh exact in double, (a1-a2)^2 rounded in float
             const float df = a1 - a2;
@@ -238,8 +245,10 @@ __device__ __forceinline__ double update2_xz(double a, double b, double sn, doub
 //     3-D:  t = a1 + fh/3 (p2 + p3 + sqrt(3 - p2^2 - p3^2 - (p3-p2)^2))  taken when p3^2 + (p3-p2)^2 < 1, which in exact
 //           arithmetic IS the reference's t2 > a3 (update3 above) -- decided before any root, so ONE v_sqrt_f32 per update
 // Both discriminants are > 1 wherever their branch is taken (no cancellation), the two branches meet continuously at the
-// switch (t2 = t3 = a3), and the scaling makes the result independent of the units of slowness and distance (fh^2 may underflow
-// fp32).  The increment t - a1 is good to a few ulp OF ITSELF, the sum rounds once like the reference's final conversion: a
+// switch (t2 = t3 = a3).  The 3-D form never squares fh, so its result scales exactly with the units of slowness and distance
+// wherever fh, 1/fh and the traveltimes are normal fp32 numbers: s dx times 2^k, k = -70 ... +60, gives the field times 2^k bit for
+// bit (fh^2 underflows fp32 from k = -63 on; tests/test_arith_small_gpu.py).  The 2-D form below squares fh in fp32 and claims this
+// for fh^2 and d^2 inside the normal range only (tested for k = -40 ... +40).  The increment t - a1 is good to a few ulp OF ITSELF, the sum rounds once like the reference's final conversion: a
 // result differs from the reference's by at most an ulp of t, and only where the increment's error straddles a rounding
 // boundary.  v_rcp_f32 / v_sqrt_f32 are the 1-ulp hardware approximations; the ~480 cycles of the fp64 chain of a level
 // become ~100.  NOT bit-identical to the reference: opt-in, within north_star's 1e-5 s RMS by orders of magnitude
