@@ -37,9 +37,11 @@ SHAPES_3D = (
     + [(7, 64, 64), (7, 80, 80), (7, 64, 40), (7, 80, 32)]       # 4 and 5 patches along an axis (fp64: 8 / 10 / 5 / 4 along z)
     + [(512, 512, 512)]                                         # 32 x 32 patches, fp64 32 x 64
     + [(9, 32, 640), (9, 32, 320), (9, 640, 32)]                # long and thin: 2 x 40 (fp64: 2 x 80, 2 x 40), 40 x 2
+    + [(17, 33, 34), (17, 34, 33), (41, 18, 5), (9, 49, 17)]    # the shapes of tests/test_weno_2d_gpu.py: last patches of 1 and 2 columns under H = 2
 )
-# 2-D shapes, NODES (nx, nz): z is the level axis, the patches tile x -- 1, 1, 2, 2, 3 and 65 patches
-SHAPES_2D = [(64, 30), (2, 40), (40, 2), (65, 130), (128, 9), (150, 70), (4097, 33)]
+# 2-D shapes, NODES (nx, nz): z is the level axis, the patches tile x -- 1, 1, 2, 2, 3 and 65 patches; then the other 2-D shapes of
+# tests/test_weno_2d_gpu.py: 3 patches (the last of 2 columns) and 2
+SHAPES_2D = [(64, 30), (2, 40), (40, 2), (65, 130), (128, 9), (150, 70), (4097, 33), (130, 65), (66, 37)]
 
 
 @pytest.fixture(scope="module")
@@ -153,7 +155,9 @@ def test_patch_counts_are_the_ones_the_shapes_were_chosen_for(lib):
     assert counts(F32, (70, 17, 9)) == (2, 1) and counts(F32, (2, 16, 10)) == (1, 1) and counts(F32, (5, 16, 8)) == counts(F64, (5, 16, 8)) == (1, 1)
     assert counts(F32, (512, 512, 512)) == (32, 32) and counts(F64, (512, 512, 512)) == (32, 64)
     assert counts(F32, (9, 32, 640)) == (2, 40) and counts(F64, (9, 32, 320)) == (2, 40)
-    assert [geometry(2, F32, s)[4] for s in SHAPES_2D] == [1, 1, 1, 2, 2, 3, 65]
+    assert [geometry(2, F32, s)[4] for s in SHAPES_2D] == [1, 1, 1, 2, 2, 3, 65, 3, 2]
+    assert counts(F32, (17, 33, 34)) == (3, 3) and counts(F64, (17, 33, 34)) == (3, 5) and counts(F64, (17, 34, 33)) == (3, 5)
+    assert counts(F32, (41, 18, 5)) == counts(F64, (41, 18, 5)) == (2, 1) and counts(F32, (9, 49, 17)) == (4, 2) and counts(F64, (9, 49, 17)) == (4, 3)
     for dtype in (F32, F64):   # the list has one word per unit, whatever the order
         assert unit_order(lib, 3, dtype, 0, 1, (37, 35, 41)).size == 8 * int(np.prod(counts(dtype, (37, 35, 41))))
     assert unit_order(lib, 2, F32, 0, 1, (4097, 33)).size == 4 * 65
