@@ -682,6 +682,40 @@ int ttcr_fsm_rjoint_solve(ttcr_fsm_adjoint* t, const void* rhs, int rhs_on_devic
                           int x_on_device, void* x_rcv, int xr_on_device, int* status, int* iterations, double* rho, double* pq, int* passes);
 int ttcr_fsm_rcv_release(ttcr_fsm_adjoint* t);
 
+/* Grid-search hypocentre location on the fields of a field tape (no reference equivalent): for the reciprocal layout, in
+ * which the tape holds the traveltime from every station (a field) to every node, the node with the smallest weighted,
+ * origin-time-corrected misfit of every hypocentre's picks -- the start a Geiger relocation (ttcr_fsm_rcv_eval) needs.  The fields are
+ * read once; nothing is solved or relaxed.  Node or cell tapes alike (the fields hold n_nodes values either way).
+ * Definition, in float64 whatever the tape's dtype, every operation rounded on its own (no fused multiply-add), sums from +0 in ascending
+ * pick order; tests/locate_reference.py restates it.  For hypocentre q with picks k (field f_k, time t_k, weight w_k) and node m:
+ *   sw = sum_k w_k      r_k = fl(t_k - double(T[f_k][m]))      a = sum_k fl(w_k * r_k)      t0 = fl(a / sw)
+ *   d_k = fl(r_k - t0)  phi = sum_k fl(w_k * fl(d_k * d_k))
+ * node_out[q] is the node of the box with the smallest phi, the lowest node index among equal ones (== on doubles); a NaN phi never wins;
+ * t0_out[q] and misfit_out[q] are t0 and phi there.  A hypocentre with sw == 0 (no picks, or all weights zero) or with every phi NaN gets
+ * node -1, t0 +0 and misfit +0.  The minimum over (phi, node) is associative and commutative: no launch shape shows in the bits.
+ * ttcr_fsm_loc_grid: hypo_off (n_hypo + 1, from 0, ascending) are the picks of every hypocentre in pick_field / pick_time / pick_weight
+ *   (host arrays; pick_weight == NULL: all ones; a field may occur several times in one hypocentre); box (may be NULL: the whole grid) =
+ *   i0, i1, j0, j1, k0, k1, half-open node ranges; node_out holds indices of the whole grid ((k nny + j) nnx + i).  volume_out (may be
+ *   NULL): phi of every box node, n_hypo x (box nodes, x fastest within the box) doubles, rows with sw == 0 all +0, on the host or
+ *   (volume_on_device != 0) on the tape's device.  At most 2^22 hypocentres and 2^31 - 1 picks per call.
+ * ttcr_fsm_loc_geometry: the node counts nn[3], the spacing and the origin in the user's coordinates -- node i of an axis lies at
+ *   origin + i dx, as ttcr_fsm_rcv_eval expects a point (translated grids included).
+ * ttcr_fsm_loc_shape: the nodes of a node tile and the hypocentres of a chunk of the search kernel on this tape, and whether the tile's
+ *   field values are staged in LDS (tests place their sizes around both).
+ * The uploaded picks, the partial minima (one per workgroup along the node tiles and hypocentre) and a host volume live in buffers of the
+ * tape that grow to the largest call; ttcr_fsm_adjoint_bytes reports them, TTCR_ERR_DEVICE with the byte count if an allocation fails,
+ * ttcr_fsm_loc_release (and ttcr_fsm_adjoint_free) return them.  No other entry's memory changes.
+ * Argument errors return TTCR_ERR_VALUE naming the argument before any device call: null hypo_off or outputs, offsets that do not start
+ * at 0 or are not ascending, a time that is not finite, a weight that is negative or not finite, a null tape, a field out of range, a box
+ * outside the grid or empty.  Two kernels: the search (a workgroup per set of node tiles and chunk of hypocentres, partial minima) and
+ * the finish (a thread per hypocentre).  No atomics.  Not covered: L1 / EDT misfits, coarse-to-fine search, differential times, 2-D. */
+int ttcr_fsm_loc_geometry(const ttcr_fsm_adjoint* t, int* nn, double* dx, double* origin);
+int ttcr_fsm_loc_shape(const ttcr_fsm_adjoint* t, int* node_tile, int* hypo_chunk, int* staged);
+int ttcr_fsm_loc_grid(const ttcr_fsm_adjoint* t, size_t n_hypo, const long long* hypo_off, const int* pick_field, const double* pick_time,
+                      const double* pick_weight, const int* box, long long* node_out, double* t0_out, double* misfit_out,
+                      void* volume_out, int volume_on_device);
+int ttcr_fsm_loc_release(ttcr_fsm_adjoint* t);
+
 /* Replaces: Grid2D::raytrace(Tx, t0, Rx, traveltimes, l_data, threadNo) (ttcr/Grid2D.h:616-640) and the overload with r_data
  * AND l_data (:583-614) -> Grid2Drn::getRaypath(Tx, t0, Rx, [r_data,] l_data, tt, threadNo) (ttcr/Grid2Drn.h:1852-2190): what
  * `compute_L=True` of the Python layer reaches for 2-D grids with cell slowness (src/ttcrpy/rgrid.pyx:3889-3893, :4060-4143).

@@ -149,6 +149,13 @@ cdef extern from "ttcr_amd.h" nogil:
                               int x_on_device, void* x_rcv, int xr_on_device, int* status, int* iterations, double* rho, double* pq,
                               int* passes)
     int ttcr_fsm_rcv_release(ttcr_fsm_adjoint* t)
+    # grid-search hypocentre location on the fields of a field tape
+    int ttcr_fsm_loc_geometry(const ttcr_fsm_adjoint* t, int* nn, double* dx, double* origin)
+    int ttcr_fsm_loc_shape(const ttcr_fsm_adjoint* t, int* node_tile, int* hypo_chunk, int* staged)
+    int ttcr_fsm_loc_grid(const ttcr_fsm_adjoint* t, size_t n_hypo, const long long* hypo_off, const int* pick_field,
+                          const double* pick_time, const double* pick_weight, const int* box, long long* node_out, double* t0_out,
+                          double* misfit_out, void* volume_out, int volume_on_device)
+    int ttcr_fsm_loc_release(ttcr_fsm_adjoint* t)
     int ttcr_fsm_slot_m_size(const ttcr_fsm_grid* g, int slot, size_t* n_rows, size_t* nnz)
     int ttcr_fsm_get_slot_m(const ttcr_fsm_grid* g, int slot, long long* row_off, long long* j, void* v)
     int ttcr_fsm_raytrace_l(ttcr_fsm_grid* g, int slot, int n_tx, const void* tx, const void* t0, int n_rx, const void* rx,

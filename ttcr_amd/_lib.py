@@ -121,6 +121,11 @@ SYMBOLS = {
     "ttcr_fsm_rjoint_solve": (_I, [_P, _P, _I, _P, _I, _P, _I, _D, C.POINTER(_D), _D, C.POINTER(_D), C.POINTER(_D), _I, _D, _I, _P, _I, _P, _I,
                                    C.POINTER(_I), C.POINTER(_I), C.POINTER(_D), C.POINTER(_D), C.POINTER(_I)]),
     "ttcr_fsm_rcv_release": (_I, [_P]),
+    "ttcr_fsm_loc_geometry": (_I, [_P, C.POINTER(_I), C.POINTER(_D), C.POINTER(_D)]),
+    "ttcr_fsm_loc_shape": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "ttcr_fsm_loc_grid": (_I, [_P, C.c_size_t, C.POINTER(C.c_longlong), C.POINTER(_I), C.POINTER(_D), C.POINTER(_D), C.POINTER(_I),
+                               C.POINTER(C.c_longlong), C.POINTER(_D), C.POINTER(_D), _P, _I]),
+    "ttcr_fsm_loc_release": (_I, [_P]),
     "ttcr_fsm_raytrace_multi_l": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I]),
     "ttcr_fsm_multi_l_size": (_I, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "ttcr_fsm_get_multi_l": (_I, [_P, _P, _P, _P]),

@@ -1287,6 +1287,7 @@ void AdjTapeDev::release() {
     for (CgSystem sys : {CG_MODEL, CG_SOURCE, CG_RECEIVER}) adj_cg_release(*this, sys);
     dev_free(rcv_p); dev_free(rcv_event); dev_free(rcv_pt); dev_free(rcv_rows); dev_free(rcv_off); dev_free(rcv_G); dev_free(rcv_tt);
     dev_free(rcv_io); dev_free(rcv_stage);
+    adj_loc_release(*this);
     rcv_stage_bytes = 0;
     rcv_bytes = 0;
     blk_owns_mu4 = false;

@@ -17,6 +17,8 @@
 //                   products summed in a fixed order (chunks of 1024, one finishing workgroup), and conjugate gradients around the
 //                   Gauss-Newton / Newton product with the scalars of the recurrence formed on the device.  One solver (adj_solve) over
 //                   three systems (CgSystem): the model vector alone, or with the source block (6j) or the receiver block (6k) behind it.
+// Grid search (fsm_locate.hip): per hypocentre the node of the tape's fields with the smallest weighted, origin-time-corrected
+//                   misfit of its picks -- one search kernel (partial minima per workgroup), one finishing kernel; no solve, no relaxation.
 // No floating-point atomics anywhere: every value is one fixed expression of final values, so the bits do not depend on the schedule.
 // Cell tapes (ttcr_fsm_raytrace_multi_adjoint_cells): the model vector holds one slowness per cell and the node slowness is
 // A times it (fsm_cells_to_nodes3d); a jvp first applies A to ds, a vjp ends with A^T on the node gradient (one thread per cell).
@@ -173,6 +175,12 @@ struct AdjTapeDev {
     size_t rcv_bytes = 0;             // what these arrays added to total_bytes
     void* rcv_stage = nullptr;        // staging of rcv_eval at arbitrary points: grow-only, returned by adj_rcv_release
     size_t rcv_stage_bytes = 0;
+    // grid search: the uploaded picks, the partial minima and the results of a call, and the misfit volume of a call that
+    // wants it on the host; both grow to the largest call and are returned by adj_loc_release
+    void* loc_work = nullptr;
+    size_t loc_work_bytes = 0;
+    void* loc_vol = nullptr;
+    size_t loc_vol_bytes = 0;
     size_t n_tiles = 0;
     size_t total_bytes = 0;
     hipStream_t stream = nullptr;
@@ -349,5 +357,35 @@ int adj_jvp_rjoint(AdjTapeDev& t, const T* d_ds, const T* d_drcv, T* d_dtt, T* d
 template <typename T>
 void adj_gn_rjoint(AdjTapeDev& t, const T* d_vs, const T* d_ve, const T* d_scale, T* d_ve_scaled, const T* d_rw, T* d_gs, T* d_ge,
                    int schedule, int* passes_jvp, int* passes_vjp);
+
+// ---- grid-search hypocentre location on the tape's fields (tests/locate_reference.py restates it; kernels in
+// fsm_locate.hip).  Where a call's arrays live in loc_work, all on the tape's device: the picks by hypocentre (CSR: off n_hypo + 1, then
+// field, time, weight per pick; sw[q] = the sum of q's weights from +0 in ascending pick order, formed by the caller), gx partial minima
+// per hypocentre and the three results
+struct LocWork {
+    int* off = nullptr;
+    int* field = nullptr;
+    double* sw = nullptr;
+    double* time = nullptr;
+    double* weight = nullptr;
+    double* part_phi = nullptr;
+    long long* part_node = nullptr;
+    long long* node = nullptr;
+    double* t0 = nullptr;
+    double* misfit = nullptr;
+    int gx = 0;
+};
+// nodes of a node tile and hypocentres of a chunk of the search kernel on this tape, and whether the tile's field values are staged in LDS
+// (they are read from global memory when not even one node per lane fits)
+void adj_loc_shape(const AdjTapeDev& t, int* node_tile, int* hypo_chunk, int* staged);
+// grows loc_work to what a call with n_hypo hypocentres, n_picks picks and a box of n_box nodes needs and names its parts; grows loc_vol
+// to `count` doubles.  Both count in bytes(); AdjDeviceError naming the byte count if an allocation fails.  The stream has to be idle.
+LocWork adj_loc_prepare(AdjTapeDev& t, size_t n_hypo, size_t n_picks, long long n_box);
+double* adj_loc_volume(AdjTapeDev& t, size_t count);
+void adj_loc_release(AdjTapeDev& t);
+// the search over box = (i0, i1, j0, j1, k0, k1), half-open node ranges inside the grid, with the picks uploaded to w: fills w.node, w.t0
+// and w.misfit (n_hypo each); d_vol (n_hypo x box nodes, x fastest within the box; may be null) receives phi of every box node
+template <typename T>
+void adj_loc_search(AdjTapeDev& t, const LocWork& w, size_t n_hypo, const int* box, double* d_vol);
 
 }  // namespace ttcr_amd

@@ -4540,6 +4540,86 @@ int ttcr_fsm_rcv_vjp(const ttcr_fsm_adjoint* t, const void* w, int w_on_device, 
     });
 }
 int ttcr_fsm_rcv_release(ttcr_fsm_adjoint* t) { return tape_release(t, ttcr_amd::adj_rcv_release); }
+
+// ---- grid-search hypocentre location on the tape's fields.  Host staging (the table above stage_in continued): the picks
+// arrive on the host, by hypocentre; offsets (as ints), fields, times, weights (ones for a null pick_weight) and the weight sums go through
+// stage_in into loc_work, the three results come back from it through stage_out, and a host volume is formed in loc_vol -- buffers of
+// the tape that grow to the largest call and are returned by loc_release: their sizes are the caller's, not the tape's.
+int ttcr_fsm_loc_geometry(const ttcr_fsm_adjoint* t, int* nn, double* dx, double* origin) {
+    if (!t || !nn || !dx || !origin) return tape_arg_error(!t ? "null tape" : (!nn ? "null nn" : (!dx ? "null dx" : "null origin")));
+    const ttcr_amd::AdjTapeDev& d = t->t;
+    nn[0] = d.nnx; nn[1] = d.nny; nn[2] = d.nnz;
+    *dx = d.dx;
+    for (int a = 0; a < 3; ++a) origin[a] = d.rcv_min[a] + d.rcv_shift[a];   // (one of the two is zero)
+    return TTCR_OK;
+}
+int ttcr_fsm_loc_shape(const ttcr_fsm_adjoint* t, int* node_tile, int* hypo_chunk, int* staged) {
+    if (!t || !node_tile || !hypo_chunk || !staged) return tape_arg_error("null tape or output pointer");
+    ttcr_amd::adj_loc_shape(t->t, node_tile, hypo_chunk, staged);
+    return TTCR_OK;
+}
+int ttcr_fsm_loc_grid(const ttcr_fsm_adjoint* t, size_t n_hypo, const long long* hypo_off, const int* pick_field, const double* pick_time,
+                      const double* pick_weight, const int* box, long long* node_out, double* t0_out, double* misfit_out,
+                      void* volume_out, int volume_on_device) {
+    // (what can be told without the tape first, the tape last but for the field range and the box: ttcr_fsm_rcv_eval's order)
+    const char* bad = !hypo_off ? "null hypo_off"
+                                : (!node_out ? "null node_out" : (!t0_out ? "null t0_out" : (!misfit_out ? "null misfit_out" : nullptr)));
+    if (bad) return tape_arg_error(bad);
+    if (n_hypo > ((size_t)1 << 22)) return tape_arg_error("n_hypo: at most 2^22 hypocentres per call");
+    if (hypo_off[0] != 0) return tape_arg_error("hypo_off: the first offset is not 0");
+    for (size_t q = 0; q < n_hypo; ++q)
+        if (hypo_off[q + 1] < hypo_off[q]) return tape_arg_error("hypo_off: the offsets are not ascending");
+    const long long n_picks = hypo_off[n_hypo];
+    if (n_picks > 0x7fffffffLL) return tape_arg_error("hypo_off: at most 2^31 - 1 picks per call");
+    if (n_picks > 0 && (!pick_field || !pick_time)) return tape_arg_error(!pick_field ? "null pick_field" : "null pick_time");
+    for (long long k = 0; k < n_picks; ++k) {
+        if (!std::isfinite(pick_time[k])) return tape_arg_error("pick_time: a time that is not finite");
+        if (pick_weight && !(std::isfinite(pick_weight[k]) && pick_weight[k] >= 0))
+            return tape_arg_error("pick_weight: a weight that is negative or not finite");
+    }
+    if (!t) return tape_arg_error("null tape");
+    const ttcr_amd::AdjTapeDev& dev = t->t;
+    for (long long k = 0; k < n_picks; ++k)
+        if (pick_field[k] < 0 || (size_t)pick_field[k] >= dev.n_events) return tape_arg_error("pick_field: a field index out of range");
+    int bx[6] = {0, dev.nnx, 0, dev.nny, 0, dev.nnz};
+    if (box)
+        for (int a = 0; a < 3; ++a) {
+            if (box[2 * a] < 0 || box[2 * a + 1] > bx[2 * a + 1]) return tape_arg_error("box: a node range outside the grid");
+            if (box[2 * a] >= box[2 * a + 1]) return tape_arg_error("box: an empty node range");
+            bx[2 * a] = box[2 * a];
+            bx[2 * a + 1] = box[2 * a + 1];
+        }
+    const long long n_box = (long long)(bx[1] - bx[0]) * (bx[3] - bx[2]) * (bx[5] - bx[4]);
+    if (n_hypo == 0) return TTCR_OK;
+    // the picks as the kernels read them (alive until the frame has waited for the stream)
+    std::vector<int> off(n_hypo + 1), field(pick_field, pick_field + n_picks);
+    std::vector<double> sw(n_hypo), weight((size_t)n_picks, 1.0);
+    if (pick_weight) weight.assign(pick_weight, pick_weight + n_picks);
+    for (size_t q = 0; q <= n_hypo; ++q) off[q] = (int)hypo_off[q];
+    for (size_t q = 0; q < n_hypo; ++q) {
+        double s = 0.0;
+        for (int k = off[q]; k < off[q + 1]; ++k) s = s + weight[k];
+        sw[q] = s;
+    }
+    return tape_call(t, 0, nullptr, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int&, int&) {
+        using T = decltype(tag);
+        const size_t np = (size_t)n_picks, n_vol = n_hypo * (size_t)n_box;
+        const ttcr_amd::LocWork w = ttcr_amd::adj_loc_prepare(d, n_hypo, np, n_box);
+        double* vol = nullptr;
+        if (volume_out) vol = volume_on_device ? (double*)volume_out : ttcr_amd::adj_loc_volume(d, n_vol);
+        stage_in<int>(d, off.data(), 0, w.off, n_hypo + 1);
+        stage_in<int>(d, field.data(), 0, w.field, np);
+        stage_in<double>(d, pick_time, 0, w.time, np);
+        stage_in<double>(d, weight.data(), 0, w.weight, np);
+        stage_in<double>(d, sw.data(), 0, w.sw, n_hypo);
+        ttcr_amd::adj_loc_search<T>(d, w, n_hypo, bx, vol);
+        stage_out<long long>(d, node_out, 0, w.node, n_hypo);
+        stage_out<double>(d, t0_out, 0, w.t0, n_hypo);
+        stage_out<double>(d, misfit_out, 0, w.misfit, n_hypo);
+        stage_out<double>(d, volume_out, volume_on_device, vol, n_vol);
+    });
+}
+int ttcr_fsm_loc_release(ttcr_fsm_adjoint* t) { return tape_release(t, ttcr_amd::adj_loc_release); }
 int ttcr_fsm_adjoint_free(ttcr_fsm_adjoint* t) {
     if (!t) return TTCR_OK;
     return guarded([&] { delete t; });

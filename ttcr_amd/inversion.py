@@ -8,7 +8,8 @@ matrices from the grid geometry alone -- no solver, no device -- and follow the 
   straight_ray_kernel  rgrid.pyx:1381-1720 (3-D), :4259-4470 (2-D, optional elliptical-anisotropy form)   segment lengths per cell
 
 One helper does use a device, through a field tape it is handed: gauss_newton_step, the right-hand side and the solve of a regularised
-Gauss-Newton step (FieldTape.solve_normal); no reference counterpart.
+Gauss-Newton step (FieldTape.solve_normal); no reference counterpart.  And locate, the hypocentres a relocation or a joint
+step starts from: the tape's grid search, an off-node start and a Geiger refinement around FieldTape.receiver_eval.
 """
 import numpy as np
 
@@ -133,6 +134,171 @@ def reciprocal_gauss_newton_step(tape, residual, model, row_weight=None, smooth=
         b = b - smooth * tape.smooth(model, solve_args.get('smooth_weights', (1., 1., 1.)))
     return tape.solve_receiver_joint(b, b_rcv, row_weight=row_weight, smooth=smooth, damp=damp, rcv_damp=rcv_damp, rcv_scale=rcv_scale,
                                      **solve_args)
+
+
+# ---- hypocentre location on a field tape in the reciprocal layout
+LOCATE_HALVINGS = 4      # halvings of a Geiger step that does not decrease the misfit before the hypocentre stops
+LOCATE_MIN_STEP = 1e-6   # ... and it stops when no coordinate of the step exceeds this fraction of dx
+
+
+def _sum_by_hypo(n_hypo, hyp, ranks, vals):
+    """sum of vals (one row per pick) over the picks of every hypocentre, from +0 in ascending pick order: ranks[r] are the picks that
+    are the r-th of their hypocentre, so every addition of a pass goes to a different hypocentre"""
+    acc = np.zeros((n_hypo,) + vals.shape[1:])
+    for sel in ranks:
+        acc[hyp[sel]] = acc[hyp[sel]] + vals[sel]
+    return acc
+
+
+def _misfit(n_hypo, hyp, ranks, sw, tm, wt, tt):
+    """(t0, phi) per hypocentre by locate_grid's formula with tt (one row per pick; further axes: alternatives) in the place of the node
+    values; hypocentres with sw == 0 get NaN"""
+    ex = (slice(None),) + (None,) * (tt.ndim - 1)
+    r = tm[ex] - tt
+    with np.errstate(invalid='ignore', divide='ignore'):
+        t0 = _sum_by_hypo(n_hypo, hyp, ranks, wt[ex] * r) / sw[(slice(None),) + (None,) * (tt.ndim - 1)]
+    d = r - t0[hyp]
+    return t0, _sum_by_hypo(n_hypo, hyp, ranks, wt[ex] * (d * d))
+
+
+def _geiger_step(n_hypo, hyp, ranks, sw, tm, wt, tt, G, damp):
+    """The damped Gauss-Newton step of every hypocentre from the rows (1, Gx, Gy, Gz) and residuals tm - tt of its picks: the origin
+    time is eliminated (weighted means taken off the residuals and the gradients), the 3 x 3 system A dx = b with A = sum w Gc Gc^T +
+    damp * (trace / 3) I, b = sum w Gc rc is solved through the adjugate, elementwise.  Returns (dx (n_hypo, 3), ok): ok is False where
+    the determinant is not a positive finite number (the step is zero there)."""
+    r = tm - tt
+    with np.errstate(invalid='ignore', divide='ignore'):
+        rbar = _sum_by_hypo(n_hypo, hyp, ranks, wt * r) / sw
+        Gbar = _sum_by_hypo(n_hypo, hyp, ranks, wt[:, None] * G) / sw[:, None]
+    rc, Gc = r - rbar[hyp], G - Gbar[hyp]
+    wG = wt[:, None] * Gc
+    b = _sum_by_hypo(n_hypo, hyp, ranks, wG * rc[:, None])
+    a = {}
+    for i in range(3):
+        for j in range(i, 3):
+            a[i, j] = _sum_by_hypo(n_hypo, hyp, ranks, wG[:, i] * Gc[:, j])
+    lam = damp * ((a[0, 0] + a[1, 1] + a[2, 2]) / 3.0)
+    a00, a11, a22, a01, a02, a12 = a[0, 0] + lam, a[1, 1] + lam, a[2, 2] + lam, a[0, 1], a[0, 2], a[1, 2]
+    c00, c01, c02 = a11 * a22 - a12 * a12, a02 * a12 - a01 * a22, a01 * a12 - a02 * a11   # the adjugate of a symmetric matrix
+    c11, c12, c22 = a00 * a22 - a02 * a02, a01 * a02 - a00 * a12, a00 * a11 - a01 * a01
+    det = a00 * c00 + a01 * c01 + a02 * c02
+    ok = np.isfinite(det) & (det > 0)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        dx = np.stack([c00 * b[:, 0] + c01 * b[:, 1] + c02 * b[:, 2], c01 * b[:, 0] + c11 * b[:, 1] + c12 * b[:, 2],
+                       c02 * b[:, 0] + c12 * b[:, 1] + c22 * b[:, 2]], axis=1) / det[:, None]
+    ok &= np.all(np.isfinite(dx), axis=1)
+    dx[~ok] = 0.0
+    return dx, ok
+
+
+def locate(tape, pick_hypo, pick_field, pick_time, pick_weight=None, n_hypo=None, box=None, refine=10, damp=1e-3):
+    """Hypocentres from picks on a field tape in the reciprocal layout (field e: the traveltimes from station e): the grid search
+    tape.locate_grid, a start off the grid planes, and up to `refine` Geiger iterations around tape.receiver_eval.  Picks, weights,
+    n_hypo and box as locate_grid takes them (ValueError alike).  Returns (t0, xyz, misfit, info): t0 (n_hypo,), xyz (n_hypo, 3) user
+    coordinates and misfit (n_hypo,), float64 numpy arrays -- the misfit is locate_grid's phi with the interpolated traveltime in the place
+    of the node value; a hypocentre the grid search gives no node (-1) gets NaN coordinates, t0 0 and misfit 0 and is left alone.  xyz can go
+    straight to raytrace_adjoint(..., rcv=xyz) and set_receiver_points.  Plain numpy in float64 on the host; the device is used by
+    locate_grid and receiver_eval only.
+      1. The grid search.
+      2. The start: of the up to 8 cells that touch the best node, the centres of those inside the grid and inside the box (an axis on
+         which the box holds a single node plane restricts nothing) are candidates; one receiver_eval call evaluates all of them, the
+         smallest misfit wins, the first in the order x outer, z inner, minus before plus among equal ones.  A point on a grid plane
+         has a zero gradient along that axis, a node along all three: a cell centre has none.
+      3. The refinement, one receiver_eval call per iteration for the hypocentres still moving.  From traveltimes and gradients at its
+         point a hypocentre forms the Geiger step (rows (1, Gx, Gy, Gz), weights w, origin time eliminated, A = sum w Gc Gc^T + damp *
+         (trace / 3) I, solved through the 3 x 3 adjugate) and proposes point + step, every coordinate clipped to the grid.  An
+         iteration evaluates the proposals: where the misfit is smaller than at the point, the proposal becomes the point (a counted
+         iteration) and a new full step is formed there; otherwise the same step is proposed halved once more, and after
+         LOCATE_HALVINGS halvings without a decrease the hypocentre stops.  It also stops when the system is singular or no
+         coordinate of a step exceeds LOCATE_MIN_STEP * dx.  The misfit therefore never increases; refine=0 returns the start.
+    info: node, grid_t0 and grid_misfit (the grid search's results), start_xyz and start_misfit (step 2), iterations (accepted steps
+    per hypocentre) and misfit (the final one, as returned)."""
+    from .rgrid import FieldTape
+
+    if not isinstance(refine, (int, np.integer)) or refine < 0:
+        raise ValueError('refine should be an integer >= 0, got %r' % (refine,))
+    nn3, dx, origin = tape.geometry
+    nq, off, fld, tm, wt, b6 = FieldTape.locate_csr(tape.n_events, nn3, pick_hypo, pick_field, pick_time, pick_weight, n_hypo, box)
+    node, t0g, phig = tape.locate_grid(pick_hypo, pick_field, pick_time, pick_weight, n_hypo=nq, box=box)
+    node = np.asarray(node, dtype=np.int64)
+    wt = np.ones(tm.shape[0]) if wt is None else wt
+    hyp = np.repeat(np.arange(nq), np.diff(off))
+    live = node >= 0
+    keep = live[hyp]                                     # the picks of the hypocentres that have a node
+    hyp, fld, tm, wt = hyp[keep], fld[keep], tm[keep], wt[keep]
+    rank = np.arange(keep.size)[keep] - off[:-1][hyp] if hyp.size else hyp
+    ranks = [np.flatnonzero(rank == r) for r in range(int(rank.max()) + 1 if rank.size else 0)]
+    sw = _sum_by_hypo(nq, hyp, ranks, wt)
+    nn = np.asarray(nn3, dtype=np.int64)
+    lo, hi = origin, origin + (nn - 1) * dx
+
+    def evaluate(pts):
+        """traveltime and gradient of every kept pick at the point of its hypocentre, float64"""
+        tt, G = tape.receiver_eval(pts[hyp], fld, return_grad=True)
+        return np.asarray(tt, dtype=np.float64), np.asarray(G, dtype=np.float64)
+
+    # 2. the start
+    ijk = np.stack([node % nn[0], (node // nn[0]) % nn[1], node // (nn[0] * nn[1])], axis=1)
+    ijk[~live] = 0
+    blo = np.array([b6[0], b6[2], b6[4]], dtype=np.int64)
+    bhi = np.array([b6[1], b6[3], b6[5]], dtype=np.int64) - 1     # last node of the box
+    single = bhi == blo
+    clo, chi = np.where(single, 0, blo), np.where(single, nn - 2, bhi - 1)   # lower nodes of the cells allowed
+    cand = np.zeros((nq, 8, 3))
+    valid = np.zeros((nq, 8), dtype=bool)
+    c = 0
+    for sx in (-1, 1):
+        for sy in (-1, 1):
+            for sz in (-1, 1):
+                cell = ijk + (np.array([sx, sy, sz]) - 1) // 2                      # lower node of the cell on that side
+                valid[:, c] = np.all((cell >= clo) & (cell <= chi), axis=1) & live
+                cand[:, c] = origin + (np.where(valid[:, c, None], cell, np.clip(cell, 0, nn - 2)) + 0.5) * dx
+                c += 1
+    n_pick = hyp.shape[0]
+    if n_pick:
+        tt8, G8 = tape.receiver_eval(cand[hyp].reshape(-1, 3), np.repeat(fld, 8), return_grad=True)
+        tt8 = np.asarray(tt8, dtype=np.float64).reshape(n_pick, 8)
+        G8 = np.asarray(G8, dtype=np.float64).reshape(n_pick, 8, 3)
+    else:
+        tt8, G8 = np.zeros((0, 8)), np.zeros((0, 8, 3))
+    t08, phi8 = _misfit(nq, hyp, ranks, sw, tm, wt, tt8)
+    phi8 = np.where(valid & ~np.isnan(phi8), phi8, np.inf)
+    best = np.argmin(phi8, axis=1)                        # (the first among equal ones)
+    rows = np.arange(nq)
+    x = cand[rows, best]
+    phi, t0 = phi8[rows, best], t08[rows, best]
+    live &= np.isfinite(phi)
+    x[~live], phi[~live], t0[~live] = np.nan, 0.0, 0.0
+    start_xyz, start_phi = x.copy(), phi.copy()
+    iterations = np.zeros(nq, dtype=np.int64)
+
+    # 3. the refinement
+    moving = live.copy()
+    halvings = np.zeros(nq, dtype=np.int64)
+    step = np.zeros((nq, 3))
+    if refine > 0 and n_pick:
+        step, ok = _geiger_step(nq, hyp, ranks, sw, tm, wt, tt8[np.arange(n_pick), best[hyp]], G8[np.arange(n_pick), best[hyp]], damp)
+        moving &= ok & (np.max(np.abs(step), axis=1) > LOCATE_MIN_STEP * dx)
+    for _ in range(int(refine)):
+        if not moving.any():
+            break
+        trial = np.where(moving[:, None], np.clip(x + step * (0.5 ** halvings)[:, None], lo, hi), x)
+        sel = moving[hyp]                                   # only the picks of the hypocentres still moving are evaluated
+        tt, G = np.zeros(n_pick), np.zeros((n_pick, 3))
+        tt[sel], G[sel] = [np.asarray(a, dtype=np.float64) for a in tape.receiver_eval(trial[hyp[sel]], fld[sel], return_grad=True)]
+        t0t, phit = _misfit(nq, hyp, ranks, sw, tm, wt, tt)
+        better = moving & (phit < phi)
+        x[better], phi[better], t0[better] = trial[better], phit[better], t0t[better]
+        iterations[better] += 1
+        halvings[better] = 0
+        new_step, ok = _geiger_step(nq, hyp, ranks, sw, tm, wt, tt, G, damp)
+        step[better] = new_step[better]
+        worse = moving & ~better
+        halvings[worse] += 1
+        moving &= np.where(better, ok & (np.max(np.abs(step), axis=1) > LOCATE_MIN_STEP * dx), halvings <= LOCATE_HALVINGS)
+    info = dict(node=node, grid_t0=np.asarray(t0g, dtype=np.float64), grid_misfit=np.asarray(phig, dtype=np.float64), start_xyz=start_xyz,
+                start_misfit=start_phi, iterations=iterations, misfit=phi.copy())
+    return t0, x, phi, info
 
 
 def straight_ray_kernel(Tx, Rx, axes, aniso=False):

@@ -568,6 +568,10 @@ class FieldTape:
     rcv_point_of_row their rows (set_receiver_points groups the rows of one hypocentre; the default is one point per row);
     jvp_joint_receiver, gauss_newton_receiver_joint and solve_receiver_joint are the joint calls with the receiver block in the place
     of the source block, release_receiver frees what these calls hold on the device.
+    The hypocentres those calls start from, in the same layout: locate_grid (per hypocentre the node of the fields with the smallest
+    weighted, origin-time-corrected misfit of its picks, optionally the whole misfit volume; no solve), geometry (node counts, spacing,
+    origin in user coordinates), node_coordinates (a node index as a point) and release_locate; inversion.locate adds the off-node start
+    and the Geiger refinement around receiver_eval.
     wrt is 'nodes' or 'cells': what the model vector of vjp / jvp / gauss_newton holds, n_cols values -- the node slowness (n_cols =
     n_nodes) or, for the tape of raytrace_adjoint(..., wrt='cells'), the cell slowness in set_slowness's flat order (n_cols = cells).
     Fields, field cotangents and field tangents hold n_nodes values per event on either tape."""
@@ -741,6 +745,21 @@ class FieldTape:
                 r = torch.from_numpy(r)
             return r
         return _ptr(o), 0, finish
+
+    @staticmethod
+    def _typed(a, ctype):
+        """a contiguous host array of fixed dtype (locate_grid's int64 / int32 / float64 arrays) as POINTER(ctype); None stays None"""
+        return None if a is None else a.ctypes.data_as(C.POINTER(ctype))
+
+    def _out64(self, on_device, n):
+        """a float64 output of n values, on the tape's device (a tensor) or on the host (numpy): (array, pointer, on_device)"""
+        if on_device:
+            import torch
+
+            o = torch.empty(max(n, 1), dtype=torch.float64, device=self._dev)
+            return o, C.c_void_p(o.data_ptr()), 1
+        o = np.empty(max(n, 1), dtype=np.float64)
+        return o, _ptr(o), 0
 
     def _model_out(self, like):
         """an output model vector where `like` lives: (pointer, on_device, finish)"""
@@ -1366,6 +1385,124 @@ class FieldTape:
         arrays of solve_receiver_joint (nbytes falls by what they added); the next receiver call uploads them again.  The receiver
         points stay as set.  Nothing of the other calls is touched."""
         _lib.check(self._lib.ttcr_fsm_rcv_release(self._handle()))
+        self._refresh_nbytes()
+
+    # ---- grid-search hypocentre location (DESIGN.md 6l)
+    @property
+    def geometry(self):
+        """(nn3, dx, origin): the node counts (nnx, nny, nnz), the spacing and the origin (3,) in the user's coordinates -- node i of an
+        axis lies at origin + i * dx, as receiver_eval expects a point (translated grids included)."""
+        nn, dx, o = (C.c_int * 3)(), C.c_double(0), (C.c_double * 3)()
+        _lib.check(self._lib.ttcr_fsm_loc_geometry(self._handle(), nn, C.byref(dx), o))
+        return tuple(nn), dx.value, np.array(o[:], dtype=np.float64)
+
+    @property
+    def locate_shape(self):
+        """(node_tile, hypo_chunk, staged) of locate_grid's search kernel on this tape: nodes per node tile, hypocentres per chunk, and
+        whether a tile's field values are staged in LDS (they are not when the tape holds too many fields)."""
+        a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+        _lib.check(self._lib.ttcr_fsm_loc_shape(self._handle(), C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, bool(c.value)
+
+    @staticmethod
+    def locate_csr(n_fields, nn3, pick_hypo, pick_field, pick_time, pick_weight=None, n_hypo=None, box=None):
+        """The checks of locate_grid and the picks by hypocentre, no device: (n_hypo, off, field, time, weight, box6) -- off (n_hypo + 1)
+        int64, the picks grouped by hypocentre in ascending pick index (a stable grouping), weight None or float64, box6 the six ints
+        i0, i1, j0, j1, k0, k1.  ValueError for what the C entry refuses."""
+        def host(a, name, kinds):
+            try:
+                a = np.asarray(a.detach().cpu().numpy() if hasattr(a, 'detach') else a)
+            except (TypeError, ValueError):
+                raise ValueError('%s should be an array of numbers, got %r' % (name, a))
+            if a.ndim != 1 or (a.size > 0 and a.dtype.kind not in kinds):
+                raise ValueError('%s should be one-dimensional %s, got shape %s and dtype %s'
+                                 % (name, 'integers' if kinds == 'iu' else 'numbers', a.shape, a.dtype))
+            return a
+        hyp, fld = host(pick_hypo, 'pick_hypo', 'iu').astype(np.int64), host(pick_field, 'pick_field', 'iu').astype(np.int64)
+        tm = host(pick_time, 'pick_time', 'iuf').astype(np.float64)
+        n = hyp.shape[0]
+        wt = None if pick_weight is None else host(pick_weight, 'pick_weight', 'iuf').astype(np.float64)
+        if fld.shape[0] != n or tm.shape[0] != n or (wt is not None and wt.shape[0] != n):
+            raise ValueError('pick_hypo, pick_field, pick_time and pick_weight should hold one value per pick, got %d, %d, %d and %s'
+                             % (n, fld.shape[0], tm.shape[0], 'None' if wt is None else wt.shape[0]))
+        top = int(hyp.max()) + 1 if n else 0
+        if n_hypo is None:
+            n_hypo = top
+        if not isinstance(n_hypo, (int, np.integer)) or n_hypo < top or n_hypo > 2 ** 22:
+            raise ValueError('n_hypo should be an integer from %d (the largest hypocentre index + 1) to 2^22, got %r' % (top, n_hypo))
+        if n and hyp.min() < 0:
+            raise ValueError('pick_hypo should be >= 0, got %d' % hyp.min())
+        if n and (fld.min() < 0 or fld.max() >= n_fields):
+            raise ValueError('pick_field should be in 0 .. %d, got %d .. %d' % (n_fields - 1, fld.min(), fld.max()))
+        if not np.all(np.isfinite(tm)):
+            raise ValueError('pick_time should be finite')
+        if wt is not None and not (np.all(np.isfinite(wt)) and np.all(wt >= 0)):
+            raise ValueError('pick_weight should be finite and >= 0')
+        if box is None:
+            box = tuple((0, int(m)) for m in nn3)
+        try:
+            b6 = [int(v) for ax in box for v in ax]
+            ok = len(b6) == 6 and len(box) == 3 and all(len(ax) == 2 for ax in box)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError('box should be ((i0, i1), (j0, j1), (k0, k1)), got %r' % (box,))
+        for a in range(3):
+            if b6[2 * a] < 0 or b6[2 * a + 1] > nn3[a]:
+                raise ValueError('box: the node range %r of axis %d is outside 0 .. %d' % (tuple(b6[2 * a:2 * a + 2]), a, nn3[a]))
+            if b6[2 * a] >= b6[2 * a + 1]:
+                raise ValueError('box: the node range %r of axis %d is empty' % (tuple(b6[2 * a:2 * a + 2]), a))
+        order = np.argsort(hyp, kind='stable')
+        off = np.zeros(int(n_hypo) + 1, dtype=np.int64)
+        np.cumsum(np.bincount(hyp, minlength=int(n_hypo)), out=off[1:])
+        return int(n_hypo), off, fld[order], tm[order], None if wt is None else wt[order], b6
+
+    def locate_grid(self, pick_hypo, pick_field, pick_time, pick_weight=None, n_hypo=None, box=None, return_misfit=False):
+        """Grid-search location on the tape's fields (reciprocal layout: field e holds the traveltime from station e to every node): per
+        hypocentre the node with the smallest weighted, origin-time-corrected misfit of its picks.  Pick i says: hypocentre
+        pick_hypo[i] was seen by field pick_field[i] at time pick_time[i], with weight pick_weight[i] (>= 0; None: all ones); n_hypo
+        defaults to the largest hypocentre index + 1.  In float64, every operation rounded on its own, for hypocentre q with picks k in
+        ascending pick index and node m:
+            sw = sum w_k;  r_k = t_k - T[f_k][m];  t0 = (sum w_k r_k) / sw;  phi = sum w_k (r_k - t0)^2
+        box = ((i0, i1), (j0, j1), (k0, k1)), half-open node ranges (default: the whole grid), restricts the search.  Returns (node, t0,
+        misfit), numpy arrays of n_hypo values: node (int64, index of the whole grid, (k nny + j) nnx + i) has the smallest phi, the
+        lowest index among equal ones, a NaN phi never winning; t0 and misfit (float64) are t0 and phi there.  A hypocentre without picks
+        or with all weights zero gets node -1, t0 0 and misfit 0.  return_misfit=True appends the volume, phi of every box node, shape
+        (n_hypo, nk, nj, ni), float64: a numpy array, or a tensor on the tape's device when pick_time is a tensor there.  No solve, no
+        relaxation; the result depends on no launch shape.  The first call allocates work arrays that grow to the largest call
+        (nbytes; release_locate returns them).  ValueError for bad arguments before any device call."""
+        self._handle()
+        nn3 = self.geometry[0]
+        nq, off, fld, tm, wt, b6 = self.locate_csr(self.n_events, nn3, pick_hypo, pick_field, pick_time, pick_weight, n_hypo, box)
+        node, t0, mis = np.full(max(nq, 1), -1, dtype=np.int64), np.zeros(max(nq, 1)), np.zeros(max(nq, 1))
+        shape = (nq, b6[5] - b6[4], b6[3] - b6[2], b6[1] - b6[0])
+        vol, pv, dv = self._out64(self._on_device(pick_time), math.prod(shape)) if return_misfit else (None, None, 0)
+        self._sync(dv)
+        fld = np.ascontiguousarray(fld, dtype=np.int32)
+        LL, D, I = C.c_longlong, C.c_double, C.c_int
+        if nq > 0:
+            _lib.check(self._lib.ttcr_fsm_loc_grid(self._h, nq, self._typed(off, LL), self._typed(fld, I), self._typed(tm, D),
+                                                   self._typed(wt, D), (C.c_int * 6)(*b6), self._typed(node, LL), self._typed(t0, D),
+                                                   self._typed(mis, D), pv, dv))
+        self._refresh_nbytes()
+        out = (node[:nq], t0[:nq], mis[:nq])
+        return out + (vol[:math.prod(shape)].reshape(shape),) if return_misfit else out
+
+    def node_coordinates(self, node):
+        """(n, 3) float64 user coordinates of the nodes `node` (indices of the whole grid, as locate_grid returns them); NaN for -1."""
+        nn3, dx, origin = self.geometry
+        node = np.asarray(node, dtype=np.int64).reshape(-1)
+        if node.size and (node.min() < -1 or node.max() >= self.n_nodes):
+            raise ValueError('node should be in -1 .. %d, got %d .. %d' % (self.n_nodes - 1, node.min(), node.max()))
+        ijk = np.stack([node % nn3[0], (node // nn3[0]) % nn3[1], node // (nn3[0] * nn3[1])], axis=1)
+        xyz = origin[None, :] + ijk.astype(np.float64) * dx
+        xyz[node < 0] = np.nan
+        return xyz
+
+    def release_locate(self):
+        """Free the work arrays of locate_grid (nbytes falls by what its calls added); the next call allocates them again.  Nothing of the
+        other calls is touched."""
+        _lib.check(self._lib.ttcr_fsm_loc_release(self._handle()))
         self._refresh_nbytes()
 
     def _refresh_nbytes(self):
