@@ -716,6 +716,53 @@ int ttcr_fsm_loc_grid(const ttcr_fsm_adjoint* t, size_t n_hypo, const long long*
                       void* volume_out, int volume_on_device);
 int ttcr_fsm_loc_release(ttcr_fsm_adjoint* t);
 
+/* Double-difference rows of a field tape (no reference equivalent): the data operator of the Gauss-Newton / Newton products
+ * and of the three solves as B = diag(row_weight) + Q^T diag(pair_weight) Q instead of the diagonal alone.  Row p of Q holds +1 at tape
+ * row a_p and -1 at tape row b_p: the difference of two rows, e.g. the arrival-time difference of two neighbouring events at one station
+ * (hypoDD / tomoDD).  Pairs may join rows of any two events of the tape, may repeat, and a row may be in no pair; the default is no pairs.
+ * Definition in the tape's dtype, every operation rounded on its own (no fused multiply-add), no atomics; tests/dd_reference.py restates it.
+ * The entries of row r are the pairs p with a_p == r (sign +) or b_p == r (sign -), in ascending p.
+ *   Q x:    d[p] = fl(x[a_p] - x[b_p])
+ *   Q^T y:  out[r] = a chain from +0 over the entries of r, acc = fl(acc + y[p]) or fl(acc - y[p])
+ *   B x:    u[p] = fl(pw[p] * d[p]);  out[r] = a chain from fl(rw[r] * x[r]) (row_weight == NULL: from x[r]) over the entries of r,
+ *           acc = fl(acc + u[p]) or fl(acc - u[p])
+ * A product with pair_weight has the bits of the product it extends with its fl(row_weight * dtt) step replaced by B dtt; everything
+ * before and after that step is unchanged.  With no pairs and an empty pair_weight the bits are those of the call without pair_weight.
+ * A vector that is constant over the rows is in the null space of Q: pure double-difference data (row_weight all zero) leave the common
+ * origin-time shift of the joint systems undetermined, which is what source_damp / rcv_damp are for.
+ * ttcr_fsm_dd_pairs: set_row_a / set_row_b (both NULL: query only) replace the pair list, set_n_pairs pairs in tape rows; the CSR by row
+ *   is built on the host and what earlier pair calls hold on the device is freed.  Refused with TTCR_ERR_VALUE, *bad_pair (may be NULL; -1
+ *   otherwise) receiving the first offending pair: a == b, a row outside 0 .. n_rows - 1; more than 2^30 - 1 pairs.  n_pairs, row_a, row_b
+ *   (may be NULL) receive the list as it stands.
+ * ttcr_fsm_dd_apply: mode 0: out (n_pairs) = Q x, x n_rows values; mode 1: out (n_rows) = Q^T x, x n_pairs values; mode 2: out (n_rows) =
+ *   B x with row_weight (n_rows, may be NULL) and pair_weight (n_pairs; NULL: ones, u = d without a multiplication).  x and out are
+ *   different arrays.
+ * ttcr_fsm_dd_gn: system 0: ttcr_fsm_adjoint_gn (newton != 0: ttcr_fsm_adjoint_newton; v_b, b_scale, out_b unused); system 1:
+ *   ttcr_fsm_joint_gn; system 2: ttcr_fsm_rjoint_gn -- with pair_weight (n_pairs values, host or device, not NULL), otherwise the
+ *   arguments, checks and results of that entry.
+ * ttcr_fsm_dd_solve: system 0: ttcr_fsm_normal_solve (rhs_b, b_damp, b_scale, x_b unused); 1: ttcr_fsm_joint_solve; 2:
+ *   ttcr_fsm_rjoint_solve (x0 and newton: system 0 only) -- the same conjugate gradients on the products above.
+ * Work arrays: the CSR, a, b, one pair array, one staging array for a host pair_weight and one row array, allocated by the first call that
+ *   uses pairs, counted by ttcr_fsm_adjoint_bytes, TTCR_ERR_DEVICE with the byte count if that fails; ttcr_fsm_dd_release (and
+ *   ttcr_fsm_adjoint_free) return them, the pairs stay as set.  Before ttcr_fsm_dd_pairs no entry's memory changes.
+ * Argument errors return TTCR_ERR_VALUE naming the argument before any device call: a bad mode / system / newton, null arrays, a null
+ *   tape, no pairs set, a host pair_weight that is negative or not finite, and the errors of the entry a call extends.  Two kernels (one
+ *   thread per pair, one thread per row) on the tape's stream.  Not covered: pairs in the block products, differential times in
+ *   ttcr_fsm_loc_grid, a relocation-only system, 2-D. */
+int ttcr_fsm_dd_pairs(ttcr_fsm_adjoint* t, const int* set_row_a, const int* set_row_b, size_t set_n_pairs, size_t* n_pairs, int* row_a,
+                      int* row_b, long long* bad_pair);
+int ttcr_fsm_dd_apply(const ttcr_fsm_adjoint* t, int mode, const void* x, int x_on_device, const void* row_weight, int rw_on_device,
+                      const void* pair_weight, int pw_on_device, void* out, int out_on_device);
+int ttcr_fsm_dd_gn(const ttcr_fsm_adjoint* t, int system, int newton, const void* v, int v_on_device, const void* v_b, int vb_on_device,
+                   const void* row_weight, int rw_on_device, const void* pair_weight, int pw_on_device, const double* b_scale, void* out,
+                   int out_on_device, void* out_b, int ob_on_device, int schedule, int* passes_jvp, int* passes_vjp);
+int ttcr_fsm_dd_solve(ttcr_fsm_adjoint* t, int system, const void* rhs, int rhs_on_device, const void* rhs_b, int rb_on_device,
+                      const void* row_weight, int rw_on_device, const void* pair_weight, int pw_on_device, double smooth,
+                      const double* smooth_weights, double damp, const double* b_damp, const double* b_scale, const void* x0,
+                      int x0_on_device, int maxiter, double rtol, int newton, int schedule, void* x, int x_on_device, void* x_b,
+                      int xb_on_device, int* status, int* iterations, double* rho, double* pq, int* passes);
+int ttcr_fsm_dd_release(ttcr_fsm_adjoint* t);
+
 /* Replaces: Grid2D::raytrace(Tx, t0, Rx, traveltimes, l_data, threadNo) (ttcr/Grid2D.h:616-640) and the overload with r_data
  * AND l_data (:583-614) -> Grid2Drn::getRaypath(Tx, t0, Rx, [r_data,] l_data, tt, threadNo) (ttcr/Grid2Drn.h:1852-2190): what
  * `compute_L=True` of the Python layer reaches for 2-D grids with cell slowness (src/ttcrpy/rgrid.pyx:3889-3893, :4060-4143).

@@ -156,6 +156,21 @@ cdef extern from "ttcr_amd.h" nogil:
                           const double* pick_time, const double* pick_weight, const int* box, long long* node_out, double* t0_out,
                           double* misfit_out, void* volume_out, int volume_on_device)
     int ttcr_fsm_loc_release(ttcr_fsm_adjoint* t)
+    # double-difference rows of a field tape
+    int ttcr_fsm_dd_pairs(ttcr_fsm_adjoint* t, const int* set_row_a, const int* set_row_b, size_t set_n_pairs, size_t* n_pairs,
+                          int* row_a, int* row_b, long long* bad_pair)
+    int ttcr_fsm_dd_apply(const ttcr_fsm_adjoint* t, int mode, const void* x, int x_on_device, const void* row_weight, int rw_on_device,
+                          const void* pair_weight, int pw_on_device, void* out, int out_on_device)
+    int ttcr_fsm_dd_gn(const ttcr_fsm_adjoint* t, int system, int newton, const void* v, int v_on_device, const void* v_b,
+                       int vb_on_device, const void* row_weight, int rw_on_device, const void* pair_weight, int pw_on_device,
+                       const double* b_scale, void* out, int out_on_device, void* out_b, int ob_on_device, int schedule,
+                       int* passes_jvp, int* passes_vjp)
+    int ttcr_fsm_dd_solve(ttcr_fsm_adjoint* t, int system, const void* rhs, int rhs_on_device, const void* rhs_b, int rb_on_device,
+                          const void* row_weight, int rw_on_device, const void* pair_weight, int pw_on_device, double smooth,
+                          const double* smooth_weights, double damp, const double* b_damp, const double* b_scale, const void* x0,
+                          int x0_on_device, int maxiter, double rtol, int newton, int schedule, void* x, int x_on_device, void* x_b,
+                          int xb_on_device, int* status, int* iterations, double* rho, double* pq, int* passes)
+    int ttcr_fsm_dd_release(ttcr_fsm_adjoint* t)
     int ttcr_fsm_slot_m_size(const ttcr_fsm_grid* g, int slot, size_t* n_rows, size_t* nnz)
     int ttcr_fsm_get_slot_m(const ttcr_fsm_grid* g, int slot, long long* row_off, long long* j, void* v)
     int ttcr_fsm_raytrace_l(ttcr_fsm_grid* g, int slot, int n_tx, const void* tx, const void* t0, int n_rx, const void* rx,

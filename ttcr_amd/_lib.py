@@ -126,6 +126,13 @@ SYMBOLS = {
     "ttcr_fsm_loc_grid": (_I, [_P, C.c_size_t, C.POINTER(C.c_longlong), C.POINTER(_I), C.POINTER(_D), C.POINTER(_D), C.POINTER(_I),
                                C.POINTER(C.c_longlong), C.POINTER(_D), C.POINTER(_D), _P, _I]),
     "ttcr_fsm_loc_release": (_I, [_P]),
+    "ttcr_fsm_dd_pairs": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(_I), C.POINTER(_I),
+                               C.POINTER(C.c_longlong)]),
+    "ttcr_fsm_dd_apply": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I]),
+    "ttcr_fsm_dd_gn": (_I, [_P, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, C.POINTER(_D), _P, _I, _P, _I, _I, C.POINTER(_I), C.POINTER(_I)]),
+    "ttcr_fsm_dd_solve": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _D, C.POINTER(_D), _D, C.POINTER(_D), C.POINTER(_D), _P, _I, _I, _D, _I,
+                               _I, _P, _I, _P, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_D), C.POINTER(_D), C.POINTER(_I)]),
+    "ttcr_fsm_dd_release": (_I, [_P]),
     "ttcr_fsm_raytrace_multi_l": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I]),
     "ttcr_fsm_multi_l_size": (_I, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "ttcr_fsm_get_multi_l": (_I, [_P, _P, _P, _P]),

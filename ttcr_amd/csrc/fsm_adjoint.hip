@@ -441,6 +441,34 @@ __global__ void tan_scale_rows_kernel(const T* __restrict__ rw, T* __restrict__ 
     if (r < n_rows) w[r] = rw[r] * w[r];
 }
 
+// ---- double-difference rows: the data operator B = diag(rw) + Q^T diag(pw) Q in a pair-major pass and one serial chain
+// per row.  out[p] = fl(x[a_p] - x[b_p]), times pw[p] (rounded on its own) if pw is given; one thread per pair, a, b, pw and out
+// coalesced, the two reads of x gathered
+template <typename T>
+__global__ void dd_pairs_kernel(const int* __restrict__ a, const int* __restrict__ b, const T* __restrict__ pw, const T* __restrict__ x,
+                                size_t n_pairs, T* __restrict__ out) {
+    const size_t p = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (p >= n_pairs) return;
+    const T d = x[a[p]] - x[b[p]];
+    out[p] = pw ? pw[p] * d : d;
+}
+
+// out[row] = a chain over the row's entries (ent[c] = 2 p + sign, ascending p): acc = fl(acc + u[p]), or fl(acc - u[p]) for sign 1.  It
+// starts from +0 (x null), from x[row] (rw null) or from fl(rw[row] * x[row]); one thread per row
+template <typename T>
+__global__ void dd_rows_kernel(const int* __restrict__ off, const int* __restrict__ ent, const T* __restrict__ u, const T* __restrict__ rw,
+                               const T* __restrict__ x, size_t n_rows, T* __restrict__ out) {
+    const size_t r = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (r >= n_rows) return;
+    T acc = x ? (rw ? rw[r] * x[r] : x[r]) : T(0);
+    for (int c = off[r]; c < off[r + 1]; ++c) {
+        const int e = ent[c];
+        const T v = u[e >> 1];
+        acc = (e & 1) ? acc - v : acc + v;
+    }
+    out[r] = acc;
+}
+
 // ---- derivatives with respect to the source points: mu = dT/d(t0, x, y, z) . dsrc per event, K columns at once.  A source
 // enters the scheme through its frozen nodes only, T[m] = t0 + d_m s[m]: there mu is set by src_seed_kernel and left alone by the
 // relaxation; everywhere else mu obeys the tangent's triangular system with the slowness term switched off.  The K values of a node are
@@ -1288,6 +1316,7 @@ void AdjTapeDev::release() {
     dev_free(rcv_p); dev_free(rcv_event); dev_free(rcv_pt); dev_free(rcv_rows); dev_free(rcv_off); dev_free(rcv_G); dev_free(rcv_tt);
     dev_free(rcv_io); dev_free(rcv_stage);
     adj_loc_release(*this);
+    adj_dd_release(*this);
     rcv_stage_bytes = 0;
     rcv_bytes = 0;
     blk_owns_mu4 = false;
@@ -1626,15 +1655,104 @@ int adj_jvp(AdjTapeDev& t, const T* d_ds, T* d_dtt, T* d_dfields, int schedule) 
     return adj_jvp_impl<T>(t, d_ds, d_dtt, d_dfields, schedule, nullptr, nullptr);
 }
 
+// ---- double-difference rows
+void adj_dd_set_pairs(AdjTapeDev& t, const int* row_a, const int* row_b, size_t n_pairs) {
+    adj_dd_release(t);   // (what is on the device belongs to the old list)
+    t.h_dd_a.assign(row_a, row_a + n_pairs);
+    t.h_dd_b.assign(row_b, row_b + n_pairs);
+    t.n_pairs = n_pairs;
+    t.dd_set = true;
+    t.h_dd_off.assign(t.n_rows + 1, 0);
+    for (size_t p = 0; p < n_pairs; ++p) {
+        t.h_dd_off[row_a[p] + 1] += 1;
+        t.h_dd_off[row_b[p] + 1] += 1;
+    }
+    for (size_t r = 0; r < t.n_rows; ++r) t.h_dd_off[r + 1] += t.h_dd_off[r];
+    t.h_dd_ent.assign(2 * n_pairs, 0);
+    std::vector<int> fill(t.h_dd_off.begin(), t.h_dd_off.end() - 1);
+    for (size_t p = 0; p < n_pairs; ++p) {   // (ascending p within a row)
+        t.h_dd_ent[fill[row_a[p]]++] = (int)(2 * p);
+        t.h_dd_ent[fill[row_b[p]]++] = (int)(2 * p + 1);
+    }
+}
+
+size_t adj_dd_bytes(const AdjTapeDev& t) {
+    auto at_least_1 = [](size_t b) { return std::max<size_t>(b, 1); };
+    return 2 * at_least_1(t.n_pairs * sizeof(int)) + at_least_1((t.n_rows + 1) * sizeof(int)) + at_least_1(2 * t.n_pairs * sizeof(int)) +
+           2 * at_least_1(t.n_pairs * t.elem) + at_least_1(t.n_rows * t.elem);
+}
+
+void adj_dd_prepare(AdjTapeDev& t) {
+    if (t.dd_off) return;
+    ADJ_CHECK(hipSetDevice(t.device));
+    Alloc alloc{t, adj_dd_bytes(t)};
+    const size_t before = t.total_bytes;
+    try {
+        alloc(t.dd_a, t.n_pairs * sizeof(int));
+        alloc(t.dd_b, t.n_pairs * sizeof(int));
+        alloc(t.dd_off, (t.n_rows + 1) * sizeof(int));
+        alloc(t.dd_ent, 2 * t.n_pairs * sizeof(int));
+        alloc(t.dd_u, t.n_pairs * t.elem);
+        alloc(t.dd_pw, t.n_pairs * t.elem);
+        alloc(t.dd_rows, t.n_rows * t.elem);
+        ADJ_CHECK(hipMemcpyAsync(t.dd_off, t.h_dd_off.data(), (t.n_rows + 1) * sizeof(int), hipMemcpyHostToDevice, t.stream));
+        if (t.n_pairs > 0) {
+            ADJ_CHECK(hipMemcpyAsync(t.dd_a, t.h_dd_a.data(), t.n_pairs * sizeof(int), hipMemcpyHostToDevice, t.stream));
+            ADJ_CHECK(hipMemcpyAsync(t.dd_b, t.h_dd_b.data(), t.n_pairs * sizeof(int), hipMemcpyHostToDevice, t.stream));
+            ADJ_CHECK(hipMemcpyAsync(t.dd_ent, t.h_dd_ent.data(), 2 * t.n_pairs * sizeof(int), hipMemcpyHostToDevice, t.stream));
+        }
+    } catch (...) {
+        dev_free(t.dd_a); dev_free(t.dd_b); dev_free(t.dd_off); dev_free(t.dd_ent); dev_free(t.dd_u); dev_free(t.dd_pw); dev_free(t.dd_rows);
+        t.total_bytes = before;
+        throw;
+    }
+    t.dd_bytes = t.total_bytes - before;
+}
+
+void adj_dd_release(AdjTapeDev& t) {
+    if (!t.dd_off) return;
+    (void)hipSetDevice(t.device);
+    if (t.stream) (void)hipStreamSynchronize(t.stream);
+    dev_free(t.dd_a); dev_free(t.dd_b); dev_free(t.dd_off); dev_free(t.dd_ent); dev_free(t.dd_u); dev_free(t.dd_pw); dev_free(t.dd_rows);
+    t.total_bytes -= t.dd_bytes;
+    t.dd_bytes = 0;
+}
+
 template <typename T>
-void adj_gn(AdjTapeDev& t, const T* d_v, const T* d_rw, T* d_out, int schedule, int* passes_jvp, int* passes_vjp) {
-    T* w = (T*)t.w_tmp;
-    *passes_jvp = adj_jvp<T>(t, d_v, w, nullptr, schedule);
-    if (d_rw && t.n_rows > 0) {
-        tan_scale_rows_kernel<T><<<blocks_for(t.n_rows), ADJ_THREADS, 0, t.stream>>>(d_rw, w, t.n_rows);
+void adj_dd_apply(AdjTapeDev& t, int mode, const T* d_x, const T* d_rw, const T* d_pw, T* d_out) {
+    ADJ_CHECK(hipSetDevice(t.device));
+    adj_dd_prepare(t);
+    hipStream_t s = t.stream;
+    if (mode != 1 && t.n_pairs > 0) {
+        dd_pairs_kernel<T><<<blocks_for(t.n_pairs), ADJ_THREADS, 0, s>>>(t.dd_a, t.dd_b, mode == 2 ? d_pw : nullptr, d_x, t.n_pairs,
+                                                                         mode == 0 ? d_out : (T*)t.dd_u);
         ADJ_CHECK(hipGetLastError());
     }
-    *passes_vjp = adj_vjp<T>(t, w, nullptr, d_out, schedule);
+    if (mode != 0 && t.n_rows > 0) {
+        dd_rows_kernel<T><<<blocks_for(t.n_rows), ADJ_THREADS, 0, s>>>(t.dd_off, t.dd_ent, mode == 1 ? d_x : (const T*)t.dd_u,
+                                                                       mode == 2 ? d_rw : nullptr, mode == 2 ? d_x : nullptr, t.n_rows, d_out);
+        ADJ_CHECK(hipGetLastError());
+    }
+}
+
+template <typename T>
+const T* adj_row_operator(AdjTapeDev& t, const RowOp<T>& op, T* d_w) {
+    if (!op.pw) {
+        if (op.rw && t.n_rows > 0) {
+            tan_scale_rows_kernel<T><<<blocks_for(t.n_rows), ADJ_THREADS, 0, t.stream>>>(op.rw, d_w, t.n_rows);
+            ADJ_CHECK(hipGetLastError());
+        }
+        return d_w;
+    }
+    adj_dd_apply<T>(t, 2, d_w, op.rw, op.pw, (T*)t.dd_rows);
+    return (const T*)t.dd_rows;
+}
+
+template <typename T>
+void adj_gn(AdjTapeDev& t, const T* d_v, const RowOp<T>& op, T* d_out, int schedule, int* passes_jvp, int* passes_vjp) {
+    T* w = (T*)t.w_tmp;
+    *passes_jvp = adj_jvp<T>(t, d_v, w, nullptr, schedule);
+    *passes_vjp = adj_vjp<T>(t, adj_row_operator<T>(t, op, w), nullptr, d_out, schedule);
 }
 
 // ---- second-order products
@@ -1675,7 +1793,7 @@ int adj_hold(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, int schedule
 // tangent relaxation of v -> dD and q from final values (q written into g, the seeds of the relaxation that follows) -> adjoint relaxation
 // of lam2 for the field cotangent q (newton: and the rows rw * J v) -> gradient with the direct term; a cell tape ends with A^T
 template <typename T>
-void adj_hess(AdjTapeDev& t, const T* d_v, const T* d_rw, bool newton, T* d_out, int schedule, int* passes_jvp, int* passes_vjp) {
+void adj_hess(AdjTapeDev& t, const T* d_v, const RowOp<T>& op, bool newton, T* d_out, int schedule, int* passes_jvp, int* passes_vjp) {
     if (!t.held) throw std::invalid_argument("no held cotangent: call hold first");
     hipStream_t s = t.stream;
     const size_t E = t.n_events, en = E * t.nn;
@@ -1684,10 +1802,7 @@ void adj_hess(AdjTapeDev& t, const T* d_v, const T* d_rw, bool newton, T* d_out,
     const T* mu = nullptr;
     const T* v_nodes = nullptr;
     *passes_jvp = adj_jvp_impl<T>(t, d_v, newton ? w : nullptr, nullptr, schedule, &mu, &v_nodes);
-    if (newton && d_rw && t.n_rows > 0) {
-        tan_scale_rows_kernel<T><<<blocks_for(t.n_rows), ADJ_THREADS, 0, s>>>(d_rw, w, t.n_rows);
-        ADJ_CHECK(hipGetLastError());
-    }
+    const T* rows = newton ? adj_row_operator<T>(t, op, w) : nullptr;
     if (en > 0) {
         const dim3 grid(blocks_for(t.nn), (unsigned)E);
         hess_dd_kernel<T><<<grid, ADJ_THREADS, 0, s>>>((const T*)t.fields, t.frozen, mu, geo, (T*)t.hess_dd);
@@ -1697,7 +1812,7 @@ void adj_hess(AdjTapeDev& t, const T* d_v, const T* d_rw, bool newton, T* d_out,
         ADJ_CHECK(hipGetLastError());
     }
     const T* lam2 = nullptr;
-    *passes_vjp = adj_vjp_impl<T>(t, newton ? w : nullptr, (const T*)t.g, nullptr, schedule, &lam2);
+    *passes_vjp = adj_vjp_impl<T>(t, rows, (const T*)t.g, nullptr, schedule, &lam2);
     if (t.nn > 0) {
         T* out_nodes = t.cells ? (T*)t.grad_tmp : d_out;   // (a cell tape: v_nodes is grad_tmp, overwritten in place)
         hess_grad_kernel<T><<<blocks_for(t.nn), ADJ_THREADS, 0, s>>>(lam2, (const T*)t.hold_lam, (const T*)t.D, (const T*)t.hess_dd, t.frozen,
@@ -1891,7 +2006,7 @@ int adj_jvp_joint(AdjTapeDev& t, const T* d_ds, const T* d_dsrc, T* d_dtt, T* d_
 }
 
 template <typename T>
-void adj_gn_joint(AdjTapeDev& t, const T* d_vs, const T* d_ve, const T* d_scale, T* d_ve_scaled, const T* d_rw, T* d_gs, T* d_ge,
+void adj_gn_joint(AdjTapeDev& t, const T* d_vs, const T* d_ve, const T* d_scale, T* d_ve_scaled, const RowOp<T>& op, T* d_gs, T* d_ge,
                   int schedule, int* passes_jvp, int* passes_vjp) {
     ADJ_CHECK(hipSetDevice(t.device));
     adj_src_prepare<T>(t);
@@ -1901,11 +2016,7 @@ void adj_gn_joint(AdjTapeDev& t, const T* d_vs, const T* d_ve, const T* d_scale,
     }
     T* w = (T*)t.w_tmp;
     *passes_jvp = adj_jvp_joint<T>(t, d_vs, d_ve, w, nullptr, schedule, nullptr);
-    if (d_rw && t.n_rows > 0) {
-        tan_scale_rows_kernel<T><<<blocks_for(t.n_rows), ADJ_THREADS, 0, t.stream>>>(d_rw, w, t.n_rows);
-        ADJ_CHECK(hipGetLastError());
-    }
-    *passes_vjp = adj_vjp_source<T>(t, w, nullptr, d_gs, d_ge, schedule);
+    *passes_vjp = adj_vjp_source<T>(t, adj_row_operator<T>(t, op, w), nullptr, d_gs, d_ge, schedule);
     if (d_scale) adj_scale<T>(t, d_scale, d_ge, d_ge, 4 * t.n_points);
 }
 
@@ -2051,7 +2162,7 @@ int adj_jvp_rjoint(AdjTapeDev& t, const T* d_ds, const T* d_drcv, T* d_dtt, T* d
 }
 
 template <typename T>
-void adj_gn_rjoint(AdjTapeDev& t, const T* d_vs, const T* d_ve, const T* d_scale, T* d_ve_scaled, const T* d_rw, T* d_gs, T* d_ge,
+void adj_gn_rjoint(AdjTapeDev& t, const T* d_vs, const T* d_ve, const T* d_scale, T* d_ve_scaled, const RowOp<T>& op, T* d_gs, T* d_ge,
                    int schedule, int* passes_jvp, int* passes_vjp) {
     ADJ_CHECK(hipSetDevice(t.device));
     adj_rcv_prepare<T>(t);
@@ -2062,12 +2173,9 @@ void adj_gn_rjoint(AdjTapeDev& t, const T* d_vs, const T* d_ve, const T* d_scale
     }
     T* w = (T*)t.w_tmp;
     *passes_jvp = adj_jvp_rjoint<T>(t, d_vs, d_ve, w, nullptr, schedule);
-    if (d_rw && t.n_rows > 0) {
-        tan_scale_rows_kernel<T><<<blocks_for(t.n_rows), ADJ_THREADS, 0, t.stream>>>(d_rw, w, t.n_rows);
-        ADJ_CHECK(hipGetLastError());
-    }
-    adj_vjp_rcv<T>(t, w, d_ge);
-    *passes_vjp = adj_vjp<T>(t, w, nullptr, d_gs, schedule);
+    const T* rows = adj_row_operator<T>(t, op, w);
+    adj_vjp_rcv<T>(t, rows, d_ge);
+    *passes_vjp = adj_vjp<T>(t, rows, nullptr, d_gs, schedule);
     if (d_scale) adj_scale<T>(t, d_scale, d_ge, d_ge, blk);
 }
 
@@ -2231,12 +2339,16 @@ template void adj_jvp_prepare<float>(AdjTapeDev&);
 template void adj_jvp_prepare<double>(AdjTapeDev&);
 template int adj_jvp<float>(AdjTapeDev&, const float*, float*, float*, int);
 template int adj_jvp<double>(AdjTapeDev&, const double*, double*, double*, int);
-template void adj_gn<float>(AdjTapeDev&, const float*, const float*, float*, int, int*, int*);
-template void adj_gn<double>(AdjTapeDev&, const double*, const double*, double*, int, int*, int*);
+template void adj_dd_apply<float>(AdjTapeDev&, int, const float*, const float*, const float*, float*);
+template void adj_dd_apply<double>(AdjTapeDev&, int, const double*, const double*, const double*, double*);
+template const float* adj_row_operator<float>(AdjTapeDev&, const RowOp<float>&, float*);
+template const double* adj_row_operator<double>(AdjTapeDev&, const RowOp<double>&, double*);
+template void adj_gn<float>(AdjTapeDev&, const float*, const RowOp<float>&, float*, int, int*, int*);
+template void adj_gn<double>(AdjTapeDev&, const double*, const RowOp<double>&, double*, int, int*, int*);
 template int adj_hold<float>(AdjTapeDev&, const float*, const float*, float*, int);
 template int adj_hold<double>(AdjTapeDev&, const double*, const double*, double*, int);
-template void adj_hess<float>(AdjTapeDev&, const float*, const float*, bool, float*, int, int*, int*);
-template void adj_hess<double>(AdjTapeDev&, const double*, const double*, bool, double*, int, int*, int*);
+template void adj_hess<float>(AdjTapeDev&, const float*, const RowOp<float>&, bool, float*, int, int*, int*);
+template void adj_hess<double>(AdjTapeDev&, const double*, const RowOp<double>&, bool, double*, int, int*, int*);
 
 template void adj_src_prepare<float>(AdjTapeDev&);
 template void adj_src_prepare<double>(AdjTapeDev&);
@@ -2247,8 +2359,9 @@ template int adj_vjp_source<double>(AdjTapeDev&, const double*, const double*, d
 
 template int adj_jvp_joint<float>(AdjTapeDev&, const float*, const float*, float*, float*, int, const float**);
 template int adj_jvp_joint<double>(AdjTapeDev&, const double*, const double*, double*, double*, int, const double**);
-template void adj_gn_joint<float>(AdjTapeDev&, const float*, const float*, const float*, float*, const float*, float*, float*, int, int*, int*);
-template void adj_gn_joint<double>(AdjTapeDev&, const double*, const double*, const double*, double*, const double*, double*, double*, int, int*,
+template void adj_gn_joint<float>(AdjTapeDev&, const float*, const float*, const float*, float*, const RowOp<float>&, float*, float*, int, int*,
+                                  int*);
+template void adj_gn_joint<double>(AdjTapeDev&, const double*, const double*, const double*, double*, const RowOp<double>&, double*, double*, int, int*,
                                    int*);
 
 template void adj_rcv_prepare<float>(AdjTapeDev&);
@@ -2263,8 +2376,9 @@ template void adj_scale<float>(AdjTapeDev&, const float*, const float*, float*, 
 template void adj_scale<double>(AdjTapeDev&, const double*, const double*, double*, size_t);
 template int adj_jvp_rjoint<float>(AdjTapeDev&, const float*, const float*, float*, float*, int);
 template int adj_jvp_rjoint<double>(AdjTapeDev&, const double*, const double*, double*, double*, int);
-template void adj_gn_rjoint<float>(AdjTapeDev&, const float*, const float*, const float*, float*, const float*, float*, float*, int, int*, int*);
-template void adj_gn_rjoint<double>(AdjTapeDev&, const double*, const double*, const double*, double*, const double*, double*, double*, int, int*,
+template void adj_gn_rjoint<float>(AdjTapeDev&, const float*, const float*, const float*, float*, const RowOp<float>&, float*, float*, int, int*,
+                                   int*);
+template void adj_gn_rjoint<double>(AdjTapeDev&, const double*, const double*, const double*, double*, const RowOp<double>&, double*, double*, int, int*,
                                     int*);
 
 template void adj_block_prepare<float>(AdjTapeDev&);

@@ -181,6 +181,22 @@ struct AdjTapeDev {
     size_t loc_work_bytes = 0;
     void* loc_vol = nullptr;
     size_t loc_vol_bytes = 0;
+    // double-difference rows.  Host lists, kept from adj_dd_set_pairs on: the two tape rows of every pair in the caller's order
+    // and the pairs of every row (CSR, ascending pair index within a row, one int per entry: 2 p + sign, sign 1 for the row that is
+    // subtracted).  The first call that uses pairs uploads them and allocates the three work arrays; adj_dd_release returns all of it
+    bool dd_set = false;              // adj_dd_set_pairs has run (an empty list counts)
+    size_t n_pairs = 0;
+    std::vector<int> h_dd_a, h_dd_b;  // n_pairs each
+    std::vector<int> h_dd_off;        // n_rows + 1
+    std::vector<int> h_dd_ent;        // 2 n_pairs
+    int* dd_a = nullptr;
+    int* dd_b = nullptr;
+    int* dd_off = nullptr;
+    int* dd_ent = nullptr;
+    void* dd_u = nullptr;             // n_pairs: d or u of the running product (a host result of Q x is staged here)
+    void* dd_pw = nullptr;            // n_pairs: a host pair_weight (or the host y of Q^T y) is staged here
+    void* dd_rows = nullptr;          // n_rows: B w of the running product (a host result of Q^T y / B x is staged here)
+    size_t dd_bytes = 0;              // what these arrays added to total_bytes
     size_t n_tiles = 0;
     size_t total_bytes = 0;
     hipStream_t stream = nullptr;
@@ -211,9 +227,37 @@ template <typename T>
 void adj_jvp_prepare(AdjTapeDev& t);   // that allocation and the upload of the row-order stencil; a no-op from the second call on
 template <typename T>
 int adj_jvp(AdjTapeDev& t, const T* d_ds, T* d_dtt, T* d_dfields, int schedule);
-// Gauss-Newton product: jvp into w_tmp -> w_tmp *= d_rw (may be null) -> vjp into d_out (n_model()), all on the tape's stream
+
+// ---- double-difference rows (tests/dd_reference.py restates them).  The data operator of a product is
+// B = diag(rw) + Q^T diag(pw) Q, row p of Q holding +1 at tape row a_p and -1 at tape row b_p.
+// replaces the pair list (rows already checked: a != b, both below n_rows, at most 2^30 - 1 pairs) and rebuilds the CSR by row; frees
+// what the pair calls hold on the device (the next call uploads the new list).  Host only apart from that.
+void adj_dd_set_pairs(AdjTapeDev& t, const int* row_a, const int* row_b, size_t n_pairs);
+// what the first call that uses pairs adds to the tape; adj_dd_prepare is a no-op while it is there (AdjDeviceError naming the byte count
+// if an allocation fails); adj_dd_release frees it and takes it off bytes().  The pairs stay as set.
+size_t adj_dd_bytes(const AdjTapeDev& t);
+void adj_dd_prepare(AdjTapeDev& t);
+void adj_dd_release(AdjTapeDev& t);
+// mode 0: d_out (n_pairs) = Q d_x, d[p] = fl(x[a_p] - x[b_p]).  mode 1: d_out (n_rows) = Q^T d_x, d_x holding n_pairs values: per row
+// a chain from +0 over its entries in ascending p, acc = fl(acc +- y[p]).  mode 2: d_out (n_rows) = B d_x: u[p] = fl(pw[p] * d[p]) (d_pw
+// null: d[p]) into dd_u, then per row the chain from fl(rw[r] * x[r]) (d_rw null: from x[r]) over u.  d_x and d_out are different arrays.
 template <typename T>
-void adj_gn(AdjTapeDev& t, const T* d_v, const T* d_rw, T* d_out, int schedule, int* passes_jvp, int* passes_vjp);
+void adj_dd_apply(AdjTapeDev& t, int mode, const T* d_x, const T* d_rw, const T* d_pw, T* d_out);
+// The data weighting of a product: rw (n_rows, may be null) alone is today's diagonal; with pw (n_pairs) the operator B above.
+template <typename T>
+struct RowOp {
+    const T* rw = nullptr;
+    const T* pw = nullptr;
+};
+// applies op to the rows d_w (n_rows) and returns the array that holds the result: without pw, d_w itself, scaled in place by rw (or
+// untouched); with pw, dd_rows.
+template <typename T>
+const T* adj_row_operator(AdjTapeDev& t, const RowOp<T>& op, T* d_w);
+
+// Gauss-Newton product: jvp into w_tmp -> the row operator (RowOp: w_tmp *= rw, or B w_tmp into dd_rows) -> vjp into d_out (n_model()),
+// all on the tape's stream
+template <typename T>
+void adj_gn(AdjTapeDev& t, const T* d_v, const RowOp<T>& op, T* d_out, int schedule, int* passes_jvp, int* passes_vjp);
 
 // ---- second-order products (tests/hessian_reference.py restates them)
 // hold: the vjp of (d_w, d_fc) -- d_grad (n_model(), may be null) with the bits of adj_vjp -- whose lam stays on the tape in hold_lam; the
@@ -224,10 +268,10 @@ template <typename T>
 int adj_hold(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, int schedule);
 void adj_release_hold(AdjTapeDev& t);
 // d_out (n_model()) = the derivative in direction d_v (n_model()) of the held vjp with (w, field_cot) fixed; newton: plus J^T (d_rw * J v)
-// (d_rw n_rows, may be null) from the same adjoint relaxation.  d_v and d_out may be the same array.  Throws std::invalid_argument
-// without a held cotangent.  Uses g, lam, lam2, w_tmp (and grad_tmp on a cell tape) as jvp and vjp do.
+// (the row operator op, as in adj_gn) from the same adjoint relaxation.  d_v and d_out may be the same array.  Throws
+// std::invalid_argument without a held cotangent.  Uses g, lam, lam2, w_tmp (and grad_tmp on a cell tape) as jvp and vjp do.
 template <typename T>
-void adj_hess(AdjTapeDev& t, const T* d_v, const T* d_rw, bool newton, T* d_out, int schedule, int* passes_jvp, int* passes_vjp);
+void adj_hess(AdjTapeDev& t, const T* d_v, const RowOp<T>& op, bool newton, T* d_out, int schedule, int* passes_jvp, int* passes_vjp);
 
 // ---- derivatives with respect to the source points (tests/source_reference.py restates them)
 // what the first jvp_source / vjp_source adds to the tape (the lists above and the two staging arrays), and what the first call with
@@ -301,14 +345,14 @@ struct NormalResult {
     int passes0[2] = {0, 0};        // ... and of A x0
 };
 // Conjugate gradients on A x = rhs for one of the three systems, w = t.cg[sys]: on entry w.r holds rhs (its block unscaled) and, if
-// with_x0, w.x holds x0; on return w.x holds the iterate.  d_rw (n_rows, may be null) on the tape's device.  Vectors in T, scalars in
+// with_x0, w.x holds x0; on return w.x holds the iterate.  rop: the row operator of the products, on the tape's device.  Vectors in T, scalars in
 // fp64, inner products as adj_dot over the flat vector of the system; one host read of the scalars per iteration.  What differs between
 // the systems: the product (adj_gn, or adj_hess if op.newton, for CG_MODEL; adj_gn_joint for CG_SOURCE; adj_gn_rjoint for CG_RECEIVER) and
 // the block -- w.scale / w.damp hold c and delta if with_scale / with_damp, the block of rhs is scaled by c before the loop and the block
 // of x after it (x_e = fl(c * z_e)), and the block of A p is fl(hp + fl(delta * p)).  x0 and op.newton are offered for CG_MODEL only
 // (std::invalid_argument otherwise), a scale and a block damping only for the other two.
 template <typename T>
-void adj_solve(AdjTapeDev& t, CgSystem sys, const T* d_rw, const NormalOperator& op, bool with_x0, bool with_scale, bool with_damp,
+void adj_solve(AdjTapeDev& t, CgSystem sys, const RowOp<T>& rop, const NormalOperator& op, bool with_x0, bool with_scale, bool with_damp,
                int maxiter, double rtol, int schedule, NormalResult& res);
 
 // ---- joint hypocentre-velocity products (tests/joint_reference.py restates them and the solve).  Source blocks are 4 n_points
@@ -317,10 +361,10 @@ void adj_solve(AdjTapeDev& t, CgSystem sys, const T* d_rw, const NormalOperator&
 // the forward mode's system; outputs as adj_jvp.  *mu_out (may be null) receives the relaxed buffer.  Returns the passes launched.
 template <typename T>
 int adj_jvp_joint(AdjTapeDev& t, const T* d_ds, const T* d_dsrc, T* d_dtt, T* d_dfields, int schedule, const T** mu_out);
-// (d_gs, d_ge) = [J_s J_e C]^T (d_rw * [J_s J_e C] (d_vs, d_ve)), C = diag(d_scale) (null: no scaling, no multiplication); d_ve_scaled (4
+// (d_gs, d_ge) = [J_s J_e C]^T (op [J_s J_e C] (d_vs, d_ve)), op the row operator as in adj_gn, C = diag(d_scale) (null: no scaling, no multiplication); d_ve_scaled (4
 // n_points, unused without a scale) receives fl(c * d_ve).  d_gs has the bits of adj_vjp_source's gradient, d_ge = fl(c * its gsrc).
 template <typename T>
-void adj_gn_joint(AdjTapeDev& t, const T* d_vs, const T* d_ve, const T* d_scale, T* d_ve_scaled, const T* d_rw, T* d_gs, T* d_ge,
+void adj_gn_joint(AdjTapeDev& t, const T* d_vs, const T* d_ve, const T* d_scale, T* d_ve_scaled, const RowOp<T>& op, T* d_gs, T* d_ge,
                   int schedule, int* passes_jvp, int* passes_vjp);
 
 // ---- derivatives with respect to the receiver points (tests/receiver_reference.py restates them).  Receiver blocks are 4
@@ -355,7 +399,7 @@ template <typename T>
 int adj_jvp_rjoint(AdjTapeDev& t, const T* d_ds, const T* d_drcv, T* d_dtt, T* d_dfields, int schedule);
 // adj_gn_joint with the receiver block in the place of the source block: one tangent relaxation, one adjoint relaxation, the row kernels
 template <typename T>
-void adj_gn_rjoint(AdjTapeDev& t, const T* d_vs, const T* d_ve, const T* d_scale, T* d_ve_scaled, const T* d_rw, T* d_gs, T* d_ge,
+void adj_gn_rjoint(AdjTapeDev& t, const T* d_vs, const T* d_ve, const T* d_scale, T* d_ve_scaled, const RowOp<T>& op, T* d_gs, T* d_ge,
                    int schedule, int* passes_jvp, int* passes_vjp);
 
 // ---- grid-search hypocentre location on the tape's fields (tests/locate_reference.py restates it; kernels in

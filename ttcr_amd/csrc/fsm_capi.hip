@@ -4087,15 +4087,46 @@ int ttcr_fsm_adjoint_jvp_source(const ttcr_fsm_adjoint* t, const void* dsrc, int
     });
 }
 
+// The pair weights of a double-difference product, checked behind the tape: pairs have to be set, and a host pair_weight
+// holds finite values >= 0 (a device one is the caller's to check).  Null pair_weight: today's diagonal weighting, nothing to check.
+static const char* dd_weight_error(const ttcr_fsm_adjoint* t, const void* pair_weight, int pw_on_device) {
+    if (!pair_weight) return nullptr;
+    if (!t->t.dd_set) return "pair_weight: the tape has no row pairs (call ttcr_fsm_dd_pairs first)";
+    if (pw_on_device) return nullptr;
+    for (size_t p = 0; p < t->t.n_pairs; ++p) {
+        const double w = t->dtype == TTCR_F32 ? (double)((const float*)pair_weight)[p] : ((const double*)pair_weight)[p];
+        if (!(w >= 0.0) || !std::isfinite(w)) return "pair_weight: finite values >= 0";
+    }
+    return nullptr;
+}
+extern "C++" {
+// the row operator of a product: a host row_weight goes through rw_tmp (allocated by adj_jvp_prepare, which therefore runs first), a
+// host pair_weight through dd_pw (allocated by adj_dd_prepare, likewise)
+template <typename T>
+static ttcr_amd::RowOp<T> stage_row_op(ttcr_amd::AdjTapeDev& d, const void* row_weight, int rw_on_device, const void* pair_weight,
+                                       int pw_on_device) {
+    if (row_weight && !rw_on_device) ttcr_amd::adj_jvp_prepare<T>(d);
+    ttcr_amd::RowOp<T> op;
+    op.rw = stage_in<T>(d, row_weight, rw_on_device, d.rw_tmp, d.n_rows);
+    if (pair_weight) {
+        ttcr_amd::adj_dd_prepare(d);
+        op.pw = stage_in<T>(d, pair_weight, pw_on_device, d.dd_pw, d.n_pairs);
+    }
+    return op;
+}
+}  // extern "C++"
+
 // gn, hvp and newton: one body.  held_for names the product that reads the held cotangent (null: gn); row_weight is null for the hvp.
+// pair_weight (null in the entries above 6m): the double-difference rows of ttcr_fsm_dd_gn.
 static int tape_normal(const ttcr_fsm_adjoint* t, const char* held_for, bool newton, const void* v, int v_on_device, const void* row_weight,
-                       int rw_on_device, void* out, int out_on_device, int schedule, int* passes_jvp, int* passes_vjp) {
+                       int rw_on_device, void* out, int out_on_device, int schedule, int* passes_jvp, int* passes_vjp,
+                       const void* pair_weight = nullptr, int pw_on_device = 0) {
     if (!t || !v || !out) return tape_arg_error(!t ? "null tape" : (!v ? "null v" : "null out"));
+    if (const char* bad = dd_weight_error(t, pair_weight, pw_on_device)) return tape_arg_error(bad);
     return tape_call(t, schedule, passes_jvp, passes_vjp, [&](ttcr_amd::AdjTapeDev& d, auto tag, int& pj, int& pv) {
         using T = decltype(tag);
         const T* dv = stage_in<T>(d, v, v_on_device, d.model_tmp(), d.n_model());
-        if (row_weight && !rw_on_device) ttcr_amd::adj_jvp_prepare<T>(d);
-        const T* drw = stage_in<T>(d, row_weight, rw_on_device, d.rw_tmp, d.n_rows);
+        const ttcr_amd::RowOp<T> drw = stage_row_op<T>(d, row_weight, rw_on_device, pair_weight, pw_on_device);
         T* dout = stage_dst<T>(out, out_on_device, d.model_tmp());
         if (held_for) ttcr_amd::adj_hess<T>(d, dv, drw, newton, dout, schedule, &pj, &pv);
         else ttcr_amd::adj_gn<T>(d, dv, drw, dout, schedule, &pj, &pv);
@@ -4286,7 +4317,7 @@ static int tape_solve(ttcr_fsm_adjoint* t, const TapeBlock* blk, const void* rhs
                       const void* row_weight, int rw_on_device, double smooth, const double* smooth_weights, double damp,
                       const double* b_damp, const double* b_scale, const void* x0, int x0_on_device, int maxiter, double rtol, int newton,
                       int schedule, void* x, int x_on_device, void* x_b, int xb_on_device, int* status, int* iterations, double* rho,
-                      double* pq, int* passes) {
+                      double* pq, int* passes, const void* pair_weight = nullptr, int pw_on_device = 0) {
     const ttcr_amd::CgSystem sys = blk ? blk->sys : ttcr_amd::CG_MODEL;
     const char* bad = nullptr;
     if (!(smooth >= 0.0) || !std::isfinite(smooth)) bad = "smooth: a finite value >= 0";
@@ -4306,6 +4337,7 @@ static int tape_solve(ttcr_fsm_adjoint* t, const TapeBlock* blk, const void* rhs
     else if (const char* c = joint_block_error(b_scale, t->t.cg_block(sys), blk ? blk->bad_scale : nullptr)) bad = c;
     else if (const char* c = joint_block_error(b_damp, t->t.cg_block(sys), blk ? blk->bad_damp : nullptr)) bad = c;
     else if (smooth != 0.0) bad = normal_axes_error(t);
+    if (!bad) bad = dd_weight_error(t, pair_weight, pw_on_device);
     if (bad) return tape_arg_error(bad);
     return tape_call(t, schedule, nullptr, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int&, int&) {
         using T = decltype(tag);
@@ -4313,8 +4345,7 @@ static int tape_solve(ttcr_fsm_adjoint* t, const TapeBlock* blk, const void* rhs
         if (sys == ttcr_amd::CG_RECEIVER) ttcr_amd::adj_rcv_prepare<T>(d);
         ttcr_amd::adj_cg_prepare(d, sys);
         const ttcr_amd::CgWork& w = d.cg[sys];
-        if (row_weight && !rw_on_device) ttcr_amd::adj_jvp_prepare<T>(d);
-        const T* drw = stage_in<T>(d, row_weight, rw_on_device, d.rw_tmp, d.n_rows);
+        const ttcr_amd::RowOp<T> drw = stage_row_op<T>(d, row_weight, rw_on_device, pair_weight, pw_on_device);
         auto copy = [&](void* dst, const void* src, size_t n, hipMemcpyKind kind) {
             if (n > 0) HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(T), kind, d.stream));
         };
@@ -4415,10 +4446,12 @@ int ttcr_fsm_rjoint_jvp(const ttcr_fsm_adjoint* t, const void* ds, int ds_on_dev
 // rjoint_gn checks the schedule before rcv_scale, joint_gn leaves the schedule to tape_call and so checks it after source_scale.
 static int tape_joint_gn(const ttcr_fsm_adjoint* t, const TapeBlock& blk, const void* v, int v_on_device, const void* v_b, int vb_on_device,
                          const void* row_weight, int rw_on_device, const double* b_scale, void* out, int out_on_device, void* out_b,
-                         int ob_on_device, int schedule, int* passes_jvp, int* passes_vjp) {
+                         int ob_on_device, int schedule, int* passes_jvp, int* passes_vjp, const void* pair_weight = nullptr,
+                         int pw_on_device = 0) {
     const char* bad = !v ? "null v" : (!v_b ? blk.null_v : (!out ? "null out" : (!out_b ? blk.null_out : (!t ? "null tape" : nullptr))));
     if (!bad && blk.sys == ttcr_amd::CG_RECEIVER) bad = schedule_error(schedule);
     if (!bad) bad = joint_block_error(b_scale, t->t.cg_block(blk.sys), blk.bad_scale);
+    if (!bad) bad = dd_weight_error(t, pair_weight, pw_on_device);
     if (bad) return tape_arg_error(bad);
     return tape_call(t, schedule, passes_jvp, passes_vjp, [&](ttcr_amd::AdjTapeDev& d, auto tag, int& pj, int& pv) {
         using T = decltype(tag);
@@ -4426,8 +4459,7 @@ static int tape_joint_gn(const ttcr_fsm_adjoint* t, const TapeBlock& blk, const 
         T* io = block_prepare<T>(d, blk.sys);
         const T* dv = stage_in<T>(d, v, v_on_device, d.model_tmp(), d.n_model());
         const T* dve = stage_in<T>(d, v_b, vb_on_device, io, nb);
-        if (row_weight && !rw_on_device) ttcr_amd::adj_jvp_prepare<T>(d);
-        const T* drw = stage_in<T>(d, row_weight, rw_on_device, d.rw_tmp, d.n_rows);
+        const ttcr_amd::RowOp<T> drw = stage_row_op<T>(d, row_weight, rw_on_device, pair_weight, pw_on_device);
         if (b_scale) joint_upload<T>(d, b_scale, nb, io + nb);
         T* dout = stage_dst<T>(out, out_on_device, d.model_tmp());
         T* dob = stage_dst<T>(out_b, ob_on_device, io + 3 * nb);
@@ -4540,6 +4572,89 @@ int ttcr_fsm_rcv_vjp(const ttcr_fsm_adjoint* t, const void* w, int w_on_device, 
     });
 }
 int ttcr_fsm_rcv_release(ttcr_fsm_adjoint* t) { return tape_release(t, ttcr_amd::adj_rcv_release); }
+
+// ---- double-difference rows of the field tape.  Host staging (the table above stage_in continued): dd_apply stages a host
+// x of Q x and B x in w_tmp and a host y of Q^T y in dd_pw, a host result of Q x in dd_u and a host result of the other two in dd_rows
+// (B x forms u in dd_u on its way); a host pair_weight of B x and of the products goes through dd_pw, a host row_weight through rw_tmp as
+// for gn.  dd_gn and dd_solve are the bodies of the entries they extend (tape_normal, tape_joint_gn, tape_solve) with pair_weight set.
+int ttcr_fsm_dd_pairs(ttcr_fsm_adjoint* t, const int* set_row_a, const int* set_row_b, size_t set_n_pairs, size_t* n_pairs, int* row_a,
+                      int* row_b, long long* bad_pair) {
+    if (bad_pair) *bad_pair = -1;
+    if ((set_row_a == nullptr) != (set_row_b == nullptr)) return tape_arg_error(!set_row_a ? "null set_row_a" : "null set_row_b");
+    if (set_row_a && set_n_pairs > (((size_t)1 << 30) - 1)) return tape_arg_error("n_pairs: at most 2^30 - 1 row pairs");
+    if (!t) return tape_arg_error("null tape");
+    std::lock_guard<std::mutex> lock(t->mu);
+    ttcr_amd::AdjTapeDev& d = t->t;
+    if (set_row_a) {
+        for (size_t p = 0; p < set_n_pairs; ++p) {
+            const int a = set_row_a[p], b = set_row_b[p];
+            const bool range = a < 0 || b < 0 || (size_t)a >= d.n_rows || (size_t)b >= d.n_rows;
+            if (!range && a != b) continue;
+            if (bad_pair) *bad_pair = (long long)p;
+            g_last_error = "row pairs: pair " + std::to_string(p) + " (tape rows " + std::to_string(a) + ", " + std::to_string(b) + ") " +
+                           (range ? "names a row outside 0 .. n_rows - 1" : "joins a row to itself");
+            return TTCR_ERR_VALUE;
+        }
+        const int st = guarded([&] { ttcr_amd::adj_dd_set_pairs(d, set_row_a, set_row_b, set_n_pairs); });
+        if (st != TTCR_OK) return st;
+    }
+    if (n_pairs) *n_pairs = d.n_pairs;
+    if (row_a) std::copy(d.h_dd_a.begin(), d.h_dd_a.end(), row_a);
+    if (row_b) std::copy(d.h_dd_b.begin(), d.h_dd_b.end(), row_b);
+    return TTCR_OK;
+}
+int ttcr_fsm_dd_apply(const ttcr_fsm_adjoint* t, int mode, const void* x, int x_on_device, const void* row_weight, int rw_on_device,
+                      const void* pair_weight, int pw_on_device, void* out, int out_on_device) {
+    const char* bad = mode < 0 || mode > 2 ? "mode: 0 (Q x), 1 (Q^T y) or 2 (B x)" : (!x ? "null x" : (!out ? "null out" : nullptr));
+    if (!bad && mode != 2 && (row_weight || pair_weight)) bad = "row_weight and pair_weight belong to mode 2 (B x) only";
+    if (!bad && !t) bad = "null tape";
+    if (!bad && !t->t.dd_set) bad = "the tape has no row pairs (call ttcr_fsm_dd_pairs first)";
+    if (!bad) bad = dd_weight_error(t, pair_weight, pw_on_device);
+    if (bad) return tape_arg_error(bad);
+    return tape_call(t, 0, nullptr, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int&, int&) {
+        using T = decltype(tag);
+        ttcr_amd::adj_dd_prepare(d);
+        const bool from_pairs = mode == 1, to_pairs = mode == 0;
+        const T* dx = stage_in<T>(d, x, x_on_device, from_pairs ? d.dd_pw : d.w_tmp, from_pairs ? d.n_pairs : d.n_rows);
+        const ttcr_amd::RowOp<T> op = stage_row_op<T>(d, row_weight, rw_on_device, pair_weight, pw_on_device);   // (null pw: u = d)
+        void* staging = to_pairs ? d.dd_u : d.dd_rows;
+        ttcr_amd::adj_dd_apply<T>(d, mode, dx, op.rw, op.pw, stage_dst<T>(out, out_on_device, staging));
+        stage_out<T>(d, out, out_on_device, staging, to_pairs ? d.n_pairs : d.n_rows);
+    });
+}
+static const char* dd_system_error(int system, int newton) {
+    if (system < 0 || system > 2) return "system: 0 (model), 1 (source joint) or 2 (receiver joint)";
+    if (newton != 0 && newton != 1) return "newton: 0 (gauss_newton) or 1 (newton)";
+    if (newton && system != 0) return "newton: offered for the model system (system 0) only";
+    return nullptr;
+}
+int ttcr_fsm_dd_gn(const ttcr_fsm_adjoint* t, int system, int newton, const void* v, int v_on_device, const void* v_b, int vb_on_device,
+                   const void* row_weight, int rw_on_device, const void* pair_weight, int pw_on_device, const double* b_scale, void* out,
+                   int out_on_device, void* out_b, int ob_on_device, int schedule, int* passes_jvp, int* passes_vjp) {
+    const char* bad = dd_system_error(system, newton);
+    if (!bad && !pair_weight) bad = "null pair_weight";
+    if (bad) return tape_arg_error(bad);
+    if (system == 0)
+        return tape_normal(t, newton ? "newton" : nullptr, newton != 0, v, v_on_device, row_weight, rw_on_device, out, out_on_device, schedule,
+                           passes_jvp, passes_vjp, pair_weight, pw_on_device);
+    return tape_joint_gn(t, system == 1 ? SOURCE_BLOCK : RCV_BLOCK, v, v_on_device, v_b, vb_on_device, row_weight, rw_on_device, b_scale, out,
+                         out_on_device, out_b, ob_on_device, schedule, passes_jvp, passes_vjp, pair_weight, pw_on_device);
+}
+int ttcr_fsm_dd_solve(ttcr_fsm_adjoint* t, int system, const void* rhs, int rhs_on_device, const void* rhs_b, int rb_on_device,
+                      const void* row_weight, int rw_on_device, const void* pair_weight, int pw_on_device, double smooth,
+                      const double* smooth_weights, double damp, const double* b_damp, const double* b_scale, const void* x0,
+                      int x0_on_device, int maxiter, double rtol, int newton, int schedule, void* x, int x_on_device, void* x_b,
+                      int xb_on_device, int* status, int* iterations, double* rho, double* pq, int* passes) {
+    const char* bad = dd_system_error(system, newton);
+    if (!bad && system != 0 && x0) bad = "x0: offered for the model system (system 0) only";
+    if (!bad && !pair_weight) bad = "null pair_weight";
+    if (bad) return tape_arg_error(bad);
+    const TapeBlock* blk = system == 0 ? nullptr : (system == 1 ? &SOURCE_BLOCK : &RCV_BLOCK);
+    return tape_solve(t, blk, rhs, rhs_on_device, blk ? rhs_b : nullptr, rb_on_device, row_weight, rw_on_device, smooth, smooth_weights, damp,
+                      blk ? b_damp : nullptr, blk ? b_scale : nullptr, x0, x0_on_device, maxiter, rtol, newton, schedule, x, x_on_device,
+                      blk ? x_b : nullptr, xb_on_device, status, iterations, rho, pq, passes, pair_weight, pw_on_device);
+}
+int ttcr_fsm_dd_release(ttcr_fsm_adjoint* t) { return tape_release(t, ttcr_amd::adj_dd_release); }
 
 // ---- grid-search hypocentre location on the tape's fields.  Host staging (the table above stage_in continued): the picks
 // arrive on the host, by hypocentre; offsets (as ints), fields, times, weights (ones for a null pick_weight) and the weight sums go through

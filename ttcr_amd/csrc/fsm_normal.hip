@@ -385,7 +385,7 @@ double adj_dot(AdjTapeDev& t, const T* d_a, const T* d_b) {
 }
 
 template <typename T>
-void adj_solve(AdjTapeDev& t, CgSystem sys, const T* d_rw, const NormalOperator& op, bool with_x0, bool with_scale, bool with_damp,
+void adj_solve(AdjTapeDev& t, CgSystem sys, const RowOp<T>& rop, const NormalOperator& op, bool with_x0, bool with_scale, bool with_damp,
                int maxiter, double rtol, int schedule, NormalResult& res) {
     if (sys != CG_MODEL && (with_x0 || op.newton))
         throw std::invalid_argument("solve: x0 and the Newton product are offered for the model system only");
@@ -406,10 +406,10 @@ void adj_solve(AdjTapeDev& t, CgSystem sys, const T* d_rw, const NormalOperator&
     NrmCtl* ctl = (NrmCtl*)wk.ctl;
     // q = A v (v is p of an iteration or x0) and the chunk partials of <v, q>: the product of the system into hp, then kernel 1
     auto apply = [&](const T* v, int* pj, int* pv) {
-        if (sys == CG_SOURCE) adj_gn_joint<T>(t, v, v + nm, c, (T*)wk.ve, d_rw, hp, hp + nm, schedule, pj, pv);
-        else if (sys == CG_RECEIVER) adj_gn_rjoint<T>(t, v, v + nm, c, (T*)wk.ve, d_rw, hp, hp + nm, schedule, pj, pv);
-        else if (op.newton) adj_hess<T>(t, v, d_rw, true, hp, schedule, pj, pv);
-        else adj_gn<T>(t, v, d_rw, hp, schedule, pj, pv);
+        if (sys == CG_SOURCE) adj_gn_joint<T>(t, v, v + nm, c, (T*)wk.ve, rop, hp, hp + nm, schedule, pj, pv);
+        else if (sys == CG_RECEIVER) adj_gn_rjoint<T>(t, v, v + nm, c, (T*)wk.ve, rop, hp, hp + nm, schedule, pj, pv);
+        else if (op.newton) adj_hess<T>(t, v, rop, true, hp, schedule, pj, pv);
+        else adj_gn<T>(t, v, rop, hp, schedule, pj, pv);
         jnt_combine_kernel<T><<<chunks, NRM_THREADS, 0, s>>>(hp, v, q, nm, n, nrm_smooth_args<T>(t, op.weights), (T)op.smooth, (T)op.damp,
                                                             op.smooth != 0.0, op.damp != 0.0, delta, partial);
         NRM_CHECK(hipGetLastError());
@@ -467,7 +467,7 @@ template void adj_smooth<float>(AdjTapeDev&, const float*, const double*, float*
 template void adj_smooth<double>(AdjTapeDev&, const double*, const double*, double*);
 template double adj_dot<float>(AdjTapeDev&, const float*, const float*);
 template double adj_dot<double>(AdjTapeDev&, const double*, const double*);
-template void adj_solve<float>(AdjTapeDev&, CgSystem, const float*, const NormalOperator&, bool, bool, bool, int, double, int, NormalResult&);
-template void adj_solve<double>(AdjTapeDev&, CgSystem, const double*, const NormalOperator&, bool, bool, bool, int, double, int, NormalResult&);
+template void adj_solve<float>(AdjTapeDev&, CgSystem, const RowOp<float>&, const NormalOperator&, bool, bool, bool, int, double, int, NormalResult&);
+template void adj_solve<double>(AdjTapeDev&, CgSystem, const RowOp<double>&, const NormalOperator&, bool, bool, bool, int, double, int, NormalResult&);
 
 }  // namespace ttcr_amd

@@ -10,6 +10,7 @@ matrices from the grid geometry alone -- no solver, no device -- and follow the 
 One helper does use a device, through a field tape it is handed: gauss_newton_step, the right-hand side and the solve of a regularised
 Gauss-Newton step (FieldTape.solve_normal); no reference counterpart.  And locate, the hypocentres a relocation or a joint
 step starts from: the tape's grid search, an off-node start and a Geiger refinement around FieldTape.receiver_eval.
+double_difference_step is gauss_newton_step's sibling for differences of two rows (FieldTape.set_row_pairs).
 """
 import numpy as np
 
@@ -134,6 +135,43 @@ def reciprocal_gauss_newton_step(tape, residual, model, row_weight=None, smooth=
         b = b - smooth * tape.smooth(model, solve_args.get('smooth_weights', (1., 1., 1.)))
     return tape.solve_receiver_joint(b, b_rcv, row_weight=row_weight, smooth=smooth, damp=damp, rcv_damp=rcv_damp, rcv_scale=rcv_scale,
                                      **solve_args)
+
+
+def double_difference_step(tape, residual, pair_residual, model, system='model', row_weight=None, pair_weight=None, smooth=0., damp=0.,
+                           block_damp=0., block_scale=None, **solve_args):
+    """One regularised Gauss-Newton step on double-difference data (hypoDD / tomoDD style) on a field tape whose row
+    pairs are set (tape.set_row_pairs): the weighted rows
+        w = row_weight * residual + tape.pair_adjoint(pair_weight * pair_residual)
+    (pair_weight=None: ones; residual=None: no absolute data and an all-zero row_weight), the right-hand sides from tape.vjp(w, ...)
+    -- with the source gradient for system='joint', the receiver gradient for system='receiver_joint' --, b -= smooth *
+    tape.smooth(model), and then the matching solve with pair_weight: tape.solve_normal ('model'), tape.solve_joint ('joint';
+    block_damp / block_scale are its source_damp / source_scale) or tape.solve_receiver_joint ('receiver_joint'; rcv_damp / rcv_scale),
+    whose result is returned as it is.  residual: one value per data row (rcv order); pair_residual: one value per row pair, the
+    observed minus the computed difference.  A common origin-time shift is invisible to pure double-difference data: give block_damp
+    > 0 on t0 then.  Host glue only."""
+    solves = {'model': None, 'joint': ('solve_joint', 'return_source_grad', 'source'),
+              'receiver_joint': ('solve_receiver_joint', 'return_receiver_grad', 'rcv')}
+    if system not in solves:
+        raise ValueError("system should be 'model', 'joint' or 'receiver_joint', got %r" % (system,))
+    if pair_weight is None:
+        torch_like = hasattr(pair_residual, 'new_ones')
+        pair_weight = pair_residual.new_ones(pair_residual.shape) if torch_like else np.ones(tape.n_pairs, dtype=tape.dtype)
+    w = tape.pair_adjoint(pair_weight * pair_residual)
+    if residual is None:
+        row_weight = w.new_zeros(w.shape) if hasattr(w, 'new_zeros') else np.zeros_like(w)
+    else:
+        w = w + (residual if row_weight is None else row_weight * residual)
+    if solves[system] is None:
+        b = tape.vjp(w)
+    else:
+        b, b_blk = tape.vjp(w, **{solves[system][1]: True})
+    if smooth != 0:
+        b = b - smooth * tape.smooth(model, solve_args.get('smooth_weights', (1., 1., 1.)))
+    if solves[system] is None:
+        return tape.solve_normal(b, row_weight=row_weight, pair_weight=pair_weight, smooth=smooth, damp=damp, **solve_args)
+    name, _, setting = solves[system]
+    return getattr(tape, name)(b, b_blk, row_weight=row_weight, pair_weight=pair_weight, smooth=smooth, damp=damp,
+                               **{setting + '_damp': block_damp, setting + '_scale': block_scale}, **solve_args)
 
 
 # ---- hypocentre location on a field tape in the reciprocal layout (DESIGN.md 6l)

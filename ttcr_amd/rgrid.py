@@ -572,11 +572,18 @@ class FieldTape:
     weighted, origin-time-corrected misfit of its picks, optionally the whole misfit volume; no solve), geometry (node counts, spacing,
     origin in user coordinates), node_coordinates (a node index as a point) and release_locate; inversion.locate adds the off-node start
     and the Geiger refinement around receiver_eval.
+    Double-difference data (differences of two rows, as in hypoDD / tomoDD): set_row_pairs names the row pairs, pair_difference,
+    pair_adjoint and row_operator apply Q, Q^T and B = diag(row_weight) + Q^T diag(pair_weight) Q, and the keyword pair_weight of
+    gauss_newton, newton, the two joint products and the three solves puts B in the place of the diagonal weighting; release_pairs
+    frees what these calls hold on the device.
     wrt is 'nodes' or 'cells': what the model vector of vjp / jvp / gauss_newton holds, n_cols values -- the node slowness (n_cols =
     n_nodes) or, for the tape of raytrace_adjoint(..., wrt='cells'), the cell slowness in set_slowness's flat order (n_cols = cells).
     Fields, field cotangents and field tangents hold n_nodes values per event on either tape."""
 
     SCHEDULES = {'tiled': 0, 'jacobi': 1}
+    _pairs_set = False         # set_row_pairs has run (DESIGN.md 6m)
+    n_pairs = 0                # row pairs of the double-difference operator
+    row_pairs = np.zeros((0, 2), dtype=np.int64)   # ... and their data rows (rcv order), (n_pairs, 2)
 
     def __init__(self, lib, handle, dtype, rows, n_data):
         self._lib = lib
@@ -881,27 +888,34 @@ class FieldTape:
             dsrc[k, :, k] = 1
         return np.ascontiguousarray(self.jvp_source(dsrc, schedule=schedule).T)
 
-    def _normal_product(self, entry, v, row_weight, like, schedule):
-        """gauss_newton, hvp and newton: a model vector in, optional row weights, a model vector out where `like` lives"""
+    def _normal_product(self, entry, v, row_weight, like, schedule, pair_weight=None):
+        """gauss_newton, hvp and newton: a model vector in, optional row weights, a model vector out where `like` lives; with
+        pair_weight the double-difference entry of the same product"""
         self._handle()
         sch = self._schedule(schedule)
         va, pv, dv = self._model_arg(v, 'v')
         ra, pr, dr = self._row_arg(row_weight, 'row_weight') if row_weight is not None else (None, None, 0)
+        qa, pq, dq = self._pair_arg(pair_weight, 'pair_weight', weight=True) if pair_weight is not None else (None, None, 0)
         pg, dg, finish = self._model_out(like)
-        self._sync(dv, dr, dg)
+        self._sync(dv, dr, dq, dg)
         pj, pa = C.c_int(0), C.c_int(0)
         weights = () if entry == 'ttcr_fsm_adjoint_hvp' else (pr, dr)
-        _lib.check(getattr(self._lib, entry)(self._h, pv, dv, *weights, pg, dg, sch, C.byref(pj), C.byref(pa)))
+        if pair_weight is not None:
+            _lib.check(self._lib.ttcr_fsm_dd_gn(self._h, 0, int(entry == 'ttcr_fsm_adjoint_newton'), pv, dv, None, 0, pr, dr, pq, dq, None,
+                                                pg, dg, None, 0, sch, C.byref(pj), C.byref(pa)))
+        else:
+            _lib.check(getattr(self._lib, entry)(self._h, pv, dv, *weights, pg, dg, sch, C.byref(pj), C.byref(pa)))
         self.passes = (pj.value, pa.value)
         self._refresh_nbytes()
         return finish()
 
-    def gauss_newton(self, v, row_weight=None, schedule='tiled'):
+    def gauss_newton(self, v, row_weight=None, schedule='tiled', pair_weight=None):
         """J^T (row_weight * (J v)): the Gauss-Newton Hessian product (n_cols values, x fastest, grid dtype), with the bits of
         vjp(row_weight * jvp(v)), the product formed in the grid dtype, and no host round trip in between.  v: n_cols values;
         row_weight: one value per data row (rcv order) or None.  Array handling and schedule as in vjp; passes becomes the pair
-        (passes of the jvp, passes of the vjp)."""
-        return self._normal_product('ttcr_fsm_adjoint_gn', v, row_weight, self._first_tensor(v, row_weight), schedule)
+        (passes of the jvp, passes of the vjp).  pair_weight (n_pairs values >= 0, after set_row_pairs): the double-difference product
+        J^T B J v with B = row_operator's, the bits of vjp(row_operator(jvp(v), row_weight, pair_weight)); None: the call as above."""
+        return self._normal_product('ttcr_fsm_adjoint_gn', v, row_weight, self._first_tensor(v, row_weight), schedule, pair_weight)
 
     # ---- second-order products (DESIGN.md 6f)
     def hold(self, w=None, field_cotangent=None, return_grad=False, schedule='tiled'):
@@ -934,11 +948,11 @@ class FieldTape:
         (ValueError otherwise).  Array handling and schedule as in jvp; passes becomes (passes of the jvp, passes of the vjp)."""
         return self._normal_product('ttcr_fsm_adjoint_hvp', v, None, v, schedule)
 
-    def newton(self, v, row_weight=None, schedule='tiled'):
+    def newton(self, v, row_weight=None, schedule='tiled', pair_weight=None):
         """J^T (row_weight * (J v)) + hvp(v) from ONE adjoint relaxation: the full Hessian product of a least-squares misfit whose weighted
-        residual is the held w, at the cost of gauss_newton plus three streaming kernels.  Arguments as gauss_newton, the result where v
-        lives; needs hold()."""
-        return self._normal_product('ttcr_fsm_adjoint_newton', v, row_weight, v, schedule)
+        residual is the held w, at the cost of gauss_newton plus three streaming kernels.  Arguments as gauss_newton (pair_weight
+        replaces the weighting of the Gauss-Newton rows only, the held part is untouched), the result where v lives; needs hold()."""
+        return self._normal_product('ttcr_fsm_adjoint_newton', v, row_weight, v, schedule, pair_weight)
 
     # ---- block products (DESIGN.md 6g)
     def jvp_block(self, ds, return_fields=False, schedule='tiled'):
@@ -1052,7 +1066,7 @@ class FieldTape:
         return out.value
 
     def solve_normal(self, rhs, row_weight=None, smooth=0.0, smooth_weights=(1., 1., 1.), damp=0.0, x0=None, maxiter=20, rtol=1e-6,
-                     hessian='gauss_newton', schedule='tiled', return_info=False):
+                     hessian='gauss_newton', schedule='tiled', return_info=False, pair_weight=None):
         """The model update x of a damped, smoothed Gauss-Newton step,
             (J^T W J + smooth * sum_d a_d K_d^T K_d + damp * I) x = rhs,        W = diag(row_weight), a = smooth_weights,
         by conjugate gradients on the device (at most maxiter iterations, stopped when |r| <= rtol |rhs|): the products are
@@ -1064,17 +1078,23 @@ class FieldTape:
         (x, info), info a dict: status (0 converged, 1 maxiter reached, 2 <p, A p> not positive: x is the iterate so far), iterations
         (completed updates), rho (<rhs, rhs>, <r, r> of the starting residual, then after every iteration), pq (<p, A p> of every
         iteration), passes ((jvp, vjp) per iteration) and passes_x0.  Array handling as in gauss_newton.  The first call allocates five
-        model vectors (nbytes; release_solve returns them)."""
+        model vectors (nbytes; release_solve returns them).  pair_weight (n_pairs values >= 0, after set_row_pairs): W becomes
+        row_operator's B = diag(row_weight) + Q^T diag(pair_weight) Q, everything else stays; None: the call as above."""
         self._handle()
         sch, w, maxiter = self._solve_settings(schedule, smooth, damp, rtol, maxiter, hessian, smooth_weights, None)
         ba, pb, db = self._model_arg(rhs, 'rhs')
         ra, pr, dr = self._row_arg(row_weight, 'row_weight') if row_weight is not None else (None, None, 0)
         xa, px0, dx0 = self._model_arg(x0, 'x0') if x0 is not None else (None, None, 0)
+        qa, pq, dq = self._pair_arg(pair_weight, 'pair_weight', weight=True) if pair_weight is not None else (None, None, 0)
         px, dx, finish = self._model_out(self._first_tensor(rhs, row_weight, x0))
-        self._sync(db, dr, dx0, dx)
+        self._sync(db, dr, dx0, dq, dx)
         res = self._solve_results(maxiter, 1)
-        _lib.check(self._lib.ttcr_fsm_normal_solve(self._h, pb, db, pr, dr, float(smooth), w, float(damp), px0, dx0, maxiter, float(rtol),
-                                                   self.HESSIANS[hessian], sch, px, dx, *res))
+        if pair_weight is not None:
+            _lib.check(self._lib.ttcr_fsm_dd_solve(self._h, 0, pb, db, None, 0, pr, dr, pq, dq, float(smooth), w, float(damp), None, None,
+                                                   px0, dx0, maxiter, float(rtol), self.HESSIANS[hessian], sch, px, dx, None, 0, *res))
+        else:
+            _lib.check(self._lib.ttcr_fsm_normal_solve(self._h, pb, db, pr, dr, float(smooth), w, float(damp), px0, dx0, maxiter,
+                                                       float(rtol), self.HESSIANS[hessian], sch, px, dx, *res))
         self._refresh_nbytes()
         x = finish()
         info = self._solve_info(res, 1, x0 is not None)
@@ -1123,9 +1143,10 @@ class FieldTape:
     # and `setting` the endings and beginnings of its argument names (dsrc, v_src, rhs_src; source_scale, source_damp), `entry` the stem
     # of its three C entries (_jvp, _gn, _solve) and `system` its name in solve's hessian message.  The receiver block is that of the
     # receiver joint system.
-    _JointBlock = collections.namedtuple('_JointBlock', 'count what arg setting entry system')
-    _SOURCE = _JointBlock('n_points', 'source', 'src', 'source', 'ttcr_fsm_joint', 'joint')
-    _RECEIVER = _JointBlock('n_rcv_points', 'receiver', 'rcv', 'rcv', 'ttcr_fsm_rjoint', 'receiver joint')
+    # `dd` is the block's system number in the double-difference entries.
+    _JointBlock = collections.namedtuple('_JointBlock', 'count what arg setting entry system dd')
+    _SOURCE = _JointBlock('n_points', 'source', 'src', 'source', 'ttcr_fsm_joint', 'joint', 1)
+    _RECEIVER = _JointBlock('n_rcv_points', 'receiver', 'rcv', 'rcv', 'ttcr_fsm_rjoint', 'receiver joint', 2)
 
     def _joint_arg(self, a, name, blk):
         """a block, (n, 4) values (t0, x, y, z) per point of blk in call order: (array, pointer, on_device)"""
@@ -1173,25 +1194,31 @@ class FieldTape:
         dtt = fin_r()[0]
         return (dtt, fin_f()) if return_fields else dtt
 
-    def _gauss_newton_joint(self, blk, v, v_blk, row_weight, scale, schedule):
+    def _gauss_newton_joint(self, blk, v, v_blk, row_weight, scale, schedule, pair_weight=None):
         self._handle()
         sch = self._schedule(schedule)
         va, pv, dv = self._model_arg(v, 'v')
         ea, pe, de = self._joint_arg(v_blk, 'v_' + blk.arg, blk)
         ra, pr, dr = self._row_arg(row_weight, 'row_weight') if row_weight is not None else (None, None, 0)
+        qa, pq, dq = self._pair_arg(pair_weight, 'pair_weight', weight=True) if pair_weight is not None else (None, None, 0)
         sc = self._joint_setting(scale, blk.setting + '_scale', True, blk)
         like = self._first_tensor(v, v_blk, row_weight)
         pg, dg, fin_g = self._model_out(like)
         ps, dsb, fin_s = self._out(like, getattr(self, blk.count), 4)
-        self._sync(dv, de, dr, dg, dsb)
+        self._sync(dv, de, dr, dq, dg, dsb)
         pj, pa = C.c_int(0), C.c_int(0)
-        _lib.check(getattr(self._lib, blk.entry + '_gn')(self._h, pv, dv, pe, de, pr, dr, sc, pg, dg, ps, dsb, sch, C.byref(pj), C.byref(pa)))
+        if pair_weight is not None:
+            _lib.check(self._lib.ttcr_fsm_dd_gn(self._h, blk.dd, 0, pv, dv, pe, de, pr, dr, pq, dq, sc, pg, dg, ps, dsb, sch, C.byref(pj),
+                                                C.byref(pa)))
+        else:
+            _lib.check(getattr(self._lib, blk.entry + '_gn')(self._h, pv, dv, pe, de, pr, dr, sc, pg, dg, ps, dsb, sch, C.byref(pj),
+                                                             C.byref(pa)))
         self.passes = (pj.value, pa.value)
         self._refresh_nbytes()
         return fin_g(), fin_s()
 
     def _solve_joint(self, blk, rhs, rhs_blk, row_weight, smooth, smooth_weights, damp, blk_damp, blk_scale, maxiter, rtol, schedule,
-                     return_info, hessian):
+                     return_info, hessian, pair_weight=None):
         self._handle()
         sch, w, maxiter = self._solve_settings(schedule, smooth, damp, rtol, maxiter, hessian, smooth_weights, blk.system)
         ba, pb, db = self._model_arg(rhs, 'rhs')
@@ -1199,13 +1226,18 @@ class FieldTape:
         ra, pr, dr = self._row_arg(row_weight, 'row_weight') if row_weight is not None else (None, None, 0)
         sd = self._joint_setting(blk_damp, blk.setting + '_damp', False, blk)
         sc = self._joint_setting(blk_scale, blk.setting + '_scale', True, blk)
+        qa, pq, dq = self._pair_arg(pair_weight, 'pair_weight', weight=True) if pair_weight is not None else (None, None, 0)
         like = self._first_tensor(rhs, rhs_blk, row_weight)
         px, dx, fin_x = self._model_out(like)
         ps, dxs, fin_s = self._out(like, getattr(self, blk.count), 4)
-        self._sync(db, de, dr, dx, dxs)
+        self._sync(db, de, dr, dq, dx, dxs)
         res = self._solve_results(maxiter, 0)
-        _lib.check(getattr(self._lib, blk.entry + '_solve')(self._h, pb, db, pe, de, pr, dr, float(smooth), w, float(damp), sd, sc, maxiter,
-                                                            float(rtol), sch, px, dx, ps, dxs, *res))
+        if pair_weight is not None:
+            _lib.check(self._lib.ttcr_fsm_dd_solve(self._h, blk.dd, pb, db, pe, de, pr, dr, pq, dq, float(smooth), w, float(damp), sd, sc,
+                                                   None, 0, maxiter, float(rtol), 0, sch, px, dx, ps, dxs, *res))
+        else:
+            _lib.check(getattr(self._lib, blk.entry + '_solve')(self._h, pb, db, pe, de, pr, dr, float(smooth), w, float(damp), sd, sc,
+                                                                maxiter, float(rtol), sch, px, dx, ps, dxs, *res))
         self._refresh_nbytes()
         x, xs = fin_x(), fin_s()
         info = self._solve_info(res, 0, False)
@@ -1219,17 +1251,19 @@ class FieldTape:
         differ).  Array handling and schedule as in jvp; the result lives where the first torch tensor of (ds, dsrc) does."""
         return self._jvp_joint(self._SOURCE, ds, dsrc, return_fields, schedule)
 
-    def gauss_newton_joint(self, v, v_src, row_weight=None, source_scale=None, schedule='tiled'):
+    def gauss_newton_joint(self, v, v_src, row_weight=None, source_scale=None, schedule='tiled', pair_weight=None):
         """The joint Gauss-Newton product (g, g_src) = [J_s  J_src C]^T (row_weight * ([J_s  J_src C] (v, v_src))), C = diag(source_scale):
         one tangent relaxation for both blocks (jvp_joint), one adjoint relaxation for both gradients (vjp(...,
         return_source_grad=True)), all on the tape's stream.  v: n_cols values; v_src: (n_points, 4); source_scale: (4,) or (n_points,
         4) values >= 0 that scale the columns of the source block (0 fixes a parameter) or None: no scaling, no multiplication.  g has the
         bits of the vjp's gradient, g_src = source_scale * its source gradient.  Array handling and schedule as in gauss_newton; passes
-        becomes (passes of the jvp, passes of the vjp)."""
-        return self._gauss_newton_joint(self._SOURCE, v, v_src, row_weight, source_scale, schedule)
+        becomes (passes of the jvp, passes of the vjp).  pair_weight as in gauss_newton: the rows between the two relaxations become
+        row_operator(dtt, row_weight, pair_weight)."""
+        return self._gauss_newton_joint(self._SOURCE, v, v_src, row_weight, source_scale, schedule, pair_weight)
 
     def solve_joint(self, rhs, rhs_src, row_weight=None, smooth=0.0, smooth_weights=(1., 1., 1.), damp=0.0, source_damp=0.0,
-                    source_scale=None, maxiter=20, rtol=1e-6, schedule='tiled', return_info=False, hessian='gauss_newton'):
+                    source_scale=None, maxiter=20, rtol=1e-6, schedule='tiled', return_info=False, hessian='gauss_newton',
+                    pair_weight=None):
         """The update (x, x_src) of slowness and source points of one regularised joint Gauss-Newton step, by conjugate gradients from
         zero on the device:
             [ Hss + smooth R + damp I    Hse C                       ] [x  ]   [ rhs       ]
@@ -1241,9 +1275,11 @@ class FieldTape:
         >= 0) acts on the SCALED unknown z_e.  Inner products over the flat joint vector (rhs, then the source block), everything
         else -- recurrence, scalars, statuses, the info dict, the bits being the same under both schedules -- as in solve_normal
         (tests/joint_reference.py restates it).  No x0; hessian other than 'gauss_newton' raises.  Returns (x, x_src), with
-        return_info=True (x, x_src, info).  The first call allocates work arrays of its own (nbytes; release_joint returns them)."""
+        return_info=True (x, x_src, info).  The first call allocates work arrays of its own (nbytes; release_joint returns them).
+        pair_weight as in solve_normal.  A common origin-time shift of all events is in the null space of Q: with pure
+        double-difference data (row_weight all zero) only source_damp > 0 on t0 determines it."""
         return self._solve_joint(self._SOURCE, rhs, rhs_src, row_weight, smooth, smooth_weights, damp, source_damp, source_scale, maxiter, rtol,
-                                 schedule, return_info, hessian)
+                                 schedule, return_info, hessian, pair_weight)
 
     def release_joint(self):
         """Free the work arrays of solve_joint (nbytes falls by what the first call added); the next call allocates them again.  The
@@ -1362,29 +1398,124 @@ class FieldTape:
         field).  Array handling and schedule as in jvp; the result lives where the first torch tensor of (ds, drcv) does."""
         return self._jvp_joint(self._RECEIVER, ds, drcv, return_fields, schedule)
 
-    def gauss_newton_receiver_joint(self, v, v_rcv, row_weight=None, rcv_scale=None, schedule='tiled'):
+    def gauss_newton_receiver_joint(self, v, v_rcv, row_weight=None, rcv_scale=None, schedule='tiled', pair_weight=None):
         """The receiver joint Gauss-Newton product (g, g_rcv) = [J_s  J_rcv C]^T (row_weight * ([J_s  J_rcv C] (v, v_rcv))), C =
         diag(rcv_scale): one tangent relaxation, one adjoint relaxation and the row kernels.  v: n_cols values; v_rcv: (n_rcv_points, 4);
         rcv_scale as gauss_newton_joint's source_scale, over the receiver points.  g has the bits of vjp's gradient, g_rcv = rcv_scale *
-        the receiver gradient.  passes becomes (passes of the jvp, passes of the vjp)."""
-        return self._gauss_newton_joint(self._RECEIVER, v, v_rcv, row_weight, rcv_scale, schedule)
+        the receiver gradient.  passes becomes (passes of the jvp, passes of the vjp).  pair_weight as in gauss_newton.  With all-zero
+        row_weight a common dt0 on every receiver point (v = 0) gives exact zeros: that shift is the null vector of pure
+        double-difference data."""
+        return self._gauss_newton_joint(self._RECEIVER, v, v_rcv, row_weight, rcv_scale, schedule, pair_weight)
 
     def solve_receiver_joint(self, rhs, rhs_rcv, row_weight=None, smooth=0.0, smooth_weights=(1., 1., 1.), damp=0.0, rcv_damp=0.0,
-                             rcv_scale=None, maxiter=20, rtol=1e-6, schedule='tiled', return_info=False, hessian='gauss_newton'):
+                             rcv_scale=None, maxiter=20, rtol=1e-6, schedule='tiled', return_info=False, hessian='gauss_newton',
+                             pair_weight=None):
         """The update (x, x_rcv) of slowness and receiver points of one regularised joint Gauss-Newton step -- solve_joint's system,
         solver and info dict with the receiver block (n_rcv_points, 4) in the place of the source block: rcv_scale scales its columns,
         rcv_damp acts on the scaled unknown, rhs_rcv goes in unscaled as vjp(..., return_receiver_grad=True) returns it.  With the
         hypocentres as receivers of solves from the stations (reciprocity) this is the joint hypocentre-velocity step whose solves and
         fields grow with the stations, not the events.  With rcv_scale all zeros x_rcv is zero and x is solve_normal's.  No x0; hessian
-        other than 'gauss_newton' raises.  The first call allocates work arrays of its own (nbytes; release_receiver returns them)."""
+        other than 'gauss_newton' raises.  The first call allocates work arrays of its own (nbytes; release_receiver returns them).
+        pair_weight as in solve_normal.  A common origin-time shift of all receiver points is in the null space of Q: with pure
+        double-difference data (row_weight all zero) the system is singular unless rcv_damp > 0 on t0 (or rcv_scale fixes it)."""
         return self._solve_joint(self._RECEIVER, rhs, rhs_rcv, row_weight, smooth, smooth_weights, damp, rcv_damp, rcv_scale, maxiter, rtol,
-                                 schedule, return_info, hessian)
+                                 schedule, return_info, hessian, pair_weight)
 
     def release_receiver(self):
         """Free what the receiver calls hold on the device -- the receivers, the point map, G of the rows, the staging arrays and the work
         arrays of solve_receiver_joint (nbytes falls by what they added); the next receiver call uploads them again.  The receiver
         points stay as set.  Nothing of the other calls is touched."""
         _lib.check(self._lib.ttcr_fsm_rcv_release(self._handle()))
+        self._refresh_nbytes()
+
+    # ---- double-difference rows (DESIGN.md 6m)
+    def set_row_pairs(self, row_a, row_b):
+        """Set the row pairs of the double-difference operator: pair p is the difference of data row row_a[p] minus data row row_b[p]
+        (rcv order, like w), e.g. the arrival-time difference of two neighbouring events at one station.  Pairs may join rows of any
+        two events, may repeat, and a row may be in no pair; two empty lists set no pairs.  ValueError naming the pair and its data
+        rows if a row is not on the tape (or out of range) or a pair joins a row to itself.  n_pairs and row_pairs (n_pairs, 2) hold the
+        list; pair_difference, pair_adjoint, row_operator and the keyword pair_weight of the products and solves use it.  Frees what
+        earlier pair calls hold on the device (as release_pairs)."""
+        self._handle()
+        ab = []
+        for name, r in (('row_a', row_a), ('row_b', row_b)):
+            try:
+                r = np.asarray(r.detach().cpu().numpy() if hasattr(r, 'detach') else r)
+            except (TypeError, ValueError):
+                raise ValueError('%s should be integers, got %r' % (name, r))
+            if r.ndim != 1 or (r.size > 0 and r.dtype.kind not in 'iu'):
+                raise ValueError('%s should be one-dimensional integers, got shape %s and dtype %s' % (name, r.shape, r.dtype))
+            ab.append(r.astype(np.int64))
+        a, b = ab
+        if a.shape != b.shape:
+            raise ValueError('row_a and row_b should hold one row per pair each, got %d and %d' % (a.shape[0], b.shape[0]))
+        if a.shape[0] >= 2 ** 30:
+            raise ValueError('at most 2^30 - 1 row pairs, got %d' % a.shape[0])
+        tape_row = np.full(self.n_data, -1, dtype=np.int64)
+        tape_row[self._rows] = np.arange(self.n_rows)
+        inside = (a >= 0) & (a < self.n_data) & (b >= 0) & (b < self.n_data)
+        ta, tb = np.where(inside, tape_row[np.where(inside, a, 0)], -1), np.where(inside, tape_row[np.where(inside, b, 0)], -1)
+        bad = np.flatnonzero((ta < 0) | (tb < 0) | (a == b))
+        if bad.size:
+            p = int(bad[0])
+            why = 'joins a row to itself' if a[p] == b[p] else 'names a data row that is not on the tape'
+            raise ValueError('row pairs: pair %d (data rows %d, %d) %s' % (p, a[p], b[p], why))
+        n = a.shape[0]
+        ca, cb = (C.c_int * max(n, 1))(*ta.tolist()), (C.c_int * max(n, 1))(*tb.tolist())
+        _lib.check(self._lib.ttcr_fsm_dd_pairs(self._h, ca, cb, n, None, None, None, None))
+        self._pairs_set = True
+        self.n_pairs = n
+        self.row_pairs = np.stack([a, b], axis=1)
+        self._refresh_nbytes()
+
+    def _pair_arg(self, y, name, weight=False):
+        """a per-pair vector: (array, pointer, on_device).  weight=True: finite values >= 0"""
+        if not self._pairs_set:
+            raise ValueError('%s: the tape has no row pairs, call set_row_pairs first' % name)
+        y = self._seen(y)
+        if len(y.shape) != 1 or y.shape[0] != self.n_pairs:
+            raise ValueError('%s should hold %d values (one per row pair), got shape %s' % (name, self.n_pairs, tuple(y.shape)))
+        if weight and y.shape[0] > 0:
+            ok = bool((y >= 0).all()) and bool(y.isfinite().all() if self._on_device(y) else np.isfinite(y).all())
+            if not ok:
+                raise ValueError('%s should be finite and >= 0' % name)
+        return self._arg(y)
+
+    def _pair_apply(self, mode, x, row_weight, pair_weight):
+        self._handle()
+        if not self._pairs_set:
+            raise ValueError('the tape has no row pairs, call set_row_pairs first')
+        xa, px, dx = self._pair_arg(x, 'y') if mode == 1 else self._row_arg(x, 'x')
+        ra, pr, dr = self._row_arg(row_weight, 'row_weight') if row_weight is not None else (None, None, 0)
+        qa, pq, dq = self._pair_arg(pair_weight, 'pair_weight', weight=True) if pair_weight is not None else (None, None, 0)
+        like = self._first_tensor(x, row_weight, pair_weight)
+        po, do, finish = self._out(like, 1, self.n_pairs) if mode == 0 else self._out(like, 1, self.n_rows, rows=True)
+        self._sync(dx, dr, dq, do)
+        _lib.check(self._lib.ttcr_fsm_dd_apply(self._h, mode, px, dx, pr, dr, pq, dq, po, do))
+        self._refresh_nbytes()
+        return finish()[0]
+
+    def pair_difference(self, x):
+        """Q x: d[p] = x[row_a[p]] - x[row_b[p]], n_pairs values in the grid dtype for x with one value per data row (rcv order).
+        Array handling as in jvp; device tensors go in and come out."""
+        return self._pair_apply(0, x, None, None)
+
+    def pair_adjoint(self, y):
+        """Q^T y: per data row the sum of +y[p] over the pairs with row_a[p] == row and -y[p] over those with row_b[p] == row, a chain
+        from +0 in ascending p (zero for a row in no pair or not on the tape); y holds n_pairs values.  Array handling as in jvp."""
+        return self._pair_apply(1, y, None, None)
+
+    def row_operator(self, x, row_weight=None, pair_weight=None):
+        """B x = row_weight * x + Q^T (pair_weight * (Q x)), the data operator of the double-difference products, one value per data
+        row: u[p] = fl(pair_weight[p] * d[p]) with d = pair_difference(x), then per row a chain from fl(row_weight * x) (None: from x)
+        over the row's pairs in ascending p, acc = fl(acc +- u[p]).  pair_weight None: ones, u = d without a multiplication.  B is
+        symmetric; a vector that is constant over the rows has Q x == 0.  Array handling as in jvp."""
+        return self._pair_apply(2, x, row_weight, pair_weight)
+
+    def release_pairs(self):
+        """Free what the pair calls hold on the device -- the pair list, its CSR by row and three work arrays (nbytes falls by what the
+        first pair call added); the next pair call uploads them again.  The pairs stay as set.  Nothing of the other calls is touched."""
+        _lib.check(self._lib.ttcr_fsm_dd_release(self._handle()))
         self._refresh_nbytes()
 
     # ---- grid-search hypocentre location (DESIGN.md 6l)
