@@ -491,8 +491,32 @@ int ttcr_fsm_tape_free(ttcr_fsm_tape* t);
  *   atomics;  gn(v) = A^T J^T W J A v, on the tape's stream without a host copy in between.  field_cot, dfields, the field of
  *   ttcr_fsm_adjoint_get_field and the third output of ttcr_fsm_adjoint_size stay n_nodes; the source-point calls are unchanged.  A cell
  *   tape holds n_cells elem bytes more (a staging vector for host arrays), which ttcr_fsm_adjoint_bytes reports.
- * ttcr_fsm_adjoint_model: *cells = 1 for a cell tape, 0 for a node tape; *n_params the length of its model vector (n_cells or n_nodes);
- *   *n_nodes the nodes of a field.
+ * ttcr_fsm_adjoint_model: *cells = 1 for a cell tape, 0 for a node tape; *n_params the length of its model vector (n_cells or n_nodes;
+ *   mx my mz on a model tape, for which *cells = 0); *n_nodes the nodes of a field.
+ * Model tapes (tests/model_reference.py restates every expression).  ttcr_fsm_model_raytrace_multi_adjoint: the call of
+ *   ttcr_fsm_raytrace_multi_adjoint for a 3-D node grid, with model_shape = (mx, my, mz), 1 <= m_d <= n_d: the model vector of the tape
+ *   holds the slowness at the nodes of a coarse grid, uniform per axis and spanning the fine grid exactly, x fastest; m_d = 1 means
+ *   constant along that axis ((1, 1, mz): a layered model).  A cell grid or a shape outside the range: TTCR_ERR_VALUE; 2-D and WENO
+ *   grids: TTCR_ERR_UNSUPPORTED; all before any device call.  The node vector is P times the model vector, P the trilinear
+ *   prolongation.  Per axis and fine index i, in 64-bit integers: q = i (m - 1), I = q div (n - 1), r = q mod (n - 1), the last fine
+ *   node taking I = m - 2, r = n - 1; wl = T((n - 1 - r) / (n - 1)), wh = T(r / (n - 1)), each quotient in double, rounded to the grid
+ *   dtype once; m = 1: I = 0, wl = 1, no upper term.  A term whose weight is exactly 0 is left out of every sum, so m = n gives the
+ *   identity bit for bit.  No fused multiply-add.  (P v)(i, j, k): lerp_x over the four x-pairs of the eight surrounding model nodes,
+ *   lerp_y over the two pairs of results, lerp_z; lerp(a, b) = fl(wl a) + fl(wh b), lower index first.  P^T g in three stages, z first:
+ *   a[i, j, K] = the sum over the fine k, ascending, from the first term, of fl(w g[i, j, k]) for the k with I_z(k) == K (w = wl) or
+ *   I_z(k) + 1 == K (w = wh); the same over j, then over i.  One thread per output element, no atomics.  On such a tape
+ *   vjp = P^T (node vjp), jvp(v) = node jvp(P v), gn(v) = P^T J^T B J P v, hold / hvp / newton and the block, joint, receiver-joint and
+ *   double-difference products compose the same way; the tape linearises at the slowness that was solved, which need not be P of
+ *   anything.  Smoothing (ttcr_fsm_normal_smooth, the solves) acts on the model grid with spacing h_d = dx (n_d - 1) / (m_d - 1) per
+ *   axis; an axis with m_d < 3 is left out of R and has to have weight 0 (TTCR_ERR_VALUE otherwise).  A model tape holds the staged
+ *   model vector, the axis tables and the two intermediates of P^T (nx ny mz and nx my mz values) more than a node tape;
+ *   ttcr_fsm_adjoint_bytes counts them.
+ * ttcr_fsm_model_shape: *is_model = 1 and shape = (mx, my, mz) for a model tape, 0 and zeros otherwise.
+ * ttcr_fsm_model_tape_prolong / ttcr_fsm_model_tape_restrict: out = P v (n_nodes values) / out = P^T g (mx my mz values) with the
+ *   tape's tables on the tape's stream; host or device pointers as for the products.  A tape without a model grid: TTCR_ERR_VALUE.
+ * ttcr_fsm_model_prolong / ttcr_fsm_model_restrict: the same maps on a grid, before any tape exists, for any model_shape the tape entry
+ *   would take (the same refusals); device pointers are on the grid's device.  ttcr_fsm_model_device: that device (the first one
+ *   of a grid on a device list).
  * Argument errors (a NULL tape or pointer, w and field_cot both NULL, dtt and dfields both NULL, n_cols outside 1 to 4, an unknown
  * schedule) return TTCR_ERR_VALUE before any device call. */
 typedef struct ttcr_fsm_adjoint ttcr_fsm_adjoint; /* opaque */
@@ -501,6 +525,14 @@ int ttcr_fsm_raytrace_multi_adjoint(ttcr_fsm_grid* g, int n_src, const int* tx_o
 int ttcr_fsm_raytrace_multi_adjoint_cells(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off,
                                           const void* rx, void* tt_out, ttcr_fsm_adjoint** tape);
 int ttcr_fsm_adjoint_model(const ttcr_fsm_adjoint* t, int* cells, size_t* n_params, size_t* n_nodes);
+int ttcr_fsm_model_raytrace_multi_adjoint(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off,
+                                          const void* rx, void* tt_out, ttcr_fsm_adjoint** tape, const int model_shape[3]);
+int ttcr_fsm_model_shape(const ttcr_fsm_adjoint* t, int* is_model, int* shape);
+int ttcr_fsm_model_tape_prolong(const ttcr_fsm_adjoint* t, const void* v, int v_on_device, void* out, int out_on_device);
+int ttcr_fsm_model_tape_restrict(const ttcr_fsm_adjoint* t, const void* g, int g_on_device, void* out, int out_on_device);
+int ttcr_fsm_model_device(const ttcr_fsm_grid* g, int* device);
+int ttcr_fsm_model_prolong(ttcr_fsm_grid* g, const int model_shape[3], const void* v, int v_on_device, void* out, int out_on_device);
+int ttcr_fsm_model_restrict(ttcr_fsm_grid* g, const int model_shape[3], const void* gr, int g_on_device, void* out, int out_on_device);
 int ttcr_fsm_adjoint_size(const ttcr_fsm_adjoint* t, size_t* n_events, size_t* n_rows, size_t* n_nodes);
 int ttcr_fsm_adjoint_bytes(const ttcr_fsm_adjoint* t, size_t* bytes);
 int ttcr_fsm_adjoint_device(const ttcr_fsm_adjoint* t, int* device);

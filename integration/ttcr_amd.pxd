@@ -76,6 +76,15 @@ cdef extern from "ttcr_amd.h" nogil:
     int ttcr_fsm_raytrace_multi_adjoint_cells(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0,
                                               const int* rx_off, const void* rx, void* tt_out, ttcr_fsm_adjoint** tape)
     int ttcr_fsm_adjoint_model(const ttcr_fsm_adjoint* t, int* cells, size_t* n_params, size_t* n_nodes)
+    # the same for a coarse model grid under a 3-D node grid (DESIGN.md 6n): the model vector holds mx my mz values; P and P^T on a tape or a grid
+    int ttcr_fsm_model_raytrace_multi_adjoint(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0,
+                                              const int* rx_off, const void* rx, void* tt_out, ttcr_fsm_adjoint** tape, const int* model_shape)
+    int ttcr_fsm_model_shape(const ttcr_fsm_adjoint* t, int* is_model, int* shape)
+    int ttcr_fsm_model_tape_prolong(const ttcr_fsm_adjoint* t, const void* v, int v_on_device, void* out, int out_on_device)
+    int ttcr_fsm_model_tape_restrict(const ttcr_fsm_adjoint* t, const void* g, int g_on_device, void* out, int out_on_device)
+    int ttcr_fsm_model_device(const ttcr_fsm_grid* g, int* device)
+    int ttcr_fsm_model_prolong(ttcr_fsm_grid* g, const int* model_shape, const void* v, int v_on_device, void* out, int out_on_device)
+    int ttcr_fsm_model_restrict(ttcr_fsm_grid* g, const int* model_shape, const void* gr, int g_on_device, void* out, int out_on_device)
     int ttcr_fsm_adjoint_size(const ttcr_fsm_adjoint* t, size_t* n_events, size_t* n_rows, size_t* n_nodes)
     int ttcr_fsm_adjoint_bytes(const ttcr_fsm_adjoint* t, size_t* bytes)
     int ttcr_fsm_adjoint_device(const ttcr_fsm_adjoint* t, int* device)

@@ -82,6 +82,13 @@ SYMBOLS = {
     "ttcr_fsm_raytrace_multi_adjoint": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, C.POINTER(_P)]),
     "ttcr_fsm_raytrace_multi_adjoint_cells": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, C.POINTER(_P)]),
     "ttcr_fsm_adjoint_model": (_I, [_P, C.POINTER(_I), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "ttcr_fsm_model_raytrace_multi_adjoint": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, C.POINTER(_P), C.POINTER(_I)]),
+    "ttcr_fsm_model_shape": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
+    "ttcr_fsm_model_tape_prolong": (_I, [_P, _P, _I, _P, _I]),
+    "ttcr_fsm_model_tape_restrict": (_I, [_P, _P, _I, _P, _I]),
+    "ttcr_fsm_model_device": (_I, [_P, C.POINTER(_I)]),
+    "ttcr_fsm_model_prolong": (_I, [_P, C.POINTER(_I), _P, _I, _P, _I]),
+    "ttcr_fsm_model_restrict": (_I, [_P, C.POINTER(_I), _P, _I, _P, _I]),
     "ttcr_fsm_adjoint_size": (_I, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "ttcr_fsm_adjoint_bytes": (_I, [_P, C.POINTER(C.c_size_t)]),
     "ttcr_fsm_adjoint_device": (_I, [_P, C.POINTER(_I)]),

@@ -42,6 +42,13 @@ Both take wrt='nodes' (default) or wrt='cells'.  With wrt='cells' `grid` is a 3-
 velocities (FieldTape of raytrace_adjoint(..., wrt='cells'): the node tape composed with the cell-to-node averaging of set_slowness);
 fields and their cotangents stay (n_events, nx, ny, nz) node arrays.
 
+    s = ttcr_amd.autograd.prolong(grid, m, model_shape)          g_m = ttcr_amd.autograd.restrict(grid, g, model_shape)
+
+are the trilinear prolongation P from a coarse model grid onto the grid's nodes and its transpose (Grid3d.prolong / Grid3d.restrict,
+DESIGN.md 6n) as torch operators: m holds (mx, my, mz) values (or flat in C order), s is (nx, ny, nz); the backward of each is the other,
+and because both are linear, forward mode and double backward follow.  raytrace_adjoint(grid, 1 / prolong(grid, m, shape), source, rcv)
+is then differentiable in the coarse slowness m; the existing operators need no new keyword.
+
 torch is imported when this module is used, never by `import ttcr_amd`.
 """
 import numpy as np
@@ -49,6 +56,7 @@ import numpy as np
 _Fn = None
 _AdjFn = None
 _EvFn = None
+_MapFns = None
 
 
 def _function():
@@ -410,3 +418,66 @@ def raytrace_events(grid, velocity, events, event_of_row, rcv, return_fields=Fal
     holder = []
     out = _events_function().apply(velocity, events, grid, event_of_row.astype(np.int64), rcv, bool(return_fields), wrt, holder)
     return _with_receiver_term(out, rcv_t, holder, return_fields)
+
+
+def _apply_map(grid, t, model_shape, prolong):
+    """P (prolong) or P^T of the tensor t in C order of its grid -- (mx, my, mz) model nodes or (nx, ny, nz) nodes -- through the
+    grid's own kernels; the result in C order of the other grid, in t's dtype, where t lives"""
+    m3 = grid._model_shape(model_shape)
+    n3 = (grid.x.size, grid.y.size, grid.z.size)
+    src, dst = (m3, n3) if prolong else (n3, m3)
+    if t.numel() != src[0] * src[1] * src[2]:
+        raise ValueError('%s should hold %d x %d x %d values, got shape %s' % (('m' if prolong else 'g',) + tuple(src) + (tuple(t.shape),)))
+    flat = t.detach().reshape(src).permute(2, 1, 0).contiguous().reshape(-1)   # C order -> x fastest
+    out = (grid.prolong if prolong else grid.restrict)(flat, m3)
+    return out.reshape(dst[2], dst[1], dst[0]).permute(2, 1, 0).contiguous().to(device=t.device, dtype=t.dtype)
+
+
+def _map_functions():
+    global _MapFns
+    if _MapFns is not None:
+        return _MapFns
+    import torch
+
+    class ProlongFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, m, grid, model_shape):
+            ctx.grid, ctx.model_shape, ctx.in_shape = grid, model_shape, tuple(m.shape)
+            return _apply_map(grid, m, model_shape, True)
+
+        @staticmethod
+        def backward(ctx, g):   # (through the public operator: differentiable again)
+            return restrict(ctx.grid, g, ctx.model_shape).reshape(ctx.in_shape), None, None
+
+        @staticmethod
+        def jvp(ctx, tm, *_):
+            return _apply_map(ctx.grid, tm, ctx.model_shape, True)
+
+    class RestrictFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, g, grid, model_shape):
+            ctx.grid, ctx.model_shape, ctx.in_shape = grid, model_shape, tuple(g.shape)
+            return _apply_map(grid, g, model_shape, False)
+
+        @staticmethod
+        def backward(ctx, gm):
+            return prolong(ctx.grid, gm, ctx.model_shape).reshape(ctx.in_shape), None, None
+
+        @staticmethod
+        def jvp(ctx, tg, *_):
+            return _apply_map(ctx.grid, tg, ctx.model_shape, False)
+
+    _MapFns = (ProlongFn, RestrictFn)
+    return _MapFns
+
+
+def prolong(grid, m, model_shape):
+    """P m: the torch tensor m of values at the (mx, my, mz) nodes of a coarse model grid (that shape, or flat in C order), interpolated
+    trilinearly onto the nodes of the 3-D node grid `grid`: an (nx, ny, nz) tensor in m's dtype where m lives (Grid3d.prolong computes
+    it in the grid dtype).  Differentiable: the backward is restrict, forward mode is prolong of the tangent."""
+    return _map_functions()[0].apply(m, grid, tuple(model_shape))
+
+
+def restrict(grid, g, model_shape):
+    """P^T g: the transpose of prolong applied to an (nx, ny, nz) tensor (or flat in C order): (mx, my, mz).  The backward is prolong."""
+    return _map_functions()[1].apply(g, grid, tuple(model_shape))

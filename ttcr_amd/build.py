@@ -4,7 +4,7 @@ hipcc cross-compiles without a GPU.  -ffp-contract=off is REQUIRED for parity: t
 solver must round a1 + s*dx (and every other product/sum pair) exactly like the reference,
 which a fused multiply-add would not (ttcr_amd/csrc/fsm_kernels.h header).
 
-Six translation units, compiled to objects under ttcr_amd/csrc/_obj and linked:
+Seven translation units, compiled to objects under ttcr_amd/csrc/_obj and linked:
   fsm_capi.hip    the C ABI, the host side and every kernel but one
   fsm_fast.hip    the sweep kernels with tolerance-grade arithmetic (option "arith" = 1)
   fsm_tape.hip    the M tape: compute_M's rows merged on the device, node index, M^T w (hipCUB sorts)
@@ -16,6 +16,8 @@ Six translation units, compiled to objects under ttcr_amd/csrc/_obj and linked:
   fsm_normal.hip  the field tape's normal equations: smoothing operator, fixed-order inner product, CG around the Gauss-Newton product;
                   CG on the joint hypocentre-velocity system and on the receiver joint system (one solver over the extra block)
   fsm_locate.hip  the field tape's grid-search hypocentre location: the misfit search over the nodes of the fields and its finishing kernel
+  fsm_model.hip   the field tape's coarse model grid: the trilinear prolongation from model nodes to grid nodes and its transpose in three
+                  fixed-order stages
 """
 import os
 import shutil
@@ -29,12 +31,13 @@ INC = os.path.join("..", "..", "include", "ttcr_amd.h")
 # source -> (extra flags, files it is compiled from)
 UNITS = {
     "fsm_capi.hip": ([], ["fsm_capi.hip", "fsm_kernels.h", "fsm_fast_api.h", "fsm_march_levels.inc", "fsm_fast.hip", "fsm_tape_api.h",
-                          "fsm_tape.hip", "fsm_adjoint_api.h", "fsm_adjoint.hip", "fsm_normal.hip", "fsm_locate.hip", "fsm_unit_order.h", "fsm_prefill_slices.h", INC]),
+                          "fsm_tape.hip", "fsm_adjoint_api.h", "fsm_adjoint.hip", "fsm_normal.hip", "fsm_locate.hip", "fsm_model.hip", "fsm_unit_order.h", "fsm_prefill_slices.h", INC]),
     "fsm_fast.hip": ([], ["fsm_fast.hip", "fsm_fast_api.h", "fsm_kernels.h", "fsm_march_levels.inc", "fsm_prefill_slices.h"]),
     "fsm_tape.hip": ([], ["fsm_tape.hip", "fsm_tape_api.h"]),
     "fsm_adjoint.hip": ([], ["fsm_adjoint.hip", "fsm_adjoint_api.h", "fsm_kernels.h", "fsm_march_levels.inc", "fsm_prefill_slices.h"]),
     "fsm_normal.hip": ([], ["fsm_normal.hip", "fsm_adjoint_api.h"]),
     "fsm_locate.hip": ([], ["fsm_locate.hip", "fsm_adjoint_api.h"]),
+    "fsm_model.hip": ([], ["fsm_model.hip", "fsm_adjoint_api.h"]),
 }
 SOURCES = list(UNITS)
 DEPS = sorted({d for _, ds in UNITS.values() for d in ds})

@@ -1290,10 +1290,17 @@ size_t tiles_of(const AdjTapeDev& t, int ed) { return (size_t)((t.nnx + ed - 1) 
 size_t tiles_of(const AdjTapeDev& t) { return tiles_of(t, adj_tile_edge(t.elem)); }
 
 // every byte the finished tape holds (the figure an allocation failure names): fields, D, g, lam, lam2; inmask, frozen; slowness and the
-// staged gradient; the staged w; the seed entries (8 per row at most); flags, stamps, error flag; a cell tape's staged cell vector
+// staged gradient; the staged w; the seed entries (8 per row at most); flags, stamps, error flag; a cell or model tape's staged model
+// vector; a model tape's axis tables and the two intermediates of P^T
+size_t model_map_planned(const AdjTapeDev& t) {
+    if (!t.model) return 0;
+    const int n[3] = {t.nnx, t.nny, t.nnz};
+    return model_map_bytes(n, t.elem) + (t.map.n_stage_z() + t.map.n_stage_y()) * t.elem;
+}
 size_t planned_bytes(const AdjTapeDev& t) {
     const size_t en = t.n_events * t.nn;
-    return 5 * en * t.elem + 2 * en + 2 * t.nn * t.elem + t.n_rows * t.elem + 8 * t.n_rows * (8 + 4 + t.elem) + (t.cells ? t.nc * t.elem : 0) +
+    return 5 * en * t.elem + 2 * en + 2 * t.nn * t.elem + t.n_rows * t.elem + 8 * t.n_rows * (8 + 4 + t.elem) +
+           (t.mapped() ? t.n_model() * t.elem : 0) + model_map_planned(t) +
            (ADJ_RING * t.n_events + t.n_events * tiles_of(t) + 1) * sizeof(int);
 }
 
@@ -1311,6 +1318,8 @@ void AdjTapeDev::release() {
     dev_free(rw_off); dev_free(rw_key); dev_free(rw_w); dev_free(rw_tmp); dev_free(tan_stamps);
     dev_free(src_off); dev_free(src_pt); dev_free(src_key); dev_free(src_node); dev_free(src_c); dev_free(src_io); dev_free(src_rows);
     dev_free(mu4); dev_free(mu4b); dev_free(cell_tmp); dev_free(hold_lam); dev_free(hess_dd);
+    dev_free(map_a); dev_free(map_b);
+    model_map_free(map);
     dev_free(g4); dev_free(blk_model); dev_free(blk_nodes); dev_free(blk_rows); dev_free(blk_rw);
     for (CgSystem sys : {CG_MODEL, CG_SOURCE, CG_RECEIVER}) adj_cg_release(*this, sys);
     dev_free(rcv_p); dev_free(rcv_event); dev_free(rcv_pt); dev_free(rcv_rows); dev_free(rcv_off); dev_free(rcv_G); dev_free(rcv_tt);
@@ -1428,7 +1437,15 @@ void adj_finish(AdjTapeDev& t, const AdjSink& sink) {
     alloc(t.err, sizeof(int));
     alloc(t.w_tmp, t.n_rows * t.elem);
     alloc(t.grad_tmp, t.nn * t.elem);
-    if (t.cells) alloc(t.cell_tmp, t.nc * t.elem);
+    if (t.mapped()) alloc(t.cell_tmp, t.n_model() * t.elem);
+    if (t.model) {   // the intermediates of P^T and the axis tables of P (the sizes of t.map were set with the tape)
+        alloc(t.map_a, t.map.n_stage_z() * t.elem);
+        alloc(t.map_b, t.map.n_stage_y() * t.elem);
+        const int n[3] = {t.nnx, t.nny, t.nnz};
+        const int m[3] = {t.map.m[0], t.map.m[1], t.map.m[2]};
+        model_map_create<T>(t.map, n, m);
+        t.total_bytes += t.map.bytes;
+    }
     long long* d_fk = nullptr;
     T* d_fd = nullptr;
     hipStream_t s = t.stream;
@@ -1541,28 +1558,35 @@ static int adj_vjp_impl(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, i
     return passes;
 }
 
-// cell tape: d_nodes = A d_cells (fsm_cells_to_nodes3d) and d_cells = A^T d_nodes (one thread per cell), on the tape's stream
+// The map between the model vector and the node vector of a tape whose model vector is not the node vector, on the tape's stream -- the
+// one place that knows the parameterisation.  Cell tape: d_nodes = A d_cells (fsm_cells_to_nodes3d), d_cells = A^T d_nodes (one thread
+// per cell).  Model tape: d_nodes = P d_model, d_model = P^T d_nodes (fsm_model.hip).
 template <typename T>
-static void adj_cells_to_nodes(AdjTapeDev& t, const T* d_cells, T* d_nodes) {
+void adj_model_to_nodes(AdjTapeDev& t, const T* d_cells, T* d_nodes) {
+    if (!t.mapped()) throw std::logic_error("adj_model_to_nodes: a node tape has no map");
     if (t.nn == 0) return;
+    if (t.model) return model_prolong<T>(t.map, d_cells, d_nodes, t.stream);
     const unsigned blocks = std::min(blocks_for(t.nn), 4096u);   // (the launch of set_slowness)
     fsm_cells_to_nodes3d<T><<<blocks, ADJ_THREADS, 0, t.stream>>>(d_cells, d_nodes, t.nnx - 1, t.nny - 1, t.nnz - 1);
     ADJ_CHECK(hipGetLastError());
 }
 
 template <typename T>
-static void adj_nodes_to_cells(AdjTapeDev& t, const T* d_nodes, T* d_cells) {
+void adj_nodes_to_model(AdjTapeDev& t, const T* d_nodes, T* d_cells) {
+    if (!t.mapped()) throw std::logic_error("adj_nodes_to_model: a node tape has no map");
+    if (t.model) return model_restrict<T>(t.map, d_nodes, (T*)t.map_a, (T*)t.map_b, d_cells, t.stream);
     if (t.nc == 0) return;
     adj_nodes_to_cells_kernel<T><<<blocks_for(t.nc), ADJ_THREADS, 0, t.stream>>>(d_nodes, d_cells, t.nnx - 1, t.nny - 1, t.nnz - 1);
     ADJ_CHECK(hipGetLastError());
 }
 
-// the vjp with respect to the model vector: on a cell tape the node gradient of 6b is formed in grad_tmp, then d_grad = A^T grad_tmp
+// the vjp with respect to the model vector: on a cell or model tape the node gradient of 6b is formed in grad_tmp, then d_grad = the
+// transposed map of grad_tmp
 template <typename T>
 static int adj_vjp_model(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, int schedule, const T** lam_final) {
-    if (!t.cells || !d_grad) return adj_vjp_impl<T>(t, d_w, d_fc, d_grad, schedule, lam_final);
+    if (!t.mapped() || !d_grad) return adj_vjp_impl<T>(t, d_w, d_fc, d_grad, schedule, lam_final);
     const int passes = adj_vjp_impl<T>(t, d_w, d_fc, (T*)t.grad_tmp, schedule, lam_final);
-    adj_nodes_to_cells<T>(t, (const T*)t.grad_tmp, d_grad);
+    adj_nodes_to_model<T>(t, (const T*)t.grad_tmp, d_grad);
     return passes;
 }
 
@@ -1613,8 +1637,8 @@ static int adj_jvp_impl(AdjTapeDev& t, const T* d_ds, T* d_dtt, T* d_dfields, in
     hipStream_t s = t.stream;
     const size_t E = t.n_events, en = E * t.nn;
     const AdjGeom<T> geo{t.nnx, t.nny, t.nnz, t.nn, (T)t.dx};
-    if (t.cells) {   // the node perturbation set_slowness would compute from the cell perturbation
-        adj_cells_to_nodes<T>(t, d_ds, (T*)t.grad_tmp);
+    if (t.mapped()) {   // the node perturbation: what set_slowness would compute from the cell perturbation, or P d_ds
+        adj_model_to_nodes<T>(t, d_ds, (T*)t.grad_tmp);
         d_ds = (const T*)t.grad_tmp;
     }
     T* mu = (T*)t.lam;
@@ -1791,7 +1815,8 @@ int adj_hold(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, int schedule
 }
 
 // tangent relaxation of v -> dD and q from final values (q written into g, the seeds of the relaxation that follows) -> adjoint relaxation
-// of lam2 for the field cotangent q (newton: and the rows rw * J v) -> gradient with the direct term; a cell tape ends with A^T
+// of lam2 for the field cotangent q (newton: and the rows rw * J v) -> gradient with the direct term; a cell or model tape ends with
+// the transposed map
 template <typename T>
 void adj_hess(AdjTapeDev& t, const T* d_v, const RowOp<T>& op, bool newton, T* d_out, int schedule, int* passes_jvp, int* passes_vjp) {
     if (!t.held) throw std::invalid_argument("no held cotangent: call hold first");
@@ -1814,11 +1839,11 @@ void adj_hess(AdjTapeDev& t, const T* d_v, const RowOp<T>& op, bool newton, T* d
     const T* lam2 = nullptr;
     *passes_vjp = adj_vjp_impl<T>(t, rows, (const T*)t.g, nullptr, schedule, &lam2);
     if (t.nn > 0) {
-        T* out_nodes = t.cells ? (T*)t.grad_tmp : d_out;   // (a cell tape: v_nodes is grad_tmp, overwritten in place)
+        T* out_nodes = t.mapped() ? (T*)t.grad_tmp : d_out;   // (a cell or model tape: v_nodes is grad_tmp, overwritten in place)
         hess_grad_kernel<T><<<blocks_for(t.nn), ADJ_THREADS, 0, s>>>(lam2, (const T*)t.hold_lam, (const T*)t.D, (const T*)t.hess_dd, t.frozen,
                                                                     (const T*)t.slowness, v_nodes, geo, E, out_nodes);
         ADJ_CHECK(hipGetLastError());
-        if (t.cells) adj_nodes_to_cells<T>(t, (const T*)t.grad_tmp, d_out);
+        if (t.mapped()) adj_nodes_to_model<T>(t, (const T*)t.grad_tmp, d_out);
     }
 }
 
@@ -1962,8 +1987,8 @@ int adj_jvp_joint(AdjTapeDev& t, const T* d_ds, const T* d_dsrc, T* d_dtt, T* d_
     hipStream_t s = t.stream;
     const size_t E = t.n_events, en = E * t.nn, n_ent = t.h_src_key.size();
     const AdjGeom<T> geo{t.nnx, t.nny, t.nnz, t.nn, (T)t.dx};
-    if (t.cells) {   // the node perturbation set_slowness would compute from the cell perturbation
-        adj_cells_to_nodes<T>(t, d_ds, (T*)t.grad_tmp);
+    if (t.mapped()) {   // the node perturbation: what set_slowness would compute from the cell perturbation, or P d_ds
+        adj_model_to_nodes<T>(t, d_ds, (T*)t.grad_tmp);
         d_ds = (const T*)t.grad_tmp;
     }
     T* mu = (T*)t.lam;
@@ -2182,7 +2207,7 @@ void adj_gn_rjoint(AdjTapeDev& t, const T* d_vs, const T* d_ve, const T* d_scale
 
 // ---- block products
 size_t adj_block_bytes(const AdjTapeDev& t) {
-    return (t.mu4 ? 1 : 2) * adj_src_column_bytes(t) + 4 * t.n_model() * t.elem + (t.cells ? 4 * t.nn * t.elem : 0) + 8 * t.n_rows * t.elem;
+    return (t.mu4 ? 1 : 2) * adj_src_column_bytes(t) + 4 * t.n_model() * t.elem + (t.mapped() ? 4 * t.nn * t.elem : 0) + 8 * t.n_rows * t.elem;
 }
 
 template <typename T>
@@ -2197,7 +2222,7 @@ void adj_block_prepare(AdjTapeDev& t) {
         alloc(t.g4, adj_src_column_bytes(t));
         if (!had_mu4) alloc(t.mu4, adj_src_column_bytes(t));
         alloc(t.blk_model, 4 * t.n_model() * t.elem);
-        if (t.cells) alloc(t.blk_nodes, 4 * t.nn * t.elem);
+        if (t.mapped()) alloc(t.blk_nodes, 4 * t.nn * t.elem);
         alloc(t.blk_rows, 4 * t.n_rows * t.elem);
         alloc(t.blk_rw, 4 * t.n_rows * t.elem);
     } catch (...) {
@@ -2237,8 +2262,8 @@ int adj_jvp_block(AdjTapeDev& t, const T* d_ds, int n_cols, T* d_dtt, T* d_dfiel
     using V = SrcVec<T, K>;
     hipStream_t s = t.stream;
     const AdjGeom<T> geo{t.nnx, t.nny, t.nnz, t.nn, (T)t.dx};
-    if (t.cells) {   // column by column, the node perturbation set_slowness would compute from the cell perturbation
-        for (int k = 0; k < n_cols; ++k) adj_cells_to_nodes<T>(t, d_ds + (size_t)k * t.nc, (T*)t.blk_nodes + (size_t)k * t.nn);
+    if (t.mapped()) {   // column by column, the node perturbation: set_slowness's from the cell perturbation, or P of the column
+        for (int k = 0; k < n_cols; ++k) adj_model_to_nodes<T>(t, d_ds + (size_t)k * t.n_model(), (T*)t.blk_nodes + (size_t)k * t.nn);
         d_ds = (const T*)t.blk_nodes;
     }
     V* mu = (V*)t.mu4;
@@ -2303,12 +2328,12 @@ int adj_vjp_block(AdjTapeDev& t, const T* d_w, int n_cols, T* d_grad, int schedu
         });
     }
     if (t.nn > 0) {
-        // a cell tape forms the node gradients of the group in blk_nodes, then d_grad = A^T of each
-        T* gn = t.cells ? (T*)t.blk_nodes : d_grad;
+        // a cell or model tape forms the node gradients of the group in blk_nodes, then d_grad = the transposed map of each
+        T* gn = t.mapped() ? (T*)t.blk_nodes : d_grad;
         adjk_grad_kernel<T, K><<<blocks_for(t.nn), ADJ_THREADS, 0, s>>>(lam, (const T*)t.D, t.frozen, (const T*)t.slowness, geo, E, n_cols, gn);
         ADJ_CHECK(hipGetLastError());
-        if (t.cells)
-            for (int k = 0; k < n_cols; ++k) adj_nodes_to_cells<T>(t, gn + (size_t)k * t.nn, d_grad + (size_t)k * t.nc);
+        if (t.mapped())
+            for (int k = 0; k < n_cols; ++k) adj_nodes_to_model<T>(t, gn + (size_t)k * t.nn, d_grad + (size_t)k * t.n_model());
     }
     return passes;
 }
@@ -2333,6 +2358,10 @@ template void adj_copy_field<float>(const float*, int, float*, size_t, hipStream
 template void adj_copy_field<double>(const double*, int, double*, size_t, hipStream_t);
 template void adj_finish<float>(AdjTapeDev&, const AdjSink&);
 template void adj_finish<double>(AdjTapeDev&, const AdjSink&);
+template void adj_model_to_nodes<float>(AdjTapeDev&, const float*, float*);
+template void adj_model_to_nodes<double>(AdjTapeDev&, const double*, double*);
+template void adj_nodes_to_model<float>(AdjTapeDev&, const float*, float*);
+template void adj_nodes_to_model<double>(AdjTapeDev&, const double*, double*);
 template int adj_vjp<float>(AdjTapeDev&, const float*, const float*, float*, int);
 template int adj_vjp<double>(AdjTapeDev&, const double*, const double*, double*, int);
 template void adj_jvp_prepare<float>(AdjTapeDev&);

@@ -22,6 +22,8 @@
 // No floating-point atomics anywhere: every value is one fixed expression of final values, so the bits do not depend on the schedule.
 // Cell tapes (ttcr_fsm_raytrace_multi_adjoint_cells): the model vector holds one slowness per cell and the node slowness is
 // A times it (fsm_cells_to_nodes3d); a jvp first applies A to ds, a vjp ends with A^T on the node gradient (one thread per cell).
+// Model tapes (ttcr_fsm_model_raytrace_multi_adjoint; kernels in fsm_model.hip): the model vector holds the slowness at the
+// nodes of a coarse grid and the node perturbation is P times it, P the trilinear prolongation; a jvp first applies P, a vjp ends with P^T.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -62,6 +64,35 @@ struct AdjSink {
     double rcv_min[3] = {0, 0, 0}, rcv_shift[3] = {0, 0, 0};
 };
 
+// ---- the coarse model grid (tests/model_reference.py restates it; fsm_model.hip).  The per-axis tables of the trilinear
+// prolongation P from m[0] x m[1] x m[2] model nodes onto n[0] x n[1] x n[2] fine nodes (both x fastest, 1 <= m[d] <= n[d]), on the
+// current device: for every fine index of every axis the lower model index and the weights wl, wh in the grid dtype.
+struct ModelMap {
+    int n[3] = {0, 0, 0}, m[3] = {0, 0, 0};
+    int* idx = nullptr;   // n[0] + n[1] + n[2]: x, then y, then z
+    void* w = nullptr;    // twice as many values: wl of the three axes, then wh
+    size_t bytes = 0;     // what the two arrays hold
+    size_t n_fine() const { return (size_t)n[0] * n[1] * n[2]; }
+    size_t n_model() const { return (size_t)m[0] * m[1] * m[2]; }
+    // elements of the intermediates of P^T: after stage z and after stage y
+    size_t n_stage_z() const { return (size_t)n[0] * n[1] * m[2]; }
+    size_t n_stage_y() const { return (size_t)n[0] * m[1] * m[2]; }
+};
+size_t model_map_bytes(const int n[3], size_t elem);
+// the stencil of fine index i on an axis of n fine and m model nodes: lower model index and the two quotients in double
+void model_axis_stencil(int i, int n, int m, int* I, double* wl, double* wh);
+// forms the tables on the host and uploads them (blocking copies); AdjDeviceError naming the byte count if an allocation fails
+template <typename T>
+void model_map_create(ModelMap& map, const int n[3], const int m[3]);
+void model_map_free(ModelMap& map);
+// d_s (n_fine()) = P d_v (n_model()): one kernel, one thread per fine node
+template <typename T>
+void model_prolong(const ModelMap& map, const T* d_v, T* d_s, hipStream_t stream);
+// d_gm (n_model()) = P^T d_g (n_fine()) in three stages, z first, through d_a (n_stage_z()) and d_b (n_stage_y()): serial sums in
+// ascending order, one thread per output element, no atomics
+template <typename T>
+void model_restrict(const ModelMap& map, const T* d_g, T* d_a, T* d_b, T* d_gm, hipStream_t stream);
+
 // The systems the conjugate-gradient solver of fsm_normal.hip runs on: the model vector alone, the model vector followed by
 // the source block (the joint hypocentre-velocity system, 6j), or followed by the receiver block (the receiver joint system, 6k).
 enum CgSystem { CG_MODEL = 0, CG_SOURCE = 1, CG_RECEIVER = 2 };
@@ -88,9 +119,15 @@ struct AdjTapeDev {
     // cell tape: the model vector of vjp / jvp / gn holds nc = (nnx - 1) (nny - 1) (nnz - 1) cell values (x fastest) instead of nn node values
     bool cells = false;
     size_t nc = 0;
-    void* cell_tmp = nullptr;         // nc (cell tape only: a host grad / ds / v / out is staged here; grad_tmp holds the node vector)
-    size_t n_model() const { return cells ? nc : nn; }
-    void* model_tmp() const { return cells ? cell_tmp : grad_tmp; }
+    void* cell_tmp = nullptr;         // n_model() (cell and model tapes only: a host grad / ds / v / out is staged here; grad_tmp holds the node vector)
+    // model tape: the model vector holds the map.n_model() values of a coarse node grid, the node vector is P times it
+    bool model = false;
+    ModelMap map;                     // the axis tables of P (counted in total_bytes)
+    void* map_a = nullptr;            // the intermediates of P^T: map.n_stage_z() values ...
+    void* map_b = nullptr;            // ... and map.n_stage_y()
+    bool mapped() const { return cells || model; }   // the model vector is not the node vector: a linear map stands between them
+    size_t n_model() const { return cells ? nc : (model ? map.n_model() : nn); }
+    void* model_tmp() const { return mapped() ? cell_tmp : grad_tmp; }
     void* fields = nullptr;           // n_events * nn
     void* slowness = nullptr;         // nn
     void* D = nullptr;                // n_events * nn: D of a non-frozen node, d of a frozen one
@@ -141,7 +178,7 @@ struct AdjTapeDev {
     // block products: allocated by the first block call, returned by adj_block_release.  lam of K columns lives in mu4.
     void* g4 = nullptr;               // 4 n_events * nn: the seeds of the running K-column vjp (a host dfields of jvp_block is staged here)
     void* blk_model = nullptr;        // 4 n_model(): a group of host ds / v / grad / out columns
-    void* blk_nodes = nullptr;        // 4 nn (cell tape only): the node vectors of a group
+    void* blk_nodes = nullptr;        // 4 nn (cell and model tapes only): the node vectors of a group
     void* blk_rows = nullptr;         // 4 n_rows: a group of host w / dtt columns; J v of a Gauss-Newton group
     void* blk_rw = nullptr;           // 4 n_rows: a group of host row_weight columns
     bool blk_owns_mu4 = false;        // mu4 came with the block arrays (no jvp_source had allocated it) and leaves with them
@@ -216,10 +253,10 @@ void adj_copy_field(const T* src, int ts, T* dst, size_t n, hipStream_t stream);
 template <typename T>
 void adj_finish(AdjTapeDev& t, const AdjSink& sink);
 // d_w (n_rows, may be null), d_fc (n_events * nn, may be null), d_grad (n_model()): all on the tape's device; returns the passes launched.
-// On a cell tape the node gradient is formed in grad_tmp and d_grad = A^T grad_tmp.
+// On a cell tape the node gradient is formed in grad_tmp and d_grad = A^T grad_tmp; on a model tape d_grad = P^T grad_tmp.
 template <typename T>
 int adj_vjp(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, int schedule);
-// forward mode (tests/tangent_reference.py restates it): d_ds (n_model(); a cell tape relaxes with grad_tmp = A d_ds), d_dtt
+// forward mode (tests/tangent_reference.py restates it): d_ds (n_model(); a cell tape relaxes with grad_tmp = A d_ds, a model tape with P d_ds), d_dtt
 // (n_rows, may be null), d_dfields (n_events * nn, may be null); relaxes mu = dT/ds . ds in lam / lam2 to its fixed point (the same two schedules), then one thread per receiver row; returns the
 // passes launched.  The first call allocates adj_jvp_extra_bytes(t) more (AdjDeviceError naming the byte count if that fails).
 size_t adj_jvp_extra_bytes(const AdjTapeDev& t);
@@ -293,7 +330,7 @@ int adj_vjp_source(AdjTapeDev& t, const T* d_w, const T* d_fc, T* d_grad, T* d_g
 // ---- block products: groups of up to 4 model vectors per relaxation.  Column k of every result has the bits of the
 // one-column call (adj_jvp / adj_vjp / adj_gn) on column k.
 // What the first block call adds to the tape: the K-column seeds g4 (4 n_events nn), the K-column lam / mu buffer mu4 (as much again, unless
-// a jvp_source with n_cols > 1 allocated it before) and the staging arrays of a group (4 n_model(), 4 nn on a cell tape, 8 n_rows); the
+// a jvp_source with n_cols > 1 allocated it before) and the staging arrays of a group (4 n_model(), 4 nn on a cell or model tape, 8 n_rows); the
 // first jvp's arrays too if no jvp came before.  AdjDeviceError naming the byte count if an allocation fails.
 size_t adj_block_bytes(const AdjTapeDev& t);
 template <typename T>
@@ -313,7 +350,17 @@ void adj_gn_block(AdjTapeDev& t, const T* d_v, const T* d_rw, size_t rw_stride, 
                   int* passes_vjp);
 
 // ---- normal equations (tests/normal_reference.py restates them; kernels in fsm_normal.hip).  Model vectors are n_model()
-// values on the tape's device, parameters x fastest: nnx x nny x nnz nodes, or the (nnx - 1) x (nny - 1) x (nnz - 1) cells of a cell tape.
+// values on the tape's device, parameters x fastest: nnx x nny x nnz nodes, the (nnx - 1) x (nny - 1) x (nnz - 1) cells of a cell tape, or
+// the model nodes of a model tape (spacing per axis dx (nn_d - 1) / (m_d - 1); an axis with fewer than 3 model nodes is left out of R and
+// has to have weight 0).
+// d_nodes (nn) = the map of the tape (A or P) applied to d_model (n_model()), and d_model = its transpose applied to d_nodes; on the
+// tape's stream.  Node tapes have no map (std::logic_error).
+template <typename T>
+void adj_model_to_nodes(AdjTapeDev& t, const T* d_model, T* d_nodes);
+template <typename T>
+void adj_nodes_to_model(AdjTapeDev& t, const T* d_nodes, T* d_model);
+// what is wrong with the smoothing weights on this tape (null: nothing): host only
+const char* adj_smooth_error(const AdjTapeDev& t, const double* weights);
 int adj_smooth_tile_edge(size_t elem);   // edge of a smoothing tile (interior parameters) for an element size
 // the work arrays of the solver for one system (CgWork): five vectors of cg_len(sys) values, one double per chunk of 1024 elements and the
 // scalars; for a system with a block three arrays of cg_block(sys) values more.  adj_cg_prepare is a no-op while they are there
@@ -323,7 +370,7 @@ size_t adj_cg_bytes(const AdjTapeDev& t, CgSystem sys);
 void adj_cg_prepare(AdjTapeDev& t, CgSystem sys);
 void adj_cg_release(AdjTapeDev& t, CgSystem sys);
 // d_out = R d_v = sum_d weights[d] K_d^T (K_d d_v), K_d the second differences of spacing dx along axis d with the centred stencil
-// shifted inwards on the two end rows; d_out and d_v are different arrays.  std::invalid_argument if an axis has fewer than 3 parameters.
+// shifted inwards on the two end rows; d_out and d_v are different arrays.  std::invalid_argument with adj_smooth_error's words.
 template <typename T>
 void adj_smooth(AdjTapeDev& t, const T* d_v, const double* weights, T* d_out);
 // <d_a, d_b> in fp64 with the fixed summation order of DESIGN.md 6i (chunks of 1024, one finishing workgroup); waits for the stream

@@ -87,6 +87,9 @@ struct Timing {
     int iterations = 0, n_sources = 0;
 };
 
+// what the model vector of a field tape holds, as the entry that makes the tape names it
+enum TapeWrt { WRT_NODES = 0, WRT_CELLS = 1, WRT_MODEL = 2 };
+
 class GridBase {
    public:
     virtual ~GridBase() {}
@@ -121,9 +124,10 @@ class GridBase {
     // (whatever tt_from_rp says); after each batch every event's field, frozen nodes and receiver stencils go to `sink`
     virtual void raytrace_multi_adjoint(int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off, const void* rx,
                                         void* tt_out, AdjSink& sink) = 0;
-    // node counts and spacing of a grid the adjoint is defined for; Unsupported (with the reason) for every other grid.  wrt_cells: the
-    // call came through the cell entry, which takes cell grids only (ValueError on a node grid); the node entry keeps refusing cell grids
-    virtual void adjoint_geometry(int* nn3, double* spacing, bool wrt_cells) const = 0;
+    // node counts and spacing of a grid the adjoint is defined for; Unsupported (with the reason) for every other grid.  wrt names the
+    // entry the call came through (TapeWrt): the cell entry takes cell grids only (ValueError on a node grid), the node entry keeps
+    // refusing cell grids (Unsupported), the model entries take node grids only (ValueError on a cell grid)
+    virtual void adjoint_geometry(int* nn3, double* spacing, TapeWrt wrt) const = 0;
     AdjSink* adj_sink = nullptr;          // set for the duration of such a call
     std::vector<int> adj_src, adj_row;    // a replica of a multi-device grid: event and first row, in the call, of each source of ITS call
     // the raytrace overloads with l_data (2-D cell grids): ray-projection matrix L, one CSR row per receiver
@@ -2378,8 +2382,11 @@ class GridT : public GridBase {
         for (auto& v : m_seg_off) std::vector<long long>().swap(v);
     }
     // ---- the field tape (fsm_adjoint_api.h)
-    void adjoint_geometry(int* nn3, double* spacing, bool wrt_cells) const override {
+    void adjoint_geometry(int* nn3, double* spacing, TapeWrt wrt) const override {
+        const bool wrt_cells = wrt == WRT_CELLS;
         if (dim != 3) throw Unsupported("the adjoint-state gradient is implemented for 3-D grids only");
+        if (cell && wrt == WRT_MODEL)
+            throw ValueError("a coarse model grid needs a grid with slowness defined at the nodes: this grid has it for cells");
         if (cell && !wrt_cells)
             throw Unsupported("the adjoint-state gradient with respect to node slowness is not implemented for grids with slowness defined for "
                               "cells: ttcr_fsm_raytrace_multi_adjoint_cells gives the gradient with respect to the cells");
@@ -2393,7 +2400,7 @@ class GridT : public GridBase {
                                 void* tt_out_v, AdjSink& sink) override {
         int nn3[3];
         double sp;
-        adjoint_geometry(nn3, &sp, sink.cells);
+        adjoint_geometry(nn3, &sp, sink.cells ? WRT_CELLS : WRT_NODES);
         adj_sink = &sink;
         try {
             raytrace_multi(n_src, tx_off, tx_v, t0_v, rx_off, rx_v, tt_out_v, -1, nullptr, false);
@@ -3159,12 +3166,12 @@ class MultiGrid : public GridBase {
         timing.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
     }
     // The field tape: the sources go to the replicas like raytrace_multi sends them; every replica copies its fields to the sink's device.
-    void adjoint_geometry(int* nn3, double* spacing, bool wrt_cells) const override { rep[0]->adjoint_geometry(nn3, spacing, wrt_cells); }
+    void adjoint_geometry(int* nn3, double* spacing, TapeWrt wrt) const override { rep[0]->adjoint_geometry(nn3, spacing, wrt); }
     void raytrace_multi_adjoint(int n_src, const int* tx_off, const void* tx_v, const void* t0_v, const int* rx_off, const void* rx_v,
                                 void* tt_out_v, AdjSink& sink) override {
         int nn3[3];
         double sp;
-        adjoint_geometry(nn3, &sp, sink.cells);
+        adjoint_geometry(nn3, &sp, sink.cells ? WRT_CELLS : WRT_NODES);
         for (auto& r : rep) r->adj_sink = &sink;
         auto clear = [&] { for (auto& r : rep) { r->adj_sink = nullptr; r->adj_src.clear(); r->adj_row.clear(); } };
         try {
@@ -3801,9 +3808,20 @@ struct ttcr_fsm_adjoint {
     ~ttcr_fsm_adjoint() { t.release(); }
 };
 
-// the two entries that make a field tape: wrt_cells = the cell entry (a cell grid, model vector = cell slowness)
+// what is wrong with a model shape on a grid of nn3 nodes (null: nothing)
+static const char* model_shape_error(const int* model_shape, const int* nn3) {
+    if (!model_shape) return "null model_shape";
+    for (int d = 0; d < 3; ++d)
+        if (model_shape[d] < 1 || model_shape[d] > nn3[d]) return "model_shape: 1 <= m <= the grid's node count on every axis (x, y, z)";
+    return nullptr;
+}
+
+// the three entries that make a field tape: WRT_CELLS = the cell entry (a cell grid, model vector = cell slowness); WRT_MODEL = the
+// model entry (a node grid, model vector = slowness at the nodes of the coarse grid model_shape; model_shape is read for
+// that entry only)
 static int raytrace_multi_adjoint_entry(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off,
-                                        const void* rx, void* tt_out, ttcr_fsm_adjoint** tape, bool wrt_cells) {
+                                        const void* rx, void* tt_out, ttcr_fsm_adjoint** tape, TapeWrt wrt, const int* model_shape) {
+    const bool wrt_cells = wrt == WRT_CELLS, wrt_model = wrt == WRT_MODEL;
     if (!tape) {
         g_last_error = "null tape output pointer";
         return TTCR_ERR_VALUE;
@@ -3811,14 +3829,17 @@ static int raytrace_multi_adjoint_entry(ttcr_fsm_grid* g, int n_src, const int* 
     *tape = nullptr;
     if (n_src < 0 || (n_src > 0 && (!tx_off || !tx || !t0 || !rx_off || !rx || !tt_out))) {
         g_last_error = wrt_cells ? "raytrace_multi_adjoint_cells: null array or negative source count"
-                                 : "raytrace_multi_adjoint: null array or negative source count";
+                                 : (wrt_model ? "model_raytrace_multi_adjoint: null array or negative source count"
+                                              : "raytrace_multi_adjoint: null array or negative source count");
         return TTCR_ERR_VALUE;
     }
     return guarded_on(g, [&] {
         GridBase& G = *g->impl;
         int nn3[3];
         double spacing = 0;
-        G.adjoint_geometry(nn3, &spacing, wrt_cells);
+        G.adjoint_geometry(nn3, &spacing, wrt);
+        if (wrt_model)
+            if (const char* bad = model_shape_error(model_shape, nn3)) throw ValueError(bad);
         std::unique_ptr<ttcr_fsm_adjoint> tp(new ttcr_fsm_adjoint());
         ttcr_amd::AdjTapeDev& t = tp->t;
         tp->dtype = G.dtype;
@@ -3831,6 +3852,9 @@ static int raytrace_multi_adjoint_entry(ttcr_fsm_grid* g, int n_src, const int* 
         t.dx = spacing;
         t.cells = wrt_cells;
         t.nc = wrt_cells ? (size_t)(nn3[0] - 1) * (size_t)(nn3[1] - 1) * (size_t)(nn3[2] - 1) : 0;
+        t.model = wrt_model;
+        if (wrt_model)
+            for (int d = 0; d < 3; ++d) { t.map.n[d] = nn3[d]; t.map.m[d] = model_shape[d]; }
         adj_device_errors([&] {
             HIP_CHECK(hipSetDevice(t.device));
             HIP_CHECK(hipStreamCreateWithFlags(&t.stream, hipStreamNonBlocking));
@@ -3855,11 +3879,15 @@ static int raytrace_multi_adjoint_entry(ttcr_fsm_grid* g, int n_src, const int* 
 }
 int ttcr_fsm_raytrace_multi_adjoint(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off,
                                     const void* rx, void* tt_out, ttcr_fsm_adjoint** tape) {
-    return raytrace_multi_adjoint_entry(g, n_src, tx_off, tx, t0, rx_off, rx, tt_out, tape, false);
+    return raytrace_multi_adjoint_entry(g, n_src, tx_off, tx, t0, rx_off, rx, tt_out, tape, WRT_NODES, nullptr);
 }
 int ttcr_fsm_raytrace_multi_adjoint_cells(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off,
                                           const void* rx, void* tt_out, ttcr_fsm_adjoint** tape) {
-    return raytrace_multi_adjoint_entry(g, n_src, tx_off, tx, t0, rx_off, rx, tt_out, tape, true);
+    return raytrace_multi_adjoint_entry(g, n_src, tx_off, tx, t0, rx_off, rx, tt_out, tape, WRT_CELLS, nullptr);
+}
+int ttcr_fsm_model_raytrace_multi_adjoint(ttcr_fsm_grid* g, int n_src, const int* tx_off, const void* tx, const void* t0, const int* rx_off,
+                                          const void* rx, void* tt_out, ttcr_fsm_adjoint** tape, const int model_shape[3]) {
+    return raytrace_multi_adjoint_entry(g, n_src, tx_off, tx, t0, rx_off, rx, tt_out, tape, WRT_MODEL, model_shape);
 }
 // ---- the host layer of the tape's entries: one frame, two staging helpers.
 //
@@ -3972,6 +4000,97 @@ int ttcr_fsm_adjoint_model(const ttcr_fsm_adjoint* t, int* cells, size_t* n_para
     *n_params = t->t.n_model();
     *n_nodes = t->t.nn;
     return TTCR_OK;
+}
+// ---- the coarse model grid
+int ttcr_fsm_model_shape(const ttcr_fsm_adjoint* t, int* is_model, int* shape) {
+    if (!t || !is_model || !shape) return tape_arg_error("null tape or output pointer");
+    *is_model = t->t.model ? 1 : 0;
+    for (int d = 0; d < 3; ++d) shape[d] = t->t.model ? t->t.map.m[d] : 0;
+    return TTCR_OK;
+}
+// P and P^T on the tape's stream with the tape's own tables: a host argument goes through cell_tmp (the model vector) or grad_tmp (the
+// node vector), which are idle outside a product
+static int model_tape_map(const ttcr_fsm_adjoint* t, const void* in, int in_on_device, void* out, int out_on_device, bool prolong) {
+    const char* bad = !in ? "null in" : (!out ? "null out" : (!t ? "null tape" : (!t->t.model ? "the tape has no coarse model grid" : nullptr)));
+    if (bad) return tape_arg_error(bad);
+    return tape_call(t, 0, nullptr, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int&, int&) {
+        using T = decltype(tag);
+        void* st_model = d.cell_tmp;
+        void* st_nodes = d.grad_tmp;
+        const size_t n_in = prolong ? d.n_model() : d.nn, n_out = prolong ? d.nn : d.n_model();
+        const T* din = stage_in<T>(d, in, in_on_device, prolong ? st_model : st_nodes, n_in);
+        T* dout = stage_dst<T>(out, out_on_device, prolong ? st_nodes : st_model);
+        if (prolong) ttcr_amd::adj_model_to_nodes<T>(d, din, dout);
+        else ttcr_amd::adj_nodes_to_model<T>(d, din, dout);
+        stage_out<T>(d, out, out_on_device, prolong ? st_nodes : st_model, n_out);
+    });
+}
+int ttcr_fsm_model_tape_prolong(const ttcr_fsm_adjoint* t, const void* v, int v_on_device, void* out, int out_on_device) {
+    return model_tape_map(t, v, v_on_device, out, out_on_device, true);
+}
+int ttcr_fsm_model_tape_restrict(const ttcr_fsm_adjoint* t, const void* g, int g_on_device, void* out, int out_on_device) {
+    return model_tape_map(t, g, g_on_device, out, out_on_device, false);
+}
+// ... and on a grid, before any tape exists: tables and intermediates live for the call, on the grid's device and the null stream
+extern "C++" {
+template <typename T>
+static void model_grid_run(const int* nn3, const int* shape, const void* in, int in_on_device, void* out, int out_on_device, bool prolong) {
+    ttcr_amd::ModelMap map;
+    struct Free {
+        ttcr_amd::ModelMap& m;
+        ~Free() { ttcr_amd::model_map_free(m); }
+    } free_map{map};
+    ttcr_amd::model_map_create<T>(map, nn3, shape);
+    const size_t n_in = prolong ? map.n_model() : map.n_fine(), n_out = prolong ? map.n_fine() : map.n_model();
+    DevBuf<T> b_in, b_out, b_a, b_b;
+    const T* din = (const T*)in;
+    T* dout = (T*)out;
+    if (!in_on_device) {
+        b_in.reserve(std::max<size_t>(n_in, 1));
+        if (n_in > 0) HIP_CHECK(hipMemcpyAsync(b_in.p, in, n_in * sizeof(T), hipMemcpyHostToDevice, nullptr));
+        din = b_in.p;
+    }
+    if (!out_on_device) {
+        b_out.reserve(std::max<size_t>(n_out, 1));
+        dout = b_out.p;
+    }
+    if (prolong) {
+        ttcr_amd::model_prolong<T>(map, din, dout, nullptr);
+    } else {
+        b_a.reserve(std::max<size_t>(map.n_stage_z(), 1));
+        b_b.reserve(std::max<size_t>(map.n_stage_y(), 1));
+        ttcr_amd::model_restrict<T>(map, din, b_a.p, b_b.p, dout, nullptr);
+    }
+    if (!out_on_device && n_out > 0) HIP_CHECK(hipMemcpyAsync(out, dout, n_out * sizeof(T), hipMemcpyDeviceToHost, nullptr));
+    HIP_CHECK(hipStreamSynchronize(nullptr));
+}
+}  // extern "C++"
+static int model_grid_map(ttcr_fsm_grid* g, const int* model_shape, const void* in, int in_on_device, void* out, int out_on_device,
+                          bool prolong) {
+    if (!in || !out) return tape_arg_error(!in ? "null in" : "null out");
+    return guarded_on(g, [&] {
+        GridBase& G = *g->impl;
+        int nn3[3];
+        double spacing = 0;
+        G.adjoint_geometry(nn3, &spacing, WRT_MODEL);
+        if (const char* bad = model_shape_error(model_shape, nn3)) throw ValueError(bad);
+        adj_device_errors([&] {
+            HIP_CHECK(hipSetDevice(G.device));
+            if (G.dtype == TTCR_F32) model_grid_run<float>(nn3, model_shape, in, in_on_device, out, out_on_device, prolong);
+            else model_grid_run<double>(nn3, model_shape, in, in_on_device, out, out_on_device, prolong);
+        });
+    });
+}
+int ttcr_fsm_model_device(const ttcr_fsm_grid* g, int* device) {
+    if (!g || !device) return tape_arg_error(!g ? "null grid handle" : "null device");
+    *device = g->impl->device;
+    return TTCR_OK;
+}
+int ttcr_fsm_model_prolong(ttcr_fsm_grid* g, const int model_shape[3], const void* v, int v_on_device, void* out, int out_on_device) {
+    return model_grid_map(g, model_shape, v, v_on_device, out, out_on_device, true);
+}
+int ttcr_fsm_model_restrict(ttcr_fsm_grid* g, const int model_shape[3], const void* gr, int g_on_device, void* out, int out_on_device) {
+    return model_grid_map(g, model_shape, gr, g_on_device, out, out_on_device, false);
 }
 int ttcr_fsm_adjoint_size(const ttcr_fsm_adjoint* t, size_t* n_events, size_t* n_rows, size_t* n_nodes) {
     if (!t || !n_events || !n_rows || !n_nodes) return tape_arg_error("null tape or output pointer");
@@ -4238,10 +4357,8 @@ static const char* normal_weights_error(const double* w, const char* if_null, co
         if (!(w[d] >= 0.0) || !std::isfinite(w[d])) return if_bad;
     return nullptr;
 }
-static const char* normal_axes_error(const ttcr_fsm_adjoint* t) {
-    const int c = t->t.cells ? 1 : 0;
-    return std::min({t->t.nnx, t->t.nny, t->t.nnz}) - c < 3 ? "smooth: second-order smoothing needs at least 3 parameters along every axis"
-                                                             : nullptr;
+static const char* normal_axes_error(const ttcr_fsm_adjoint* t, const double* weights) {
+    return ttcr_amd::adj_smooth_error(t->t, weights);
 }
 static const char* joint_block_error(const double* v, size_t n, const char* if_bad) {
     for (size_t i = 0; v && i < n; ++i)
@@ -4287,7 +4404,7 @@ static T* block_prepare(ttcr_amd::AdjTapeDev& d, ttcr_amd::CgSystem sys) {
 int ttcr_fsm_normal_tile_edge(int dtype) { return ttcr_amd::adj_smooth_tile_edge(dtype == TTCR_F32 ? 4 : 8); }
 int ttcr_fsm_normal_smooth(ttcr_fsm_adjoint* t, const void* v, int v_on_device, const double* weights, void* out, int out_on_device) {
     const char* bad = normal_weights_error(weights, "null weights", "weights: three finite values >= 0 (x, y, z)");
-    if (!bad) bad =!v ? "null v" : (!out ? "null out" : (!t ? "null tape" : normal_axes_error(t)));
+    if (!bad) bad =!v ? "null v" : (!out ? "null out" : (!t ? "null tape" : normal_axes_error(t, weights)));
     if (bad) return tape_arg_error(bad);
     return tape_call(t, 0, nullptr, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int&, int&) {
         using T = decltype(tag);
@@ -4336,7 +4453,7 @@ static int tape_solve(ttcr_fsm_adjoint* t, const TapeBlock* blk, const void* rhs
     else if (!t) bad = "null tape";
     else if (const char* c = joint_block_error(b_scale, t->t.cg_block(sys), blk ? blk->bad_scale : nullptr)) bad = c;
     else if (const char* c = joint_block_error(b_damp, t->t.cg_block(sys), blk ? blk->bad_damp : nullptr)) bad = c;
-    else if (smooth != 0.0) bad = normal_axes_error(t);
+    else if (smooth != 0.0) bad = normal_axes_error(t, smooth_weights);
     if (!bad) bad = dd_weight_error(t, pair_weight, pw_on_device);
     if (bad) return tape_arg_error(bad);
     return tape_call(t, schedule, nullptr, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int&, int&) {

@@ -73,17 +73,25 @@ __device__ __forceinline__ T nrm_axis(const T* c, int sd, int i, int n, T ih2, T
 template <typename T>
 struct NrmSmooth {
     NrmDims g;
-    T ih2, ax, ay, az;   // T(1 / dx^2) and the weights of the axes
+    T ihx, ihy, ihz;   // T(1 / h_d^2) per axis, h_d the spacing of the parameters along it (node and cell tapes: dx on all three)
+    T ax, ay, az;      // the weights of the axes
+    int ex, ey, ez;    // the axis is evaluated (node and cell tapes: all three; a model tape leaves out an axis with fewer than 3 nodes)
 };
 
 // (R v) at the parameter (gx, gy, gz) whose value is c[0]; sx, sy, sz are the strides of the three axes in the array c points into
 template <typename T>
 __device__ __forceinline__ T nrm_smooth_at(const T* c, int sx, int sy, int sz, int gx, int gy, int gz, const NrmSmooth<T>& sm) {
-    const T m2ih2 = T(-2) * sm.ih2;
-    const T zx = nrm_axis<T>(c, sx, gx, sm.g.mx, sm.ih2, m2ih2);
-    const T zy = nrm_axis<T>(c, sy, gy, sm.g.my, sm.ih2, m2ih2);
-    const T zz = nrm_axis<T>(c, sz, gz, sm.g.mz, sm.ih2, m2ih2);
-    return (sm.ax * zx + sm.ay * zy) + sm.az * zz;
+    // the left-to-right sum over the evaluated axes in x, y, z order, starting from its first term: (ax zx + ay zy) + az zz with all three
+    T z = T(0);
+    bool first = true;
+    auto add = [&](T term) {
+        z = first ? term : z + term;
+        first = false;
+    };
+    if (sm.ex) add(sm.ax * nrm_axis<T>(c, sx, gx, sm.g.mx, sm.ihx, T(-2) * sm.ihx));
+    if (sm.ey) add(sm.ay * nrm_axis<T>(c, sy, gy, sm.g.my, sm.ihy, T(-2) * sm.ihy));
+    if (sm.ez) add(sm.az * nrm_axis<T>(c, sz, gz, sm.g.mz, sm.ihz, T(-2) * sm.ihz));
+    return z;
 }
 
 // out = R v: one workgroup per tile of TI^3 parameters; the tile of v with a two-node halo (cut at the faces of the grid) sits in LDS,
@@ -281,6 +289,7 @@ void cg_free_all(CgWork& w) {
 size_t nrm_chunks(size_t n) { return std::max<size_t>(1, (n + NRM_CHUNK - 1) / NRM_CHUNK); }
 
 NrmDims nrm_dims(const AdjTapeDev& t) {
+    if (t.model) return NrmDims{t.map.m[0], t.map.m[1], t.map.m[2]};
     const int c = t.cells ? 1 : 0;
     return NrmDims{t.nnx - c, t.nny - c, t.nnz - c};
 }
@@ -295,10 +304,33 @@ void nrm_close(AdjTapeDev& t, CgSystem sys, int what) {
 
 template <typename T>
 NrmSmooth<T> nrm_smooth_args(const AdjTapeDev& t, const double* weights) {
-    return NrmSmooth<T>{nrm_dims(t), (T)(1.0 / (t.dx * t.dx)), (T)weights[0], (T)weights[1], (T)weights[2]};
+    const NrmDims g = nrm_dims(t);
+    const T ih2 = (T)(1.0 / (t.dx * t.dx));
+    if (!t.model) return NrmSmooth<T>{g, ih2, ih2, ih2, (T)weights[0], (T)weights[1], (T)weights[2], 1, 1, 1};
+    // a model tape: spacing h_d = dx (n_d - 1) / (m_d - 1) in double; an axis with fewer than 3 model nodes is not evaluated
+    const int n[3] = {t.nnx, t.nny, t.nnz}, m[3] = {g.mx, g.my, g.mz};
+    T ih[3];
+    int ev[3];
+    for (int d = 0; d < 3; ++d) {
+        ev[d] = m[d] >= 3 ? 1 : 0;
+        const double h = ev[d] ? t.dx * (double)(n[d] - 1) / (double)(m[d] - 1) : t.dx;
+        ih[d] = (T)(1.0 / (h * h));
+    }
+    return NrmSmooth<T>{g, ih[0], ih[1], ih[2], (T)weights[0], (T)weights[1], (T)weights[2], ev[0], ev[1], ev[2]};
 }
 
 }  // namespace
+
+const char* adj_smooth_error(const AdjTapeDev& t, const double* weights) {
+    const NrmDims g = nrm_dims(t);
+    const int m[3] = {g.mx, g.my, g.mz};
+    if (!t.model)
+        return std::min({m[0], m[1], m[2]}) < 3 ? "smooth: second-order smoothing needs at least 3 parameters along every axis" : nullptr;
+    for (int d = 0; d < 3; ++d)
+        if (m[d] < 3 && weights[d] != 0.0)
+            return "smooth: a model axis with fewer than 3 nodes is left out of the smoothing operator and takes weight 0";
+    return nullptr;
+}
 
 int adj_smooth_tile_edge(size_t elem) { return elem == 4 ? NrmTile<float>::edge : NrmTile<double>::edge; }
 
@@ -362,8 +394,7 @@ void adj_cg_release(AdjTapeDev& t, CgSystem sys) {
 template <typename T>
 void adj_smooth(AdjTapeDev& t, const T* d_v, const double* weights, T* d_out) {
     const NrmDims g = nrm_dims(t);
-    if (g.mx < 3 || g.my < 3 || g.mz < 3)
-        throw std::invalid_argument("smooth: second-order smoothing needs at least 3 parameters along every axis");
+    if (const char* bad = adj_smooth_error(t, weights)) throw std::invalid_argument(bad);
     constexpr int ed = NrmTile<T>::edge;
     const int ntx = (g.mx + ed - 1) / ed, nty = (g.my + ed - 1) / ed, ntz = (g.mz + ed - 1) / ed;
     nrm_smooth_kernel<T, ed><<<(unsigned)((size_t)ntx * nty * ntz), NRM_THREADS, 0, t.stream>>>(d_v, d_out, nrm_smooth_args<T>(t, weights), ntx,

@@ -106,6 +106,13 @@ def gauss_newton_step(tape, residual, model, row_weight=None, smooth=0., damp=0.
     return tape.solve_normal(b, row_weight=row_weight, smooth=smooth, damp=damp, **solve_args)
 
 
+def apply_model_update(tape, slowness, dm):
+    """The node slowness after a step dm (n_cols values) on a model tape (raytrace_adjoint(..., wrt='model')):
+    slowness + tape.prolong(dm), in slowness's flat node order (x fastest).  The slowness need not be P of anything: the tape
+    linearises at whatever was solved and the step moves it by P dm."""
+    return slowness + tape.prolong(dm)
+
+
 def joint_gauss_newton_step(tape, residual, model, row_weight=None, smooth=0., damp=0., source_damp=0., source_scale=None, **solve_args):
     """The update (x, x_src) of slowness and source points of one regularised joint hypocentre-velocity Gauss-Newton step on a field
     tape: the right-hand sides

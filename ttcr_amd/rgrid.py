@@ -68,6 +68,19 @@ def _first_rows(a):
     return np.sort(order[bounds[:-1]])
 
 
+def _model_shape_arg(model_shape, nn):
+    """model_shape of a coarse model grid under a grid of nn = (nx, ny, nz) nodes as three ints: 1 <= m_d <= n_d"""
+    try:
+        m = tuple(int(v) for v in model_shape)
+        ok = len(m) == 3 and all(float(v) == int(v) for v in model_shape)
+    except (TypeError, ValueError):
+        m, ok = (), False
+    if not ok or any(not 1 <= m[d] <= nn[d] for d in range(3)):
+        raise ValueError('model_shape should be three integers (mx, my, mz) with 1 <= m <= %s, the node counts of the grid, got %r'
+                         % (tuple(int(v) for v in nn), model_shape))
+    return m
+
+
 def _device_arg(device):
     """`device` keyword of the grid classes: a HIP device ordinal (-1: the current device; with TTCR_AMD_DEVICES set,
     the devices it lists), or a sequence of ordinals -- one replica of the grid per entry, the traveltime slots
@@ -384,8 +397,8 @@ class _GridBase:
         rx_off[1:] = np.cumsum([len(r) for r in vRx])
         return tx_off, tx, t0, rx_off, rx, np.empty(max(rx.shape[0], 1), dtype=dt)
 
-    def raytrace_adjoint(self, source, rcv, slowness=None, aggregate_src=False, wrt='nodes'):
-        """raytrace_adjoint(source, rcv, slowness=None, aggregate_src=False, wrt='nodes') -> (tt, tape)
+    def raytrace_adjoint(self, source, rcv, slowness=None, aggregate_src=False, wrt='nodes', model_shape=None):
+        """raytrace_adjoint(source, rcv, slowness=None, aggregate_src=False, wrt='nodes', model_shape=None) -> (tt, tape)
 
         Traveltimes at the receivers (same source / receiver handling as raytrace_tape) and a FieldTape that keeps every event's
         traveltime field on the device for the adjoint-state gradient: tape.vjp(w, field_cotangent) is the exact derivative, with
@@ -395,13 +408,21 @@ class _GridBase:
         wrt='nodes' (default): a node grid, the model vector of the tape is the node slowness.  wrt='cells': a grid with slowness defined
         for cells; the tape differentiates with respect to the cell slowness (tape.n_cols = number of cells, the flat order of
         set_slowness, x fastest) through the cell-to-node averaging of set_slowness; its fields stay node-sized (tape.n_nodes).  A
-        cell grid with wrt='nodes' raises NotImplementedError, a node grid with wrt='cells' ValueError."""
+        cell grid with wrt='nodes' raises NotImplementedError, a node grid with wrt='cells' ValueError.
+        wrt='model' with model_shape=(mx, my, mz), 1 <= m <= the node counts: a node grid; the model vector of the tape holds the slowness
+        at the nodes of a coarse grid that spans the fine one (tape.n_cols = mx my mz, x fastest) and the node slowness moves by P times
+        its change, P the trilinear prolongation (Grid3d.prolong).  m = 1 on an axis: constant along it.  The solve itself
+        uses the grid's slowness as it is.  model_shape with another wrt, wrt='model' without it or on a cell grid: ValueError."""
         source = np.asarray(source)
         rcv = np.asarray(rcv)
         if source.ndim != 2 or rcv.ndim != 2:
             raise ValueError('source and rcv should be 2D arrays')
-        if wrt not in ('nodes', 'cells'):
-            raise ValueError("wrt should be 'nodes' or 'cells', got %r" % (wrt,))
+        if wrt not in ('nodes', 'cells', 'model'):
+            raise ValueError("wrt should be 'nodes' or 'cells', got %r (or 'model' with model_shape=(mx, my, mz): a coarse model grid)" % (wrt,))
+        if model_shape is not None and wrt != 'model':
+            raise ValueError("model_shape goes with wrt='model', got wrt=%r" % (wrt,))
+        if wrt == 'model' and model_shape is None:
+            raise ValueError("wrt='model' needs model_shape=(mx, my, mz)")
         if self._ndim != 3:
             raise NotImplementedError('the adjoint-state gradient is implemented for 3-D grids only')
         if self.cell_slowness and wrt == 'nodes':
@@ -409,19 +430,79 @@ class _GridBase:
                                       "slowness defined for cells: wrt='cells' gives the gradient with respect to the cells")
         if not self.cell_slowness and wrt == 'cells':
             raise ValueError("wrt='cells' needs a grid with slowness defined for cells (cell_slowness=1); this grid has it at the nodes")
+        m3 = self._model_shape(model_shape) if wrt == 'model' else None
         vTx, vt0, vRx, iRx = self._split_sources(source, rcv, aggregate_src)
         if slowness is not None:
             self.set_slowness(slowness)
         dt = self._dtype
         tx_off, tx, t0, rx_off, rx, out = self._event_arrays(vTx, vt0, vRx)
         h = C.c_void_p()
-        entry = self._lib.ttcr_fsm_raytrace_multi_adjoint_cells if wrt == 'cells' else self._lib.ttcr_fsm_raytrace_multi_adjoint
-        _lib.check(entry(self._h, len(vTx), _ptr(tx_off), _ptr(tx), _ptr(t0), _ptr(rx_off), _ptr(rx), _ptr(out), C.byref(h)))
+        args = (self._h, len(vTx), _ptr(tx_off), _ptr(tx), _ptr(t0), _ptr(rx_off), _ptr(rx), _ptr(out), C.byref(h))
+        if wrt == 'model':
+            _lib.check(self._lib.ttcr_fsm_model_raytrace_multi_adjoint(*args, (C.c_int * 3)(*m3)))
+        else:
+            entry = self._lib.ttcr_fsm_raytrace_multi_adjoint_cells if wrt == 'cells' else self._lib.ttcr_fsm_raytrace_multi_adjoint
+            _lib.check(entry(*args))
         tape = FieldTape(self._lib, h, dt, np.concatenate(iRx).astype(np.int64), rcv.shape[0])
         tt = np.zeros((rcv.shape[0],), dtype=dt)
         for n in range(len(vTx)):
             tt[iRx[n]] = out[rx_off[n]:rx_off[n + 1]]
         return tt, tape
+
+    # ---- the coarse model grid: P and P^T on the grid, before any tape exists
+    def _model_shape(self, model_shape):
+        """the checks of a model_shape on this grid, before any device call: (mx, my, mz)"""
+        if self._ndim != 3:
+            raise NotImplementedError('the adjoint-state gradient is implemented for 3-D grids only')
+        if self.cell_slowness:
+            raise ValueError("wrt='model' needs a grid with slowness defined at the nodes (cell_slowness=0); this grid has it for cells")
+        return _model_shape_arg(model_shape, (self._x.size, self._y.size, self._z.size))
+
+    def _model_map(self, a, model_shape, prolong):
+        m3 = self._model_shape(model_shape)
+        n_model, n_nodes = math.prod(m3), self.get_number_of_nodes()
+        n_in, n_out = (n_model, n_nodes) if prolong else (n_nodes, n_model)
+        name, per = ('v', 'model node') if prolong else ('g', 'node')
+        on_dev = type(a).__module__.startswith('torch') and a.device.type == 'cuda'
+        is_torch = type(a).__module__.startswith('torch')
+        seen = a if on_dev else np.asarray(a.detach().numpy() if hasattr(a, 'detach') else a)
+        if math.prod(seen.shape) != n_in:
+            raise ValueError('%s should hold %d values (one per %s), got shape %s' % (name, n_in, per, tuple(seen.shape)))
+        entry = self._lib.ttcr_fsm_model_prolong if prolong else self._lib.ttcr_fsm_model_restrict
+        shape = (C.c_int * 3)(*m3)
+        if on_dev:   # the kernels run on the grid's device: a tensor of another device goes there and the result comes back to it
+            import torch
+
+            d = C.c_int(0)
+            _lib.check(self._lib.ttcr_fsm_model_device(self._h, C.byref(d)))
+            dev = torch.device('cuda', d.value)
+            tdt = torch.float32 if self._dtype == np.float32 else torch.float64
+            src = a.detach().to(device=dev, dtype=tdt).contiguous().reshape(-1)
+            out = torch.empty(n_out, dtype=tdt, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            _lib.check(entry(self._h, shape, C.c_void_p(src.data_ptr()), 1, C.c_void_p(out.data_ptr()), 1))
+            return out.to(a.device)
+        src = np.ascontiguousarray(seen, dtype=self._dtype).reshape(-1)
+        out = np.empty(n_out, dtype=self._dtype)
+        _lib.check(entry(self._h, shape, _ptr(src), 0, _ptr(out), 0))
+        if is_torch:
+            import torch
+
+            return torch.from_numpy(out)
+        return out
+
+    def prolong(self, v, model_shape):
+        """P v: the values v at the mx x my x mz nodes of a coarse model grid that spans this grid (x fastest), interpolated trilinearly
+        onto the grid's nodes: n_nodes values, x fastest, grid dtype, every one the fixed expression of DESIGN.md 6n
+        (tests/model_reference.py restates it).  model_shape = (mx, my, mz), 1 <= m <= the node counts; m = 1: constant along the axis.
+        v: a numpy array (numpy out), a CPU tensor (CPU tensor out) or a CUDA tensor (used in place on the grid's device, moved there
+        and the result moved back from any other; tensor out).  3-D node grids with weno=0."""
+        return self._model_map(v, model_shape, True)
+
+    def restrict(self, g, model_shape):
+        """P^T g: the transpose of prolong applied to n_nodes values g (x fastest): mx my mz values, summed in the fixed order of
+        DESIGN.md 6n (three stages, z first, ascending, no atomics).  Array handling as in prolong."""
+        return self._model_map(g, model_shape, False)
 
     def _run(self, vTx, vt0, vRx, iRx, n_rcv, thread_no, return_rays=False):
         dt = self._dtype
@@ -576,9 +657,12 @@ class FieldTape:
     pair_adjoint and row_operator apply Q, Q^T and B = diag(row_weight) + Q^T diag(pair_weight) Q, and the keyword pair_weight of
     gauss_newton, newton, the two joint products and the three solves puts B in the place of the diagonal weighting; release_pairs
     frees what these calls hold on the device.
-    wrt is 'nodes' or 'cells': what the model vector of vjp / jvp / gauss_newton holds, n_cols values -- the node slowness (n_cols =
-    n_nodes) or, for the tape of raytrace_adjoint(..., wrt='cells'), the cell slowness in set_slowness's flat order (n_cols = cells).
-    Fields, field cotangents and field tangents hold n_nodes values per event on either tape."""
+    wrt is 'nodes', 'cells' or 'model': what the model vector of vjp / jvp / gauss_newton holds, n_cols values -- the node slowness
+    (n_cols = n_nodes), for the tape of raytrace_adjoint(..., wrt='cells') the cell slowness in set_slowness's flat order (n_cols =
+    cells), or for the tape of raytrace_adjoint(..., wrt='model', model_shape=(mx, my, mz)) the slowness at the nodes of a coarse model
+    grid (n_cols = mx my mz, x fastest; model_shape, prolong, restrict, model_coordinates): every product and solve then
+    works on that vector through the trilinear prolongation P, and the smoothing operator acts on the model grid.
+    Fields, field cotangents and field tangents hold n_nodes values per event on every tape."""
 
     SCHEDULES = {'tiled': 0, 'jacobi': 1}
     _pairs_set = False         # set_row_pairs has run (DESIGN.md 6m)
@@ -599,6 +683,11 @@ class FieldTape:
         self.wrt = 'cells' if cells.value else 'nodes'
         self.n_cols = npar.value   # length of the model vector
         self._per = 'cell' if cells.value else 'node'
+        is_model, m3 = C.c_int(0), (C.c_int * 3)()
+        _lib.check(lib.ttcr_fsm_model_shape(handle, C.byref(is_model), m3))
+        self.model_shape = tuple(m3) if is_model.value else None   # (mx, my, mz) of a model tape
+        if is_model.value:
+            self.wrt, self._per = 'model', 'model node'
         d, b = C.c_int(0), C.c_size_t(0)
         _lib.check(lib.ttcr_fsm_adjoint_device(handle, C.byref(d)))
         _lib.check(lib.ttcr_fsm_adjoint_bytes(handle, C.byref(b)))
@@ -1629,6 +1718,46 @@ class FieldTape:
         xyz = origin[None, :] + ijk.astype(np.float64) * dx
         xyz[node < 0] = np.nan
         return xyz
+
+    # ---- the coarse model grid of a model tape
+    def _need_model(self):
+        self._handle()
+        if self.model_shape is None:
+            raise ValueError("the tape has no coarse model grid: it comes from raytrace_adjoint(..., wrt=%r)" % (self.wrt,))
+
+    def prolong(self, v):
+        """P v on the tape's stream: n_cols model values -> n_nodes values (x fastest, grid dtype), the node vector that jvp relaxes with.
+        Array handling as in jvp.  ValueError on a tape without a model grid."""
+        self._need_model()
+        va, pv, dv = self._model_arg(v, 'v')
+        po, do, finish = self._out(v, 1, self.n_nodes)
+        self._sync(dv, do)
+        _lib.check(self._lib.ttcr_fsm_model_tape_prolong(self._h, pv, dv, po, do))
+        return finish()[0]
+
+    def restrict(self, g):
+        """P^T g on the tape's stream: n_nodes values -> n_cols model values, what vjp ends with.  Array handling as in jvp."""
+        self._need_model()
+        g_seen = self._seen(g)
+        if math.prod(g_seen.shape) != self.n_nodes:
+            raise ValueError('g should hold %d values (one per node), got shape %s' % (self.n_nodes, tuple(g_seen.shape)))
+        ga, pg, dg = self._arg(g_seen)
+        po, do, finish = self._model_out(g)
+        self._sync(dg, do)
+        _lib.check(self._lib.ttcr_fsm_model_tape_restrict(self._h, pg, dg, po, do))
+        return finish()
+
+    def model_coordinates(self):
+        """(x, y, z): float64 coordinates of the model nodes along each axis in the user's coordinates (the grid's origin included); an
+        axis with one model node names the middle of the grid's extent, along which the model is constant."""
+        self._need_model()
+        nn3, dx, origin = self.geometry
+        axes = []
+        for d in range(3):
+            n, m = nn3[d], self.model_shape[d]
+            ext = dx * (n - 1)
+            axes.append(origin[d] + (np.arange(m, dtype=np.float64) * ext / (m - 1) if m > 1 else np.array([0.5 * ext])))
+        return tuple(axes)
 
     def release_locate(self):
         """Free the work arrays of locate_grid (nbytes falls by what its calls added); the next call allocates them again.  Nothing of the
