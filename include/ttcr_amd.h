@@ -795,6 +795,47 @@ int ttcr_fsm_dd_solve(ttcr_fsm_adjoint* t, int system, const void* rhs, int rhs_
                       int xb_on_device, int* status, int* iterations, double* rho, double* pq, int* passes);
 int ttcr_fsm_dd_release(ttcr_fsm_adjoint* t);
 
+/* Moving the receiver points of a field tape without a solve, and the relocation-only system (no reference equivalent) --
+ * what a relocation loop on a fixed model needs in the reciprocal layout: the fields of the stations stay, the hypocentres (the receiver
+ * points of the tape) move, and the step that moves them is the receiver block alone.  tests/relocation_reference.py restates both.
+ * ttcr_fsm_reloc_move: pts holds 3 n_rcv_points values of the grid dtype (user coordinates, host or the tape's device); every row of
+ *   receiver point q gets the receiver pts[q].  Per row, one thread: the origin of a translated grid is subtracted as the raytrace entry
+ *   subtracts it, then the row's interpolation stencil, its traveltime (the bits of ttcr_fsm_interp on the event's field) and G are
+ *   evaluated.  The stencil entries in row order (the forward mode's list) are written by that kernel at offsets the host formed; the
+ *   adjoint's seed list is that list stably sorted by (event * n_nodes + node) on the device (radix sort) -- the order the host builds for
+ *   a new tape.  tt (n_rows values in tape row order, host or device, may be NULL) receives the new traveltimes.  Afterwards the tape is,
+ *   bit for bit and in every result of every entry, the tape that ttcr_fsm_raytrace_multi_adjoint builds with the same grid, slowness and
+ *   sources and with the moved receivers, followed by the same ttcr_fsm_rcv_points and ttcr_fsm_dd_pairs.  No field, coupling term,
+ *   mask or frozen list changes.  A held cotangent is released as by ttcr_fsm_adjoint_release (its adjoint belonged to the old
+ *   stencils); the point map, the pairs and every work array stay.  Every point has to be finite and has to pass the bounds check the
+ *   raytrace entries apply to a receiver ("Receiver outside grid"), else TTCR_ERR_VALUE before any device write and the tape is unchanged.
+ *   The first move gives both lists room for 8 entries per row and allocates three index arrays of that length and the sort's workspace;
+ *   ttcr_fsm_adjoint_bytes reports them, TTCR_ERR_DEVICE with the byte count if that fails, ttcr_fsm_adjoint_free returns them.  Later
+ *   moves allocate nothing.
+ * ttcr_fsm_reloc_get_points: pts (3 n_rcv_points doubles) receives the current user coordinates of the receiver points: the values of the
+ *   last move, or, before any move (and after ttcr_fsm_rcv_points replaced the map), the receiver of the point's first row with the
+ *   origin of a translated grid added again in the grid dtype; NaN for a point without rows that no move has placed.
+ * ttcr_fsm_reloc_gn: out_rcv = C G^T B (G C v_rcv), 4 n_rcv_points values: G is ttcr_fsm_rcv_jvp's operator, C = diag(rcv_scale) (NULL:
+ *   none), B the row operator of ttcr_fsm_dd_apply's mode 2 (pair_weight NULL: diag(row_weight), NULL: the identity).  The kernels of
+ *   ttcr_fsm_rjoint_gn without its two relaxations; its bits are those of ttcr_fsm_rjoint_gn's out_rcv for v = 0 (the sign of a zero
+ *   may differ).
+ * ttcr_fsm_reloc_solve: (C G^T B G C + diag(rcv_damp)) z = C rhs_rcv by the conjugate gradients of ttcr_fsm_rjoint_solve on a vector
+ *   that is the receiver block alone (n_joint = 4 n_rcv_points): the same scaling, damping of the scaled unknown, inner products,
+ *   recurrence, statuses and outputs; x_rcv = C z.  No relaxation in any iteration.  With pure double-difference data (row_weight all
+ *   zero) and no damping of t0 the system is singular: the common origin-time shift is in the null space of Q.  The first call allocates
+ *   five vectors of n_joint values and three of the block; ttcr_fsm_rcv_release returns them.
+ * Pairs go straight into these two entries (pair_weight); the `system` argument of ttcr_fsm_dd_gn / ttcr_fsm_dd_solve stays 0 .. 2.
+ * Argument errors return TTCR_ERR_VALUE naming the argument before any device call.  Two new kernels (a thread per row; a thread per
+ * seed entry) and the device radix sort; everything else is the existing kernels.  No floating-point atomics.  Not covered: a direct
+ * 4 x 4 solve per point, moving source points, S-P rows, 2-D, WENO, tt_from_rp = 1. */
+int ttcr_fsm_reloc_move(ttcr_fsm_adjoint* t, const void* pts, int pts_on_device, void* tt, int tt_on_device);
+int ttcr_fsm_reloc_get_points(const ttcr_fsm_adjoint* t, double* pts);
+int ttcr_fsm_reloc_gn(const ttcr_fsm_adjoint* t, const void* v_rcv, int vr_on_device, const void* row_weight, int rw_on_device,
+                      const void* pair_weight, int pw_on_device, const double* rcv_scale, void* out_rcv, int or_on_device);
+int ttcr_fsm_reloc_solve(ttcr_fsm_adjoint* t, const void* rhs_rcv, int rr_on_device, const void* row_weight, int rw_on_device,
+                         const void* pair_weight, int pw_on_device, const double* rcv_damp, const double* rcv_scale, int maxiter,
+                         double rtol, void* x_rcv, int xr_on_device, int* status, int* iterations, double* rho, double* pq);
+
 /* Replaces: Grid2D::raytrace(Tx, t0, Rx, traveltimes, l_data, threadNo) (ttcr/Grid2D.h:616-640) and the overload with r_data
  * AND l_data (:583-614) -> Grid2Drn::getRaypath(Tx, t0, Rx, [r_data,] l_data, tt, threadNo) (ttcr/Grid2Drn.h:1852-2190): what
  * `compute_L=True` of the Python layer reaches for 2-D grids with cell slowness (src/ttcrpy/rgrid.pyx:3889-3893, :4060-4143).

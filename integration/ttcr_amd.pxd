@@ -180,6 +180,14 @@ cdef extern from "ttcr_amd.h" nogil:
                           int x0_on_device, int maxiter, double rtol, int newton, int schedule, void* x, int x_on_device, void* x_b,
                           int xb_on_device, int* status, int* iterations, double* rho, double* pq, int* passes)
     int ttcr_fsm_dd_release(ttcr_fsm_adjoint* t)
+    # moving the receiver points of a field tape, and the relocation-only system
+    int ttcr_fsm_reloc_move(ttcr_fsm_adjoint* t, const void* pts, int pts_on_device, void* tt, int tt_on_device)
+    int ttcr_fsm_reloc_get_points(const ttcr_fsm_adjoint* t, double* pts)
+    int ttcr_fsm_reloc_gn(const ttcr_fsm_adjoint* t, const void* v_rcv, int vr_on_device, const void* row_weight, int rw_on_device,
+                          const void* pair_weight, int pw_on_device, const double* rcv_scale, void* out_rcv, int or_on_device)
+    int ttcr_fsm_reloc_solve(ttcr_fsm_adjoint* t, const void* rhs_rcv, int rr_on_device, const void* row_weight, int rw_on_device,
+                             const void* pair_weight, int pw_on_device, const double* rcv_damp, const double* rcv_scale, int maxiter,
+                             double rtol, void* x_rcv, int xr_on_device, int* status, int* iterations, double* rho, double* pq)
     int ttcr_fsm_slot_m_size(const ttcr_fsm_grid* g, int slot, size_t* n_rows, size_t* nnz)
     int ttcr_fsm_get_slot_m(const ttcr_fsm_grid* g, int slot, long long* row_off, long long* j, void* v)
     int ttcr_fsm_raytrace_l(ttcr_fsm_grid* g, int slot, int n_tx, const void* tx, const void* t0, int n_rx, const void* rx,

@@ -128,6 +128,11 @@ SYMBOLS = {
     "ttcr_fsm_rjoint_solve": (_I, [_P, _P, _I, _P, _I, _P, _I, _D, C.POINTER(_D), _D, C.POINTER(_D), C.POINTER(_D), _I, _D, _I, _P, _I, _P, _I,
                                    C.POINTER(_I), C.POINTER(_I), C.POINTER(_D), C.POINTER(_D), C.POINTER(_I)]),
     "ttcr_fsm_rcv_release": (_I, [_P]),
+    "ttcr_fsm_reloc_move": (_I, [_P, _P, _I, _P, _I]),
+    "ttcr_fsm_reloc_get_points": (_I, [_P, C.POINTER(_D)]),
+    "ttcr_fsm_reloc_gn": (_I, [_P, _P, _I, _P, _I, _P, _I, C.POINTER(_D), _P, _I]),
+    "ttcr_fsm_reloc_solve": (_I, [_P, _P, _I, _P, _I, _P, _I, C.POINTER(_D), C.POINTER(_D), _I, _D, _P, _I, C.POINTER(_I), C.POINTER(_I),
+                                  C.POINTER(_D), C.POINTER(_D)]),
     "ttcr_fsm_loc_geometry": (_I, [_P, C.POINTER(_I), C.POINTER(_D), C.POINTER(_D)]),
     "ttcr_fsm_loc_shape": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "ttcr_fsm_loc_grid": (_I, [_P, C.c_size_t, C.POINTER(C.c_longlong), C.POINTER(_I), C.POINTER(_D), C.POINTER(_D), C.POINTER(_I),

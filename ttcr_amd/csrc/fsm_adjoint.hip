@@ -5,7 +5,10 @@
 #include "fsm_adjoint_api.h"
 #include "fsm_kernels.h"   // fsm_cells_to_nodes3d: the forward direction of a cell tape is set_slowness's own kernel
 
+#include <hipcub/hipcub.hpp>   // the stable radix sort of a moved tape's seed list
+
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <limits>
@@ -633,6 +636,57 @@ __global__ void rcv_grad_kernel(const int* __restrict__ off, const int* __restri
         acc = k == 0 ? acc + w[r] : acc + w[r] * G[3 * (size_t)r + k - 1];
     }
     grcv[i] = acc;
+}
+
+// ---- moving the receiver points.  One thread per row r of receiver point q = pt[r]: the point as the solver sees it
+// (p = fl(pts[q] - shift) per axis, the arithmetic of the raytrace entry; a grid that is not translated has shift +0), its stencil
+// (interp3d_stencil) written into the row-order list at off[r] -- the host formed the offsets from the same function; a count that
+// differs raises *err and nothing is written past the row's room --, with the row and the place of every entry for the sort that follows;
+// then tt (interp3d_pt on the event's field) and G (rcv_grad_pt), as rcv_eval_kernel computes them.
+template <typename T>
+__global__ void rcv_move_kernel(const T* __restrict__ fields, const T* __restrict__ pts, const int* __restrict__ pt,
+                                const int* __restrict__ event, const int* __restrict__ off, size_t n_rows, RcvGeom<T> g,
+                                T* __restrict__ rcv_p, T* __restrict__ tt, T* __restrict__ grad, long long* __restrict__ rw_key,
+                                T* __restrict__ rw_w, int* __restrict__ ent_row, int* __restrict__ ent_idx, int* __restrict__ err) {
+    const size_t r = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (r >= n_rows) return;
+    const size_t q = (size_t)pt[r];
+    T p[3];
+    for (int a = 0; a < 3; ++a) {
+        p[a] = pts[3 * q + a] - g.shift[a];
+        rcv_p[3 * r + a] = p[a];
+    }
+    long long nd[8];
+    T wt[8];
+    const int cnt = interp3d_stencil<T>(p[0], p[1], p[2], g.nn[0], g.nn[1], g.nn[2], g.dx, g.cmin[0], g.cmin[1], g.cmin[2], nd, wt);
+    const int o = off[r], room = off[r + 1] - o;
+    if (cnt != room) atomicOr(err, 1);
+    const long long base = (long long)((size_t)event[r] * g.nodes);
+    for (int c = 0; c < room; ++c) {   // (every place of the row's room is written, so the sort never sees a stale entry)
+        const bool real = c < cnt;
+        rw_key[o + c] = base + (real ? nd[c] : 0);
+        rw_w[o + c] = real ? wt[c] : (T)0;
+        ent_row[o + c] = (int)r;
+        ent_idx[o + c] = o + c;
+    }
+    const T* Tn = fields + (size_t)event[r] * g.nodes;
+    tt[r] = interp3d_pt<T>(Tn, 1, p[0], p[1], p[2], g.nn[0], g.nn[1], g.nn[2], g.dx, g.cmin[0], g.cmin[1], g.cmin[2]);
+    T G[3];
+    rcv_grad_pt<T>(Tn, p, g, G);
+    grad[3 * r] = G[0];
+    grad[3 * r + 1] = G[1];
+    grad[3 * r + 2] = G[2];
+}
+
+// the seed list behind the sorted keys: place i holds entry perm[i] of the row-order list
+template <typename T>
+__global__ void rcv_move_gather_kernel(const int* __restrict__ perm, const int* __restrict__ ent_row, const T* __restrict__ rw_w, size_t n,
+                                       int* __restrict__ sd_row, T* __restrict__ sd_w) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int e = perm[i];
+    sd_row[i] = ent_row[e];
+    sd_w[i] = rw_w[e];
 }
 
 // Global Jacobi pass of the K-column relaxation (the correctness baseline): for a node that is not frozen
@@ -1321,7 +1375,10 @@ void AdjTapeDev::release() {
     dev_free(map_a); dev_free(map_b);
     model_map_free(map);
     dev_free(g4); dev_free(blk_model); dev_free(blk_nodes); dev_free(blk_rows); dev_free(blk_rw);
-    for (CgSystem sys : {CG_MODEL, CG_SOURCE, CG_RECEIVER}) adj_cg_release(*this, sys);
+    for (CgSystem sys : {CG_MODEL, CG_SOURCE, CG_RECEIVER, CG_RELOC}) adj_cg_release(*this, sys);
+    dev_free(mv_row); dev_free(mv_idx); dev_free(mv_perm); dev_free(mv_sort);
+    mv_cap = 0;
+    mv_sort_bytes = 0;
     dev_free(rcv_p); dev_free(rcv_event); dev_free(rcv_pt); dev_free(rcv_rows); dev_free(rcv_off); dev_free(rcv_G); dev_free(rcv_tt);
     dev_free(rcv_io); dev_free(rcv_stage);
     adj_loc_release(*this);
@@ -1417,6 +1474,7 @@ void adj_finish(AdjTapeDev& t, const AdjSink& sink) {
         t.h_rcv_event.assign(sink.st_event.begin(), sink.st_event.end());
         std::copy(sink.rcv_min, sink.rcv_min + 3, t.rcv_min);
         std::copy(sink.rcv_shift, sink.rcv_shift + 3, t.rcv_shift);
+        std::copy(sink.rcv_max, sink.rcv_max + 3, t.rcv_max);
         std::vector<int> one(t.n_rows);
         std::iota(one.begin(), one.end(), 0);
         adj_rcv_set_points(t, one.data(), t.n_rows);
@@ -2048,6 +2106,7 @@ void adj_gn_joint(AdjTapeDev& t, const T* d_vs, const T* d_ve, const T* d_scale,
 // ---- derivatives with respect to the receiver points
 void adj_rcv_set_points(AdjTapeDev& t, const int* point_of_row, size_t n_points) {
     adj_rcv_release(t);   // (what is on the device belongs to the old map)
+    t.h_mv_pts.clear();   // (... and the points of the last move to the old points)
     t.h_rcv_pt.assign(point_of_row, point_of_row + t.n_rows);
     t.n_rcv_points = n_points;
     t.h_rcv_off.assign(n_points + 1, 0);
@@ -2125,6 +2184,7 @@ void* adj_rcv_stage(AdjTapeDev& t, size_t bytes) {
 
 void adj_rcv_release(AdjTapeDev& t) {
     adj_cg_release(t, CG_RECEIVER);
+    adj_cg_release(t, CG_RELOC);
     if (!t.rcv_p && !t.rcv_stage) return;
     (void)hipSetDevice(t.device);
     if (t.stream) (void)hipStreamSynchronize(t.stream);
@@ -2170,6 +2230,153 @@ void adj_vjp_rcv(AdjTapeDev& t, const T* d_w, T* d_grcv) {
     rcv_grad_kernel<T><<<blocks_for(4 * t.n_rcv_points), ADJ_THREADS, 0, t.stream>>>(t.rcv_off, t.rcv_rows, (const T*)t.rcv_G, d_w,
                                                                                     t.n_rcv_points, d_grcv);
     ADJ_CHECK(hipGetLastError());
+}
+
+// ---- moving the receiver points, and the relocation-only product
+template <typename T>
+const char* adj_rcv_move_error(const AdjTapeDev& t, const T* h_pts) {
+    for (size_t q = 0; q < t.n_rcv_points; ++q)
+        for (int a = 0; a < 3; ++a) {
+            const T v = h_pts[3 * q + a];
+            if (!std::isfinite((double)v)) return "xyz: a coordinate that is not finite";
+            const T p = v - (T)t.rcv_shift[a];
+            if (p < (T)t.rcv_min[a] || p > (T)t.rcv_max[a]) return "Receiver outside grid";
+        }
+    return nullptr;
+}
+
+namespace {
+int mv_end_bit(const AdjTapeDev& t) {   // the bits of the largest key, event * nn + node
+    unsigned long long top = (unsigned long long)t.n_events * t.nn;
+    int bits = 1;
+    while (bits < 64 && (top >> bits) != 0) ++bits;
+    return bits;
+}
+size_t mv_sort_need(const AdjTapeDev& t, size_t n) {
+    size_t bytes = 0;
+    ADJ_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, (const long long*)nullptr, (long long*)nullptr, (const int*)nullptr,
+                                                 (int*)nullptr, n, 0, mv_end_bit(t), t.stream));
+    return std::max<size_t>(bytes, 1);
+}
+}  // namespace
+
+size_t adj_rcv_move_bytes(const AdjTapeDev& t) {
+    const size_t cap = 8 * t.n_rows;
+    auto at_least_1 = [](size_t b) { return std::max<size_t>(b, 1); };
+    return 2 * at_least_1(cap * sizeof(long long)) + 2 * at_least_1(cap * t.elem) + 4 * at_least_1(cap * sizeof(int)) + mv_sort_need(t, cap);
+}
+
+// the first move: room for 8 entries per row in the seed list and the row-order list (the old arrays, sized by the first stencils,
+// leave), the three index arrays and the sort's workspace.  The stream is idle (every entry waits for it before it returns).
+static void mv_prepare(AdjTapeDev& t) {
+    if (t.mv_row) return;
+    const size_t cap = 8 * t.n_rows;
+    Alloc alloc{t, adj_rcv_move_bytes(t)};
+    const size_t before = t.total_bytes;
+    long long *k1 = nullptr, *k2 = nullptr;
+    int* r1 = nullptr;
+    void *w1 = nullptr, *w2 = nullptr;
+    try {
+        alloc(k1, cap * sizeof(long long));
+        alloc(r1, cap * sizeof(int));
+        alloc(w1, cap * t.elem);
+        alloc(k2, cap * sizeof(long long));
+        alloc(w2, cap * t.elem);
+        alloc(t.mv_row, cap * sizeof(int));
+        alloc(t.mv_idx, cap * sizeof(int));
+        alloc(t.mv_perm, cap * sizeof(int));
+        t.mv_sort_bytes = mv_sort_need(t, cap);
+        alloc(t.mv_sort, t.mv_sort_bytes);
+    } catch (...) {
+        dev_free(k1); dev_free(r1); dev_free(w1); dev_free(k2); dev_free(w2);
+        dev_free(t.mv_row); dev_free(t.mv_idx); dev_free(t.mv_perm); dev_free(t.mv_sort);
+        t.mv_sort_bytes = 0;
+        t.total_bytes = before;
+        throw;
+    }
+    auto was = [](size_t b) { return std::max<size_t>(b, 1); };   // (what Alloc counted for the arrays that leave)
+    t.total_bytes -= 2 * was(t.n_seed * sizeof(long long)) + was(t.n_seed * sizeof(int)) + 2 * was(t.n_seed * t.elem);
+    dev_free(t.sd_key); dev_free(t.sd_row); dev_free(t.sd_w); dev_free(t.rw_key); dev_free(t.rw_w);
+    t.sd_key = k1; t.sd_row = r1; t.sd_w = w1; t.rw_key = k2; t.rw_w = w2;
+    t.mv_cap = cap;
+}
+
+template <typename T>
+void adj_rcv_move(AdjTapeDev& t, const T* h_pts, const T* d_pts, T* d_tt) {
+    ADJ_CHECK(hipSetDevice(t.device));
+    adj_rcv_prepare<T>(t);
+    adj_jvp_prepare<T>(t);   // (the row-order list lives on the device from here on)
+    mv_prepare(t);
+    adj_release_hold(t);     // (the held adjoint belongs to the old stencils)
+    hipStream_t s = t.stream;
+    const size_t n_pts = t.n_rcv_points;
+    // host: the stencil of every point as the kernel will compute it -- the offsets of the row-order list come from its counts --, and
+    // the mirrors of what the device rebuilds
+    std::vector<int> cnt(n_pts);
+    std::vector<long long> nd(8 * n_pts);
+    std::vector<T> wt(8 * n_pts), ps(3 * n_pts);
+    for (size_t q = 0; q < n_pts; ++q) {
+        for (int a = 0; a < 3; ++a) ps[3 * q + a] = h_pts[3 * q + a] - (T)t.rcv_shift[a];
+        cnt[q] = interp3d_stencil<T>(ps[3 * q], ps[3 * q + 1], ps[3 * q + 2], t.nnx, t.nny, t.nnz, (T)t.dx, (T)t.rcv_min[0], (T)t.rcv_min[1],
+                                     (T)t.rcv_min[2], &nd[8 * q], &wt[8 * q]);
+    }
+    for (size_t r = 0; r < t.n_rows; ++r) t.h_rw_off[r + 1] = t.h_rw_off[r] + cnt[t.h_rcv_pt[r]];
+    const size_t n_seed = t.n_rows > 0 ? (size_t)t.h_rw_off[t.n_rows] : 0;
+    t.h_rw_key.resize(n_seed);
+    t.h_rw_w.resize(n_seed);
+    for (size_t r = 0; r < t.n_rows; ++r) {
+        const size_t q = (size_t)t.h_rcv_pt[r], o = (size_t)t.h_rw_off[r];
+        for (int c = 0; c < cnt[q]; ++c) {
+            t.h_rw_key[o + c] = (long long)((size_t)t.h_rcv_event[r] * t.nn) + nd[8 * q + c];
+            t.h_rw_w[o + c] = (double)wt[8 * q + c];
+        }
+        for (int a = 0; a < 3; ++a) t.h_rcv_p[3 * r + a] = (double)ps[3 * q + a];
+    }
+    t.h_mv_pts.assign(h_pts, h_pts + 3 * n_pts);
+    t.n_seed = n_seed;
+    if (t.n_rows > 0) {
+        ADJ_CHECK(hipMemcpyAsync(t.rw_off, t.h_rw_off.data(), (t.n_rows + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+        if (!d_pts) {
+            ADJ_CHECK(hipMemcpyAsync(t.rcv_io, h_pts, 3 * n_pts * sizeof(T), hipMemcpyHostToDevice, s));
+            d_pts = (const T*)t.rcv_io;
+        }
+        ADJ_CHECK(hipMemsetAsync(t.err, 0, sizeof(int), s));
+        rcv_move_kernel<T><<<blocks_for(t.n_rows), ADJ_THREADS, 0, s>>>((const T*)t.fields, d_pts, t.rcv_pt, t.rcv_event, t.rw_off, t.n_rows,
+                                                                      rcv_geom<T>(t), (T*)t.rcv_p, (T*)t.rcv_tt, (T*)t.rcv_G, t.rw_key,
+                                                                      (T*)t.rw_w, t.mv_row, t.mv_idx, t.err);
+        ADJ_CHECK(hipGetLastError());
+        if (n_seed > 0) {
+            size_t bytes = mv_sort_need(t, n_seed);
+            if (bytes > t.mv_sort_bytes) throw std::logic_error("move_receiver_points: the sort asks for more workspace than at its capacity");
+            bytes = t.mv_sort_bytes;
+            ADJ_CHECK(hipcub::DeviceRadixSort::SortPairs(t.mv_sort, bytes, (const long long*)t.rw_key, t.sd_key, (const int*)t.mv_idx,
+                                                         t.mv_perm, n_seed, 0, mv_end_bit(t), s));
+            rcv_move_gather_kernel<T><<<blocks_for(n_seed), ADJ_THREADS, 0, s>>>(t.mv_perm, t.mv_row, (const T*)t.rw_w, n_seed, t.sd_row,
+                                                                                (T*)t.sd_w);
+            ADJ_CHECK(hipGetLastError());
+        }
+        if (d_tt) ADJ_CHECK(hipMemcpyAsync(d_tt, t.rcv_tt, t.n_rows * sizeof(T), hipMemcpyDeviceToDevice, s));
+        int h_err = 0;
+        ADJ_CHECK(hipMemcpyAsync(&h_err, t.err, sizeof(int), hipMemcpyDeviceToHost, s));
+        ADJ_CHECK(hipStreamSynchronize(s));
+        if (h_err) throw std::runtime_error("move_receiver_points: internal error, the stencil of a row differs between the host and the device");
+    }
+}
+
+template <typename T>
+void adj_gn_reloc(AdjTapeDev& t, const T* d_ve, const T* d_scale, T* d_ve_scaled, const RowOp<T>& op, T* d_ge) {
+    ADJ_CHECK(hipSetDevice(t.device));
+    adj_rcv_prepare<T>(t);
+    const size_t blk = 4 * t.n_rcv_points;
+    if (d_scale) {
+        adj_scale<T>(t, d_scale, d_ve, d_ve_scaled, blk);
+        d_ve = d_ve_scaled;
+    }
+    T* w = (T*)t.w_tmp;
+    adj_jvp_rcv<T>(t, d_ve, nullptr, w);
+    const T* rows = adj_row_operator<T>(t, op, w);
+    adj_vjp_rcv<T>(t, rows, d_ge);
+    if (d_scale) adj_scale<T>(t, d_scale, d_ge, d_ge, blk);
 }
 
 template <typename T>
@@ -2401,6 +2608,12 @@ template void adj_jvp_rcv<float>(AdjTapeDev&, const float*, const float*, float*
 template void adj_jvp_rcv<double>(AdjTapeDev&, const double*, const double*, double*);
 template void adj_vjp_rcv<float>(AdjTapeDev&, const float*, float*);
 template void adj_vjp_rcv<double>(AdjTapeDev&, const double*, double*);
+template const char* adj_rcv_move_error<float>(const AdjTapeDev&, const float*);
+template const char* adj_rcv_move_error<double>(const AdjTapeDev&, const double*);
+template void adj_rcv_move<float>(AdjTapeDev&, const float*, const float*, float*);
+template void adj_rcv_move<double>(AdjTapeDev&, const double*, const double*, double*);
+template void adj_gn_reloc<float>(AdjTapeDev&, const float*, const float*, float*, const RowOp<float>&, float*);
+template void adj_gn_reloc<double>(AdjTapeDev&, const double*, const double*, double*, const RowOp<double>&, double*);
 template void adj_scale<float>(AdjTapeDev&, const float*, const float*, float*, size_t);
 template void adj_scale<double>(AdjTapeDev&, const double*, const double*, double*, size_t);
 template int adj_jvp_rjoint<float>(AdjTapeDev&, const float*, const float*, float*, float*, int);

@@ -16,7 +16,10 @@
 // Normal equations (fsm_normal.hip): the smoothing operator on the model vector (a tile with a two-node halo in LDS), inner
 //                   products summed in a fixed order (chunks of 1024, one finishing workgroup), and conjugate gradients around the
 //                   Gauss-Newton / Newton product with the scalars of the recurrence formed on the device.  One solver (adj_solve) over
-//                   three systems (CgSystem): the model vector alone, or with the source block (6j) or the receiver block (6k) behind it.
+//                   four systems (CgSystem): the model vector alone, or with the source block (6j) or the receiver block (6k) behind it,
+//                   or the receiver block alone (6o).
+// Moving receivers: the rows' points, traveltimes, gradients and stencils from one kernel (a thread per row), the seed list
+//                   of the adjoint from a stable device radix sort of the stencil entries and a gather -- no solve, no relaxation.
 // Grid search (fsm_locate.hip): per hypocentre the node of the tape's fields with the smallest weighted, origin-time-corrected
 //                   misfit of its picks -- one search kernel (partial minima per workgroup), one finishing kernel; no solve, no relaxation.
 // No floating-point atomics anywhere: every value is one fixed expression of final values, so the bits do not depend on the schedule.
@@ -62,6 +65,8 @@ struct AdjSink {
     // translated grid; T values held exactly, 3 per row), the origin the solver interpolates with and the shift of a translated grid
     std::vector<double> st_p;
     double rcv_min[3] = {0, 0, 0}, rcv_shift[3] = {0, 0, 0};
+    // ... and the upper corner the solver checks a point against (after the shift), for a tape that moves its receivers
+    double rcv_max[3] = {0, 0, 0};
 };
 
 // ---- the coarse model grid (tests/model_reference.py restates it; fsm_model.hip).  The per-axis tables of the trilinear
@@ -94,8 +99,10 @@ template <typename T>
 void model_restrict(const ModelMap& map, const T* d_g, T* d_a, T* d_b, T* d_gm, hipStream_t stream);
 
 // The systems the conjugate-gradient solver of fsm_normal.hip runs on: the model vector alone, the model vector followed by
-// the source block (the joint hypocentre-velocity system, 6j), or followed by the receiver block (the receiver joint system, 6k).
-enum CgSystem { CG_MODEL = 0, CG_SOURCE = 1, CG_RECEIVER = 2 };
+// the source block (the joint hypocentre-velocity system, 6j), or followed by the receiver block (the receiver joint system, 6k) -- or the
+// receiver block alone, its model block empty (the relocation-only system, 6o).
+enum CgSystem { CG_MODEL = 0, CG_SOURCE = 1, CG_RECEIVER = 2, CG_RELOC = 3 };
+constexpr int CG_SYSTEMS = 4;
 // the work arrays of the solver for one system, all on the tape's device; n = cg_len(system), b = cg_block(system)
 struct CgWork {
     void* x = nullptr;        // n each: the iterate (a host x0 and the host result are staged here; its block in the scaled unknown z_e), ...
@@ -185,11 +192,12 @@ struct AdjTapeDev {
     size_t blk_bytes = 0;             // what the block arrays added to total_bytes
     // the conjugate-gradient solver: one set of work arrays per system, allocated by the first call that needs it
     // (smooth, dot or solve for the model system; the first solve for the other two) and returned by adj_cg_release
-    CgWork cg[3];                     // by CgSystem
-    // elements of a system's extra block, (t0, x, y, z) of every source point in call order or of every receiver point, and of its vector:
-    // the model vector, then the block
+    CgWork cg[CG_SYSTEMS];            // by CgSystem
+    // elements of a system's extra block, (t0, x, y, z) of every source point in call order or of every receiver point, of its model
+    // block (empty for the relocation-only system) and of its vector: the model block, then the extra block
     size_t cg_block(CgSystem s) const { return s == CG_MODEL ? 0 : 4 * (s == CG_SOURCE ? n_points : n_rcv_points); }
-    size_t cg_len(CgSystem s) const { return n_model() + cg_block(s); }
+    size_t cg_model(CgSystem s) const { return s == CG_RELOC ? 0 : n_model(); }
+    size_t cg_len(CgSystem s) const { return cg_model(s) + cg_block(s); }
     // receiver points.  Host lists, kept from adj_finish on: the receiver of every row as the solver sees it, the point of
     // every row (default: one point per row) and the rows of every point (CSR, rows ascending within a point).  The first receiver call
     // uploads them, evaluates G of the tape's rows and allocates the staging arrays; adj_rcv_release returns all of it
@@ -201,6 +209,7 @@ struct AdjTapeDev {
     size_t n_rcv_points = 0;
     double rcv_min[3] = {0, 0, 0};    // the origin the solver interpolates with
     double rcv_shift[3] = {0, 0, 0};  // what a translated grid subtracts from a point first (zeros otherwise)
+    double rcv_max[3] = {0, 0, 0};    // the upper corner the solver checks a shifted point against
     void* rcv_p = nullptr;            // 3 n_rows
     int* rcv_event = nullptr;         // n_rows
     int* rcv_pt = nullptr;            // n_rows
@@ -212,6 +221,17 @@ struct AdjTapeDev {
     size_t rcv_bytes = 0;             // what these arrays added to total_bytes
     void* rcv_stage = nullptr;        // staging of rcv_eval at arbitrary points: grow-only, returned by adj_rcv_release
     size_t rcv_stage_bytes = 0;
+    // moving the receiver points.  The first move gives the seed list (sd_*) and the row-order list (rw_key, rw_w) room
+    // for mv_cap = 8 n_rows entries -- a row has 1, 2, 4 or 8 -- and allocates what the rebuild on the device works in; all of it stays
+    // until the tape is freed.  h_mv_pts: the points of the last move as the caller gave them (T values held exactly, 3 per receiver
+    // point; empty before the first move and after adj_rcv_set_points)
+    size_t mv_cap = 0;
+    int* mv_row = nullptr;            // mv_cap: the row of every entry of the row-order list
+    int* mv_idx = nullptr;            // mv_cap: 0, 1, 2, ... (the values the sort carries)
+    int* mv_perm = nullptr;           // mv_cap: the entry of the row-order list that stands at each place of the seed list
+    void* mv_sort = nullptr;          // the radix sort's workspace
+    size_t mv_sort_bytes = 0;
+    std::vector<double> h_mv_pts;
     // grid search: the uploaded picks, the partial minima and the results of a call, and the misfit volume of a call that
     // wants it on the host; both grow to the largest call and are returned by adj_loc_release
     void* loc_work = nullptr;
@@ -391,10 +411,10 @@ struct NormalResult {
     std::vector<int> passes;        // (jvp, vjp) passes of the product of every such iteration
     int passes0[2] = {0, 0};        // ... and of A x0
 };
-// Conjugate gradients on A x = rhs for one of the three systems, w = t.cg[sys]: on entry w.r holds rhs (its block unscaled) and, if
+// Conjugate gradients on A x = rhs for one of the four systems, w = t.cg[sys]: on entry w.r holds rhs (its block unscaled) and, if
 // with_x0, w.x holds x0; on return w.x holds the iterate.  rop: the row operator of the products, on the tape's device.  Vectors in T, scalars in
 // fp64, inner products as adj_dot over the flat vector of the system; one host read of the scalars per iteration.  What differs between
-// the systems: the product (adj_gn, or adj_hess if op.newton, for CG_MODEL; adj_gn_joint for CG_SOURCE; adj_gn_rjoint for CG_RECEIVER) and
+// the systems: the product (adj_gn, or adj_hess if op.newton, for CG_MODEL; adj_gn_joint for CG_SOURCE; adj_gn_rjoint for CG_RECEIVER; adj_gn_reloc for CG_RELOC, whose model block is empty) and
 // the block -- w.scale / w.damp hold c and delta if with_scale / with_damp, the block of rhs is scaled by c before the loop and the block
 // of x after it (x_e = fl(c * z_e)), and the block of A p is fl(hp + fl(delta * p)).  x0 and op.newton are offered for CG_MODEL only
 // (std::invalid_argument otherwise), a scale and a block damping only for the other two.
@@ -438,6 +458,24 @@ void adj_jvp_rcv(AdjTapeDev& t, const T* d_drcv, const T* d_base, T* d_dtt);
 // d_grcv (4 n_rcv_points) = the reverse chains of d_w (n_rows) over the rows of every point
 template <typename T>
 void adj_vjp_rcv(AdjTapeDev& t, const T* d_w, T* d_grcv);
+// ---- moving the receiver points, and the relocation-only system (tests/relocation_reference.py restates both)
+// what is wrong with the new receiver points h_pts (3 n_rcv_points values on the host, the caller's coordinates), null: nothing.  A point
+// has to be finite and, after the shift of a translated grid, inside the box the solver checks its receivers against.  Host only.
+template <typename T>
+const char* adj_rcv_move_error(const AdjTapeDev& t, const T* h_pts);
+// what the first move adds to the tape
+size_t adj_rcv_move_bytes(const AdjTapeDev& t);
+// gives every row of receiver point q the receiver h_pts[q] (checked by adj_rcv_move_error): rcv_p, rcv_tt and rcv_G of every row from
+// one kernel (one thread per row: shift, interp3d_stencil, interp3d_pt, rcv_grad_pt), the row-order list of the forward mode written by
+// the same kernel at the offsets the host formed, the seed list from a stable radix sort of that list by (event, node) and a gather.
+// n_seed, the host mirrors (h_rcv_p, h_rw_*) and h_mv_pts follow; a held cotangent is released.  d_pts: the same points on the tape's
+// device, or null (h_pts is uploaded through rcv_io).  d_tt (n_rows, may be null) receives rcv_tt.  On the tape's stream; waits for it.
+template <typename T>
+void adj_rcv_move(AdjTapeDev& t, const T* h_pts, const T* d_pts, T* d_tt);
+// d_ge (4 n_rcv_points) = C G^T (op (G C d_ve)), G the operator of adj_jvp_rcv, C = diag(d_scale) (null: none): adj_gn_rjoint without
+// its two relaxations -- adj_scale, rcv_rows_kernel, the row operator, rcv_grad_kernel, adj_scale.  d_ve_scaled as in adj_gn_joint.
+template <typename T>
+void adj_gn_reloc(AdjTapeDev& t, const T* d_ve, const T* d_scale, T* d_ve_scaled, const RowOp<T>& op, T* d_ge);
 // out = fl(c * in) over n values (in and out may be the same array)
 template <typename T>
 void adj_scale(AdjTapeDev& t, const T* d_c, const T* d_in, T* d_out, size_t n);

@@ -2477,6 +2477,7 @@ class GridT : public GridBase {
             if (e == 0) {   // (written once, like the slowness: the replicas of a multi-device grid share the geometry)
                 sk.rcv_min[0] = (double)xmin; sk.rcv_min[1] = (double)ymin; sk.rcv_min[2] = (double)zmin;
                 sk.rcv_shift[0] = (double)ox; sk.rcv_shift[1] = (double)oy; sk.rcv_shift[2] = (double)oz;
+                sk.rcv_max[0] = (double)xmax; sk.rcv_max[1] = (double)ymax; sk.rcv_max[2] = (double)zmax;
             }
         }
         HIP_CHECK(hipStreamSynchronize(stream));
@@ -4772,6 +4773,103 @@ int ttcr_fsm_dd_solve(ttcr_fsm_adjoint* t, int system, const void* rhs, int rhs_
                       blk ? x_b : nullptr, xb_on_device, status, iterations, rho, pq, passes, pair_weight, pw_on_device);
 }
 int ttcr_fsm_dd_release(ttcr_fsm_adjoint* t) { return tape_release(t, ttcr_amd::adj_dd_release); }
+
+// ---- moving the receiver points of the field tape, and the relocation-only system.  Host staging (the table above
+// stage_in continued): rcv_move uploads host points through rcv_io (device points are copied to the host once, for the checks and the
+// offsets the host forms) and hands a host tt out of rcv_tt itself; reloc_gn parts rcv_io as the joint products do (a host v block, the
+// scale, fl(c * v), a host out block); reloc_solve copies its right-hand side into r of cg[CG_RELOC] and reads x from its x.
+int ttcr_fsm_reloc_move(ttcr_fsm_adjoint* t, const void* pts, int pts_on_device, void* tt, int tt_on_device) {
+    if (!pts || !t) return tape_arg_error(!pts ? "null pts" : "null tape");
+    return tape_call(t, 0, nullptr, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int&, int&) {
+        using T = decltype(tag);
+        const size_t n = d.n_rcv_points;
+        std::vector<T> host;
+        const T* hp = (const T*)pts;
+        if (pts_on_device) {
+            host.resize(std::max<size_t>(3 * n, 1));
+            if (n > 0) HIP_CHECK(hipMemcpyAsync(host.data(), pts, 3 * n * sizeof(T), hipMemcpyDeviceToHost, d.stream));
+            HIP_CHECK(hipStreamSynchronize(d.stream));
+            hp = host.data();
+        }
+        if (const char* bad = ttcr_amd::adj_rcv_move_error<T>(d, hp)) throw ValueError(bad);
+        ttcr_amd::adj_rcv_move<T>(d, hp, pts_on_device ? (const T*)pts : nullptr, tt_on_device ? (T*)tt : nullptr);
+        stage_out<T>(d, tt, tt_on_device, d.rcv_tt, d.n_rows);
+    });
+}
+int ttcr_fsm_reloc_get_points(const ttcr_fsm_adjoint* t, double* pts) {
+    if (!t || !pts) return tape_arg_error(!t ? "null tape" : "null pts");
+    ttcr_fsm_adjoint* tm = const_cast<ttcr_fsm_adjoint*>(t);
+    std::lock_guard<std::mutex> lock(tm->mu);
+    const ttcr_amd::AdjTapeDev& d = t->t;
+    if (d.h_mv_pts.size() == 3 * d.n_rcv_points && d.n_rcv_points > 0) {
+        std::copy(d.h_mv_pts.begin(), d.h_mv_pts.end(), pts);
+        return TTCR_OK;
+    }
+    const bool f32 = t->dtype == TTCR_F32;
+    for (size_t q = 0; q < d.n_rcv_points; ++q) {
+        const bool rows = d.h_rcv_off[q + 1] > d.h_rcv_off[q];
+        const size_t r = rows ? (size_t)d.h_rcv_rows[d.h_rcv_off[q]] : 0;
+        for (int a = 0; a < 3; ++a) {
+            if (!rows) pts[3 * q + a] = std::numeric_limits<double>::quiet_NaN();
+            else if (f32) pts[3 * q + a] = (double)((float)d.h_rcv_p[3 * r + a] + (float)d.rcv_shift[a]);
+            else pts[3 * q + a] = d.h_rcv_p[3 * r + a] + d.rcv_shift[a];
+        }
+    }
+    return TTCR_OK;
+}
+int ttcr_fsm_reloc_gn(const ttcr_fsm_adjoint* t, const void* v_rcv, int vr_on_device, const void* row_weight, int rw_on_device,
+                      const void* pair_weight, int pw_on_device, const double* rcv_scale, void* out_rcv, int or_on_device) {
+    const char* bad = !v_rcv ? RCV_BLOCK.null_v : (!out_rcv ? RCV_BLOCK.null_out : (!t ? "null tape" : nullptr));
+    if (!bad) bad = joint_block_error(rcv_scale, t->t.cg_block(ttcr_amd::CG_RELOC), RCV_BLOCK.bad_scale);
+    if (!bad) bad = dd_weight_error(t, pair_weight, pw_on_device);
+    if (bad) return tape_arg_error(bad);
+    return tape_call(t, 0, nullptr, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int&, int&) {
+        using T = decltype(tag);
+        const size_t nb = d.cg_block(ttcr_amd::CG_RELOC);
+        T* io = block_prepare<T>(d, ttcr_amd::CG_RECEIVER);
+        const T* dve = stage_in<T>(d, v_rcv, vr_on_device, io, nb);
+        const ttcr_amd::RowOp<T> drw = stage_row_op<T>(d, row_weight, rw_on_device, pair_weight, pw_on_device);
+        if (rcv_scale) joint_upload<T>(d, rcv_scale, nb, io + nb);
+        T* dob = stage_dst<T>(out_rcv, or_on_device, io + 3 * nb);
+        ttcr_amd::adj_gn_reloc<T>(d, dve, rcv_scale ? io + nb : nullptr, io + 2 * nb, drw, dob);
+        stage_out<T>(d, out_rcv, or_on_device, io + 3 * nb, nb);
+    });
+}
+int ttcr_fsm_reloc_solve(ttcr_fsm_adjoint* t, const void* rhs_rcv, int rr_on_device, const void* row_weight, int rw_on_device,
+                         const void* pair_weight, int pw_on_device, const double* rcv_damp, const double* rcv_scale, int maxiter,
+                         double rtol, void* x_rcv, int xr_on_device, int* status, int* iterations, double* rho, double* pq) {
+    const ttcr_amd::CgSystem sys = ttcr_amd::CG_RELOC;
+    const char* bad = nullptr;
+    if (maxiter < 1) bad = "maxiter: at least one iteration";
+    else if (!(rtol >= 0.0) || !std::isfinite(rtol)) bad = "rtol: a finite value >= 0";
+    else if (!rhs_rcv) bad = RCV_BLOCK.null_rhs;
+    else if (!x_rcv) bad = RCV_BLOCK.null_x;
+    else if (!status || !iterations || !rho || !pq) bad = "null status, iterations, rho or pq";
+    else if (!t) bad = "null tape";
+    else if (const char* c = joint_block_error(rcv_scale, t->t.cg_block(sys), RCV_BLOCK.bad_scale)) bad = c;
+    else if (const char* c = joint_block_error(rcv_damp, t->t.cg_block(sys), RCV_BLOCK.bad_damp)) bad = c;
+    if (!bad) bad = dd_weight_error(t, pair_weight, pw_on_device);
+    if (bad) return tape_arg_error(bad);
+    return tape_call(t, 0, nullptr, nullptr, [&](ttcr_amd::AdjTapeDev& d, auto tag, int&, int&) {
+        using T = decltype(tag);
+        const size_t nb = d.cg_block(sys);
+        ttcr_amd::adj_rcv_prepare<T>(d);
+        ttcr_amd::adj_cg_prepare(d, sys);
+        const ttcr_amd::CgWork& w = d.cg[sys];
+        const ttcr_amd::RowOp<T> drw = stage_row_op<T>(d, row_weight, rw_on_device, pair_weight, pw_on_device);
+        if (nb > 0) HIP_CHECK(hipMemcpyAsync(w.r, rhs_rcv, nb * sizeof(T), rr_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d.stream));
+        const bool with_damp = joint_any(rcv_damp, nb);   // (a term whose factor is 0 everywhere is not evaluated)
+        if (rcv_scale) joint_upload<T>(d, rcv_scale, nb, w.scale);
+        if (with_damp) joint_upload<T>(d, rcv_damp, nb, w.damp);
+        ttcr_amd::NormalResult res;
+        ttcr_amd::adj_solve<T>(d, sys, drw, ttcr_amd::NormalOperator(), false, rcv_scale != nullptr, with_damp, maxiter, rtol, 0, res);
+        if (nb > 0) HIP_CHECK(hipMemcpyAsync(x_rcv, w.x, nb * sizeof(T), xr_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, d.stream));
+        *status = res.status;
+        *iterations = res.iterations;
+        std::copy(res.rho.begin(), res.rho.end(), rho);
+        std::copy(res.pq.begin(), res.pq.end(), pq);
+    });
+}
 
 // ---- grid-search hypocentre location on the tape's fields.  Host staging (the table above stage_in continued): the picks
 // arrive on the host, by hypocentre; offsets (as ints), fields, times, weights (ones for a null pick_weight) and the weight sums go through

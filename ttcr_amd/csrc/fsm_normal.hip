@@ -2,7 +2,8 @@
 // R v = sum_d a_d K_d^T (K_d v) on the tape's model vector, the inner product with a fixed summation order, and conjugate gradients on
 // (H + lam R + mu I) x = b with H the tape's Gauss-Newton (or Newton) product; see fsm_adjoint_api.h.  tests/normal_reference.py restates
 // all of it in numpy.  The same solver runs the joint hypocentre-velocity system (6j) and the receiver joint system (6k), whose vectors
-// carry an extra block behind the model vector (tests/joint_reference.py, tests/receiver_reference.py).  Compiled with -ffp-contract=off like every other unit: each product, difference, quotient and sum below is
+// carry an extra block behind the model vector (tests/joint_reference.py, tests/receiver_reference.py), and the relocation-only system
+// (6o), whose vector is the receiver block alone (tests/relocation_reference.py).  Compiled with -ffp-contract=off like every other unit: each product, difference, quotient and sum below is
 // rounded on its own, in the order the definition writes them.  No floating-point atomics.
 #include "fsm_adjoint_api.h"
 
@@ -344,7 +345,8 @@ void adj_cg_prepare(AdjTapeDev& t, CgSystem sys) {
     CgWork& w = t.cg[sys];
     if (w.x) return;
     NRM_CHECK(hipSetDevice(t.device));
-    static const char* const what[3] = {"the normal-equation solver", "the joint solver", "the receiver joint solver"};
+    static const char* const what[CG_SYSTEMS] = {"the normal-equation solver", "the joint solver", "the receiver joint solver",
+                                                 "the relocation solver"};
     const size_t planned = adj_cg_bytes(t, sys);
     size_t got = 0;
     auto alloc = [&](void*& p, size_t bytes) {
@@ -424,7 +426,7 @@ void adj_solve(AdjTapeDev& t, CgSystem sys, const RowOp<T>& rop, const NormalOpe
     adj_cg_prepare(t, sys);
     const CgWork& wk = t.cg[sys];
     hipStream_t s = t.stream;
-    const size_t nm = t.n_model(), n = t.cg_len(sys), blk = t.cg_block(sys);
+    const size_t nm = t.cg_model(sys), n = t.cg_len(sys), blk = t.cg_block(sys);   // (nm = 0: the relocation-only system)
     const unsigned chunks = (unsigned)nrm_chunks(n);
     T* x = (T*)wk.x;
     T* r = (T*)wk.r;
@@ -439,6 +441,7 @@ void adj_solve(AdjTapeDev& t, CgSystem sys, const RowOp<T>& rop, const NormalOpe
     auto apply = [&](const T* v, int* pj, int* pv) {
         if (sys == CG_SOURCE) adj_gn_joint<T>(t, v, v + nm, c, (T*)wk.ve, rop, hp, hp + nm, schedule, pj, pv);
         else if (sys == CG_RECEIVER) adj_gn_rjoint<T>(t, v, v + nm, c, (T*)wk.ve, rop, hp, hp + nm, schedule, pj, pv);
+        else if (sys == CG_RELOC) adj_gn_reloc<T>(t, v, c, (T*)wk.ve, rop, hp);   // (no relaxation: the passes stay 0)
         else if (op.newton) adj_hess<T>(t, v, rop, true, hp, schedule, pj, pv);
         else adj_gn<T>(t, v, rop, hp, schedule, pj, pv);
         jnt_combine_kernel<T><<<chunks, NRM_THREADS, 0, s>>>(hp, v, q, nm, n, nrm_smooth_args<T>(t, op.weights), (T)op.smooth, (T)op.damp,

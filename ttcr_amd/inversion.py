@@ -346,6 +346,109 @@ def locate(tape, pick_hypo, pick_field, pick_time, pick_weight=None, n_hypo=None
     return t0, x, phi, info
 
 
+# ---- relocation on a fixed model, on a field tape in the reciprocal layout
+def relocation_step(tape, residual, pair_residual=None, row_weight=None, pair_weight=None, rcv_damp=0., rcv_scale=None, **solve_args):
+    """One relocation-only Gauss-Newton step on a field tape: the sibling of double_difference_step without the slowness block.  The
+    weighted rows
+        w = row_weight * residual + tape.pair_adjoint(pair_weight * pair_residual)
+    (row_weight=None: ones; pair_residual=None: no pairs; pair_weight=None: ones; residual=None: no absolute data and an all-zero
+    row_weight), the right-hand side rhs_rcv = tape.vjp_receiver(w) -- no relaxation --, and tape.solve_receiver with the same weights,
+    whose result (x_rcv, or (x_rcv, info) with return_info=True) is returned as it is: (dt0, dx, dy, dz) per receiver point.  Host glue
+    only; arrays stay where they are (numpy or torch)."""
+    w = None
+    if pair_residual is not None:
+        if pair_weight is None:
+            torch_like = hasattr(pair_residual, 'new_ones')
+            pair_weight = pair_residual.new_ones(pair_residual.shape) if torch_like else np.ones(tape.n_pairs, dtype=tape.dtype)
+        w = tape.pair_adjoint(pair_weight * pair_residual)
+    if residual is None:
+        if w is None:
+            raise ValueError('residual and pair_residual are both None: no data')
+        row_weight = w.new_zeros(w.shape) if hasattr(w, 'new_zeros') else np.zeros_like(w)
+    else:
+        rows = residual if row_weight is None else row_weight * residual
+        w = rows if w is None else w + rows
+    return tape.solve_receiver(tape.vjp_receiver(w), row_weight=row_weight, rcv_damp=rcv_damp, rcv_scale=rcv_scale,
+                               pair_weight=pair_weight if pair_residual is not None else None, **solve_args)
+
+
+def relocate(tape, t_obs, t0, row_weight=None, pair_dt=None, pair_weight=None, n_iter=10, rcv_damp=1e-3, rcv_scale=None, maxiter=20,
+             rtol=1e-6):
+    """Relocate the receiver points of a field tape on a fixed model -- the hypocentres of a reciprocal layout, absolute times and
+    (with pair_dt) double-difference times together, hypoDD proper --, with no solve and no relaxation: the loop runs on
+    tape.move_receiver_points, tape.vjp_receiver and tape.solve_receiver.
+      t_obs: the observed arrival time of every data row (rcv order); t0: the origin time of every receiver point, (n_rcv_points,);
+      row_weight: a weight per data row or None (ones); pair_dt: the observed difference of every row pair (tape.set_row_pairs) or
+      None (no pairs); pair_weight: a weight per pair or None (ones); rcv_damp, rcv_scale, maxiter, rtol: solve_receiver's.
+    It starts from tape.receiver_points() (a point without rows that was never moved sits at the grid's lower corner).  Per iteration:
+    the residuals r = t_obs - (tt + t0[point]) and r_p = pair_dt - Q (tt + t0[point]) from the tape's current traveltimes, one
+    relocation_step, and the proposal (t0 + f d_t0, xyz + f d_xyz) with f = 1, every coordinate clipped to the grid, applied by
+    move_receiver_points.  It is accepted if the total weighted misfit sum(row_weight r^2) + sum(pair_weight r_p^2) did not rise;
+    otherwise the same step is tried with f halved, LOCATE_HALVINGS times at most, after which the points are moved back and the
+    loop ends.  Everything is in the tape's dtype except the misfit, which is summed in float64.  Returns (t0, xyz, misfit_history, info):
+    the misfit at the start and after every accepted iteration (it never rises); info holds iterations (accepted), halvings (per
+    accepted iteration) and cg (the info dict of every solve).  The tape is left at the returned points, ready for the next
+    solve_receiver_joint.  With torch tensors on the tape's device nothing but the scalar misfits crosses to the host."""
+    if not isinstance(n_iter, (int, np.integer)) or n_iter < 0:
+        raise ValueError('n_iter should be an integer >= 0, got %r' % (n_iter,))
+    on_dev = type(t_obs).__module__.startswith('torch') and t_obs.device.type == 'cuda'
+    dt = np.dtype(tape.dtype)
+    nn3, dx, origin = tape.geometry
+    lo = np.asarray(origin, dtype=dt)
+    hi = lo + (np.asarray(nn3) - 1).astype(dt) * dt.type(dx)
+    por = np.asarray(tape.rcv_point_of_row, dtype=np.int64)
+    if por.size and por.min() < 0:
+        raise ValueError('relocate needs every data row on the tape')
+    xyz = tape.receiver_points()
+    xyz = np.where(np.isnan(xyz), lo, xyz).astype(dt)
+    if on_dev:
+        import torch
+
+        tdt = torch.float32 if dt == np.float32 else torch.float64
+        as_t = lambda a: None if a is None else torch.as_tensor(a, device=t_obs.device).to(tdt)   # noqa: E731
+        lo, hi, xyz, por = as_t(lo), as_t(hi), as_t(xyz), torch.as_tensor(por, device=t_obs.device)
+        clip = lambda a: torch.minimum(torch.maximum(a, lo), hi)   # noqa: E731
+        total = lambda a: float(a.double().sum())   # noqa: E731
+    else:
+        as_t = lambda a: None if a is None else np.asarray(a.detach().cpu().numpy() if hasattr(a, 'detach') else a, dtype=dt)   # noqa: E731
+        clip = lambda a: np.minimum(np.maximum(a, lo), hi)   # noqa: E731
+        total = lambda a: float(np.sum(np.asarray(a, dtype=np.float64)))   # noqa: E731
+    t_obs, t0, row_weight, pair_dt, pair_weight = as_t(t_obs), as_t(t0), as_t(row_weight), as_t(pair_dt), as_t(pair_weight)
+    if tuple(t0.shape) != (tape.n_rcv_points,):
+        raise ValueError('t0 should hold %d values (one per receiver point), got shape %s' % (tape.n_rcv_points, tuple(t0.shape)))
+
+    def residuals(tt, t0_):
+        tc = tt + t0_[por]
+        r = t_obs - tc
+        rp = pair_dt - tape.pair_difference(tc) if pair_dt is not None else None
+        m = total((r * r) if row_weight is None else (row_weight * (r * r)))
+        if rp is not None:
+            m = m + total((rp * rp) if pair_weight is None else (pair_weight * (rp * rp)))
+        return r, rp, m
+
+    tt = tape.move_receiver_points(xyz)
+    r, rp, m = residuals(tt, t0)
+    history, halvings, cg = [m], [], []
+    for _ in range(int(n_iter)):
+        d, info = relocation_step(tape, r, rp, row_weight, pair_weight, rcv_damp=rcv_damp, rcv_scale=rcv_scale, maxiter=maxiter, rtol=rtol,
+                                  return_info=True)
+        cg.append(info)
+        accepted = False
+        for h in range(LOCATE_HALVINGS + 1):
+            f = 0.5 ** h   # (a power of two: exact in either dtype)
+            t0_new, xyz_new = t0 + f * d[:, 0], clip(xyz + f * d[:, 1:])
+            r_new, rp_new, m_new = residuals(tape.move_receiver_points(xyz_new), t0_new)
+            if m_new <= m:
+                t0, xyz, r, rp, m, accepted = t0_new, xyz_new, r_new, rp_new, m_new, True
+                history.append(m)
+                halvings.append(h)
+                break
+        if not accepted:
+            tape.move_receiver_points(xyz)
+            break
+    return t0, xyz, history, dict(iterations=len(halvings), halvings=halvings, cg=cg)
+
+
 def straight_ray_kernel(Tx, Rx, axes, aniso=False):
     """L (nrays x ncells) with L @ slowness = traveltimes along the straight segments Tx[n] -> Rx[n] through the cells of the grid `axes`
     (node coordinates per dimension, any spacing).  Cells in C order ((ix * ncy + iy) * ncz + iz).  aniso (2-D only): L is nrays x 2 ncells,

@@ -657,6 +657,9 @@ class FieldTape:
     pair_adjoint and row_operator apply Q, Q^T and B = diag(row_weight) + Q^T diag(pair_weight) Q, and the keyword pair_weight of
     gauss_newton, newton, the two joint products and the three solves puts B in the place of the diagonal weighting; release_pairs
     frees what these calls hold on the device.
+    Relocation on a fixed model, with no solve and no relaxation: move_receiver_points gives the receiver points new
+    coordinates and leaves the tape a fresh raytrace_adjoint would build there, receiver_points returns them; vjp_receiver,
+    gauss_newton_receiver and solve_receiver are the receiver block alone (inversion.relocation_step and inversion.relocate run on them).
     wrt is 'nodes', 'cells' or 'model': what the model vector of vjp / jvp / gauss_newton holds, n_cols values -- the node slowness
     (n_cols = n_nodes), for the tape of raytrace_adjoint(..., wrt='cells') the cell slowness in set_slowness's flat order (n_cols =
     cells), or for the tape of raytrace_adjoint(..., wrt='model', model_shape=(mx, my, mz)) the slowness at the nodes of a coarse model
@@ -1516,6 +1519,123 @@ class FieldTape:
         points stay as set.  Nothing of the other calls is touched."""
         _lib.check(self._lib.ttcr_fsm_rcv_release(self._handle()))
         self._refresh_nbytes()
+
+    # ---- moving the receiver points, and the relocation-only system (DESIGN.md 6o)
+    @staticmethod
+    def move_check(n_rcv_points, geometry, dtype, xyz):
+        """The checks of move_receiver_points, no device call: xyz -- a numpy array, a sequence or a torch tensor -- has to be
+        (n_rcv_points, 3) real numbers, finite, and inside the grid of `geometry` (FieldTape.geometry) once cast to the grid dtype:
+        per axis origin <= x <= origin + (nn - 1) * dx with the upper corner formed in the grid dtype, the test raytrace_adjoint applies
+        to rcv ('Receiver outside grid').  Returns the array as the checks saw it (a CUDA tensor stays on its device)."""
+        dtype = np.dtype(dtype)
+        a = xyz if FieldTape._on_device(xyz) else np.asarray(xyz.detach().numpy() if hasattr(xyz, 'detach') else xyz)
+        if tuple(a.shape) != (n_rcv_points, 3):
+            raise ValueError('xyz should be (%d, 3), one row (x, y, z) per receiver point, got shape %s' % (n_rcv_points, tuple(a.shape)))
+        nn3, dx, origin = geometry
+        lo = np.asarray(origin, dtype=dtype)
+        hi = lo + (np.asarray(nn3) - 1).astype(dtype) * dtype.type(dx)
+        if FieldTape._on_device(a):
+            import torch
+
+            if a.is_complex() or a.dtype == torch.bool:
+                raise ValueError('xyz should be real numbers, got dtype %s' % (a.dtype,))
+            t = a.detach().to(torch.float32 if dtype == np.float32 else torch.float64)
+            finite = bool(t.isfinite().all())
+            tlo, thi = torch.as_tensor(lo, device=t.device), torch.as_tensor(hi, device=t.device)
+            outside = finite and t.numel() > 0 and bool(((t < tlo) | (t > thi)).any())
+        else:
+            if a.dtype.kind not in 'fiu':
+                raise ValueError('xyz should be real numbers, got dtype %s' % (a.dtype,))
+            t = a.astype(dtype)
+            finite = bool(np.isfinite(t).all())
+            outside = finite and t.size > 0 and bool(((t < lo) | (t > hi)).any())
+        if not finite:
+            raise ValueError('xyz should be finite, got a NaN or an infinite coordinate')
+        if outside:
+            raise ValueError('Receiver outside grid')
+        return a
+
+    def move_receiver_points(self, xyz):
+        """Give every row of receiver point q the receiver xyz[q] -- (n_rcv_points, 3) user coordinates -- WITHOUT a solve: no traveltime
+        field changes when only the receivers move, so the tape keeps its fields, coupling terms, masks and frozen lists and rebuilds, on
+        the device, what depends on the receivers: the point, traveltime and gradient G of every row, the stencil list of the forward
+        mode and the sorted seed list of the adjoint.  Returns the new receiver traveltimes in rcv order, as jvp returns dtt.
+        Afterwards the tape is, bit for bit and in every result of every method, the tape raytrace_adjoint builds for the same grid,
+        slowness and sources with the moved coordinates in rcv, followed by the same set_receiver_points and set_row_pairs (DESIGN.md
+        6o) -- what a relocation loop in the reciprocal layout calls between its steps (inversion.relocate).  What hold() kept is released
+        as by release() (the held adjoint belonged to the old stencils): hvp / newton ask for a new hold.  The point map, the row pairs
+        and the work arrays of the other calls stay.  Every point has to be finite and inside the grid (ValueError, 'Receiver outside
+        grid' as raytrace_adjoint says it; the tape is unchanged then).  Array handling as in jvp.  The first move allocates room for 8
+        stencil entries per row and the workspace of the device sort (nbytes grows once); later moves allocate nothing."""
+        self._handle()
+        a, pa, da = self._arg(self.move_check(self.n_rcv_points, self.geometry, self.dtype, xyz))
+        pr, dr, fin_r = self._out(xyz, 1, self.n_rows, rows=True)
+        self._sync(da, dr)
+        _lib.check(self._lib.ttcr_fsm_reloc_move(self._h, pa, da, pr if self.n_rows > 0 else None, dr))
+        self._refresh_nbytes()
+        return fin_r()[0]
+
+    def receiver_points(self):
+        """(n_rcv_points, 3), grid dtype, numpy: the current user coordinates of the receiver points -- the values of the last
+        move_receiver_points, or before any move the receiver of the point's rows.  A point without rows that was never moved reads NaN."""
+        h, n = self._handle(), self.n_rcv_points
+        out = (C.c_double * max(3 * n, 1))()
+        _lib.check(self._lib.ttcr_fsm_reloc_get_points(h, out))
+        return np.array(out[:3 * n], dtype=np.float64).reshape(n, 3).astype(self.dtype)
+
+    def vjp_receiver(self, w):
+        """G^T w: the receiver gradient (n_rcv_points, 4) = d (w . tt) / d (t0, x, y, z) of every receiver point -- per point the sum of
+        w[row] and of w[row] * G[row] over its rows in ascending row order -- with NO relaxation (vjp(..., return_receiver_grad=True)
+        pays one for the slowness gradient).  w: one value per data row (rcv order).  Array handling as in jvp."""
+        self._handle()
+        return self._vjp_receiver(w, w)
+
+    def gauss_newton_receiver(self, v_rcv, row_weight=None, rcv_scale=None, pair_weight=None):
+        """The relocation-only Gauss-Newton product C G^T B (G C v_rcv): G is jvp_receiver's operator, C = diag(rcv_scale), B
+        row_operator's data operator (row_weight, pair_weight).  The receiver block of gauss_newton_receiver_joint alone -- its row
+        kernels without the two relaxations, so passes becomes (0, 0) --, with the bits of the g_rcv that call returns for v = zeros (the
+        sign of a zero may differ).  v_rcv: (n_rcv_points, 4); rcv_scale, row_weight and pair_weight as there.  Array handling as in
+        gauss_newton."""
+        self._handle()
+        blk = self._RECEIVER
+        ea, pe, de = self._joint_arg(v_rcv, 'v_rcv', blk)
+        ra, pr, dr = self._row_arg(row_weight, 'row_weight') if row_weight is not None else (None, None, 0)
+        qa, pq, dq = self._pair_arg(pair_weight, 'pair_weight', weight=True) if pair_weight is not None else (None, None, 0)
+        sc = self._joint_setting(rcv_scale, 'rcv_scale', True, blk)
+        ps, dsb, fin_s = self._out(self._first_tensor(v_rcv, row_weight), self.n_rcv_points, 4)
+        self._sync(de, dr, dq, dsb)
+        _lib.check(self._lib.ttcr_fsm_reloc_gn(self._h, pe, de, pr, dr, pq, dq, sc, ps, dsb))
+        self.passes = (0, 0)
+        self._refresh_nbytes()
+        return fin_s()
+
+    def solve_receiver(self, rhs_rcv, row_weight=None, rcv_damp=0.0, rcv_scale=None, maxiter=20, rtol=1e-6, return_info=False,
+                       pair_weight=None):
+        """The relocation step on a fixed model (hypoDD proper with pair_weight): x_rcv = C z with
+            (C G^T B G C + diag(rcv_damp)) z = C rhs_rcv,        C = diag(rcv_scale),
+        by solve_receiver_joint's conjugate gradients on the receiver block alone -- the same scaling, damping of the scaled unknown,
+        inner products (over the 4 n_rcv_points values), recurrence, statuses and info dict -- around gauss_newton_receiver's product: no
+        iteration relaxes anything, every pass count is (0, 0).  rhs_rcv goes in unscaled, as vjp_receiver returns it.  Returns x_rcv
+        (n_rcv_points, 4), with return_info=True (x_rcv, info).  With pure double-difference data (row_weight all zero) a common
+        origin-time shift is a null vector: the system is singular unless rcv_damp > 0 on t0 (or rcv_scale fixes it).  The first call
+        allocates work arrays of its own (nbytes; release_receiver returns them).  DESIGN.md 6o; tests/relocation_reference.py restates it."""
+        self._handle()
+        blk = self._RECEIVER
+        _, _, maxiter = self._solve_settings('tiled', 0.0, 0.0, rtol, maxiter, 'gauss_newton', (1., 1., 1.), 'relocation')
+        ea, pe, de = self._joint_arg(rhs_rcv, 'rhs_rcv', blk)
+        ra, pr, dr = self._row_arg(row_weight, 'row_weight') if row_weight is not None else (None, None, 0)
+        sd = self._joint_setting(rcv_damp, 'rcv_damp', False, blk)
+        sc = self._joint_setting(rcv_scale, 'rcv_scale', True, blk)
+        qa, pq, dq = self._pair_arg(pair_weight, 'pair_weight', weight=True) if pair_weight is not None else (None, None, 0)
+        ps, dxs, fin_s = self._out(self._first_tensor(rhs_rcv, row_weight), self.n_rcv_points, 4)
+        self._sync(de, dr, dq, dxs)
+        res = self._solve_results(maxiter, 0)
+        _lib.check(self._lib.ttcr_fsm_reloc_solve(self._h, pe, de, pr, dr, pq, dq, sd, sc, maxiter, float(rtol), ps, dxs, *res[:4]))
+        self._refresh_nbytes()
+        xs = fin_s()
+        info = self._solve_info(res, 0, False)
+        self.passes = (0, 0)
+        return (xs, info) if return_info else xs
 
     # ---- double-difference rows (DESIGN.md 6m)
     def set_row_pairs(self, row_a, row_b):
