@@ -242,9 +242,9 @@ size_t ttcr_fsm_n_cells(const ttcr_fsm_grid* g);
  *                  TTCR_FSM_PAIR_UNITS; TTCR_FSM_PAIR = 1 / 0 forces / forbids the pair layout at grid creation) the sources
  *                  of a batch are paired by distance before they share a workgroup two by two
  *   "pair_layout"  grids whose slots x patches lie between the pairing threshold and 2.5 x that (512^3 nodes: 8 ... 15 slots) change their
- *                  field layout between calls that restart every slot: pairs while the call before evaluated more than 0.55 of its node
+ *                  field layout between calls that restart every slot: pairs while the call before evaluated more than 0.45 of its node
  *                  updates (rough models: 311 against 360 ms per solve of 8 sources), one field per workgroup on 16-level chunks once it
- *                  evaluated less (smooth models: 31.5 against 35.5 ms per step), back to pairs above 0.70.  -1 (default): that rule;
+ *                  evaluated less (smooth models: 31.5 against 35.5 ms per step), back to pairs above 0.55.  -1 (default): that rule;
  *                  0 / 1: one field per workgroup / pairs, always.  Results do not depend on the layout.  tests/test_pair_layout_gpu.py
  *   "combine_window_us"  single-source calls from several host threads wait this long for one another before they go
  *                  to the device as one batch (default 200; 0: every call on its own)
@@ -899,6 +899,14 @@ int ttcr_fsm_last_kernel(const ttcr_fsm_grid* g, char* buf, size_t n);
  * of the list; out may be NULL (size query), else capacity (in words) must be >= *n_units.  No reference equivalent. */
 int ttcr_fsm_unit_order(int dim, int dtype, int stage, int by_time, uint32_t nnx, uint32_t nny, uint32_t nnz, uint32_t* out,
                         size_t capacity, size_t* n_units);
+/* Test infrastructure, device free: the dirty bits a changed node sets for the next sweep (ttcr_amd/csrc/fsm_chunk_dirty.h), exactly the
+ * arithmetic of the first-order 3-D sweep kernels with exact skipping.  For every node (i, j, k) of a grid of nnx x nny x nnz NODES, as
+ * if it had changed in the sweep of direction dir (0 .. 7), the units of the sweep after it -- direction (dir + 1) % 8, patches of THAT
+ * direction's oriented partition, with the patch size the library uses for dtype and chunks of `chunk` (8 or 16) levels -- whose chunks
+ * it marks: out[12 n .. 12 n + 11] for node n = (k nny + j) nnx + i holds up to three entries (TJ, TK, first chunk, last chunk), unused
+ * entries -1.  edge_rule 0 leaves out the patches beyond a patch edge (a negative control for tests).  capacity: words of out, at least
+ * 12 per node.  tests/test_chunk_dirty_marks.py.  No reference equivalent. */
+int ttcr_fsm_chunk_dirty_marks(int dtype, int chunk, int dir, int edge_rule, uint32_t nnx, uint32_t nny, uint32_t nnz, int32_t* out, size_t capacity);
 /* Test infrastructure, device free: the slice of the spare traveltime fields that the unit with ticket `ticket` of a launch of n_tickets
  * units sets to max() (option "prefill_inline"), exactly the arithmetic the kernel does (ttcr_amd/csrc/fsm_prefill_slices.h).  n_el:
  * elements of the spare set.  *slice_len: elements per ticket, a multiple of the 16-byte vector (4 fp32, 2 fp64 elements); [*begin, *end):

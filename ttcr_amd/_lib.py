@@ -60,6 +60,7 @@ SYMBOLS = {
     "ttcr_fsm_stopping_stats": (_I, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "ttcr_fsm_prefill_swaps": (_I, [_P, C.POINTER(C.c_longlong)]),
     "ttcr_fsm_prefill_inline_fills": (_I, [_P, C.POINTER(C.c_longlong)]),
+    "ttcr_fsm_chunk_dirty_marks": (_I, [_I, _I, _I, _I, _U32, _U32, _U32, C.POINTER(C.c_int32), C.c_size_t]),
     "ttcr_fsm_prefill_slice": (_I, [_I, C.c_uint64, _U32, _U32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "ttcr_fsm_reference_change": (_I, [_P, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "ttcr_fsm_rays_size": (_I, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),

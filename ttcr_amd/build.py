@@ -31,10 +31,10 @@ INC = os.path.join("..", "..", "include", "ttcr_amd.h")
 # source -> (extra flags, files it is compiled from)
 UNITS = {
     "fsm_capi.hip": ([], ["fsm_capi.hip", "fsm_kernels.h", "fsm_fast_api.h", "fsm_march_levels.inc", "fsm_fast.hip", "fsm_tape_api.h",
-                          "fsm_tape.hip", "fsm_adjoint_api.h", "fsm_adjoint.hip", "fsm_normal.hip", "fsm_locate.hip", "fsm_model.hip", "fsm_unit_order.h", "fsm_prefill_slices.h", INC]),
-    "fsm_fast.hip": ([], ["fsm_fast.hip", "fsm_fast_api.h", "fsm_kernels.h", "fsm_march_levels.inc", "fsm_prefill_slices.h"]),
+                          "fsm_tape.hip", "fsm_adjoint_api.h", "fsm_adjoint.hip", "fsm_normal.hip", "fsm_locate.hip", "fsm_model.hip", "fsm_unit_order.h", "fsm_prefill_slices.h", "fsm_chunk_dirty.h", INC]),
+    "fsm_fast.hip": ([], ["fsm_fast.hip", "fsm_fast_api.h", "fsm_kernels.h", "fsm_march_levels.inc", "fsm_prefill_slices.h", "fsm_chunk_dirty.h"]),
     "fsm_tape.hip": ([], ["fsm_tape.hip", "fsm_tape_api.h"]),
-    "fsm_adjoint.hip": ([], ["fsm_adjoint.hip", "fsm_adjoint_api.h", "fsm_kernels.h", "fsm_march_levels.inc", "fsm_prefill_slices.h"]),
+    "fsm_adjoint.hip": ([], ["fsm_adjoint.hip", "fsm_adjoint_api.h", "fsm_kernels.h", "fsm_march_levels.inc", "fsm_prefill_slices.h", "fsm_chunk_dirty.h"]),
     "fsm_normal.hip": ([], ["fsm_normal.hip", "fsm_adjoint_api.h"]),
     "fsm_locate.hip": ([], ["fsm_locate.hip", "fsm_adjoint_api.h"]),
     "fsm_model.hip": ([], ["fsm_model.hip", "fsm_adjoint_api.h"]),

@@ -29,6 +29,7 @@
 #include "fsm_tape_api.h"
 #include "fsm_adjoint_api.h"
 #include "fsm_unit_order.h"
+#include "fsm_chunk_dirty.h"
 
 #ifndef FSM_CHUNK3
 #define FSM_CHUNK3 8
@@ -374,6 +375,7 @@ class GridT : public GridBase {
     int n_patches = 0;
     int* h_abort = nullptr;    // pinned
     DevBuf<int> d_stamp;       // dirty-brick stamps [n_slots][nbf*nbj*nbk]
+    DevBuf<unsigned> d_cdirty;   // first-order 3-D SKIP kernels: chunk-shaped dirty bits [slot group][dir][patch][cdirty_wpu] (fsm_chunk_dirty.h)
     DevBuf<unsigned long long> d_cmap;   // SKIP kernels: per-chunk edge-change flags of every unit of a launch [dir][entry][patch][2][cmap_words]
     int cmap_words = 1;
     DevBuf<unsigned long long> d_sw;   // SKIP kernels: per (global sweep, slot group) units finished | units that changed a node
@@ -536,6 +538,8 @@ class GridT : public GridBase {
             cmap_words = max_chunks / 32 + 1;
             d_cmap.reserve((size_t)n_patches * n_slots * (dim == 3 ? 8 : 4) * 2 * cmap_words);
             HIP_CHECK(hipMemset(d_cmap.p, 0, (size_t)n_patches * n_slots * (dim == 3 ? 8 : 4) * 2 * cmap_words * sizeof(unsigned long long)));
+            cdirty_wpu = ((geom.NF + 2 * (PJ + PK)) / 8 + 4) / 32 + 1;   // (chunks of 8 levels or more)
+            if (dim == 3) d_cdirty.reserve(cdirty_words());   // (one set per slot group, at most n_slots of them; zeroed by every solve)
             // whole-sweep tallies: one entry per sweep of a solve (both stages); solves with more sweeps simply stop using them
             sw_sweeps = (dim == 3 ? 8 : 4) * (2 * std::min(nitermax, 256) + 2);
             d_sw.reserve((size_t)sw_sweeps * n_slots);   // (one entry per slot group: at most n_slots of them, whichever the layout)
@@ -666,6 +670,8 @@ class GridT : public GridBase {
         pa.skip = skip_now(batch) ? (std::getenv("TTCR_FSM_SKIP_ALL_DIRTY") ? 2 : 1) : 0;
         pa.cmap = d_cmap.p;
         pa.cw = cmap_words;
+        pa.cdirty = d_cdirty.p;
+        pa.cdw = cdirty_wpu;
         pa.sw = std::getenv("TTCR_FSM_NO_SW") ? nullptr : d_sw.p;   // (tuning / bisecting: no whole-sweep shortcut)
         pa.n_sw_groups = n_groups();
         pa.n_sw_sweeps = sw_sweeps;
@@ -1056,7 +1062,9 @@ class GridT : public GridBase {
     bool ns_window = false;       // the grid may change its layout between calls (see the constructor)
     int pair_layout = -1;         // option "pair_layout": -1 (default) by the rule above, 0 one field per workgroup, 1 pairs (grids in the window only)
     double last_eval_frac = -1;   // evaluated / all node updates of the last batch that restarted every slot (-1: none yet)
-    double layout_lo = 0.55, layout_hi = 0.70;   // pairs -> one field per workgroup below lo, back above hi (TTCR_FSM_LAYOUT_LO / _HI: tests, tuning)
+    // (with chunk-shaped dirty bits the 8-source legs of the bench evaluate 0.25 on the gradient model and 0.67 on the rough one, one field per
+    // workgroup; with the slab mask it was 0.28 and 0.83 in pairs, and the thresholds 0.55 / 0.70 -- which left the rough model on the slower layout)
+    double layout_lo = 0.45, layout_hi = 0.55;   // pairs -> one field per workgroup below lo, back above hi (TTCR_FSM_LAYOUT_LO / _HI: tests, tuning)
     // Called at the top of a batch that restarts EVERY slot (no field of an earlier call survives it): pairs (NS = 2) or one field per
     // workgroup (NS = 1) for this and the following calls.  Nothing else depends on the layout across calls: stamps, change maps, sweep
     // tallies and snapshots are per solve, the second set of fields is filled with max() whatever its layout, host-side results are per slot.
@@ -1136,12 +1144,15 @@ class GridT : public GridBase {
         return (long long)n_patches * entries >= skip_units_min ? 1 : 0;
     }
     bool persistent_now() const { return mode >= 1 || stage == 1; }
+    int cdirty_wpu = 1;   // words of dirty bits per unit
+    size_t cdirty_words() const { return (size_t)n_patches * n_slots * 8 * cdirty_wpu; }
     // the rotated-template sweeps change nodes without stamping their bricks: no skipping next to them
     // `entries`: batch entries (slot groups / slots) swept together
     bool skip_now(int entries) const {
         const int on = skip < 0 ? skip_default(entries) : skip;
         // (the SKIP kernels pack a level count and 8 flag bits into one progress word, and keep one mask bit per F brick)
-        const bool fits = (long long)geom.NF + geom.NJ + geom.NK < (1ll << 22) && nbf <= 32 * FSM_SLAB_WORDS;
+        // (... and, first-order 3-D sweeps, one dirty bit per chunk of a unit in FSM_CD_WORDS words: true of every grid with that many F bricks)
+        const bool fits = (long long)geom.NF + geom.NJ + geom.NK < (1ll << 22) && nbf <= 32 * FSM_SLAB_WORDS && (dim != 3 || cdirty_wpu <= FSM_CD_WORDS);
         return on != 0 && fits && !(dim == 2 && rotated && !weno && dx == dz);
     }
 
@@ -1675,6 +1686,7 @@ class GridT : public GridBase {
         if (persistent_now() || weno) HIP_CHECK(hipMemsetAsync(d_sync.p + 4, 0, sizeof(int), stream));
         HIP_CHECK(hipMemsetAsync(d_evals.p, 0, sizeof(unsigned long long) * n_slots, stream));
         HIP_CHECK(hipMemsetAsync(d_sw.p, 0, sizeof(unsigned long long) * (size_t)sw_sweeps * n_groups(), stream));
+        if (d_cdirty.p) HIP_CHECK(hipMemsetAsync(d_cdirty.p, 0, cdirty_words() * sizeof(unsigned), stream));   // (no sweep before the first one)
         HIP_CHECK(hipEventRecord(ev0, stream));
         int it_total = 0;  // global iteration index: sweep numbers for the dirty-brick stamps
         for (stage = 0; stage < (weno ? 2 : 1); ++stage) {
@@ -5130,6 +5142,33 @@ int ttcr_fsm_unit_order(int dim, int dtype, int stage, int by_time, uint32_t nnx
         const std::vector<uint32_t> xs = fsm_xs_order(dim, (int)NF, (int)NJ, (int)NK, PJ, PK, C, stage == 0 ? 1 : 2, by_time != 0,
                                                       fsm_diag_order((int)npj, (int)npk));
         std::copy(xs.begin(), xs.end(), out);
+    });
+}
+
+int ttcr_fsm_chunk_dirty_marks(int dtype, int chunk, int dir, int edge_rule, uint32_t nnx, uint32_t nny, uint32_t nnz, int32_t* out, size_t capacity) {
+    return guarded([&] {   // (host arithmetic only: no device is looked for)
+        if (dtype != TTCR_F32 && dtype != TTCR_F64) throw ValueError("dtype must be TTCR_F32 or TTCR_F64");
+        if (chunk != 8 && chunk != 16) throw ValueError("chunk must be 8 or 16 levels");
+        if (dir < 0 || dir > 7) throw ValueError("dir must be one of the eight sweep directions");
+        if (nnx < 2 || nny < 2 || nnz < 2) throw ValueError("grid needs at least two nodes per axis");
+        if (!out) throw ValueError("null output");
+        const int PJ = dtype == TTCR_F32 ? TileCfg<float, 3>::PJ : TileCfg<double, 3>::PJ, PK = dtype == TTCR_F32 ? TileCfg<float, 3>::PK : TileCfg<double, 3>::PK;
+        const uint64_t n = (uint64_t)nnx * nny * nnz;
+        if (n >= (1ull << 31)) throw ValueError("grid too large");
+        if (capacity < (size_t)n * 12) throw ValueError("output buffer too small: 12 words per node");
+        const int NF = (int)nnx, NJ = (int)nny, NK = (int)nnz, dn = (dir + 1) % 8;
+        for (int k = 0; k < NK; ++k)
+            for (int j = 0; j < NJ; ++j)
+                for (int i = 0; i < NF; ++i) {
+                    int32_t* o = out + (((size_t)k * NJ + j) * NF + i) * 12;
+                    int m = 0;
+                    for (int q = 0; q < 12; ++q) o[q] = -1;
+                    fsm_chunk_marks(NF, NJ, NK, PJ, PK, chunk, 1, dn, j, k, i, i, edge_rule != 0, [&](int tj, int tk, int c0, int c1) {
+                        if (m == 3) throw std::logic_error("ttcr_fsm_chunk_dirty_marks: a node marks more than three units");
+                        o[4 * m] = tj; o[4 * m + 1] = tk; o[4 * m + 2] = c0; o[4 * m + 3] = c1;
+                        ++m;
+                    });
+                }
     });
 }
 

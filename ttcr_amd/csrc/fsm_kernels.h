@@ -38,6 +38,7 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "fsm_chunk_dirty.h"
 #include "fsm_prefill_slices.h"
 
 namespace ttcr_amd {
@@ -616,6 +617,10 @@ struct PersistArgs {
     unsigned long long* sw;   // [global sweep number][n_sw_groups]: units finished (low 32) | units that changed a node (high 32);
                               // zeroed per solve; nullptr: no whole-sweep shortcut
     int n_sw_groups, n_sw_sweeps;
+    // chunk-shaped dirty bits of the first-order 3-D SKIP kernels (fsm_chunk_dirty.h): [slot group][direction][patch of that direction's
+    // partition][cdw] 32-bit words, one bit per chunk of the unit; zeroed per solve, set by the sweep before, cleared by their one reader
+    unsigned* cdirty;
+    int cdw;                  // words per unit
     // whole-iteration launch (XS): all directions in one grid, sheared copies by family
     const T* ssh;             // [families][ssh_stride]
     size_t ssh_stride;
@@ -940,6 +945,14 @@ __device__ __forceinline__ float solve3_literal_fast(float a1, float a2, float a
 // SKIP kernels publish progress as (levels << 8) | change flags of the last four chunks (two bits each: J-edge, K-edge columns);
 // a finished unit publishes FSM_FIN | (ever changed its J edge) | (ever changed its K edge) << 1
 #define FSM_FIN 0x3ffffff0
+// first-order 3-D SKIP kernels: the scheduler reads chunk-shaped dirty bits written by the sweep that changed a node (1), or, like the
+// 2-D and WENO kernels, the slab mask of brick stamps (0: A/B builds)
+#ifndef FSM_CHUNK_DIRTY
+#define FSM_CHUNK_DIRTY 1
+#endif
+// ... words of a unit's dirty bits the kernel has room for (chunks of 8 levels or more: a unit has at most (NF + 2 (PJ + PK)) / 8 + 4 of
+// them, and NF <= 512 FSM_SLAB_WORDS)
+#define FSM_CD_WORDS (2 * FSM_SLAB_WORDS + 4)
 #ifndef FSM_SKIP_ABL
 #define FSM_SKIP_ABL 0   // tuning builds: leave parts of the skip bookkeeping out (wrong results unless every brick is dirty)
 #endif
@@ -1022,6 +1035,8 @@ template <typename T, int PJ, int PK, int C, bool IS3D, bool SKIP, int H, int NS
 __device__ __forceinline__ bool fsm_sweep_unit(const PersistArgs<T>& pa) {
     static_assert(AR == 0 || std::is_same<T, float>::value, "tolerance-grade arithmetic: fp32 kernels");
     constexpr bool LOOPED = fsm_looped(IS3D, H);   // the workgroup comes back for another unit (see fsm_sweep_persistent)
+    constexpr bool CD = FSM_CHUNK_DIRTY && SKIP && IS3D && H == 1;   // chunk-shaped dirty bits instead of the slab mask
+    static_assert(!CD || C >= 8, "the host sizes the dirty bits for chunks of 8 levels or more");
     using P = Pack<T, NS>;
     constexpr int NT = PJ * PK;
     constexpr int RJ = PJ + 2 * H;
@@ -1075,7 +1090,12 @@ __device__ __forceinline__ bool fsm_sweep_unit(const PersistArgs<T>& pa) {
     // scheduler state of the SKIP kernels (thread 0 only, apart from s_slab's set-up and s_next / s_act)
     constexpr int SLABW = SKIP ? FSM_SLAB_WORDS : 1;
     __shared__ unsigned s_stamped[SKIP ? 9 : 1][SLABW];   // bricks of the read set (J/K position, F index) this unit has already stamped
-    __shared__ unsigned s_slab[SLABW];   // bit bf: some brick of the unit's read set with F index bf changed in sweep sigma-1 or in this one
+    __shared__ unsigned s_slab[CD ? 1 : SLABW];   // (not CD) bit bf: some brick of the unit's read set with F index bf changed in sweep sigma-1 or in this one
+    constexpr int CDW = CD ? FSM_CD_WORDS : 1;
+    __shared__ unsigned s_cd[CDW];        // CD: bit ci: chunk ci of this unit reads a node that changed in sweep sigma-1
+    __shared__ int s_cmp[CD ? 3 * NT : 1], s_cml[CD ? 3 * NT : 1];   // CD: the <= 3 units of sweep sigma+1 that read this thread's column:
+                                          // (place among the 3 x 3) | chunks << 4, or -1; and rel (fsm_chunk_mark_units)
+    __shared__ unsigned s_mark[9 * CDW];  // CD: the same for the units of sweep sigma+1 this unit's changes reach ([<= 3 x 3 patches][cdw])
     __shared__ int s_next, s_act;        // chunk the scheduler stopped at, and what to do there (1: evaluate, 2: drain first, 0: leave)
     __shared__ int s_cwi[2], s_cwl[2];   // upwind change maps: cached word index, upwind level known when it was loaded
     __shared__ unsigned s_cwv[2];        // ... and the word
@@ -1083,8 +1103,8 @@ __device__ __forceinline__ bool fsm_sweep_unit(const PersistArgs<T>& pa) {
     __shared__ unsigned s_mywv[2];
     // per-unit constants and the little state of the scheduler live in LDS, not in registers: they are touched once per
     // chunk by one lane, and the level march has no register to spare (a resident wave per SIMD is at stake)
-    enum { U_THR, U_RSJLO, U_RSKLO, U_RSNJ, U_RSNK, U_LCF, U_UPLCF0, U_UPLCF1, U_HIST, U_EVER, U_UCHG, U_PENDV, U_LCHG, U_N };
-    __shared__ int s_u[U_N];
+    enum { U_THR, U_RSJLO, U_RSKLO, U_RSNJ, U_RSNK, U_LCF, U_UPLCF0, U_UPLCF1, U_HIST, U_EVER, U_UCHG, U_PENDV, U_LCHG, U_MKJ0, U_MKK0 };
+    __shared__ int s_u[CD ? U_MKK0 + 1 : U_MKJ0];   // (the last two: CD kernels only -- the others keep the LDS they had)
 
     int tid = threadIdx.x;
     if constexpr (LOOPED) asm volatile("" : "+v"(tid));   // (see the loop in fsm_sweep_persistent)
@@ -1555,8 +1575,10 @@ __device__ __forceinline__ bool fsm_sweep_unit(const PersistArgs<T>& pa) {
         // upwind patches of THIS sweep change afterwards arrives with their progress values, what the unit changes
         // itself it adds to the mask.  Changes of other nodes of a straddling brick may or may not be seen: they do
         // not matter (not in the read set), seeing them only costs an evaluation.
-        const int nsw = (pa.nbf + 31) >> 5;
-        for (int w = tid; w < nsw; w += NT) s_slab[w] = 0u;
+        if constexpr (!CD) {
+            const int nsw = (pa.nbf + 31) >> 5;
+            for (int w = tid; w < nsw; w += NT) s_slab[w] = 0u;
+        }
         for (int w = tid; w < 9 * SLABW; w += NT) s_stamped[w / SLABW][w % SLABW] = 0u;
         if (tid == 0) {
             s_cwi[0] = -1; s_cwi[1] = -1; s_mywi = -1;
@@ -1575,9 +1597,64 @@ __device__ __forceinline__ bool fsm_sweep_unit(const PersistArgs<T>& pa) {
             s_u[U_UPLCF0] = lsj - (((lsj - mu) % C + C) % C);
             s_u[U_UPLCF1] = lsk - (((lsk - mu) % C + C) % C);
             s_u[U_HIST] = 0; s_u[U_EVER] = 0; s_u[U_UCHG] = 0; s_u[U_PENDV] = 0; s_u[U_LCHG] = 0;
+            if constexpr (CD) {
+                // first patch, in the NEXT sweep's oriented partition, of the <= 3 x 3 that hold a column within H of this unit's
+                const int dn = (dir + 1) % pa.ndir;
+                const int fj = rj != ((dn >> 1) & 1), fk = rk != ((dn >> 2) & 1);
+                const int ja2 = (fj ? NJ - 1 - jmaxp : j0) - H, ka2 = (fk ? NK - 1 - kmaxp : k0) - H;
+                s_u[U_MKJ0] = (ja2 < 0 ? 0 : ja2) / PJ;
+                s_u[U_MKK0] = (ka2 < 0 ? 0 : ka2) / PK;
+            }
+        }
+        if constexpr (CD) {
+            // Dirty bits of the unit: chunk ci holds, or reads across its one-node halo, a node that changed during sweep sigma-1
+            // (set by that sweep's units before their final progress values, which the wait above has seen -- one launch per
+            // sweep: the previous launch).  Each word has this one reader per launch, who leaves it zero for the sweep that
+            // marks it next (eight sweeps on: it waits, link by link, for this unit's final progress value, which goes out
+            // after these stores have drained).  What the upwind patches of THIS sweep change arrives with their progress
+            // values, what the unit changes itself reaches the chunk after (U_LCHG).  A bit too many costs an evaluation.
+            // The first sweep of a solve has no sweep before it: there the chunks that hold a node within one step of a
+            // source's frozen box are dirty -- every other node has nothing but max() around it.
+            unsigned* cdw = pa.cdirty + ((((size_t)grp * pa.ndir + dir) * pa.n_patches) + (size_t)(TK * npj + TJ)) * pa.cdw;
+            const bool first_sweep = pa.iter_ptr[0] == 0 && dir == 0;
+            for (int w = tid; w < pa.cdw && w < CDW; w += NT) {
+                unsigned v = pa.skip == 2 ? 0xffffffffu : __hip_atomic_exchange(cdw + w, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (first_sweep) {
+                    const int jlo = (rj ? NJ - 1 - jmaxp : j0) - 1, jhi = (rj ? NJ - 1 - j0 : jmaxp) + 1;
+                    const int klo = (rk ? NK - 1 - kmaxp : k0) - 1, khi = (rk ? NK - 1 - k0 : kmaxp) + 1;
+#pragma unroll 1
+                    for (int l = 0; l < NS; ++l) {
+                        const int* b6 = bb + 6 * l;
+                        if (jhi < b6[2] || jlo > b6[3] || khi < b6[4] || klo > b6[5]) continue;
+                        const int b0 = (rf ? NF - 1 - b6[1] : b6[0]) - 1, b1 = (rf ? NF - 1 - b6[0] : b6[1]) + 1;   // oriented F range
+                        // chunks whose levels Lc + ci C .. + C - 1 meet the levels b0 + j0 + k0 .. b1 + jmaxp + kmaxp
+                        int ca = b0 + j0 + k0 - Lc, cb = b1 + jmaxp + kmaxp - Lc;
+                        if (cb < 0) continue;
+                        ca = (ca < 0 ? 0 : ca / C) - 32 * w;
+                        cb = cb / C - 32 * w;
+                        if (cb < 0 || ca > 31) continue;
+                        v |= (ca <= 0 ? 0xffffffffu : 0xffffffffu << ca) & (cb >= 31 ? 0xffffffffu : (2u << cb) - 1u);
+                    }
+                }
+                s_cd[w] = v;
+            }
+            for (int w = tid; w < 9 * pa.cdw && w < 9 * CDW; w += NT) s_mark[w] = 0u;
         }
         __syncthreads();
-        {
+        if constexpr (CD) {
+            int q = 0;
+            const int mj0 = s_u[U_MKJ0], mk0 = s_u[U_MKK0];
+            if (col_ok)
+                fsm_chunk_mark_units(NF, NJ, NK, PJ, PK, C, H, (dir + 1) % pa.ndir, jn, kn, true, [&](int tj_, int tk_, int rel, int nch) {
+                    const int pj = tj_ - mj0, pk = tk_ - mk0;
+                    if (q >= 3 || (unsigned)pj >= 3u || (unsigned)pk >= 3u) return;   // (cannot happen: PJ + 2H columns lie in <= 3 patches)
+                    s_cmp[q * NT + tid] = (pk * 3 + pj) | (nch << 4);
+                    s_cml[q * NT + tid] = rel;
+                    ++q;
+                });
+            for (; q < 3; ++q) s_cmp[q * NT + tid] = -1;
+        }
+        if constexpr (!CD) {
             const int jlo = s_u[U_RSJLO], nj = s_u[U_RSNJ], klo = s_u[U_RSKLO], nk = s_u[U_RSNK], thr = s_u[U_THR];
             const int* __restrict__ stamp = pa.stamp + (size_t)grp * pa.nbf * pa.nbj * pa.nbk;   // one stamp set per group
             const int total = pa.nbf * nj * nk;
@@ -1708,7 +1785,11 @@ __device__ __forceinline__ bool fsm_sweep_unit(const PersistArgs<T>& pa) {
                         // both upwind units are over and never touched the columns this unit reads: with a clean slab
                         // mask the whole unit is a no-op
                         bool any = false;
-                        for (int w = 0; w < ((pa.nbf + 31) >> 5); ++w) any |= s_slab[w] != 0u;
+                        if constexpr (CD) {
+                            for (int w = 0; w < pa.cdw; ++w) any |= s_cd[w] != 0u;
+                        } else {
+                            for (int w = 0; w < ((pa.nbf + 31) >> 5); ++w) any |= s_slab[w] != 0u;
+                        }
                         if (!any) {
                             st_prog(my_prog, FSM_FIN);
                             L = Le + 1;
@@ -1716,9 +1797,15 @@ __device__ __forceinline__ bool fsm_sweep_unit(const PersistArgs<T>& pa) {
                             break;
                         }
                     }
-                    int flo, fhi;
-                    chunk_frange(L, H, flo, fhi);
-                    bool dirty = slab_any(flo, fhi);
+                    bool dirty;
+                    if constexpr (CD) {
+                        const int ci = (L - lcf) / C;
+                        dirty = (s_cd[ci >> 5] >> (ci & 31)) & 1u;
+                    } else {
+                        int flo, fhi;
+                        chunk_frange(L, H, flo, fhi);
+                        dirty = slab_any(flo, fhi);
+                    }
                     if (!dirty && up_j) dirty = up_dirty(vj, need, 0);
                     if (!dirty && up_k) dirty = up_dirty(vk, need, 1);
                     if (dirty) break;
@@ -1963,6 +2050,27 @@ __device__ __forceinline__ bool fsm_sweep_unit(const PersistArgs<T>& pa) {
                 const int jk = my_bk * s_u[U_RSNJ] + my_bj;
                 atomicOr(&s_stamped[jk][ba >> 5], 1u << (ba & 31));
                 if (bb2 != ba) atomicOr(&s_stamped[jk][bb2 >> 5], 1u << (bb2 & 31));
+                if constexpr (CD) {
+                    // ... and the chunks of the next sweep's units that read them (fsm_chunk_dirty.h; the units of this thread's column:
+                    // s_cmp / s_cml, set up once per unit): bits in LDS, out with the stamps
+                    const int fa = rf ? NF - 1 - ib : ia, fb = rf ? NF - 1 - ia : ib, cw = pa.cdw, dn = (dir + 1) % pa.ndir;
+#pragma unroll 1
+                    for (int q = 0; q < 3; ++q) {   // (one unit after the other: side by side they cost the march registers)
+                        const int pn = s_cmp[q * NT + tid];
+                        int c0, c1;
+                        if (pn < 0 || !fsm_chunk_mark_range(NF, C, dn, s_cml[q * NT + tid], pn >> 4, fa, fb, &c0, &c1)) continue;
+                        unsigned* mrow = s_mark + (pn & 15) * cw;
+                        const int w0 = c0 >> 5, w1 = c1 >> 5;
+                        const unsigned m0 = ~0u << (c0 & 31), m1 = (2u << (c1 & 31)) - 1u;
+                        if (w1 >= cw || w1 >= CDW) continue;   // (cannot happen: the host sizes cdw for the chunks of a unit)
+                        if (w0 == w1) {
+                            atomicOr(mrow + w0, m0 & m1);
+                        } else {
+                            atomicOr(mrow + w0, m0);
+                            atomicOr(mrow + w1, m1);
+                        }
+                    }
+                }
             }
         } else {
             if (wave_any(changed) && (tid & 63) == 0) s_anychg = 1;
@@ -1989,12 +2097,18 @@ __device__ __forceinline__ bool fsm_sweep_unit(const PersistArgs<T>& pa) {
             if (!(FSM_SKIP_ABL & 4) && tid == 0) {
                 if (any_changed) {
                     // own changes into the slab mask (the next chunks read these bricks) and into the unit's change map
-                    int flo, fhi;
-                    chunk_frange(L0, 0, flo, fhi);
-                    for (int b = flo / FSM_BRICK; b <= fhi / FSM_BRICK; ++b) s_slab[b >> 5] |= 1u << (b & 31);
+                    if constexpr (!CD) {
+                        int flo, fhi;
+                        chunk_frange(L0, 0, flo, fhi);
+                        for (int b = flo / FSM_BRICK; b <= fhi / FSM_BRICK; ++b) s_slab[b >> 5] |= 1u << (b & 31);
+                    }
                     const int ci = (L0 - s_u[U_LCF]) / C, w = ci >> 5;
                     if ((chg_flags & 6) && w < pa.cw) {
-                        if (s_mywi != w) { s_mywi = w; s_mywv[0] = 0u; s_mywv[1] = 0u; }
+                        if (s_mywi != w) {
+                            unsigned z0 = 0u;
+                            if constexpr (CD) asm volatile("" : "+v"(z0));   // (a zero made here: kept in a register pair across the unit loop it was spilled)
+                            s_mywi = w; s_mywv[0] = z0; s_mywv[1] = z0;
+                        }
                         for (int e2 = 0; e2 < 2; ++e2)
                             if (chg_flags & (2 << e2)) {
                                 s_mywv[e2] |= 1u << (ci & 31);
@@ -2038,6 +2152,16 @@ __device__ __forceinline__ bool fsm_sweep_unit(const PersistArgs<T>& pa) {
                 const int jk = q / (nsw * 32), bf = q % (nsw * 32);
                 if (bf < pa.nbf && ((s_stamped[jk][bf >> 5] >> (bf & 31)) & 1u))
                     atomicMax(stamp + ((size_t)(rs_klo + jk / rs_nj) * pa.nbj + rs_jlo + jk % rs_nj) * pa.nbf + bf, sigma);
+            }
+            if constexpr (CD) {
+                // the next sweep's dirty bits, like the stamps final before this unit's final progress value
+                const int cw = pa.cdw, mj0 = s_u[U_MKJ0], mk0 = s_u[U_MKK0], npk = a.g.npk;
+                unsigned* cdn = pa.cdirty + (((size_t)grp * pa.ndir + (dir + 1) % pa.ndir) * pa.n_patches) * cw;
+                for (int q = tid; q < 9 * cw && q < 9 * CDW; q += NT) {
+                    const unsigned v = s_mark[q];
+                    const int p9 = q / cw, tj_ = mj0 + p9 % 3, tk_ = mk0 + p9 / 3;
+                    if (v && tj_ < npj && tk_ < npk) atomicOr(cdn + (size_t)(tk_ * npj + tj_) * cw + q % cw, v);
+                }
             }
             pending = 1;   // (the drain below covers the atomics; the value to publish is already in s_u[U_PENDV])
         }
@@ -2102,6 +2226,7 @@ template <typename T, int PJ, int PK, int C, bool IS3D, bool SKIP, int H, int NS
 #define FSM_WENO_MINW FSM_MINW   // resident workgroups per SIMD asked of the fp32 3-D WENO kernel (one field per workgroup)
 #endif
 __global__ __launch_bounds__(PJ* PK, (SKIP && IS3D && H == 1 && NS == 2 && sizeof(T) == 4) ? 3
+                                     : (FSM_CHUNK_DIRTY && SKIP && IS3D && H == 1 && NS == 2 && sizeof(T) == 8) ? 2   // (where they stood unasked, at 253-256 VGPRs)
                                      : (IS3D && H == 2 && NS == 1 && sizeof(T) == 4) ? FSM_WENO_MINW : FSM_MINW) void fsm_sweep_persistent(const PersistArgs<T> pa) {
     if constexpr (fsm_looped(IS3D, H)) {
         // Nothing is to be carried from one unit to the next: the arguments are read again from the kernel argument segment
