@@ -19,8 +19,9 @@ import pytest
 F32, F64 = 0, 1
 PATCH = {F32: (16, 16), F64: (16, 8)}
 # NODES (nx, ny, nz): x is the level axis, the patches tile (y, z).  (70, 53, 41): J and K no multiples of the patch, so the partitions
-# of two sweeps that walk an axis in opposite directions differ
-SHAPES = [(37, 35, 41), (70, 53, 41), (2, 16, 10), (17, 33, 34)]
+# of two sweeps that walk an axis in opposite directions differ.  (600, 35, 19) and (300, 20, 18): marks with chunk indices >= 32, on chunks
+# of 8 and of 16 / of 8 (tests/long_axis_cases.py)
+SHAPES = [(37, 35, 41), (70, 53, 41), (2, 16, 10), (17, 33, 34), (600, 35, 19), (300, 20, 18)]
 
 
 @pytest.fixture(scope="module")
