@@ -899,6 +899,20 @@ int ttcr_fsm_last_kernel(const ttcr_fsm_grid* g, char* buf, size_t n);
  * of the list; out may be NULL (size query), else capacity (in words) must be >= *n_units.  No reference equivalent. */
 int ttcr_fsm_unit_order(int dim, int dtype, int stage, int by_time, uint32_t nnx, uint32_t nny, uint32_t nnz, uint32_t* out,
                         size_t capacity, size_t* n_units);
+/* Test infrastructure, device free: the sweep kernel a grid of nnx x nny x nnz NODES (dim = 2: nny is ignored) with n_slots slots would launch
+ * for `batch` batch entries (slot groups; slots with option mode = 0) in stage 0 (first-order sweeps) or 1 (WENO sweeps), exactly the
+ * arithmetic of the solver (ttcr_amd/csrc/fsm_sweep_plan.h) under the TTCR_FSM_* variables of the environment.  keys / values: n_options
+ * pairs as for ttcr_fsm_set_option -- "mode", "skip", "lone_chunk", "arith" -- and two that stand for what else a grid knows: "rotated"
+ * (2-D rotated template with dx == dz) and "probe_skip" (0: the grid's last skipping solve evaluated too much, see SweepTuning).  wg_cap:
+ * the workgroups a launch is capped at (a grid: 8 per compute unit of its device).  layout: -1, or 0 / 1 for a grid inside the window where
+ * the layout follows the model (option "pair_layout").  name: what ttcr_fsm_last_kernel reports after such a launch.  out[12]:
+ * [0] 0 the library holds that instantiation, 1 the launch is refused (option 'arith' without whole-iteration launches), 2 no such
+ * instantiation; [1] workgroups, [2] threads per workgroup, [3] bytes of dynamic LDS, [4] ticket list (0 per sweep, 1 whole iteration
+ * sweep by sweep, 2 by start time), [5] launches per sweep-iteration, [6] levels per chunk, [7] SKIP (2: every chunk taken for dirty),
+ * [8] XS, [9] PRE, [10] fields per workgroup, [11] AR.  tests/test_sweep_plan.py.  No reference equivalent. */
+int ttcr_fsm_sweep_plan(int dim, int dtype, int weno, uint32_t nnx, uint32_t nny, uint32_t nnz, int n_slots, const char* const* keys,
+                        const double* values, int n_options, int wg_cap, int stage, int batch, int layout, char* name, size_t name_len,
+                        long long* out);
 /* Test infrastructure, device free: the dirty bits a changed node sets for the next sweep (ttcr_amd/csrc/fsm_chunk_dirty.h), exactly the
  * arithmetic of the first-order 3-D sweep kernels with exact skipping.  For every node (i, j, k) of a grid of nnx x nny x nnz NODES, as
  * if it had changed in the sweep of direction dir (0 .. 7), the units of the sweep after it -- direction (dir + 1) % 8, patches of THAT

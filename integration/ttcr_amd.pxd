@@ -201,4 +201,7 @@ cdef extern from "ttcr_amd.h" nogil:
     int ttcr_fsm_last_timing(const ttcr_fsm_grid* g, ttcr_fsm_timing* out)
     int ttcr_fsm_unit_order(int dim, int dtype, int stage, int by_time, uint32_t nnx, uint32_t nny, uint32_t nnz, uint32_t* out,
                             size_t capacity, size_t* n_units)
+    int ttcr_fsm_sweep_plan(int dim, int dtype, int weno, uint32_t nnx, uint32_t nny, uint32_t nnz, int n_slots, const char* const* keys,
+                            const double* values, int n_options, int wg_cap, int stage, int batch, int layout, char* name, size_t name_len,
+                            long long* out)
     const char* ttcr_fsm_build_id()

@@ -134,13 +134,13 @@ def test_batches_per_node(oracle, capsys, monkeypatch, n_threads, n_src, pair):
 
 
 # ---- every AR = 1 instantiation of fsm_fast.hip once ---------------------------------------------------------------------------------------
-# (stage, dim, fields per workgroup, chunk, skip, PRE) -> how the host is brought to launch it (fsm_capi.hip, launch_sweeps_persistent*):
+# (stage, dim, fields per workgroup, chunk, skip, PRE) -> how the host is brought to launch it (fsm_sweep_plan.h, fsm_sweep_plan):
 #   first order 3-D, one field: any grid with one slot group layout NS = 1; chunks of 16 whatever the batch, PRE compiled out (NO_PRE)
 #   first order 3-D, pairs:     TTCR_FSM_PAIR = 1 and n_threads >= 2; chunks of 8; PRE = batch >= TTCR_FSM_PRE_MIN (2 slot groups here)
 #   2-D:                        chunks of 16, PRE always on
 #   WENO 3-D (arith = 2):       one field per workgroup; chunks of 16 while batch < TTCR_FSM_WENO_C16_BELOW, else 8; PRE = batch >= PRE_MIN
 # UNREACHABLE by the host's rules, and absent from fsm_fast.hip accordingly: first-order 3-D one field with PRE (NO_PRE), pairs in the WENO
-# stage (the stage keeps the exact kernels there: fast_now<H>() && (H == 1 || NSV == 1)), 2-D without PRE (pre = DIM == 2 || ...).
+# stage (the stage keeps the exact kernels there: SweepPlan::AR), 2-D without PRE (pre = DIM == 2 || ...).
 def _inst(stage, dim, ns, chunk, skip, pre):
     env, n_threads = {}, 1
     if dim == 3 and stage == 1 and ns == 2:

@@ -37,7 +37,7 @@ def _b(v):
 
 class Inst:
     """one instantiation fsm_sweep_persistent<T,PJ,PK,CH,true,SKIP,1,NS,XS,PRE> and how the host is brought to launch it
-    (launch_sweeps_persistent*, ttcr_amd/csrc/fsm_capi.hip)"""
+    (fsm_sweep_plan, ttcr_amd/csrc/fsm_sweep_plan.h; tests/test_sweep_plan.py checks every row on the CPU)"""
 
     def __init__(self, dtype, ns, ch, xs, skip, pre):
         self.dtype, self.ns, self.ch, self.xs, self.skip, self.pre = dtype, ns, ch, xs, skip, pre

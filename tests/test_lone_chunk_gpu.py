@@ -83,3 +83,31 @@ def test_paired_grids_keep_chunks_of_8():
     src = np.random.default_rng(1).uniform(1.0, 13.0, (4, 3))
     g.raytrace(src, np.zeros((4, 3)))
     assert ",16,16,8," in g.last_kernel() and ",1,2," in g.last_kernel(), g.last_kernel()
+
+
+def test_captured_launch_follows_the_chunk_length(oracle):
+    """option use_graph = 2 replays a captured launch (one stream, kernel nodes only) for as long as the plan of the launch
+    (ttcr_amd/csrc/fsm_sweep_plan.h) stays what was captured: a change of option "lone_chunk" between two calls changes the kernel, so the
+    next call captures again instead of replaying the other chunk length under the new one's name"""
+    import few_workgroups_cases as fw
+    import ttcr_amd
+
+    shape, dtype, n_threads = fw.SHAPES[0], np.float32, 3
+    assert shape == (37, 35, 41)
+    g = ttcr_amd.Grid3d(*fw.axes(shape), n_threads=n_threads, cell_slowness=0, method="FSM", tt_from_rp=0, weno=0, dtype=dtype)
+    g.set_option("skip", 1)
+    g.set_option("use_graph", 2)
+    g.set_slowness(fw.slowness(shape, dtype))
+    src, rcv = fw.sources(shape), fw.receivers(shape)
+    order = list(range(fw.N_SRC))
+    refs = [fw.reference(oracle, shape, dtype, k) for k in order]
+    slots, _ = fw.held(order, n_threads)
+    for call, chunk in enumerate((None, 8, 16)):
+        if chunk is not None:
+            g.set_option("lone_chunk", chunk)
+        g.raytrace(np.repeat(src[order], len(rcv), axis=0), np.tile(rcv, (len(order), 1)))
+        name = g.last_kernel()
+        assert name.startswith("fsm_sweep_persistent<float,16,16,") and _chunk_of(name) == (chunk or 16), (call, name)
+        for slot, k in slots.items():
+            np.testing.assert_array_equal(g.get_grid_traveltimes(slot).flatten("F"), refs[k]["tt"], err_msg=str((call, name, slot, k)))
+            assert g.get_niter(slot) == refs[k]["niter"], (call, name, slot, k)

@@ -19,7 +19,7 @@ oracle still changes nodes there after the first iteration):
                      this long its WENO stage converges for some sources only (39 - 78 iterations) and leaves at maxit = 80 for the
                      others (one of four on (130, 600), three of four on (66, 1100)): there the fields after 80 WENO iterations
                      are compared, bit for bit all the same
-  the limit          skip_now() (ttcr_amd/csrc/fsm_capi.hip) lets a grid skip up to 32 FSM_SLAB_WORDS = 1024 F bricks: (16384, 17, 2)
+  the limit          fsm_skip() (ttcr_amd/csrc/fsm_sweep_plan.h) lets a grid skip up to 32 FSM_SLAB_WORDS = 1024 F bricks: (16384, 17, 2)
                      must run the SKIP = true kernel with the top bit of the top word live, (16385, 17, 2) the SKIP = false one -- with
                      one field per workgroup on chunks of 16 and with pairs on chunks of 8; no other limit of the library rejects
                      these shapes

@@ -122,7 +122,7 @@ print("SKIP_WORKER " + json.dumps(out))
 def test_exact_skipping_follows_the_model_in_the_probe_window(tmp_path, capsys):
     """launches of skip_probe_min ... skip_units_min - 1 work units (fp32, 3-D, first order): exact skipping stays on while the grid's last
     skipping solve evaluated less than 0.6 of its node updates, goes off above, and is tried again after eight solves without
-    (GridT::skip_default) -- and no result depends on it.  The two thresholds are lowered so that a 64^3 grid (16 patches) sits in the window."""
+    (fsm_skip_default, ttcr_amd/csrc/fsm_sweep_plan.h) -- and no result depends on it.  The two thresholds are lowered so that a 64^3 grid (16 patches) sits in the window."""
     script = tmp_path / "skip_worker.py"
     script.write_text(SKIP_WORKER % dict(root=ROOT))
     env = dict(os.environ, TTCR_FSM_SKIP_PROBE_UNITS="8", TTCR_FSM_SKIP_UNITS="32")

@@ -2,7 +2,7 @@
 for bit (-m gpu).
 
 tests/test_few_workgroups_gpu.py and tests/test_arith_small_gpu.py do this for the first-order 3-D kernels.  This is the other half of the
-table the host picks from (launch_sweeps_persistent*, ttcr_amd/csrc/fsm_capi.hip): the 3-D WENO stage with one field per workgroup on
+table the host picks from (fsm_sweep_plan, ttcr_amd/csrc/fsm_sweep_plan.h): the 3-D WENO stage with one field per workgroup on
 chunks of 16 and of 8 levels and with pairs (TTCR_FSM_PAIR=1) on chunks of 8 and of 4, and both stages of the 2-D solver -- each with and
 without exact skipping, as a whole-iteration launch with and without the upwind counters sampled ahead (PRE), and as one launch per
 sweep (option "mode" = 1): 22 + 16 names per precision, 76 in all.  Here the patches exchange a halo of two columns, the whole-iteration
@@ -39,7 +39,7 @@ def _b(v):
 
 class Inst:
     """one instantiation fsm_sweep_persistent<T,PJ,PK,CH,IS3D,SKIP,H,NS,XS,PRE> and how the host is brought to launch it
-    (launch_sweeps_persistent*, ttcr_amd/csrc/fsm_capi.hip).  The name is that of the LAST launch of a call: the WENO stage of the last
+    (fsm_sweep_plan, ttcr_amd/csrc/fsm_sweep_plan.h; tests/test_sweep_plan.py checks every row on the CPU).  The name is that of the LAST launch of a call: the WENO stage of the last
     round (weno = 0: its first-order stage), so every row is built for the batch size of its last round."""
 
     def __init__(self, dtype, dim, h, ns, ch, xs, skip, pre):
@@ -236,7 +236,7 @@ def test_cell_grids(oracle, monkeypatch, capsys, inst):
 
 @pytest.mark.parametrize("dtype", wc.DTYPES, ids=["fp32", "fp64"])
 def test_weno_grid_under_mode_0_takes_the_launch_per_sweep_kernel(oracle, monkeypatch, capsys, dtype):
-    """persistent_now(): stage 1 goes to the persistent kernel whatever the mode -- under mode 0 (first-order stage: fsm_sweep_tile) the WENO
+    """fsm_persistent(): stage 1 goes to the persistent kernel whatever the mode -- under mode 0 (first-order stage: fsm_sweep_tile) the WENO
     stage is the launch-per-sweep instantiation, skipping by default"""
     inst = Inst(dtype, 3, 2, 1, 8, False, 1, 0)   # (a row of its own: the table's keeps "mode" = 1 and forces "skip")
     inst.opts = {"mode": 0}

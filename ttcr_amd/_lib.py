@@ -57,6 +57,8 @@ SYMBOLS = {
     "ttcr_fsm_last_kernel": (_I, [_P, C.c_char_p, C.c_size_t]),
     "ttcr_fsm_build_id": (C.c_char_p, []),
     "ttcr_fsm_unit_order": (_I, [_I, _I, _I, _I, _U32, _U32, _U32, C.POINTER(_U32), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ttcr_fsm_sweep_plan": (_I, [_I, _I, _I, _U32, _U32, _U32, _I, C.POINTER(C.c_char_p), C.POINTER(C.c_double), _I, _I, _I, _I, _I, C.c_char_p, C.c_size_t,
+                                 C.POINTER(C.c_longlong)]),
     "ttcr_fsm_stopping_stats": (_I, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "ttcr_fsm_prefill_swaps": (_I, [_P, C.POINTER(C.c_longlong)]),
     "ttcr_fsm_prefill_inline_fills": (_I, [_P, C.POINTER(C.c_longlong)]),

@@ -7,6 +7,7 @@ which a fused multiply-add would not (ttcr_amd/csrc/fsm_kernels.h header).
 Seven translation units, compiled to objects under ttcr_amd/csrc/_obj and linked:
   fsm_capi.hip    the C ABI, the host side and every kernel but one
   fsm_fast.hip    the sweep kernels with tolerance-grade arithmetic (option "arith" = 1)
+                  (both list their sweep kernels for fsm_sweep_dispatch.h, which launches the one a plan of fsm_sweep_plan.h names)
   fsm_tape.hip    the M tape: compute_M's rows merged on the device, node index, M^T w (hipCUB sorts)
   fsm_adjoint.hip the field tape: discrete adjoint of the first-order 3-D update (coupling, seeds, relaxation, gradient)
                   and its forward mode (tangent relaxation, receiver rows); the source derivative (K-column relaxation, source gradient);
@@ -30,9 +31,9 @@ LIB = os.path.join(HERE, "libttcr_amd.so")
 INC = os.path.join("..", "..", "include", "ttcr_amd.h")
 # source -> (extra flags, files it is compiled from)
 UNITS = {
-    "fsm_capi.hip": ([], ["fsm_capi.hip", "fsm_kernels.h", "fsm_fast_api.h", "fsm_march_levels.inc", "fsm_fast.hip", "fsm_tape_api.h",
+    "fsm_capi.hip": ([], ["fsm_capi.hip", "fsm_kernels.h", "fsm_fast_api.h", "fsm_sweep_plan.h", "fsm_sweep_dispatch.h", "fsm_march_levels.inc", "fsm_fast.hip", "fsm_tape_api.h",
                           "fsm_tape.hip", "fsm_adjoint_api.h", "fsm_adjoint.hip", "fsm_normal.hip", "fsm_locate.hip", "fsm_model.hip", "fsm_unit_order.h", "fsm_prefill_slices.h", "fsm_chunk_dirty.h", INC]),
-    "fsm_fast.hip": ([], ["fsm_fast.hip", "fsm_fast_api.h", "fsm_kernels.h", "fsm_march_levels.inc", "fsm_prefill_slices.h", "fsm_chunk_dirty.h"]),
+    "fsm_fast.hip": ([], ["fsm_fast.hip", "fsm_fast_api.h", "fsm_sweep_plan.h", "fsm_sweep_dispatch.h", "fsm_kernels.h", "fsm_march_levels.inc", "fsm_prefill_slices.h", "fsm_chunk_dirty.h"]),
     "fsm_tape.hip": ([], ["fsm_tape.hip", "fsm_tape_api.h"]),
     "fsm_adjoint.hip": ([], ["fsm_adjoint.hip", "fsm_adjoint_api.h", "fsm_kernels.h", "fsm_march_levels.inc", "fsm_prefill_slices.h", "fsm_chunk_dirty.h"]),
     "fsm_normal.hip": ([], ["fsm_normal.hip", "fsm_adjoint_api.h"]),

@@ -31,10 +31,6 @@
 #include "fsm_unit_order.h"
 #include "fsm_chunk_dirty.h"
 
-#ifndef FSM_CHUNK3
-#define FSM_CHUNK3 8
-#endif
-
 namespace ttcr_amd {
 
 static thread_local std::string g_last_error;
@@ -198,7 +194,7 @@ class GridBase {
     int arith = 0;      // option "arith" / TTCR_FSM_ARITH: 0 (default) the reference's arithmetic, results bit-identical to it; 1 tolerance-grade
                         // fp32 local solvers in the first-order sweeps of fp32 grids without the WENO stage (update3_fast / update2_fast,
                         // fsm_kernels.h): within north_star's 1e-5 s RMS of the reference, NOT bit-identical; 2: the WENO stage too
-                        // (weno_axis_fast; outside that bound, see fast_now); whole-iteration launches only
+                        // (weno_axis_fast; outside that bound, see fsm_fast_arith); whole-iteration launches only
     int prefill = -1;   // option "prefill" / TTCR_FSM_PREFILL: a second set of traveltime fields, re-initialised on a side stream while a
                         // solve runs, which the next call that restarts EVERY slot swaps in instead of filling (GridT::solve_batch);
                         // 1 on, 0 off, -1 (default): on when the fields take at least 64 MiB and twice that is at most half the device memory
@@ -285,26 +281,31 @@ class GridBase {
     }
 };
 
-// tile shapes (threads = PJ*PK); see DESIGN.md section 4 for the LDS budget
-template <typename T, int DIM> struct TileCfg;
-#ifndef FSM_PJ3
-#define FSM_PJ3 16
-#endif
-#ifndef FSM_PK3
-#define FSM_PK3 16
-#endif
-template <> struct TileCfg<float, 3> { static constexpr int PJ = FSM_PJ3, PK = FSM_PK3, BL = 16; };
-template <> struct TileCfg<double, 3> { static constexpr int PJ = 16, PK = 8, BL = 16; };
-#ifndef FSM_PJ2
-#define FSM_PJ2 64
-#endif
-#ifndef FSM_CHUNK2
-#define FSM_CHUNK2 16
-#endif
-template <> struct TileCfg<float, 2> { static constexpr int PJ = FSM_PJ2, PK = 1, BL = 32; };
-template <> struct TileCfg<double, 2> { static constexpr int PJ = FSM_PJ2, PK = 1, BL = 32; };
-// chunk length of the persistent kernel
-template <typename T, int DIM> struct ChunkCfg { static constexpr int C = DIM == 3 ? FSM_CHUNK3 : FSM_CHUNK2; };
+// Every exact sweep kernel there is (T, DIM, H, NS, chunk[, PRE]); the tolerance-grade ones: fsm_fast.hip
+template <typename T>
+using ExactSweepKernels = SweepKernels<
+    // 3-D WENO stage: one field per workgroup on chunks of 16 levels (whole-iteration launch), pairs and one field on chunks of 4 and of 8
+    WholeIteration<T, 3, 2, 1, 16>, EveryLaunch<T, 3, 2, 2, 4>, EveryLaunch<T, 3, 2, 1, 4>, EveryLaunch<T, 3, 2, 2, ChunkCfg<T, 3>::C>,
+    EveryLaunch<T, 3, 2, 1, ChunkCfg<T, 3>::C>,
+    // 2-D WENO stage
+    EveryLaunch<T, 2, 2, 2, ChunkCfg<T, 2>::C>, EveryLaunch<T, 2, 2, 1, ChunkCfg<T, 2>::C>,
+    // first-order 3-D sweeps: one field on chunks of 16 (whole-iteration launch, no PRE), pairs and one field on chunks of 8
+    WholeIterationPre<T, 3, 1, 1, 16, false>, EveryLaunch<T, 3, 1, 2, ChunkCfg<T, 3>::C>, EveryLaunch<T, 3, 1, 1, ChunkCfg<T, 3>::C>,
+    // first-order 2-D sweeps
+    EveryLaunch<T, 2, 1, 2, ChunkCfg<T, 2>::C>, EveryLaunch<T, 2, 1, 1, ChunkCfg<T, 2>::C>>;
+// Whether the library holds the kernel a plan names (fsm_sweep_tile exists for every grid), and its launch.
+template <typename T>
+static bool sweep_kernel_exists(const SweepPlan& p) {
+    if (!p.persistent) return true;
+    if (p.AR) return std::is_same<T, float>::value && fsm_fast_sweep_exists(p);
+    return ExactSweepKernels<T>::has(p);
+}
+template <typename T>
+static void launch_sweep_kernel(const SweepPlan& p, const PersistArgs<T>& pa, hipStream_t stream) {
+    if constexpr (std::is_same<T, float>::value)
+        if (p.AR) { fsm_fast_sweep(p, pa, stream); return; }
+    ExactSweepKernels<T>::run(p, pa, stream);
+}
 
 template <typename T>
 class GridT : public GridBase {
@@ -337,25 +338,7 @@ class GridT : public GridBase {
     void set_pair_layout(int v) override { pair_layout = v; }
     DevBuf<int> d_rslot;
     DevBuf<RaySrc> d_rdesc;
-    int weno_ch4_min = 8;  // pair layout: slot groups from which the 3-D WENO stage uses chunks of 4 levels
-    int weno_c16_below = 3;  // one field per workgroup: batch entries below which the 3-D WENO stage uses chunks of 16 levels (option lone_chunk = 16)
-    int f64_c16_below = 5;   // ... below which the fp64 first-order 3-D sweeps do
-    int pre_min = 2;           // 3-D: slot groups in a batch from which the upwind counters are sampled one chunk ahead (PRE)
-    // extra (unused) dynamic LDS per workgroup of the whole-iteration launch: caps the resident workgroups per CU.  A lone
-    // source is bound by the dependent chain of a marching unit, and a unit that shares its CU's SIMDs with another
-    // marching unit runs that chain slower (TTCR_FSM_XS_LDS=bytes, TTCR_FSM_XS_LDS_BELOW=groups; 0: off)
-    // Measured, 512^3: one source 8.49 -> 7.37 ms per sweep-iteration with two workgroups per CU instead of four (7.14 with
-    // the counters sampled ahead as well), one source pair 10.5 -> 9.96; one per CU 9.95 (too few units in flight);
-    // from two slot groups on, and for the 2-D and WENO kernels, the cap does not pay (profiles/r02/occupancy_cap.txt).
-    size_t xs_lds_bytes = 40000;
-    int xs_lds_below = 2;
-    size_t xs_dyn_lds(int batch) const { return (dim == 3 && stage == 0 && batch < xs_lds_below) ? xs_lds_bytes : 0; }
-    int time_order_below = 1 << 30; // fewer batch entries (slot groups / slots) than this in a batch: the whole-iteration launch hands its units out in the
-                               // order of their expected start times instead of sweep by sweep (build_persistent_lists).  Until round 5: 17 -- with
-                               // the kernels of round 5 the start-time order wins at every size measured (512^3, two sweep-iterations: 64 sources
-                               // 169.8 -> 166.8 ms, 34 sources 99.6 -> 96.0, 48: 134.4 -> 133.8; rough model, 64 sources to convergence 2 004 ->
-                               // 1 917 ms; 256^3 x 24 sources 8.17 -> 7.67 ms per sweep-iteration; 2-D 4096^2 x 64 18.5 -> 18.4;
-                               // profiles/r05/experiment_ticket_order.txt)
+    SweepTuning tune;   // thresholds of the kernel choice (fsm_sweep_plan.h), read from the environment when the grid is created
     DevBuf<T> d_gather;      // scratch for de-interleaving one field
     DevBuf<T> d_rsrc, d_rt0;  // source points / origin times of the source whose rays are traced
     DevBuf<int> d_rstat;
@@ -398,7 +381,7 @@ class GridT : public GridBase {
     // one captured launch sequence per stage (first-order / WENO3)
     hipGraph_t graphs[2] = {nullptr, nullptr};
     hipGraphExec_t graph_execs[2] = {nullptr, nullptr};
-    int graph_batches[2] = {0, 0}, graph_modes[2] = {-1, -1};
+    SweepPlan graph_plans[2];   // what each holds (batch -1: no longer valid)
 
     GridT(int dim_, bool cell_, uint32_t nx, uint32_t ny, uint32_t nz, double ddx, double ddz, double minx,
           double miny, double minz, double eps, int maxit, int nslots, bool translate_, int dev, bool weno_) {
@@ -443,40 +426,18 @@ class GridT : public GridBase {
         {
             int cus = 0;
             HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-            persist_wgs = 8 * std::max(cus, 1);
+            tune = fsm_sweep_tuning(8 * std::max(cus, 1));
+            const SweepOptions o = fsm_sweep_options();
+            mode = o.mode; skip = o.skip; lone_chunk = o.lone_chunk; arith = o.arith;
         }
         HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         HIP_CHECK(hipEventCreate(&ev0));
         HIP_CHECK(hipEventCreate(&ev1));
         d_s.reserve(n_nodes, 64);
-        // source pairs (fields interleaved, marched together) for the first-order 3-D solver only.  The one-wave 2-D
-        // patches issue in order, a second source doubles the instructions of a level and buys nothing (4096^2:
-        // 16 sources 28.0 -> 20.8 ms, 64 sources 35.8 -> 28.9 ms, 256 sources 112 -> 87 ms unpaired); the WENO stage
-        // is bound by its arithmetic, and pairs cost it a resident wave (256^3: 2 sources 761 -> 483 ms, 8 sources
-        // 1208 -> 973 ms, 16 sources 1740 -> 1672 ms, 64 sources 5986 -> 6221 ms).  profiles/r02/pairing.txt
-        // Round 4, with exact skipping on by default for batches: on a model where most chunks are skipped, pairs only pay once the
-        // chip has more work units than it can keep in flight -- a chunk of a pair is evaluated when EITHER source needs it and a
-        // pair's level is the longer chain; on a model where most chunks are evaluated they pay from 4 sources on.
-        // 512^3 (1 024 patches), ms per sweep-iteration paired / unpaired, gradient model (66 % of the updates skipped):
-        //   2 sources 10.1 / 8.1, 4: 12.0 / 10.6, 8: 17.3 / 16.2, 16: 27.2 / 30.2, 32: 45.9 / 58.4; 256^3: 8 sources 5.7 / 4.5, 16: 6.5 / 6.1
-        // ms per solve, random 16^3-block model (8-11 iterations, 75-83 % evaluated):
-        //   2 sources 109.9 / 110.5, 4: 191 / 203, 8: 314 / 372, 16: 556 / 710      (profiles/r04/README.md)
-        // So: pairs when slots x patches of a sweep exceed pair_units_min = 6 144 (512^3: from 8 sources on, where the smooth model
-        // loses 7 % and the rough one gains 18 %; below, the smooth model gains 13-25 % and the rough one loses 0-6 %).
-        {
-            long long pair_units_min = 6144;
-            if (const char* e = std::getenv("TTCR_FSM_PAIR_UNITS")) pair_units_min = std::atoll(e);   // tuning only
+        {   // source pairs for the first-order 3-D solver only (fsm_pair_layout)
             const long long patches = dim == 3 ? (long long)((ny + 1 + TileCfg<T, 3>::PJ - 1) / TileCfg<T, 3>::PJ) * ((nz + 1 + TileCfg<T, 3>::PK - 1) / TileCfg<T, 3>::PK) : 0;
-            NS = (n_slots >= 2 && dim == 3 && !weno && (long long)n_slots * patches > pair_units_min) ? 2 : 1;
-            // Round 6: between the threshold and 2.5 x the threshold (512^3: 8 ... 15 slots) which layout is faster depends on the MODEL --
-            // smooth (most chunks skipped): one field per workgroup on 16-level chunks, 15.2 against 17.2 ms per sweep-iteration for 8 sources;
-            // rough (most chunks evaluated): pairs, 311 against 360 ms per solve.  Both layouts take the same memory, so such a grid follows
-            // the evaluated fraction of its last call that restarted every slot (choose_layout); option "pair_layout" pins it.
-            ns_window = NS == 2 && (long long)n_slots * patches <= (5 * pair_units_min) / 2;
+            NS = fsm_pair_layout(tune, dim, weno, n_slots, patches, &ns_window);
         }
-        if (const char* e = std::getenv("TTCR_FSM_PAIR")) { NS = (std::atoi(e) != 0 && n_slots >= 2) ? 2 : 1; ns_window = false; }
-        if (const char* e = std::getenv("TTCR_FSM_LAYOUT_LO")) layout_lo = std::atof(e);
-        if (const char* e = std::getenv("TTCR_FSM_LAYOUT_HI")) layout_hi = std::atof(e);
         d_tt.reserve(n_nodes * tt_fields(), 64);   // (room for either layout)
         mask_words = (n_nodes + 31) / 32;
         d_mask.reserve(mask_words * (size_t)n_slots);
@@ -503,13 +464,13 @@ class GridT : public GridBase {
             geom.NF = nx + 1; geom.NJ = ny + 1; geom.NK = nz + 1;
             geom.npj = (geom.NJ + C::PJ - 1) / C::PJ;
             geom.npk = (geom.NK + C::PK - 1) / C::PK;
-            n_launch = count_launches(C::BL);
+            n_launch = fsm_tile_launches(geom.NF, geom.NJ, geom.NK, geom.npj, geom.npk, C::BL);
         } else {  // F = z (fastest), J = x
             using C = TileCfg<T, 2>;
             geom.NF = nz + 1; geom.NJ = nx + 1; geom.NK = 1;
             geom.npj = (geom.NJ + C::PJ - 1) / C::PJ;
             geom.npk = 1;
-            n_launch = count_launches(C::BL);
+            n_launch = fsm_tile_launches(geom.NF, geom.NJ, geom.NK, geom.npj, geom.npk, C::BL);
         }
         geom.n_nodes = (uint32_t)n_nodes;
         geom.M = (std::max(geom.NF, geom.NJ) + 1) & ~1;
@@ -538,7 +499,7 @@ class GridT : public GridBase {
             cmap_words = max_chunks / 32 + 1;
             d_cmap.reserve((size_t)n_patches * n_slots * (dim == 3 ? 8 : 4) * 2 * cmap_words);
             HIP_CHECK(hipMemset(d_cmap.p, 0, (size_t)n_patches * n_slots * (dim == 3 ? 8 : 4) * 2 * cmap_words * sizeof(unsigned long long)));
-            cdirty_wpu = ((geom.NF + 2 * (PJ + PK)) / 8 + 4) / 32 + 1;   // (chunks of 8 levels or more)
+            cdirty_wpu = fsm_cdirty_wpu(geom.NF, PJ, PK);
             if (dim == 3) d_cdirty.reserve(cdirty_words());   // (one set per slot group, at most n_slots of them; zeroed by every solve)
             // whole-sweep tallies: one entry per sweep of a solve (both stages); solves with more sweeps simply stop using them
             sw_sweeps = (dim == 3 ? 8 : 4) * (2 * std::min(nitermax, 256) + 2);
@@ -550,22 +511,8 @@ class GridT : public GridBase {
             HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&fsm_sweep45_rows<T>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
         if (const char* e = std::getenv("TTCR_FSM_SWEEP45")) sweep45_strips = std::string(e) == "strips";
-        if (const char* e = std::getenv("TTCR_FSM_WENO_CH4_MIN")) weno_ch4_min = std::atoi(e);   // tuning only
-        if (const char* e = std::getenv("TTCR_FSM_WENO_C16_BELOW")) weno_c16_below = std::atoi(e);   // tuning only
-        if (const char* e = std::getenv("TTCR_FSM_F64_C16_BELOW")) f64_c16_below = std::atoi(e);     // tuning only
-        if (const char* e = std::getenv("TTCR_FSM_TIME_ORDER_BELOW")) time_order_below = std::atoi(e);   // tuning only
-        if (const char* e = std::getenv("TTCR_FSM_PRE_MIN")) pre_min = std::atoi(e);                     // tuning only
-        if (const char* e = std::getenv("TTCR_FSM_SKIP")) skip = std::atoi(e);
-        if (const char* e = std::getenv("TTCR_FSM_SKIP_UNITS")) skip_units_min = std::atoi(e);   // tuning only
-        if (const char* e = std::getenv("TTCR_FSM_SKIP_PROBE_UNITS")) skip_probe_min = std::atoi(e);   // tuning only
         if (const char* e = std::getenv("TTCR_FSM_RS_FIELDS")) rs_fields_max = (size_t)std::max(0, std::atoi(e));   // tests: batches of the stopping rule's sums (0: strided fields)
-        if (const char* e = std::getenv("TTCR_FSM_WGS")) persist_wgs = std::atoi(e);              // tuning only
-        if (const char* e = std::getenv("TTCR_FSM_XS_LDS")) xs_lds_bytes = (size_t)std::atol(e);
-        if (const char* e = std::getenv("TTCR_FSM_XS_LDS_BELOW")) xs_lds_below = std::atoi(e);
-        if (const char* e = std::getenv("TTCR_FSM_MODE")) mode = std::atoi(e);
         if (const char* e = std::getenv("TTCR_FSM_PREFILL")) prefill = std::atoi(e);
-        if (const char* e = std::getenv("TTCR_FSM_LONE_CHUNK")) lone_chunk = std::atoi(e) == 8 ? 8 : 16;   // tuning only
-        if (const char* e = std::getenv("TTCR_FSM_ARITH")) arith = std::max(0, std::min(2, std::atoi(e)));
     }
 
     // persistent kernel: ticket order = anti-diagonal m = TJ+TK major (a topological order of the
@@ -594,182 +541,6 @@ class GridT : public GridBase {
         const int PJ = dim == 3 ? TileCfg<T, 3>::PJ : TileCfg<T, 2>::PJ, PK = dim == 3 ? TileCfg<T, 3>::PK : 1;
         const int C = dim == 3 ? ChunkCfg<T, 3>::C : ChunkCfg<T, 2>::C;
         return fsm_xs_order(dim, geom.NF, geom.NJ, geom.NK, PJ, PK, C, H, by_time, diag_order);
-    }
-
-    // The 3-D WENO stage exists with two chunk lengths: 8 levels (the kernel is latency bound with few
-    // sources: fewer chunk boundaries) and 4 levels (157 instead of 208 VGPRs in pair mode, no spills, three
-    // waves per SIMD: +14 % throughput once >= 8 slot groups are swept together).  Same results either way.
-    template <int DIM, int H>
-    void launch_sweeps_persistent(int batch) {
-        constexpr int C0 = ChunkCfg<T, DIM>::C;
-        // One field per workgroup (lone sources, batches below the pairing threshold): such launches are bound by the chains of their
-        // chunks rather than by registers, and chunks of 16 levels halve the staging, the write-back and the hand-offs per level --
-        // ms per sweep-iteration with chunks of 8 / 16 levels, 512^3: lone source 7.20 / 6.87, 2 sources 8.11 / 7.15, 4: 10.57 / 9.72,
-        // 8 (unpaired): 16.36 / 15.24; 256^3: 1 source 3.29 / 3.15, 2: 3.69 / 3.30, 4: 4.28 / 3.55, 8: 4.49 / 4.04 (chunks of 4: 11.99 /
-        // 4.96 for the lone source; PAIRS with chunks of 16: 48 ms instead of 17 for 8 sources, 22 ms with two workgroups per CU and no
-        // spills).  fp64: the lone source 8.08 / 7.39 (256^3), 13.03 / 11.40 (384^3), 2 sources 9.01 / 7.62, 4: 10.39 / 9.12, but 8 sources
-        // 12.0 / 12.3 and 36.0 / 43.9 (384^3): up to four.  Same partial order, same results, same exact skipping (a chunk is the unit
-        // that is skipped: twice as coarse).
-        // The WENO stage likewise where it is bound by its chains: 256^3 fp32 1 source 380.6 / 318.3 ms per solve (46 WENO iterations),
-        // 2 sources 397 / 371, but 4: 501 / 564, 8: 761 / 981 (bound by its arithmetic there, and the longer chunk costs it registers);
-        // fp64 1 source 663.5 / 536.7, 2 sources 757 / 589.  profiles/r05/experiment_chunk_length.txt
-        if constexpr (DIM == 3 && C0 == 8) {
-            const int below = H == 2 ? weno_c16_below : sizeof(T) == 4 ? std::numeric_limits<int>::max() : f64_c16_below;
-            // (the tolerance-grade kernels of one field per workgroup exist with chunks of 16 levels only)
-            if (NS == 1 && mode == 2 && (lone_chunk == 16 || fast_now<H>()) && batch < below) {
-                launch_sweeps_persistent_ns<DIM, H, 1, 16, true>(batch);
-                return;
-            }
-        }
-        // (pair layout only: with one field per slot -- the default of weno grids since round 2 -- the 8-level chunks are
-        // 2-4 % faster at every batch size, profiles/r02/weno_chunk.txt)
-        if (H == 2 && DIM == 3 && NS == 2 && batch >= weno_ch4_min && C0 == 8) {
-            if (NS == 2) launch_sweeps_persistent_ns<DIM, H, 2, (H == 2 && DIM == 3) ? 4 : C0>(batch);
-            else launch_sweeps_persistent_ns<DIM, H, 1, (H == 2 && DIM == 3) ? 4 : C0>(batch);
-        } else {
-            if (NS == 2) launch_sweeps_persistent_ns<DIM, H, 2, C0>(batch); else launch_sweeps_persistent_ns<DIM, H, 1, C0>(batch);
-        }
-    }
-
-    template <int DIM, int H, int NSV, int CH, bool XS_ONLY = false>   // XS_ONLY: only the whole-iteration launch (mode 2) is instantiated
-    void launch_sweeps_persistent_ns(int batch) {
-        using C = TileCfg<T, DIM>;
-        PersistArgs<T> pa;
-        SweepArgs<T>& a = pa.s;
-        // (the occupancy cap of the lone source and the upwind counters sampled one chunk ahead (PRE) were tuned for chunks of 8 levels: on
-        // first-order chunks of 16 they cost -- lone source 512^3 6.89 -> 6.68 ms per sweep-iteration without both, 256^3 3.19 -> 3.07, fp64
-        // 256^3 7.35 -> 7.11; batches without PRE: 512^3 x 2 / 4 sources 7.21 -> 7.09 / 9.69 -> 9.64, 256^3 x 2 / 4 / 8 3.30 -> 3.15 /
-        // 3.57 -> 3.47 / 4.04 -> 3.97)
-        constexpr bool NO_PRE = CH == 16 && H == 1 && DIM == 3;
-        const size_t dyn_lds = NO_PRE ? 0 : xs_dyn_lds(batch);
-        a.tt = d_tt.p;
-        a.ts = NS;
-        a.lmask = d_lmask.p;
-        a.frozen = d_mask.p;
-        a.bbox = d_bbox.p;
-        a.change = d_change.p;
-        a.slots = d_slots.p;
-        a.tiles = nullptr;
-        a.g = geom;
-        a.prof = d_prof.p;
-        a.mask_words = (uint32_t)mask_words;
-        a.dx = dx;
-        a.dz = dz;
-        a.w = 0;
-        a.variant = DIM == 3 ? 0 : (dx == dz ? 1 : 2);
-        pa.order = d_order.p;
-        pa.sync = d_sync.p;
-        pa.n_patches = n_patches;
-        pa.batch = batch;
-        pa.timeout_ticks = 300000000ull;  // 3 s at 100 MHz
-        pa.stamp = d_stamp.p;
-        pa.iter_ptr = d_iter.p;
-        pa.evals = d_evals.p;
-        pa.nbf = nbf; pa.nbj = nbj; pa.nbk = nbk;
-        pa.ndir = DIM == 3 ? 8 : 4;
-        pa.skip = skip_now(batch) ? (std::getenv("TTCR_FSM_SKIP_ALL_DIRTY") ? 2 : 1) : 0;
-        pa.cmap = d_cmap.p;
-        pa.cw = cmap_words;
-        pa.cdirty = d_cdirty.p;
-        pa.cdw = cdirty_wpu;
-        pa.sw = std::getenv("TTCR_FSM_NO_SW") ? nullptr : d_sw.p;   // (tuning / bisecting: no whole-sweep shortcut)
-        pa.n_sw_groups = n_groups();
-        pa.n_sw_sweeps = sw_sweeps;
-        pa.fill_dst = nullptr;
-        pa.fill_slice = 0;
-        pa.fill_n = 0;
-
-        // first-order 3-D kernels: workgroups take units until the tickets run out -- no more of them than can be resident
-        // (8 per CU is more than any instantiation fits; the surplus finds the ticket counter exhausted).  The others (and
-        // TTCR_FSM_WGS=0, tuning): one workgroup per unit.
-        const size_t wg_cap = (fsm_looped(DIM == 3, H) && persist_wgs > 0) ? (size_t)persist_wgs : ~(size_t)0;
-        const dim3 block(C::PJ * C::PK), grid((unsigned)std::min<size_t>((size_t)n_patches * batch, wg_cap));
-        const int ndir = DIM == 3 ? 8 : 4;
-        {
-            const bool pre_ = mode == 2 && !NO_PRE && (DIM == 2 || batch >= pre_min || dyn_lds > 0);
-            char nm[160];
-            std::snprintf(nm, sizeof nm, "fsm_sweep_persistent<%s,%d,%d,%d,%s,%s,%d,%d,%s,%s>", sizeof(T) == 4 ? "float" : "double", C::PJ, C::PK, CH,
-                          DIM == 3 ? "true" : "false", skip_now(batch) ? "true" : "false", H, NSV, mode == 2 ? "true" : "false", pre_ ? "true" : "false");
-            last_kernel = nm;
-        }
-        if (mode == 2) {
-            // whole iteration in one launch: tickets direction-major, sweeps overlap at their ends
-            pa.ssh = d_ssh.p;
-            pa.ssh_stride = ssh_stride;
-            pa.dir = 0;
-            a.rf = a.rj = a.rk = a.rev = 0;
-            a.s_sheared = nullptr;
-            pa.timeout_ticks = 1000000000ull;  // 10 s: a unit may wait for most of the previous sweep
-            const dim3 gridx((unsigned)std::min<size_t>((size_t)n_patches * batch * ndir, wg_cap));
-            pa.order = d_order_xs[H == 2 ? 1 : 0][batch < time_order_below ? 1 : 0].p;
-            const bool pre = DIM == 2 || batch >= pre_min || dyn_lds > 0;   // counters sampled one chunk ahead (template PRE)
-            if (fill_arm) {
-                // (solve_batch: first launch of a call that restarts every slot) the spare set, one slice per ticket of this launch
-                pa.fill_dst = d_tt_alt.p;
-                pa.fill_n = n_nodes * tt_fields();
-                pa.fill_slice = fsm_fill_slice_len(pa.fill_n, (size_t)n_patches * batch * ndir, 16 / sizeof(T));
-                fill_arm = false;
-                fill_in_flight = true;
-            }
-            if constexpr (std::is_same<T, float>::value) {
-                // tolerance-grade arithmetic: the AR = 1 instantiation of the kernel chosen below (fsm_fast.hip); the WENO stage of grids
-                // that keep their fields in pairs (TTCR_FSM_PAIR = 1 on a weno grid: tuning only) has none and keeps the exact kernels
-                if (fast_now<H>() && (H == 1 || NSV == 1)) {
-                    const FastCfg fc{H, DIM, NSV, CH, skip_now(batch), NO_PRE ? false : pre};
-                    last_kernel.insert(last_kernel.size() - 1, ",1");
-                    const hipError_t e = fsm_fast_launch(pa, fc, gridx.x, dyn_lds, stream);
-                    if (e == hipErrorInvalidValue) throw std::logic_error("arith = 1: no such kernel (" + last_kernel + ")");
-                    HIP_CHECK(e);
-                    return;
-                }
-            }
-            if constexpr (NO_PRE) {
-                (void)pre;
-                if (skip_now(batch))
-                    fsm_sweep_persistent<T, C::PJ, C::PK, CH, DIM == 3, true, H, NSV, true><<<gridx, block, dyn_lds, stream>>>(pa);
-                else
-                    fsm_sweep_persistent<T, C::PJ, C::PK, CH, DIM == 3, false, H, NSV, true><<<gridx, block, dyn_lds, stream>>>(pa);
-            } else {
-                if (skip_now(batch) && pre)
-                    fsm_sweep_persistent<T, C::PJ, C::PK, CH, DIM == 3, true, H, NSV, true, true><<<gridx, block, dyn_lds, stream>>>(pa);
-                else if (skip_now(batch))
-                    fsm_sweep_persistent<T, C::PJ, C::PK, CH, DIM == 3, true, H, NSV, true><<<gridx, block, dyn_lds, stream>>>(pa);
-                else if (pre)
-                    fsm_sweep_persistent<T, C::PJ, C::PK, CH, DIM == 3, false, H, NSV, true, true><<<gridx, block, dyn_lds, stream>>>(pa);
-                else
-                    fsm_sweep_persistent<T, C::PJ, C::PK, CH, DIM == 3, false, H, NSV, true><<<gridx, block, dyn_lds, stream>>>(pa);
-            }
-            HIP_CHECK(hipGetLastError());
-            return;
-        }
-        if (fast_now<H>() && H == 1) throw ValueError("option 'arith' = 1 needs whole-iteration launches (option 'mode' = 2)");
-        if constexpr (XS_ONLY) throw std::logic_error("launch_sweeps_persistent_ns: whole-iteration launches only");
-        else {
-        pa.ssh = nullptr;
-        pa.ssh_stride = 0;
-        static const int RX2[4] = {0, 1, 1, 0}, RZ2[4] = {0, 0, 1, 1};
-        for (int d = 0; d < ndir; ++d) {
-            int fam;
-            if (DIM == 3) {
-                a.rf = d & 1; a.rj = (d >> 1) & 1; a.rk = (d >> 2) & 1;
-                a.rev = a.rk;
-                fam = (a.rf ^ a.rk) | ((a.rj ^ a.rk) << 1);
-            } else {
-                a.rj = RX2[d]; a.rf = RZ2[d]; a.rk = 0;
-                a.rev = a.rj;
-                fam = a.rf ^ a.rj;
-            }
-            a.s_sheared = d_ssh.p + (size_t)fam * ssh_stride;
-            pa.dir = d;
-            // (no reset of tickets, progress words or change maps: launch epoch pa.iter_ptr[1] + d; the abort word is sticky
-            // within an iteration)
-            if (skip_now(batch))
-                fsm_sweep_persistent<T, C::PJ, C::PK, CH, DIM == 3, true, H, NSV, false><<<grid, block, 0, stream>>>(pa);
-            else
-                fsm_sweep_persistent<T, C::PJ, C::PK, CH, DIM == 3, false, H, NSV, false><<<grid, block, 0, stream>>>(pa);
-        }
-        HIP_CHECK(hipGetLastError());
-        }
     }
 
     // For every launch w of a sweep, the patches (TJ,TK) whose level window
@@ -814,12 +585,6 @@ class GridT : public GridBase {
         if (fill_stream) { (void)hipStreamSynchronize(fill_stream); (void)hipStreamDestroy(fill_stream); }
         if (ev_fill) (void)hipEventDestroy(ev_fill);
         if (stream) (void)hipStreamDestroy(stream);
-    }
-
-    int count_launches(int BL) const {
-        const int Lhi = (geom.NJ - 1) + (geom.NK - 1) + geom.NF - 1;
-        const int m = geom.npj + geom.npk - 2;
-        return (Lhi + m * (BL - 1)) / BL + 1;
     }
 
     // ---- slowness ---------------------------------------------------------------------
@@ -1007,50 +772,127 @@ class GridT : public GridBase {
     }
 
     // ---- sweeps -----------------------------------------------------------------------
-    template <int DIM>
-    void launch_sweeps(int batch) {
-        using C = TileCfg<T, DIM>;
-        if (fast_now<1>()) throw ValueError("option 'arith' = 1 needs whole-iteration launches (option 'mode' = 2)");
-        SweepArgs<T> a;
+    // What the kernel choice depends on (fsm_sweep_plan.h), for `entries` batch entries (slot groups / slots) swept together
+    SweepFacts facts(int entries) const {
+        SweepFacts f;
+        fsm_sweep_tiles<T>(f, dim);
+        f.weno = weno;
+        f.rot45 = rotated && dx == dz;
+        f.n_patches = n_patches; f.NF = geom.NF; f.NJ = geom.NJ; f.NK = geom.NK; f.nbf = nbf; f.cdirty_wpu = cdirty_wpu; f.n_launch = n_launch;
+        f.slab_bits = 32 * FSM_SLAB_WORDS; f.cd_words = FSM_CD_WORDS;
+        f.NS = NS;
+        f.opt.mode = mode; f.opt.skip = skip; f.opt.lone_chunk = lone_chunk; f.opt.arith = arith;
+        f.stage = stage; f.probe_skip = probe_skip; f.batch = entries;
+        return f;
+    }
+    bool persistent_now() const { return fsm_persistent(facts(0)); }
+    bool skip_now(int entries) const { return fsm_skip(facts(entries), tune); }
+
+    // Sweep direction d: which axes run backwards, and the sheared copy of the slowness that direction reads.
+    // 3-D: ttcr/Grid3Drn.h:2816-2899.  2-D direction order (i+,j+), (i-,j+), (i-,j-), (i+,j-)  (ttcr/Grid2Drn.h:717-751);
+    // here F = z (the reference's j), J = x (the reference's i)
+    void set_direction(SweepArgs<T>& a, int d) const {
+        static const int RX2[4] = {0, 1, 1, 0}, RZ2[4] = {0, 0, 1, 1};
+        int fam;
+        if (dim == 3) {
+            a.rf = d & 1; a.rj = (d >> 1) & 1; a.rk = (d >> 2) & 1;
+            a.rev = a.rk;
+            fam = (a.rf ^ a.rk) | ((a.rj ^ a.rk) << 1);
+        } else {
+            a.rj = RX2[d]; a.rf = RZ2[d]; a.rk = 0;
+            a.rev = a.rj;
+            fam = a.rf ^ a.rj;
+        }
+        a.s_sheared = d_ssh.p + (size_t)fam * ssh_stride;
+    }
+
+    // The sweeps of one iteration as the plan has them: one whole-iteration launch, one launch per sweep, or one per tile wavefront
+    void launch_sweeps(const SweepPlan& p) {
+        if (p.arith_needs_xs) throw ValueError("option 'arith' = 1 needs whole-iteration launches (option 'mode' = 2)");
+        if (!sweep_kernel_exists<T>(p)) throw std::logic_error("no such sweep kernel (" + fsm_sweep_name(p) + ")");
+        PersistArgs<T> pa;
+        SweepArgs<T>& a = pa.s;
         a.tt = d_tt.p;
         a.ts = NS;
-        a.lmask = nullptr;
+        a.lmask = d_lmask.p;
         a.frozen = d_mask.p;
         a.bbox = d_bbox.p;
         a.change = d_change.p;
         a.slots = d_slots.p;
+        a.tiles = nullptr;
         a.g = geom;
         a.prof = d_prof.p;
         a.mask_words = (uint32_t)mask_words;
         a.dx = dx;
         a.dz = dz;
-        a.variant = DIM == 3 ? 0 : (dx == dz ? 1 : 2);
-        const dim3 block(C::PJ * C::PK);
-        const int ndir = DIM == 3 ? 8 : 4;
-        // 2-D direction order (i+,j+), (i-,j+), (i-,j-), (i+,j-)  (ttcr/Grid2Drn.h:717-751);
-        // here F = z (the reference's j), J = x (the reference's i)
-        static const int RX2[4] = {0, 1, 1, 0}, RZ2[4] = {0, 0, 1, 1};
-        for (int d = 0; d < ndir; ++d) {
-            int fam;
-            if (DIM == 3) {
-                a.rf = d & 1; a.rj = (d >> 1) & 1; a.rk = (d >> 2) & 1;  // ttcr/Grid3Drn.h:2816-2899
-                a.rev = a.rk;
-                fam = (a.rf ^ a.rk) | ((a.rj ^ a.rk) << 1);
+        a.w = 0;
+        a.variant = dim == 3 ? 0 : (dx == dz ? 1 : 2);
+        const int ndir = dim == 3 ? 8 : 4;
+        if (p.persistent) {
+            pa.sync = d_sync.p;
+            pa.n_patches = n_patches;
+            pa.batch = p.batch;
+            pa.stamp = d_stamp.p;
+            pa.iter_ptr = d_iter.p;
+            pa.evals = d_evals.p;
+            pa.nbf = nbf; pa.nbj = nbj; pa.nbk = nbk;
+            pa.ndir = ndir;
+            pa.skip = p.skip;
+            pa.cmap = d_cmap.p;
+            pa.cw = cmap_words;
+            pa.cdirty = d_cdirty.p;
+            pa.cdw = cdirty_wpu;
+            pa.sw = p.sw ? d_sw.p : nullptr;
+            pa.n_sw_groups = n_groups();
+            pa.n_sw_sweeps = sw_sweeps;
+            pa.fill_dst = nullptr;
+            pa.fill_slice = 0;
+            pa.fill_n = 0;
+            if (p.XS) {
+                pa.order = d_order_xs[p.H == 2 ? 1 : 0][p.tickets == SweepPlan::XS_BY_TIME ? 1 : 0].p;
+                pa.ssh = d_ssh.p;
+                pa.ssh_stride = ssh_stride;
+                pa.dir = 0;
+                a.rf = a.rj = a.rk = a.rev = 0;
+                a.s_sheared = nullptr;
+                pa.timeout_ticks = 1000000000ull;  // 10 s at 100 MHz: a unit may wait for most of the previous sweep
+                if (fill_arm) {
+                    // (solve_batch: first launch of a call that restarts every slot) the spare set, one slice per ticket of this launch
+                    pa.fill_dst = d_tt_alt.p;
+                    pa.fill_n = n_nodes * tt_fields();
+                    pa.fill_slice = fsm_fill_slice_len(pa.fill_n, (size_t)n_patches * p.batch * ndir, 16 / sizeof(T));
+                    fill_arm = false;
+                    fill_in_flight = true;
+                }
+                launch_sweep_kernel<T>(p, pa, stream);
             } else {
-                a.rj = RX2[d]; a.rf = RZ2[d]; a.rk = 0;
-                a.rev = a.rj;
-                fam = a.rf ^ a.rj;
+                pa.order = d_order.p;
+                pa.ssh = nullptr;
+                pa.ssh_stride = 0;
+                pa.timeout_ticks = 300000000ull;  // 3 s
+                for (int d = 0; d < ndir; ++d) {
+                    set_direction(a, d);
+                    pa.dir = d;
+                    // (no reset of tickets, progress words or change maps: launch epoch pa.iter_ptr[1] + d; the abort word is sticky
+                    // within an iteration)
+                    launch_sweep_kernel<T>(p, pa, stream);
+                }
             }
-            a.s_sheared = d_ssh.p + (size_t)fam * ssh_stride;
+            HIP_CHECK(hipGetLastError());
+            return;
+        }
+        // one launch per tile wavefront
+        for (int d = 0; d < ndir; ++d) {
+            set_direction(a, d);
             for (int w = 0; w < n_launch; ++w) {
                 if (tile_cnt[w] == 0) continue;
                 a.w = w;
                 a.tiles = d_tiles.p + tile_off[w];
-                const dim3 grid(tile_cnt[w], 1, batch);
-                fsm_sweep_tile<T, C::PJ, C::PK, C::BL, DIM == 3><<<grid, block, 0, stream>>>(a);
+                const dim3 grid(tile_cnt[w], 1, p.batch);
+                if (dim == 3) fsm_sweep_tile<T, TileCfg<T, 3>::PJ, TileCfg<T, 3>::PK, TileCfg<T, 3>::BL, true><<<grid, dim3(p.block), 0, stream>>>(a);
+                else fsm_sweep_tile<T, TileCfg<T, 2>::PJ, TileCfg<T, 2>::PK, TileCfg<T, 2>::BL, false><<<grid, dim3(p.block), 0, stream>>>(a);
             }
         }
-        last_kernel = std::string("fsm_sweep_tile<") + (sizeof(T) == 4 ? "float" : "double") + "," + std::to_string(C::PJ) + "," + std::to_string(C::PK) + "," + std::to_string(C::BL) + "," + (DIM == 3 ? "true" : "false") + ">";
         HIP_CHECK(hipGetLastError());
     }
 
@@ -1059,12 +901,9 @@ class GridT : public GridBase {
     // marches the NS sources of a group together: one address computation, one 8-byte load/store
     // and one LDS access serve both, and the per-level bookkeeping is shared.
     int NS = 1;
-    bool ns_window = false;       // the grid may change its layout between calls (see the constructor)
+    bool ns_window = false;       // the grid may change its layout between calls (fsm_pair_layout)
     int pair_layout = -1;         // option "pair_layout": -1 (default) by the rule above, 0 one field per workgroup, 1 pairs (grids in the window only)
     double last_eval_frac = -1;   // evaluated / all node updates of the last batch that restarted every slot (-1: none yet)
-    // (with chunk-shaped dirty bits the 8-source legs of the bench evaluate 0.25 on the gradient model and 0.67 on the rough one, one field per
-    // workgroup; with the slab mask it was 0.28 and 0.83 in pairs, and the thresholds 0.55 / 0.70 -- which left the rough model on the slower layout)
-    double layout_lo = 0.45, layout_hi = 0.55;   // pairs -> one field per workgroup below lo, back above hi (TTCR_FSM_LAYOUT_LO / _HI: tests, tuning)
     // Called at the top of a batch that restarts EVERY slot (no field of an earlier call survives it): pairs (NS = 2) or one field per
     // workgroup (NS = 1) for this and the following calls.  Nothing else depends on the layout across calls: stamps, change maps, sweep
     // tallies and snapshots are per solve, the second set of fields is filled with max() whatever its layout, host-side results are per slot.
@@ -1072,24 +911,16 @@ class GridT : public GridBase {
         if (!ns_window) return;
         int want = NS;
         if (pair_layout >= 0) want = pair_layout ? 2 : 1;
-        else if (last_eval_frac >= 0) want = NS == 2 ? (last_eval_frac < layout_lo ? 1 : 2) : (last_eval_frac > layout_hi ? 2 : 1);
+        else if (last_eval_frac >= 0) want = NS == 2 ? (last_eval_frac < tune.layout_lo ? 1 : 2) : (last_eval_frac > tune.layout_hi ? 2 : 1);
         if (want == NS) return;
         NS = want;
-        graph_batches[0] = graph_batches[1] = -1;   // (captured launches hold the layout)
+        graph_plans[0].batch = graph_plans[1].batch = -1;   // (captured launches hold the layout)
         for (int q = 0; q < n_slots; ++q) phys[q] = q;
     }
     int n_groups() const { return (n_slots + NS - 1) / NS; }
     // fields of a set (d_tt, d_tt_alt): an odd slot count is padded to whole pairs only where the pair layout is or may come in use
     size_t tt_fields() const { return (size_t)n_slots + ((ns_window || NS == 2) ? (size_t)(n_slots & 1) : 0); }
     T* tt_ptr(int slot) const { return d_tt.p + (size_t)(slot / NS) * n_nodes * NS + slot % NS; }
-    // Tolerance-grade arithmetic (fp32 grids).  arith = 1: the first-order sweeps of grids WITHOUT the WENO stage -- within north_star's
-    // 1e-5 s RMS of the reference.  A grid with the WENO stage keeps the reference's arithmetic in BOTH stages under arith = 1: the WENO
-    // iteration amplifies differences of an ulp in its input field to 1e-3 s (measured, profiles/r06/weno_sensitivity.txt: the exact WENO
-    // stage behind a tolerance-grade first-order stage ends 4e-5 s RMS / 4e-3 s max away from the reference) -- only the bit-identical
-    // first-order field reproduces the reference there.  arith = 2: both stages of such grids as well, outside that bound, for callers
-    // who take the WENO stage's own sensitivity as their tolerance.
-    template <int H>
-    bool fast_now() const { return sizeof(T) == 4 && (arith == 2 || (arith == 1 && !weno)); }
     bool prefill_on() const {
         if (prefill >= 0) return prefill != 0;
         const size_t bytes = n_nodes * tt_fields() * sizeof(T);
@@ -1104,7 +935,7 @@ class GridT : public GridBase {
     // fsm_sweep_persistent issued directly (a captured launch would be replayed with the fill armed).  -1 (default): launches with at
     // least skip_units_min units per sweep of a 3-D grid -- those are bound by throughput; a lone source or a small batch lives on the
     // hop of its patch wavefront, and a burst of stores in front of a unit's first drain would sit on that path.
-    bool fill_arm = false;         // the next whole-iteration launch carries the fill (taken by launch_sweeps_persistent_ns)
+    bool fill_arm = false;         // the next whole-iteration launch carries the fill (taken by launch_sweeps)
     bool fill_in_flight = false;   // ... and it did
     bool inline_fill_now(int entries) const {
         if (prefill_inline == 0 || !d_tt_alt.p || d_tt_alt.n < n_nodes * tt_fields()) return false;
@@ -1113,48 +944,15 @@ class GridT : public GridBase {
         // (measured, 512^3 x 64, profiles/inline_prefill: 182.0 -> 179.1 ms per step with the reference's arithmetic; the tolerance-grade
         // kernels march faster and sit nearer the memory system's limit -- there the stores cost the launch more than the wait they
         // replace, 147.5 -> 148.5 ... 149.4 ms -- and keep the side stream)
-        return dim == 3 && !fast_now<1>() && (long long)n_patches * entries >= skip_units_min;
+        const SweepFacts f = facts(entries);
+        return dim == 3 && !fsm_fast_arith(f) && fsm_units_per_sweep(f) >= tune.skip_units_min;
     }
 
     int stage = 0;  // 0: first-order sweeps, 1: WENO3 sweeps (persistent kernel only)
-    // Exact skipping of chunks / units / sweeps that cannot change a node: on wherever it was measured to pay
-    // (profiles/r03/skip_sweep.txt).  What it saves is work, what it costs is a little of every chunk's time: a win once
-    // the chip is busy (512^3: from two slot groups on, 1.13x ... 1.7x at 32 groups), a loss of 1-15 % where a 3-D solve is
-    // bound by the dependent chain of its units anyway (a lone source or pair; 256^3 and smaller up to 8 sources).  The
-    // WENO stage gains at every batch size (its chunks are expensive), and so do the one-wave patches of the 2-D solver
-    // (1.03x ... 1.19x from 1 to 64 sources on 1024^2 ... 8192^2 nodes, although the SKIP kernels do not follow the
-    // previous sweep up the columns).  TTCR_FSM_SKIP_UNITS: work units per sweep from which the first-order 3-D sweeps skip.
-    int skip_units_min = 2048;
-    // Round 6: between 1 024 and 2 048 units (a lone 512^3 source, 2 - 4 sources at 384^3 ...) whether skipping pays depends on the MODEL -- 512^3,
-    // one source, ms per solve without / with: gradient model 13.3 / 12.8 (arith = 1: 10.9 / 9.6), rough 16^3-block model 65.5 / 68.2 (52.2 / 54.9);
-    // 384^3: 9.4 / 9.2 and 32.5 / 35.1 (profiles/r06/lone_skip_models.txt).  Such fp32 launches follow the evaluated fraction of the grid's last
-    // skipping solve: on while it stayed below 0.6, off above, and tried again after eight solves without.
-    int skip_probe_min = 1024;
-    bool probe_skip = true;      // what a launch in that window does now
+    bool probe_skip = true;      // what a launch in the probe window does now (SweepTuning::skip_probe_min)
     int probe_off_calls = 0;     // solves in the window since skipping was switched off
-    int persist_wgs = 2048;   // workgroups of a sweep launch (each takes units until none is left): 8 per CU; 0: one per unit
-    bool in_probe_window(int entries) const {
-        const long long u = (long long)n_patches * entries;
-        return dim == 3 && sizeof(T) == 4 && u >= skip_probe_min && u < skip_units_min;
-    }
-    int skip_default(int entries) const {
-        if (dim != 3) return 1;
-        if (stage == 1) return 1;
-        if (in_probe_window(entries)) return probe_skip ? 1 : 0;
-        return (long long)n_patches * entries >= skip_units_min ? 1 : 0;
-    }
-    bool persistent_now() const { return mode >= 1 || stage == 1; }
     int cdirty_wpu = 1;   // words of dirty bits per unit
     size_t cdirty_words() const { return (size_t)n_patches * n_slots * 8 * cdirty_wpu; }
-    // the rotated-template sweeps change nodes without stamping their bricks: no skipping next to them
-    // `entries`: batch entries (slot groups / slots) swept together
-    bool skip_now(int entries) const {
-        const int on = skip < 0 ? skip_default(entries) : skip;
-        // (the SKIP kernels pack a level count and 8 flag bits into one progress word, and keep one mask bit per F brick)
-        // (... and, first-order 3-D sweeps, one dirty bit per chunk of a unit in FSM_CD_WORDS words: true of every grid with that many F bricks)
-        const bool fits = (long long)geom.NF + geom.NJ + geom.NK < (1ll << 22) && nbf <= 32 * FSM_SLAB_WORDS && (dim != 3 || cdirty_wpu <= FSM_CD_WORDS);
-        return on != 0 && fits && !(dim == 2 && rotated && !weno && dx == dz);
-    }
 
     // Grid2Drn::sweep45 for every source of the batch (entries as handed to the sweep kernels)
     void launch_sweep45(int batch) {
@@ -1187,33 +985,23 @@ class GridT : public GridBase {
         HIP_CHECK(hipGetLastError());
     }
 
-    void issue_sweeps(int batch) {
-        issue_sweeps_axis(batch);
-        if (dim == 2 && rotated && !weno && dx == dz) launch_sweep45(batch);
-    }
-
-    void issue_sweeps_axis(int batch) {
-        if (stage == 1) {
-            if (dim == 3) launch_sweeps_persistent<3, 2>(batch); else launch_sweeps_persistent<2, 2>(batch);
-        } else if (mode >= 1) {
-            if (dim == 3) launch_sweeps_persistent<3, 1>(batch); else launch_sweeps_persistent<2, 1>(batch);
-        } else {
-            if (dim == 3) launch_sweeps<3>(batch); else launch_sweeps<2>(batch);
-        }
+    void issue_sweeps(const SweepPlan& p) {
+        launch_sweeps(p);
+        if (dim == 2 && rotated && !weno && dx == dz) launch_sweep45(p.batch);
     }
 
     void run_iteration(int batch) {
-        const int ndir = dim == 3 ? 8 : 4;
-        if (use_graph >= 2 || (use_graph == 1 && !persistent_now())) {
+        const SweepPlan plan = fsm_sweep_plan(facts(batch), tune);
+        last_kernel = fsm_sweep_name(plan);
+        if (use_graph >= 2 || (use_graph == 1 && !plan.persistent)) {
             hipGraph_t& graph = graphs[stage];
             hipGraphExec_t& graph_exec = graph_execs[stage];
-            const int key = mode * 2 + (skip_now(batch) ? 1 : 0);
-            if (!graph_exec || graph_batches[stage] != batch || graph_modes[stage] != key) {
+            if (!graph_exec || plan != graph_plans[stage]) {
                 if (graph_exec) { (void)hipGraphExecDestroy(graph_exec); graph_exec = nullptr; }
                 if (graph) { (void)hipGraphDestroy(graph); graph = nullptr; }
                 HIP_CHECK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
                 try {
-                    issue_sweeps(batch);
+                    issue_sweeps(plan);
                 } catch (...) {
                     hipGraph_t junk = nullptr;
                     (void)hipStreamEndCapture(stream, &junk);
@@ -1222,14 +1010,13 @@ class GridT : public GridBase {
                 }
                 HIP_CHECK(hipStreamEndCapture(stream, &graph));
                 HIP_CHECK(hipGraphInstantiate(&graph_exec, graph, nullptr, nullptr, 0));
-                graph_batches[stage] = batch;
-                graph_modes[stage] = key;
+                graph_plans[stage] = plan;
             }
             HIP_CHECK(hipGraphLaunch(graph_exec, stream));
         } else {
-            issue_sweeps(batch);
+            issue_sweeps(plan);
         }
-        timing.launches += mode == 2 ? 1 : persistent_now() ? (long long)ndir : (long long)ndir * n_launch;
+        timing.launches += plan.launches;
     }
 
     // One batch: sources src_ids[b] solved concurrently, source b in slot slot_ids[b].
@@ -1616,7 +1403,7 @@ class GridT : public GridBase {
             std::swap(d_tt.guard, d_tt_alt.guard);
             alt_filled = false;
             ++prefill_swaps;
-            graph_batches[0] = graph_batches[1] = -1;   // (captured launches hold the field pointer)
+            graph_plans[0].batch = graph_plans[1].batch = -1;   // (captured launches hold the field pointer)
             std::fill(group_filled.begin(), group_filled.end(), 1);
         }
         if (NS > 1) {
@@ -1851,7 +1638,7 @@ class GridT : public GridBase {
         const bool skipped_now = skip_now(n_groups());
         if (nb == n_slots && timing.node_updates > node_updates_before && skipped_now)   // (what choose_layout goes by; kernels that skip only)
             last_eval_frac = (double)(timing.evaluated_updates - evaluated_before) / (double)(timing.node_updates - node_updates_before);
-        if (skip < 0 && !weno && in_probe_window((nb + NS - 1) / NS) && timing.node_updates > node_updates_before) {   // (see skip_probe_min)
+        if (skip < 0 && !weno && fsm_in_probe_window(facts((nb + NS - 1) / NS), tune) && timing.node_updates > node_updates_before) {   // (see skip_probe_min)
             if (skipped_now) {
                 probe_skip = (double)(timing.evaluated_updates - evaluated_before) / (double)(timing.node_updates - node_updates_before) < 0.6;
                 probe_off_calls = 0;
@@ -5142,6 +4929,66 @@ int ttcr_fsm_unit_order(int dim, int dtype, int stage, int by_time, uint32_t nnx
         const std::vector<uint32_t> xs = fsm_xs_order(dim, (int)NF, (int)NJ, (int)NK, PJ, PK, C, stage == 0 ? 1 : 2, by_time != 0,
                                                       fsm_diag_order((int)npj, (int)npk));
         std::copy(xs.begin(), xs.end(), out);
+    });
+}
+
+int ttcr_fsm_sweep_plan(int dim, int dtype, int weno, uint32_t nnx, uint32_t nny, uint32_t nnz, int n_slots, const char* const* keys,
+                        const double* values, int n_options, int wg_cap, int stage, int batch, int layout, char* name, size_t name_len,
+                        long long* out) {
+    return guarded([&] {   // (host arithmetic only: no device is looked for)
+        if (dim != 2 && dim != 3) throw ValueError("dim must be 2 or 3");
+        if (dtype != TTCR_F32 && dtype != TTCR_F64) throw ValueError("dtype must be TTCR_F32 or TTCR_F64");
+        if (stage != 0 && stage != 1) throw ValueError("stage must be 0 (first order) or 1 (WENO)");
+        if (stage == 1 && !weno) throw ValueError("stage 1 needs a grid with the WENO stage");
+        if (nnx < 2 || nnz < 2 || (dim == 3 && nny < 2)) throw ValueError("grid needs at least two nodes per axis");
+        if (n_slots < 1 || batch < 1 || batch > n_slots) throw ValueError("1 <= batch <= n_slots");
+        if (wg_cap < 1) throw ValueError("the workgroup cap must be positive");
+        if (layout < -1 || layout > 1) throw ValueError("layout: -1 (default), 0 or 1");
+        if (n_options < 0 || (n_options > 0 && (!keys || !values))) throw ValueError("null options");
+        if (!name || name_len == 0 || !out) throw ValueError("null output");
+        SweepFacts f;
+        if (dtype == TTCR_F32) fsm_sweep_tiles<float>(f, dim); else fsm_sweep_tiles<double>(f, dim);
+        // F, J, K axes as in the GridT constructor: 3-D x, y, z; 2-D z, x
+        f.NF = (int)(dim == 3 ? nnx : nnz); f.NJ = (int)(dim == 3 ? nny : nnx); f.NK = (int)(dim == 3 ? nnz : 1);
+        const uint64_t npj = ((uint64_t)f.NJ + f.PJ - 1) / f.PJ, npk = ((uint64_t)f.NK + f.PK - 1) / f.PK;
+        if (nnx >= (1u << 30) || nny >= (1u << 30) || nnz >= (1u << 30) || npj >= (1u << 14) || npk >= (1u << 14))
+            throw ValueError("grid too large for the patch index of the sweep kernel");
+        f.weno = weno != 0;
+        f.n_patches = (int)(npj * npk);
+        f.nbf = (f.NF + FSM_BRICK - 1) / FSM_BRICK;
+        f.cdirty_wpu = fsm_cdirty_wpu(f.NF, f.PJ, f.PK);
+        f.n_launch = fsm_tile_launches(f.NF, f.NJ, f.NK, (int)npj, (int)npk, f.BL);
+        f.slab_bits = 32 * FSM_SLAB_WORDS; f.cd_words = FSM_CD_WORDS;
+        const SweepTuning tune = fsm_sweep_tuning(wg_cap);
+        f.opt = fsm_sweep_options();
+        for (int q = 0; q < n_options; ++q) {
+            const std::string k = keys[q] ? keys[q] : "";
+            const double v = values[q];
+            if (k == "mode") f.opt.mode = (int)v;
+            else if (k == "skip") f.opt.skip = (int)v;
+            else if (k == "lone_chunk") { if (v != 8 && v != 16) throw ValueError("option 'lone_chunk': 8 or 16"); f.opt.lone_chunk = (int)v; }
+            else if (k == "arith") { if (v != 0 && v != 1 && v != 2) throw ValueError("option 'arith': 0, 1 or 2"); f.opt.arith = (int)v; }
+            else if (k == "rotated") f.rot45 = dim == 2 && v != 0;     // (2-D rotated template with dx == dz)
+            else if (k == "probe_skip") f.probe_skip = v != 0;         // (state: what a launch in the probe window does now)
+            else throw ValueError("unknown option '" + k + "'");
+        }
+        bool window = false;
+        f.NS = fsm_pair_layout(tune, dim, f.weno, n_slots, dim == 3 ? (long long)f.n_patches : 0, &window);
+        if (window && layout >= 0) f.NS = layout ? 2 : 1;
+        f.stage = stage;
+        if (fsm_persistent(f) && batch > (n_slots + f.NS - 1) / f.NS) throw ValueError("more batch entries than slot groups");
+        f.batch = batch;
+        const SweepPlan p = fsm_sweep_plan(f, tune);
+        std::snprintf(name, name_len, "%s", fsm_sweep_name(p).c_str());
+        bool have;
+#ifdef FSM_DEV_F32_ONLY   // tuning builds: half the instantiations
+        have = dtype == TTCR_F32 && sweep_kernel_exists<float>(p);
+#else
+        have = dtype == TTCR_F32 ? sweep_kernel_exists<float>(p) : sweep_kernel_exists<double>(p);
+#endif
+        const long long o[12] = {p.arith_needs_xs ? 1 : have ? 0 : 2, (long long)p.wgs, (long long)p.block, (long long)p.dyn_lds, p.tickets, p.launches,
+                                 p.chunk, p.skip, p.XS, p.PRE, p.NS, p.AR};
+        std::copy(o, o + 12, out);
     });
 }
 

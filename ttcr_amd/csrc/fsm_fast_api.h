@@ -3,19 +3,12 @@
 // AR = 1 instantiations of fsm_sweep_persistent -- same arguments, synchronisation words, ticket lists and launch geometry as the
 // exact kernels the host would launch otherwise -- compiled in a translation unit of their own (fsm_fast.hip).
 #pragma once
-#include "fsm_kernels.h"
+#include "fsm_sweep_dispatch.h"
 
 namespace ttcr_amd {
 
-struct FastCfg {
-    int h;        // 1: first-order stage, 2: WENO stage
-    int dim;      // 3: patches of 16 x 16 columns; 2: one-wave patches of 64 columns
-    int ns;       // fields marched per workgroup (1, or 2: source pairs, 3-D only)
-    int chunk;    // levels per chunk (3-D: 8 or 16 with ns == 1, 8 with ns == 2; 2-D: 16)
-    bool skip;    // exact skipping (template SKIP)
-    bool pre;     // upwind counters sampled one chunk ahead (template PRE)
-};
-// whole-iteration launch (template XS) of the instantiation `c` names; hipErrorInvalidValue when there is none
-hipError_t fsm_fast_launch(const PersistArgs<float>& pa, const FastCfg& c, unsigned wgs, size_t dyn_lds, hipStream_t stream);
+// the AR = 1 instantiation the plan names: whether there is one, and its launch (false: there is none)
+bool fsm_fast_sweep_exists(const SweepPlan& p);
+bool fsm_fast_sweep(const SweepPlan& p, const PersistArgs<float>& pa, hipStream_t stream);
 
 }  // namespace ttcr_amd
